@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: interpolated 3-D fields/s (nCells x nLev -> nx x ny) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" = one Regrid (ESMF_FieldBundleRegrid, interp.F90:251) of a bundle of F 3-D fields through a
@@ -11,7 +11,11 @@ GPU); for N > 1 the same global problem is split by target rows with a source ha
 RCCL (strong scaling).  RegridStore (weight generation) is timed once and reported separately
 (`store_ms`): weights are data, built once per (mesh, grid) and reused for every field and time.
 
-Prints ONE JSON line on rank 0 (see the task contract) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run sets up, warms up, times the K steps,
+writes the last step's results if --dump-outputs is given, and prints the line.  --full adds everything
+else: the in-bench self-checks, the live device-copy rates, the CPU baseline, the other paths, sizes and
+numberings (`production_path`, `cell_numbering`, `end_to_end_pcie`), the fresh-process `store` / `job` /
+`c3` legs and, for N > 1, the torch.distributed transport leg beside the C-ABI one.
 """
 import argparse
 import ctypes
@@ -37,12 +41,17 @@ def parse():
     ap.add_argument("--fields", type=int, default=13, help="3-D fields per Regrid bundle (histlist_3d has 13 nz fields)")
     ap.add_argument("--layout", default="cell_fast", choices=["cell_fast", "lev_fast"])
     ap.add_argument("--io", default="f64", choices=["f64", "f32"], help="field element type in HBM; f64 = reference-faithful headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the extra legs (profiling runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip production_path / store / job / cell_numbering / end_to_end_pcie")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-checks, device-copy rates, CPU baseline, extra legs and (N > 1) the comparison transport; "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results to DIR/*.npy (a fixed seeded sample when larger than 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the extra legs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip production_path / store / job / cell_numbering / end_to_end_pcie")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--calib", action="store_true", help="also launch a known-byte-count streaming kernel (PMC calibration)")
     ap.add_argument("--leg", default=None, choices=["job", "store", "c3"],
-                    help="internal: run only this leg in THIS (fresh) process and print its JSON object -- the default run starts one "
+                    help="internal: run only this leg in THIS (fresh) process and print its JSON object -- a --full run starts one "
                          "child process per leg so that its first-call numbers are first-in-process ones")
     ap.add_argument("--ownership", default="auto", choices=["auto", "aligned", "para_range", "need"],
                     help="N > 1: who owns which source cells -- aligned / para_range: the library's id blocks; need: every cell to the lowest rank whose "
@@ -67,6 +76,27 @@ def synth_fields_device(torch, lat, lon, nlev, nfields, out_rows, seed=20240807)
     co = torch.as_tensor(rng.uniform(-1.0, 1.0, (nfields * nlev, 4)), device=dev)
     for r in range(nfields * nlev):
         out_rows[r].copy_(co[r, 0] + co[r, 1] * x + co[r, 2] * y + co[r, 3] * z + wig)
+
+
+DUMP_BYTES = 32 << 20     # --dump-outputs: at most this many bytes of results over all ranks
+
+
+def dump_outputs(dirname, out, rank, world, budget=DUMP_BYTES, seed=20240807):
+    """--dump-outputs DIR: what the timed path computed in its last step, the result bundle `out` [F][nlev][ny][nx] (N > 1: this rank's
+    rows), in its own element type (float64, or float32 with --io f32).  Whole as DIR/out.npy when it fits the budget (budget / N per
+    rank), else DIR/out_sample.npy: the values at a fixed seeded sample of flat indices (np.random.default_rng(seed).integers(0, out.numel(),
+    budget // N // element size), then np.unique: sorted, distinct) -- the same indices for the same arguments.  N > 1: out_rank<r>*.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    flat = out.reshape(-1)
+    n = budget // world // out.element_size()
+    if flat.numel() <= n:
+        np.save(os.path.join(dirname, "out%s.npy" % suffix), out.cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), n))
+    import torch
+    vals = flat[torch.as_tensor(idx, device=flat.device)]
+    np.save(os.path.join(dirname, "out_sample%s.npy" % suffix), vals.cpu().numpy())
 
 
 def self_launch(args):
@@ -193,8 +223,8 @@ def main():
 
     # N > 1: the product's own transport is the C-ABI's (mpg_comm_init -> mpg_halo_build -> mpg_halo_exchange_dev: librccl directly, what the
     # Fortran / C hosts call); `value` is timed on it.  The same schedule on torch.distributed (all_to_all_single over the nccl backend =
-    # RCCL) is timed FIRST in the same run as the comparison leg.  MPASSIT_BENCH_TRANSPORT=torch | cabi runs one leg only.  Under the gloo
-    # rehearsal backend (ranks sharing a card, where RCCL refuses a second rank per device) the default is the torch leg alone.
+    # RCCL) is timed FIRST in the same run as the comparison leg (--full only).  MPASSIT_BENCH_TRANSPORT=torch | cabi runs one leg only.
+    # Under the gloo rehearsal backend (ranks sharing a card, where RCCL refuses a second rank per device) the default is the torch leg alone.
     want = os.environ.get("MPASSIT_BENCH_TRANSPORT", "both")
     if want not in ("both", "torch", "cabi"):
         raise SystemExit("MPASSIT_BENCH_TRANSPORT must be both, torch or cabi")
@@ -202,6 +232,8 @@ def main():
         legs = ["torch"]
     elif want == "both":
         legs = ["torch", "cabi"] if backend == "nccl" or os.environ.get("MPASSIT_BENCH_FORCE_CABI_LEG") == "1" else ["torch"]
+        if not args.full:
+            legs = legs[-1:]           # the leg that supplies `value`
     else:
         legs = [want]
     import uuid
@@ -369,21 +401,22 @@ def main():
                        "halo_bytes_per_step": sum(r["received"] for r in per_rank),
                        "halo_bytes_per_step_max_rank": max(r["received"] for r in per_rank),
                        "per_rank": per_rank}
-        # correctness guard inside the bench, on every transport's own handle: constant field -> constant on mapped points (sum of weights = 1)
-        chk = torch.full((nlev, sr.sched.n_local), 2.5, dtype=torch.float64, device=dev)
-        if layout == R.LAYOUT_LEV_FAST:
-            chk = chk.t().contiguous()
-        o1 = sr.rh.regrid(chk.view(-1), nlev=nlev, nfields=1, layout=layout)
-        torch.cuda.synchronize()
-        bad = int(((o1 != 0.0) & ((o1 - 2.5).abs() > 1e-12)).sum().item())
-        L_.n_unmapped = int((o1[0, 0] == 0.0).sum().item())
-        del chk, o1
-        if bad:
-            raise SystemExit("bench self-check failed: %d points off" % bad)
-        # a bundle's first and last field against the same fields regridded alone (any 32-bit overflow in field * level * point
-        # offsets would show in the last one): bit for bit
-        L_.bundle_check = None
-        if world == 1:
+        L_.n_unmapped = L_.bundle_check = None
+        if args.full:
+            # correctness guard inside the bench, on every transport's own handle: constant field -> constant on mapped points (sum of weights = 1)
+            chk = torch.full((nlev, sr.sched.n_local), 2.5, dtype=torch.float64, device=dev)
+            if layout == R.LAYOUT_LEV_FAST:
+                chk = chk.t().contiguous()
+            o1 = sr.rh.regrid(chk.view(-1), nlev=nlev, nfields=1, layout=layout)
+            torch.cuda.synchronize()
+            bad = int(((o1 != 0.0) & ((o1 - 2.5).abs() > 1e-12)).sum().item())
+            L_.n_unmapped = int((o1[0, 0] == 0.0).sum().item())
+            del chk, o1
+            if bad:
+                raise SystemExit("bench self-check failed: %d points off" % bad)
+        if args.full and world == 1:
+            # a bundle's first and last field against the same fields regridded alone (any 32-bit overflow in field * level * point
+            # offsets would show in the last one): bit for bit
             L_.bundle_check = True
             for f in sorted({0, F - 1}):
                 sf = src_for_kernel.view(F, -1)[f]
@@ -442,30 +475,36 @@ def main():
         if world > 1 and "cabi" not in legs:
             halo["transports"]["cabi"] = {"skipped": "MPASSIT_BENCH_TRANSPORT=torch" if want == "torch" else
                                                      "backend %s: ranks may share a card, RCCL refuses a second rank per device" % backend}
+        if world > 1 and "torch" not in legs and want == "both":
+            halo["transports"]["torch"] = {"skipped": "comparison leg: --full"}
 
-    # live streaming reference of THIS device (boxes differ by >10 %): plain 2 GiB -> 2 GiB device copy
-    cp_a = torch.empty(1 << 28, dtype=torch.float64, device=dev)
-    cp_b = torch.empty_like(cp_a)
-    cp_b.copy_(cp_a)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
+    copy_gbs, mix = None, {}
+    if args.full:
+        # live streaming reference of THIS device (boxes differ by >10 %): plain 2 GiB -> 2 GiB device copy
+        cp_a = torch.empty(1 << 28, dtype=torch.float64, device=dev)
+        cp_b = torch.empty_like(cp_a)
         cp_b.copy_(cp_a)
-    e1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 5 * 2 * cp_a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    # ... and what the same memory system gives a 2 reads : 1 write mix (the headline kernel's traffic is 61 : 39) and pure writes
-    # (profiles/r05_hbm_mix.md: no mix reaches the data sheet's 8 TB/s; a copy's 1 : 1 is the slowest)
-    mix = {}
-    for key, fn, nbytes in (("device_add_2r1w_GBs", lambda: torch.add(cp_a, cp_b, out=cp_b), 3), ("device_fill_GBs", lambda: cp_b.fill_(1.5), 1)):
-        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(5):
-            fn()
+            cp_b.copy_(cp_a)
         e1.record()
         torch.cuda.synchronize()
-        mix[key] = 5 * nbytes * cp_a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del cp_a, cp_b
+        copy_gbs = 5 * 2 * cp_a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        # ... and what the same memory system gives a 2 reads : 1 write mix (the headline kernel's traffic is 61 : 39) and pure writes
+        # (profiles/r05_hbm_mix.md: no mix reaches the data sheet's 8 TB/s; a copy's 1 : 1 is the slowest)
+        for key, fn, nbytes in (("device_add_2r1w_GBs", lambda: torch.add(cp_a, cp_b, out=cp_b), 3), ("device_fill_GBs", lambda: cp_b.fill_(1.5), 1)):
+            fn()
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            mix[key] = 5 * nbytes * cp_a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        del cp_a, cp_b
 
     U = primary.U
     esz = 4.0 if io32 else 8.0  # element size of the field values in HBM (float64 = reference-faithful headline)
@@ -476,13 +515,13 @@ def main():
         traffic, traffic_source = recorded_traffic(args.workload, F, args.layout, io32)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not io32:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not io32:
         cpu = cpu_baseline(sr, src_for_kernel if layout == R.LAYOUT_CELL_FAST else local, nlev, args.cpu_seconds, m, g)
 
     # "report two timings" -- kernel-only above, and end to end through the PCIe link (one 3-D field from
     # pageable host memory to pageable host memory: upload, Regrid, download; never `value`)
     e2e = None
-    extras = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extras
     if extras and layout == R.LAYOUT_CELL_FAST and not io32:
         e2e = {}
         for name, dt_np in (("f64", np.float64), ("f32", np.float32)):

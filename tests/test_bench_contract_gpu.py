@@ -1,11 +1,12 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric / value / unit / n_gpus / steps / warmup /
-ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the roofline and
-cpu_baseline objects; checked here on the tiny workload so that a change to bench.py cannot silently break the contract."""
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the roofline object and,
+with --full, the cpu_baseline one; checked here on the tiny workload so that a change to bench.py cannot silently break the contract."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_the_contract_line(gpu_lib):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--fields", "2", "--steps", "3", "--warmup", "1",
-                        "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -29,6 +30,31 @@ def test_bench_prints_the_contract_line(gpu_lib):
     assert abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 1e-12 and (ro["traffic"] is None or ro["traffic"] > 0)
     cb = rec["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "fields/s" and cb["value"] > 0 and cb["cores"] >= 1 and isinstance(cb["sample"], str)
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(gpu_lib, tmp_path):
+    """A plain run (no --full) times the headline and nothing else: the same contract fields, no CPU baseline, no extra legs, no
+    device-copy rates; --dump-outputs writes the last timed step's results, and the same arguments give the same bits twice."""
+    F, steps = 2, 4
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--fields", str(F), "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64" and rec["higher_is_better"] is True
+        assert abs(rec["value"] - F * steps / (rec["ms_per_step"] * steps * 1e-3)) < 1e-6 * rec["value"]
+        assert rec["cpu_baseline"] is None and rec["store"] is None and rec["job"] is None and rec["production_path"] is None
+        assert rec["roofline"]["device_copy_GBs"] is None and rec["roofline"]["kernel_ms"] > 0
+        assert sorted(os.listdir(d)) == ["out.npy"]
+        out = np.load(d / "out.npy")
+        assert out.dtype == np.float64 and out.shape[:2] == (F, rec["config"]["nlev"]) and out.shape[2] * out.shape[3] == rec["config"]["target_points"]
+        assert np.isfinite(out).all() and np.abs(out).max() > 0
+        got.append(out)
+    assert np.array_equal(got[0], got[1])
 
 
 def test_bench_gpus2_launches_itself(gpu_lib):
@@ -66,7 +92,7 @@ def test_bench_failing_cabi_leg_is_reported_and_ends_nonzero(gpu_lib):
     env = dict(os.environ, MPASSIT_DIST_BACKEND="gloo", MPASSIT_BENCH_FORCE_CABI_LEG="1", MPG_COMM_TIMEOUT_S="30")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
@@ -103,8 +129,8 @@ def test_default_line_carries_the_production_numbers_inside_roofline(gpu_lib):
     characters and strings at 120: what the shipped driver's paths measure rides there as flat scalars with short keys -- the
     float32 file-order Regrid, the whole job (cold = FIRST-IN-PROCESS, from a fresh child process; warm fraction of the HBM
     peak), the Stores' first-in-process sum, mpg_init of the fresh children, the counted : algorithmic traffic ratio.  The full
-    objects stay at the top level.  The default command on the headline workload, a short CPU leg."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
+    objects stay at the top level.  The --full command on the headline workload, a short CPU leg."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=1100, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
