@@ -184,6 +184,20 @@ int mpg_regrid_store_grid_begin(mpg_grid grid, int src_staggerloc, int dst_stagg
 int mpg_regrid(mpg_handle rh, const double *src_host, int src_layout, int nlev, int nfields, double *dst_host);
 int mpg_regrid_dev(mpg_handle rh, const double *src_dev, int src_layout, int nlev, int nfields,
                    double *dst_dev, void *hip_stream);
+/* Pitched destinations.  The dense block above puts level k of a field k * ny_dst * nx_dst elements after level 0, which starts on
+ * a 128-byte line only when the plane is a multiple of 32 (float32) / 16 (float64) points -- on most grids (1799 x 1059, every
+ * stagger of 1800 x 1060) each plane starts partway into a line and its stores pay for the partial lines at both ends.  A host that
+ * owns its result arrays can instead lay the planes out dst_level_stride ELEMENTS apart: plane k of field f starts at
+ * (f * nlev + k) * dst_level_stride; elements [ny_dst * nx_dst, dst_level_stride) of each plane are never written.
+ * mpg_dst_level_stride gives the smallest stride >= plane_points at which every plane of dst_type starts on a 128-byte line (with a
+ * base pointer that does, as hipMalloc's do): pure arithmetic, callable before mpg_init.  On such planes the kernels' stores are
+ * whole-line non-temporal stores whatever the grid.
+ * Every _pitched_dev call takes the arguments of its dense twin plus dst_level_stride: 0 = dense (the dense twin is exactly that
+ * call), a stride below the plane size -> MPG_ERR_INVALID_ARG.  Same kernels, same bits per plane, and capturable in a hipGraph
+ * like the dense calls. */
+int mpg_dst_level_stride(int64_t plane_points, int dst_type, int64_t *ld);
+int mpg_regrid_pitched_dev(mpg_handle rh, const double *src_dev, int src_layout, int nlev, int nfields, double *dst_dev,
+                           int64_t dst_level_stride, void *hip_stream);
 /* Fused ingest/egress Regrid (the callers either side of the hot path): the source may be
  * float32 (MPAS history variables are single precision; the reference widens them at read, input_data.F90:630-655)
  * and the destination float32 (every output variable is NF90_FLOAT, write_data.F90:779).  The arithmetic stays
@@ -197,6 +211,9 @@ int mpg_regrid_dev(mpg_handle rh, const double *src_dev, int src_layout, int nle
 enum { MPG_TYPE_F64 = 0, MPG_TYPE_F32 = 1, MPG_TYPE_BE = 2 };
 int mpg_regrid_typed_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields,
                          void *dst_dev, int dst_type, double scale, double offset, void *hip_stream);
+/* ... with the destination's level planes dst_level_stride elements apart (mpg_regrid_pitched_dev) */
+int mpg_regrid_typed_pitched_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev,
+                                 int dst_type, double scale, double offset, int64_t dst_level_stride, void *hip_stream);
 /* ESMF_FieldBundleRegrid as interp.F90:240-254 issues it: ONE Regrid over every field of a bundle whose fields are SEPARATE
  * arrays (an ESMF bundle holds independent fields; here: nfields device pointers on either side, host arrays of pointers).
  * All fields share the handle, the layout, nlev and the element types; offsets (nfields values, or NULL for 0) is the
@@ -205,6 +222,10 @@ int mpg_regrid_typed_dev(mpg_handle rh, const void *src_dev, int src_type, int s
  * bits as nfields single calls; 10 % (configuration 4) to 18 % (configuration 5) faster than those. */
 int mpg_regrid_bundle_typed_dev(mpg_handle rh, int nfields, const void *const *src_dev, int src_type, int src_layout, int nlev,
                                 void *const *dst_dev, int dst_type, double scale, const double *offsets, void *hip_stream);
+/* ... with the level planes of every destination array dst_level_stride elements apart (plane k of field f at dst_dev[f] + k * stride) */
+int mpg_regrid_bundle_typed_pitched_dev(mpg_handle rh, int nfields, const void *const *src_dev, int src_type, int src_layout, int nlev,
+                                        void *const *dst_dev, int dst_type, double scale, const double *offsets, int64_t dst_level_stride,
+                                        void *hip_stream);
 /* The same on HOST buffers (pageable memory: Fortran allocatables, numpy arrays), for hosts that keep the reference's
  * file -> host array -> regrid -> host array -> file shape and are therefore bound by the PCIe link: float32 sources
  * and results cross the link as they are stored in the files (half the bytes of the float64 route), and the field is cut
@@ -244,6 +265,11 @@ int mpg_rotate_winds_dev(int64_t npts, int nlev, const double *cosa_dev, const d
 int mpg_wind_destagger_dev(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *cosa_dev, const double *sina_dev,
                            const double *umass_dev, const double *vmass_dev, int nlev, void *u_dev, void *v_dev, int dst_type,
                            double *umass_rot_dev, double *vmass_rot_dev, void *hip_stream);
+/* ... with U's and V's level planes dst_level_stride elements apart: ONE stride for both, at least ny * (nx + 1) and (ny + 1) * nx
+ * (mpg_dst_level_stride of the larger plane); umass_rot_dev / vmass_rot_dev stay dense. */
+int mpg_wind_destagger_pitched_dev(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *cosa_dev, const double *sina_dev,
+                                   const double *umass_dev, const double *vmass_dev, int nlev, void *u_dev, void *v_dev, int dst_type,
+                                   double *umass_rot_dev, double *vmass_rot_dev, int64_t dst_level_stride, void *hip_stream);
 /* The same chain for a host that keeps its fields in HOST arrays, as the reference does (farrayPtr in, farrayPtr out: interp.F90:702-735
  * fetches the pointers, :291-328 runs the chain).  The three separate host calls -- mpg_rotate_winds, then mpg_regrid on each handle --
  * move 4 fields up and 4 down over the link; this one moves the earth-relative mass winds up ONCE in chunks of levels and only U and V
@@ -286,6 +312,11 @@ int mpg_bswap_dev(void *buf_dev, int64_t n, int elem_size, void *hip_stream);
  * concurrently from two host threads. */
 int mpg_file_to_dev(const char *path, int64_t offset, int64_t nbytes, void *dst_dev, void *hip_stream);
 int mpg_dev_to_file(const char *path, int64_t offset, int64_t nbytes, const void *src_dev, void *hip_stream);
+/* ... from pitched planes: nplanes planes of plane_bytes, src_pitch_bytes apart in device memory (>= plane_bytes; the results of
+ * the _pitched_dev calls), -> the contiguous range [offset, offset + nplanes * plane_bytes) of the file.  The range is cut into
+ * chunks and written by the same threads as mpg_dev_to_file; each chunk is gathered from the planes it covers. */
+int mpg_dev_to_file_planes(const char *path, int64_t offset, int64_t plane_bytes, int64_t nplanes, const void *src_dev,
+                           int64_t src_pitch_bytes, void *hip_stream);
 int mpg_post_cast_dev(const double *src_dev, int64_t n, double scale, double offset, float *dst_dev, int dst_be, void *hip_stream);
 int mpg_post_layer_mean_dev(const double *src_dev, int nlevp1, int64_t n_pts, float *dst_dev, int dst_be, void *hip_stream);
 int mpg_post_ptop_dev(const double *p_hyd_dev, int nlev, int64_t n_pts, double *ptop_host, void *hip_stream);

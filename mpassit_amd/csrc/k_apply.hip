@@ -39,7 +39,7 @@
 // slower, profiles/r01_sweep_apply*.txt.)
 __global__ __launch_bounds__(256) void k_apply3_cf(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                    const double *__restrict__ src, double *__restrict__ dst, int nx, int ny,
-                                                   int64_t nsrc, int nlev, int ntx, int nty) {
+                                                   int64_t nsrc, int nlev, int ntx, int nty, int64_t ld) {
   constexpr int RPT = 2, TY = 4 * RPT;
   int64_t P = (int64_t)nx * ny;
   unsigned ntile = (unsigned)ntx * nty;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf(const int32_t *__restrict__ i
     for (int q = 0; q < 3; ++q) c[r][q] = max(c[r][q], 0);
   }
   const double *s = src + (int64_t)f * nlev * nsrc;
-  double *d = dst + (int64_t)f * nlev * P;
+  double *d = dst + (int64_t)f * nlev * ld;
   for (int k = 0; k < nlev; ++k) {
     __syncthreads();
     double v[RPT];
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf(const int32_t *__restrict__ i
     for (int r = 0; r < RPT; ++r)
       if (act[r]) stream_store_lane(mapped[r] ? v[r] : 0.0, d + po[r], (unsigned)(threadIdx.x & 63) * 8u);   // geom.h: per lane
     s += nsrc;
-    d += P;
+    d += ld;
   }
 }
 static int g_a3_staged = -1;  // "a3_staged" knob: -2 lane-gather only, -1 per-handle choice (default), 0..2 that LDS-staged variant
@@ -100,7 +100,7 @@ static int g_a3_staged = -1;  // "a3_staged" knob: -2 lane-gather only, -1 per-h
 // LDS tile [nlev][65] doubles (row pad 1: conflict-free ds_write_b64 column writes).
 __global__ __launch_bounds__(512) void k_apply3_lf(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                    const double *__restrict__ src, double *__restrict__ dst, int nx, int ny,
-                                                   int64_t nsrc, int nlev, int ntx, int nty) {
+                                                   int64_t nsrc, int nlev, int ntx, int nty, int64_t ld) {
   constexpr int WAVES = 8, PPW = 64 / WAVES, BATCH = 4;
   extern __shared__ double tile[];  // [nlev][65] | sw[3][64] | sidx[3][64]
   double *sw = tile + (size_t)nlev * 65;
@@ -153,9 +153,9 @@ __global__ __launch_bounds__(512) void k_apply3_lf(const int32_t *__restrict__ i
     }
   }
   __syncthreads();
-  double *df = dst + (int64_t)fld * nlev * P;
+  double *df = dst + (int64_t)fld * nlev * ld;
   if (oact)
-    for (int k = wave; k < nlev; k += WAVES) stream_store_lane(tile[k * 65 + lane], df + (int64_t)k * P + op, (unsigned)lane * 8u);
+    for (int k = wave; k < nlev; k += WAVES) stream_store_lane(tile[k * 65 + lane], df + (int64_t)k * ld + op, (unsigned)lane * 8u);
 }
 // "lf_variant" knob: -1 per-handle choice (default) between 0 and 1; 0 row gather on linear aligned tiles
 // (k_apply3_lf_rows), 1 level-chunked LDS-staged kernel (k_apply_lfu.hip), 2 row gather on grid-row tiles (k_apply3_lf /
@@ -167,7 +167,7 @@ static int g_lf_variant = -1;
 // written once and never read by this kernel, it must not push the gathered source lines out of L2 (round-5 review, item 6).
 template <bool LEVF>
 __global__ __launch_bounds__(256) void k_apply1(const int32_t *__restrict__ idx, const double *__restrict__ src,
-                                                double *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk) {
+                                                double *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk, int64_t ld) {
   unsigned blk = blockIdx.x % nblk;
   int fld = blockIdx.x / nblk;
   int64_t p = (int64_t)blk * 256 + threadIdx.x;
@@ -175,18 +175,18 @@ __global__ __launch_bounds__(256) void k_apply1(const int32_t *__restrict__ idx,
   int32_t c = idx[p];
   const double *sf = src + (int64_t)fld * nlev * nsrc + (c >= 0 ? (LEVF ? (int64_t)c * nlev : (int64_t)c) : 0);
   const int64_t step = LEVF ? 1 : nsrc;
-  double *df = dst + (int64_t)fld * nlev * P + p;
+  double *df = dst + (int64_t)fld * nlev * ld + p;
   for (int k = 0; k < nlev; ++k) {
     double v = 0.0;
     if (c >= 0) v = sf[k * step];
-    stream_store_lane(v, df + (int64_t)k * P, (unsigned)(threadIdx.x & 63) * 8u);
+    stream_store_lane(v, df + (int64_t)k * ld, (unsigned)(threadIdx.x & 63) * 8u);
   }
 }
 
 template <int NNZ, bool LEVF>
 __global__ __launch_bounds__(256) void k_applyN(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                 const double *__restrict__ src, double *__restrict__ dst, int64_t P,
-                                                int64_t nsrc, int nlev, int nblk) {
+                                                int64_t nsrc, int nlev, int nblk, int64_t ld) {
   unsigned blk = blockIdx.x % nblk;
   int fld = blockIdx.x / nblk;
   int64_t p = (int64_t)blk * 256 + threadIdx.x;
@@ -202,35 +202,35 @@ __global__ __launch_bounds__(256) void k_applyN(const int32_t *__restrict__ idx,
   bool mapped = c[0] >= 0;
   const int64_t step = LEVF ? 1 : nsrc;
   const double *sf = src + (int64_t)fld * nlev * nsrc;
-  double *df = dst + (int64_t)fld * nlev * P + p;
+  double *df = dst + (int64_t)fld * nlev * ld + p;
   for (int k = 0; k < nlev; ++k) {
     double acc = 0.0;
     if (mapped) {
 #pragma unroll
       for (int q = 0; q < NNZ; ++q) acc = fma(ww[q], sf[c[q] + k * step], acc);
     }
-    stream_store_lane(acc, df + (int64_t)k * P, (unsigned)(threadIdx.x & 63) * 8u);
+    stream_store_lane(acc, df + (int64_t)k * ld, (unsigned)(threadIdx.x & 63) * 8u);
   }
 }
 
 template <bool LEVF>
 __global__ __launch_bounds__(256) void k_apply_csr(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                    const double *__restrict__ val, const double *__restrict__ src,
-                                                   double *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk) {
+                                                   double *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk, int64_t ld) {
   unsigned blk = blockIdx.x % nblk;
   int fld = blockIdx.x / nblk;
   int64_t p = (int64_t)blk * 256 + threadIdx.x;
   if (p >= P) return;
   int b = rowptr[p], e = rowptr[p + 1];
   const double *sf = src + (int64_t)fld * nlev * nsrc;
-  double *df = dst + (int64_t)fld * nlev * P + p;
+  double *df = dst + (int64_t)fld * nlev * ld + p;
   for (int k = 0; k < nlev; ++k) {
     double acc = 0.0;
     for (int q = b; q < e; ++q) {
       int32_t c = col[q];
       acc = fma(val[q], LEVF ? sf[(int64_t)c * nlev + k] : sf[(int64_t)k * nsrc + c], acc);
     }
-    stream_store_lane(acc, df + (int64_t)k * P, (unsigned)(threadIdx.x & 63) * 8u);
+    stream_store_lane(acc, df + (int64_t)k * ld, (unsigned)(threadIdx.x & 63) * 8u);
   }
 }
 
@@ -343,25 +343,24 @@ int mpg_k_tune(const char *key, int value) {
   return MPG_ERR_INVALID_ARG;
 }
 
-int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nfields, double *dst, hipStream_t s) {
+int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld) {
   int64_t P = h->n_dst;
   int lev_fast = layout == MPG_LAYOUT_LEV_FAST;
   if (P == 0 || nlev == 0 || nfields == 0) return MPG_SUCCESS;
-  if (h->n_src == 0) {  // nothing is mapped (e.g. a row shard entirely outside the mesh): zero-filled destination
-    MPG_HIP(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)P * nlev * nfields, s));
-    return MPG_SUCCESS;
-  }
+  if (ld == 0) ld = P;
+  if (h->n_src == 0)  // nothing is mapped (e.g. a row shard entirely outside the mesh): zero-filled destination planes
+    return mpg_zero_planes(dst, sizeof(double), P, (int64_t)nlev * nfields, ld, s);
   int nblk = (int)((P + 255) / 256);
   const bool levf = lev_fast && nlev > 1;   // (a single level is the same memory in both layouts)
   if (h->kind == MPG_KIND_CSR) {
-    if (levf) k_apply_csr<true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->rowptr.p, h->col.p, h->val.p, src, dst, P, h->n_src, nlev, nblk);
-    else k_apply_csr<false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->rowptr.p, h->col.p, h->val.p, src, dst, P, h->n_src, nlev, nblk);
+    if (levf) k_apply_csr<true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->rowptr.p, h->col.p, h->val.p, src, dst, P, h->n_src, nlev, nblk, ld);
+    else k_apply_csr<false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->rowptr.p, h->col.p, h->val.p, src, dst, P, h->n_src, nlev, nblk, ld);
   } else if (h->nnz_per_row == 1) {
-    if (levf) k_apply1<true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, src, dst, P, h->n_src, nlev, nblk);
-    else k_apply1<false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, src, dst, P, h->n_src, nlev, nblk);
+    if (levf) k_apply1<true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, src, dst, P, h->n_src, nlev, nblk, ld);
+    else k_apply1<false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, src, dst, P, h->n_src, nlev, nblk, ld);
   } else if (h->nnz_per_row == 4) {
-    if (levf) k_applyN<4, true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, nblk);
-    else k_applyN<4, false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, nblk);
+    if (levf) k_applyN<4, true><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, nblk, ld);
+    else k_applyN<4, false><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, nblk, ld);
   } else if (h->nnz_per_row == 3 && lev_fast && nlev > 1) {
     int lfv = g_lf_variant;
     if (lfv < 0) {  // per handle, by the (sampled) reuse statistic of its tiles (k_apply_lfu.hip); short bundles: row gather
@@ -372,12 +371,12 @@ int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nf
       }
     }
     if (lfv == MPG_LF_STAGED) {
-      int rc = mpg_k_apply3_lfu(h, src, nlev, nfields, dst, s);
+      int rc = mpg_k_apply3_lfu(h, src, nlev, nfields, dst, s, ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
       lfv = MPG_LF_ROWS;     // the tile lists outgrow the LDS: row gather
     }
     if (lfv == MPG_LF_ROWS) {
-      int rc = mpg_k_apply3_lf_rows(h, src, nlev, nfields, dst, s);   // k_apply_typed.hip
+      int rc = mpg_k_apply3_lf_rows(h, src, nlev, nfields, dst, s, ld);   // k_apply_typed.hip
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
     int ntx = mpg_tile_ntx(h->nx_dst, 64), nty = h->ny_dst;
@@ -387,7 +386,7 @@ int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nf
       return MPG_ERR_UNSUPPORTED;
     }
     if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)k_apply3_lf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_apply3_lf<<<(unsigned)ntx * nty * nfields, 512, lds, s>>>(h->idx.p, h->w.p, src, dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntx, nty);
+    k_apply3_lf<<<(unsigned)ntx * nty * nfields, 512, lds, s>>>(h->idx.p, h->w.p, src, dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntx, nty, ld);
   } else if (h->nnz_per_row == 3) {
     // cell-fast (a single level is the same memory in both layouts).  g_a3_staged: -2 = lane-gather kernel only, -1 =
     // per-handle choice by the reuse statistic of the tile lists, >= 0 = that LDS-staged variant (k_apply_lfu.hip)
@@ -404,17 +403,23 @@ int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nf
       if (!fits) staged = -2;  // hardly any cell shared inside a tile: the lane-gather kernel serves this handle
     }
     if (staged >= 0) {
-      int rc = mpg_k_apply3_cfu(h, staged, src, 0, nlev, nfields, dst, 0, false, 1.0, 0.0, s);
+      int rc = mpg_k_apply3_cfu(h, staged, src, 0, nlev, nfields, dst, 0, false, 1.0, 0.0, s, FieldTab(), ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
     int ntx = mpg_tile_ntx(h->nx_dst, A3_TX), nty = (h->ny_dst + 7) / 8;
-    k_apply3_cf<<<(unsigned)ntx * nty * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntx, nty);
+    k_apply3_cf<<<(unsigned)ntx * nty * nfields, 256, 0, s>>>(h->idx.p, h->w.p, src, dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntx, nty, ld);
   } else {
     mpg_set_error("Regrid: unsupported handle");
     return MPG_ERR_UNSUPPORTED;
   }
   MPG_HIP(hipGetLastError());
-  if (h->n_pole) return mpg_k_pole_fix(h, src, 0, layout, nlev, nfields, dst, 0, 1.0, 0.0, s);
+  if (h->n_pole) return mpg_k_pole_fix(h, src, 0, layout, nlev, nfields, dst, 0, 1.0, 0.0, s, FieldTab(), ld);
+  return MPG_SUCCESS;
+}
+
+int mpg_zero_planes(void *dst, size_t esz, int64_t P, int64_t nplanes, int64_t ld, hipStream_t s) {
+  if (ld == P) MPG_HIP(hipMemsetAsync(dst, 0, esz * (size_t)P * (size_t)nplanes, s));
+  else MPG_HIP(hipMemset2DAsync(dst, esz * (size_t)ld, 0, esz * (size_t)P, (size_t)nplanes, s));
   return MPG_SUCCESS;
 }
 

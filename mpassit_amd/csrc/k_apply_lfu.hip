@@ -188,7 +188,8 @@ template <typename TS, typename TD, int RPT, int NT, bool EPI>
 __global__ __launch_bounds__(NT) void k_apply3_cfu(const int32_t *__restrict__ ut_cnt, const int32_t *__restrict__ ut_cells, int stride,
                                                    const uint16_t *__restrict__ lidx, const double *__restrict__ w,
                                                    const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int talign, int64_t nsrc,
-                                                   int nlev, int ntx, int nty, int ut_max, double scale, double offset, int band, int st_all_nt, FieldTab tab) {
+                                                   int nlev, int ntx, int nty, int ut_max, double scale, double offset, int band, int st_all_nt, FieldTab tab,
+                                                   int64_t ld) {
   constexpr int LC = 4, UPT = 4, NPF = LC * UPT;
   extern __shared__ double lds[];  // [LC][nup]
   const int nup = ut_max;
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(NT) void k_apply3_cfu(const int32_t *__restrict__ u
   LfuPoints<RPT, NT> pts;
   pts.load(lidx, w, nx, ny, talign, tile % ntx, tile / ntx, 1);
   const TS *sf = mpg_field_src(tab, src, f, (int64_t)nlev * nsrc);
-  TD *df = mpg_field_dst(tab, dst, f, (int64_t)nlev * P);
+  TD *df = mpg_field_dst(tab, dst, f, (int64_t)nlev * ld);
   if constexpr (EPI) offset = mpg_field_off(tab, f, offset);
   const unsigned lane_bytes = (unsigned)(t & 63) * (unsigned)sizeof(TD);   // geom.h stream_store_lane
   int32_t cell[UPT];
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(NT) void k_apply3_cfu(const int32_t *__restrict__ u
         double val = wsum3(pts.ww[r][0], a, pts.ww[r][1], b, pts.ww[r][2], e);
         val = pts.mapped[r] ? val : 0.0;
         if constexpr (EPI) val = fma(val, scale, offset);
-        if (pts.act[r]) stream_store_lane((TD)val, df + (int64_t)(k0 + kk) * P + pts.off[r], lane_bytes, st_all_nt != 0);
+        if (pts.act[r]) stream_store_lane((TD)val, df + (int64_t)(k0 + kk) * ld + pts.off[r], lane_bytes, st_all_nt != 0);
       }
     }
     __syncthreads();
@@ -509,7 +510,7 @@ int mpg_cfu_fits(mpg_handle_s *h, int variant, hipStream_t s, int *fits) {
 
 template <typename TS, typename TD, int RPT, int NT, bool EPI>
 static int launch_cfu(mpg_handle_s *h, const void *src, int nlev, int nfields, void *dst, double scale, double offset, hipStream_t s,
-                      const FieldTab &tab) {
+                      const FieldTab &tab, int64_t ld) {
   constexpr int TYU = NT * RPT / 64;
   const int ntx = mpg_tile_ntx(h->nx_dst, 64, h->ut_align), nty = (h->ny_dst + TYU - 1) / TYU;
   const size_t um = h->ut_max > 0 ? h->ut_max : 1;   // unmapped points read slot 0
@@ -522,31 +523,32 @@ static int launch_cfu(mpg_handle_s *h, const void *src, int nlev, int nfields, v
   auto fn = k_apply3_cfu<TS, TD, RPT, NT, EPI>;
   if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fn<<<(unsigned)ntx * nty * nfields, NT, lds, s>>>(h->ut_cnt.p, h->ut_cells.p, h->ut_stride, h->lidx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst,
-                                                   h->ny_dst, h->ut_align, h->n_src, nlev, ntx, nty, (int)um, scale, offset, mpg_field_band(0), g_staged_store == 2, tab);
+                                                   h->ny_dst, h->ut_align, h->n_src, nlev, ntx, nty, (int)um, scale, offset, mpg_field_band(0), g_staged_store == 2, tab, ld);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }
 
 template <int RPT, int NT>
 static int launch_cfu_types(mpg_handle_s *h, const void *src, int src_f32, int nlev, int nfields, void *dst, int dst_f32, bool epi, double scale,
-                            double offset, hipStream_t s, const FieldTab &tab) {
-  if (!epi) return launch_cfu<double, double, RPT, NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, s, tab);
-  if (src_f32 && dst_f32) return launch_cfu<float, float, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab);
-  if (src_f32) return launch_cfu<float, double, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab);
-  if (dst_f32) return launch_cfu<double, float, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab);
-  return launch_cfu<double, double, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab);
+                            double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
+  if (!epi) return launch_cfu<double, double, RPT, NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, s, tab, ld);
+  if (src_f32 && dst_f32) return launch_cfu<float, float, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab, ld);
+  if (src_f32) return launch_cfu<float, double, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab, ld);
+  if (dst_f32) return launch_cfu<double, float, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab, ld);
+  return launch_cfu<double, double, RPT, NT, true>(h, src, nlev, nfields, dst, scale, offset, s, tab, ld);
 }
 
 // The staged cell-fast Regrid of one variant (lists built / swapped in as needed).  epi = false: mpg_regrid_dev (float64
 // both sides, the result as it stands, sign of zero included).
 int mpg_k_apply3_cfu(mpg_handle_s *h, int variant, const void *src, int src_f32, int nlev, int nfields, void *dst, int dst_f32, bool epi,
-                     double scale, double offset, hipStream_t s, const FieldTab &tab) {
+                     double scale, double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
+  if (ld == 0) ld = h->n_dst;
   int rc = cfu_build(h, variant, s);
   if (rc) return rc;
   if (h->ut_max > cfu_capacity(variant) && h->ut_max * 4 * sizeof(double) > 150 * 1024) return MPG_ERR_UNSUPPORTED;
-  if (variant == CFU_TALL) return launch_cfu_types<2, 512>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab);
-  if (variant == CFU_WIDE) return launch_cfu_types<4, 256>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab);
-  return launch_cfu_types<2, 256>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab);
+  if (variant == CFU_TALL) return launch_cfu_types<2, 512>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab, ld);
+  if (variant == CFU_WIDE) return launch_cfu_types<4, 256>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab, ld);
+  return launch_cfu_types<2, 256>(h, src, src_f32, nlev, nfields, dst, dst_f32, epi, scale, offset, s, tab, ld);
 }
 
 // ---- level-fast, level chunks --------------------------------------------------------------------------------
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(NT) void k_apply3_lfu(const int32_t *__restrict__ u
                                                    const uint16_t *__restrict__ lidx, const double *__restrict__ w, const TS *__restrict__ src,
                                                    TD *__restrict__ dst, int nx, int ny, int talign, int64_t nsrc, int nlev, int ntx,
                                                    const int32_t *__restrict__ order, unsigned n_cls,
-                                                   double scale, double offset, int sbe, int dbe, int band, FieldTab tab) {
+                                                   double scale, double offset, int sbe, int dbe, int band, FieldTab tab, int64_t ld) {
   constexpr int LC = 16, LS = LC + 1, RPP = NT / LC, TY = NT / 64, ZROW = NPF * RPP;
   extern __shared__ double lds_raw[];
   TS *slab = (TS *)lds_raw;                                  // [ZROW + 1][LS]; row ZROW stays zero
@@ -615,9 +617,9 @@ __global__ __launch_bounds__(NT) void k_apply3_lfu(const int32_t *__restrict__ u
   }
   const uint32_t pb = act ? (uint32_t)p * (uint32_t)sizeof(TD) : MPG_BUF_NONE;
   const BufRsrc rs = buf_rsrc(mpg_field_src(tab, src, f, (int64_t)nlev * nsrc), (uint32_t)((uint64_t)nsrc * nlev * sizeof(TS)));
-  TD *dlev = mpg_field_dst(tab, dst, f, (int64_t)nlev * P);  // the level plane the next store goes to
+  TD *dlev = mpg_field_dst(tab, dst, f, (int64_t)nlev * ld);  // the level plane the next store goes to (ld elements apart; 64-bit base)
   if constexpr (EPI) offset = mpg_field_off(tab, f, offset);
-  const uint32_t plane = (uint32_t)(P * sizeof(TD));
+  const uint32_t plane = (uint32_t)(P * sizeof(TD));   // one descriptor per level plane: it covers the plane's P points, never the pad
   const int nch = (nlev + LC - 1) / LC, k0_last = max(nlev - LC, 0);
   if (t < LS) slab[ZROW * LS + t] = (TS)0;
   TS pf[NPF];
@@ -634,7 +636,7 @@ __global__ __launch_bounds__(NT) void k_apply3_lfu(const int32_t *__restrict__ u
     double val = wsum3(w0, a, w1, b, w2, e);
     if constexpr (EPI) val = fma(val, scale, offset);
     buf_store_nt(swz<SWZ>((TD)val, zd), buf_rsrc(dlev, plane), pb);   // every lane non-temporal: the per-lane form of geom.h cost this 16-times unrolled body 16 % on configuration 5's (aligned) planes, profiles/r06_plane_alignment.md
-    dlev += P;
+    dlev += ld;
   };
   fetch(nch > 1 ? 0 : k0_last);
   park();
@@ -665,7 +667,7 @@ void mpg_lfu_set_npf(int v) { g_lfu_npf = v; }
 
 template <typename TS, typename TD, int NT, bool EPI, int NPF>
 static int launch_lfu_n(mpg_handle_s *h, const void *src, int nlev, int nfields, void *dst, double scale, double offset, int sbe, int dbe,
-                        hipStream_t s, const FieldTab &tab, const int32_t *order, unsigned n_cls) {
+                        hipStream_t s, const FieldTab &tab, const int32_t *order, unsigned n_cls, int64_t ld) {
   if (n_cls == 0) return MPG_SUCCESS;
   const int ntx = mpg_tile_ntx(h->nx_dst, 64, h->ut_align);
   constexpr int ROWS = NT / 16 * NPF;   // rows of the slab
@@ -675,7 +677,7 @@ static int launch_lfu_n(mpg_handle_s *h, const void *src, int nlev, int nfields,
   auto fn = (sbe || dbe) ? k_apply3_lfu<TS, TD, NT, EPI, true, NPF> : k_apply3_lfu<TS, TD, NT, EPI, false, NPF>;
   if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fn<<<n_cls * (unsigned)nfields, NT, lds, s>>>(h->ut_cells.p, h->ut_stride, h->lidx.p, h->w.p, (const TS *)src, (TD *)dst,
-                                               h->nx_dst, h->ny_dst, h->ut_align, h->n_src, nlev, ntx, order, n_cls, scale, offset, sbe, dbe, mpg_field_band(0), tab);
+                                               h->nx_dst, h->ny_dst, h->ut_align, h->n_src, nlev, ntx, order, n_cls, scale, offset, sbe, dbe, mpg_field_band(0), tab, ld);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }
@@ -683,7 +685,7 @@ static int launch_lfu_n(mpg_handle_s *h, const void *src, int nlev, int nfields,
 // threads).  "lfu_npf" (A/B): a forced value serves every class it can hold, as rounds 1-5 did with 16.
 template <typename TS, typename TD, int NT, bool EPI>
 static int launch_lfu(mpg_handle_s *h, const void *src, int nlev, int nfields, void *dst, double scale, double offset, int sbe, int dbe,
-                      hipStream_t s, const FieldTab &tab) {
+                      hipStream_t s, const FieldTab &tab, int64_t ld) {
   constexpr int RPP = NT / 16, NPF0 = 64 / RPP;   // class c holds 64 << c rows = RPP * (NPF0 << c)
   static_assert(RPP * NPF0 == 64, "class c holds 64 << c rows");
   if (h->ut_cls_off[6] > h->ut_cls_off[5] || !h->ut_order.p || h->ut_stride < 64 || (uint64_t)h->n_src * (uint64_t)nlev * sizeof(TS) >= 0xFFFFFFFFull ||
@@ -698,11 +700,11 @@ static int launch_lfu(mpg_handle_s *h, const void *src, int nlev, int nfields, v
     while (cc < 4 && (NPF0 << cc) < g_lfu_npf && h->ut_stride >= (64 << (cc + 1))) ++cc;   // "lfu_npf": at least that many (A/B)
     int rc;
     switch (cc) {
-      case 0: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls); break;
-      case 1: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 2>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls); break;
-      case 2: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 4>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls); break;
-      case 3: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 8>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls); break;
-      default: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 16>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls); break;
+      case 0: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls, ld); break;
+      case 1: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 2>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls, ld); break;
+      case 2: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 4>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls, ld); break;
+      case 3: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 8>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls, ld); break;
+      default: rc = launch_lfu_n<TS, TD, NT, EPI, NPF0 * 16>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, order, n_cls, ld); break;
     }
     if (rc) return rc;
   }
@@ -716,19 +718,21 @@ static int launch_lfu(mpg_handle_s *h, const void *src, int nlev, int nfields, v
 
 // -> MPG_ERR_UNSUPPORTED when a tile's list does not fit the slab (the caller takes the row gather)
 int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
-                           double offset, hipStream_t s, const FieldTab &tab) {
+                           double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
+  if (ld == 0) ld = h->n_dst;
   const int sbe = (src_type & MPG_TYPE_BE) != 0, dbe = (dst_type & MPG_TYPE_BE) != 0, sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
   int rc = lfu_build_shape(h, 64, LFU_NT / 64, s, LFU_LIST_PAD);
   if (rc) return rc;
-  if (sf32 && df32) return launch_lfu<float, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  if (sf32) return launch_lfu<float, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  if (df32) return launch_lfu<double, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  return launch_lfu<double, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
+  if (sf32 && df32) return launch_lfu<float, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (sf32) return launch_lfu<float, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (df32) return launch_lfu<double, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  return launch_lfu<double, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
 }
-int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s) {
+int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld) {
+  if (ld == 0) ld = h->n_dst;
   int rc = lfu_build_shape(h, 64, LFU_NT / 64, s, LFU_LIST_PAD);
   if (rc) return rc;
-  return launch_lfu<double, double, LFU_NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, 0, 0, s, FieldTab());
+  return launch_lfu<double, double, LFU_NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, 0, 0, s, FieldTab(), ld);
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

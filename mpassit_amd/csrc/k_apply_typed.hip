@@ -22,7 +22,7 @@
 template <typename TS, typename TD, bool SWZ>
 __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                      const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
-                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab) {
+                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
   constexpr int RPT = 2, TY = 4 * RPT;
   const Swz zs = make_swz(sbe), zd = make_swz(dbe);
   int64_t P = (int64_t)nx * ny;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__
     for (int q = 0; q < 3; ++q) c[r][q] = max(c[r][q], 0);
   }
   const TS *s = mpg_field_src(tab, src, fld, (int64_t)nlev * nsrc);
-  TD *d = mpg_field_dst(tab, dst, fld, (int64_t)nlev * P);
+  TD *d = mpg_field_dst(tab, dst, fld, (int64_t)nlev * ld);
   offset = mpg_field_off(tab, fld, offset);
   for (int k = 0; k < nlev; ++k) {
     __syncthreads();
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__
     for (int r = 0; r < RPT; ++r)
       if (act[r]) stream_store_lane(swz<SWZ>((TD)fma(mapped[r] ? v[r] : 0.0, scale, offset), zd), d + po[r], (unsigned)lane * (unsigned)sizeof(TD));   // geom.h: per lane
     s += nsrc;
-    d += P;
+    d += ld;
   }
 }
 
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf_fields(const int32_t *__restr
 template <typename TS, typename TD, bool SWZ>
 __global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                      const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
-                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab) {
+                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
   extern __shared__ double sw[];    // sw[3][64] | sidx[3][64] | tile[nlev][65] in the DESTINATION type (narrowing at the tile
   int32_t *sidx = (int32_t *)(sw + 192);            // write or at the store gives the same bits; float32 halves the LDS -> 8 WGs / CU)
   TD *tile = (TD *)(sidx + 192);
@@ -178,11 +178,11 @@ __global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__
     }
   }
   __syncthreads();
-  TD *df = mpg_field_dst(tab, dst, fld, (int64_t)nlev * P);
+  TD *df = mpg_field_dst(tab, dst, fld, (int64_t)nlev * ld);
   int j = ty, i = tx * 64 + lane - mpg_tile_shift(j, nx);
   if (i >= 0 && i < nx && j < ny) {
     int64_t p = (int64_t)j * nx + i;
-    for (int k = wave; k < nlev; k += 4) stream_store_lane(tile[k * 65 + lane], df + (int64_t)k * P + p, (unsigned)lane * (unsigned)sizeof(TD));   // geom.h: per lane
+    for (int k = wave; k < nlev; k += 4) stream_store_lane(tile[k * 65 + lane], df + (int64_t)k * ld + p, (unsigned)lane * (unsigned)sizeof(TD));   // geom.h: per lane
   }
 }
 
@@ -210,7 +210,7 @@ template <> struct Row2<double> { typedef f64x2_u type; };
 template <typename TS, typename TD, int UNR, bool EPI, bool SWZ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_apply3_lf_rows(
     const int32_t *__restrict__ idx, const double *__restrict__ w, const TS *__restrict__ src, TD *__restrict__ dst, int64_t P, int64_t nsrc,
-    int nlev, unsigned ntile, double scale, double offset, int sbe, int dbe, int band, int st_mode, FieldTab tab) {
+    int nlev, unsigned ntile, double scale, double offset, int sbe, int dbe, int band, int st_mode, FieldTab tab, int64_t ld) {
   typedef typename Row2<TS>::type row2;
   extern __shared__ double sw[];                    // sw[3][64] | soff[3][64] | tile[nlev][65] in the destination type
   uint32_t *soff = (uint32_t *)(sw + 192);
@@ -280,10 +280,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
   }
   __syncthreads();
-  TD *df = mpg_field_dst(tab, dst, f, (int64_t)nlev * P) + p0;
+  TD *df = mpg_field_dst(tab, dst, f, (int64_t)nlev * ld) + p0;
   if (p0 + lane < P)
     for (int k = wave; k < nlev; k += 4) {
-      TD *row = df + (int64_t)k * P;   // wave-uniform.  st_mode: the "lf_rows_store" knob -- 0: float64 results per lane (+22 % on planes 8 / 24 bytes off a line), float32 per level
+      TD *row = df + (int64_t)k * ld;   // wave-uniform.  st_mode: the "lf_rows_store" knob -- 0: float64 results per lane (+22 % on planes 8 / 24 bytes off a line), float32 per level
       // (their 256-byte runs hold one whole line at most: per lane and per level measured equal); 1 plain, 2 non-temporal, 3 per lane (A/B)
       const bool per_lane = st_mode == 3 || (st_mode == 0 && sizeof(TD) == 8);
       stream_store(tile[k * 65 + lane], row + lane, per_lane ? stream_lane_full(row + lane, (unsigned)lane * (unsigned)sizeof(TD)) : st_mode ? st_mode == 2 : stream_nt(row));
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
                                                          const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                          const double *__restrict__ val, const TS *__restrict__ src,
                                                          TD *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk,
-                                                         double scale, double offset, int sbe, int dbe, FieldTab tab) {
+                                                         double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
   constexpr bool lev_fast = LEVF;   // the layout is part of the instantiation: no per-level branch on it (round-5 review, item 6)
   const Swz zs = make_swz(sbe), zd = make_swz(dbe);
   unsigned blk = blockIdx.x % nblk;
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
   int64_t p = (int64_t)blk * 256 + threadIdx.x;
   if (p >= P) return;
   const TS *sf = mpg_field_src(tab, src, fld, (int64_t)nlev * nsrc);
-  TD *df = mpg_field_dst(tab, dst, fld, (int64_t)nlev * P);
+  TD *df = mpg_field_dst(tab, dst, fld, (int64_t)nlev * ld);
   offset = mpg_field_off(tab, fld, offset);
   if constexpr (NNZ == 0) {
     for (int k = 0; k < nlev; ++k) {
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
         int32_t c = col[q];
         acc = fma(val[q], (double)swz<SWZ>(lev_fast ? sf[(int64_t)c * nlev + k] : sf[(int64_t)k * nsrc + c], zs), acc);
       }
-      stream_store_lane(swz<SWZ>((TD)fma(acc, scale, offset), zd), df + (int64_t)k * P + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD));
+      stream_store_lane(swz<SWZ>((TD)fma(acc, scale, offset), zd), df + (int64_t)k * ld + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD));
     }
   } else {
     int32_t c[NNZ];
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
     // share one in-order counter on gfx950, so a load issued after a store cannot be consumed before that store has been
     // acknowledged -- with the loads in front, a step waits for its own data only (s_waitcnt vmcnt(2): the two stores stay
     // in flight).
-    auto put = [&](int k, const double *v) { stream_store_lane(swz<SWZ>((TD)fma(combine(v), scale, offset), zd), df + (int64_t)k * P + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD)); };
+    auto put = [&](int k, const double *v) { stream_store_lane(swz<SWZ>((TD)fma(combine(v), scale, offset), zd), df + (int64_t)k * ld + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD)); };
     double a0[NNZ], a1[NNZ];
     level(0, a0);
     level(nlev > 1 ? 1 : 0, a1);
@@ -389,7 +389,7 @@ static bool lf_rows_fits(const mpg_handle_s *h, size_t dst_size, int nlev) {
 
 template <typename TS, typename TD, bool SWZ>
 static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, int nfields, void *dst, double scale, double offset, int sbe,
-                        int dbe, hipStream_t s, const FieldTab &tab) {
+                        int dbe, hipStream_t s, const FieldTab &tab, int64_t ld) {
   int64_t P = h->n_dst;
   int lev_fast = layout == MPG_LAYOUT_LEV_FAST && nlev > 1;
   if (h->kind == MPG_KIND_FIXED && h->nnz_per_row == 3) {
@@ -398,7 +398,7 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
       const unsigned ntile = (unsigned)((P + 63) / 64);
       auto fn = k_apply3_lf_rows<TS, TD, sizeof(TS) == 4 ? 2 : 1, true, SWZ>;   // measured: unroll 2 for float32 rows, 1 for float64
       if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, P, h->n_src, nlev, ntile, scale, offset, sbe, dbe, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, tab);
+      fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, P, h->n_src, nlev, ntile, scale, offset, sbe, dbe, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, tab, ld);
     } else if (lev_fast) {
       size_t lds = sizeof(TD) * 65 * (size_t)nlev + sizeof(double) * 192 + sizeof(int32_t) * 192;
       if (lds > 160 * 1024) {
@@ -409,11 +409,11 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
       if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int ntxs = mpg_tile_ntx(h->nx_dst, 64), nty = h->ny_dst;
       fn<<<(unsigned)ntxs * nty * nfields, 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntxs, nty,
-                                                         scale, offset, sbe, dbe, tab);
+                                                         scale, offset, sbe, dbe, tab, ld);
     } else {
       int ntx = mpg_tile_ntx(h->nx_dst, 64), nty = (h->ny_dst + 7) / 8;
       k_apply3_cf_t<TS, TD, SWZ><<<(unsigned)ntx * nty * nfields, 256, 0, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst, h->ny_dst,
-                                                                              h->n_src, nlev, ntx, nty, scale, offset, sbe, dbe, tab);
+                                                                              h->n_src, nlev, ntx, nty, scale, offset, sbe, dbe, tab, ld);
     }
   } else {
     int nblk = (int)((P + 255) / 256);
@@ -425,7 +425,7 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
     auto fn = lev_fast ? (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, true> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, true> : k_apply_generic_t<TS, TD, SWZ, 4, true>))
                        : (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, false> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, false> : k_apply_generic_t<TS, TD, SWZ, 4, false>));
     fn<<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, h->rowptr.p, h->col.p, h->val.p, (const TS *)src, (TD *)dst, P, h->n_src, nlev,
-                                               nblk, scale, offset, sbe, dbe, tab);
+                                               nblk, scale, offset, sbe, dbe, tab, ld);
   }
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
@@ -433,30 +433,32 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
 
 // float64 rows in, float64 out, no epilogue: the level-fast row gather of mpg_regrid_dev (k_apply.hip).
 // -> MPG_ERR_UNSUPPORTED when the 32-bit row offsets or the LDS tile do not fit (the caller keeps its older kernel).
-int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s) {
+int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld) {
   const int64_t P = h->n_dst;
+  if (ld == 0) ld = P;
   if (!lf_rows_fits(h, sizeof(double), nlev)) return MPG_ERR_UNSUPPORTED;
   const size_t lds = lf_rows_lds(sizeof(double), nlev);
   const unsigned ntile = (unsigned)((P + 63) / 64);
   auto fn = k_apply3_lf_rows<double, double, 1, false, false>;
   if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, ntile, 1.0, 0.0, 0, 0, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, FieldTab());
+  fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, ntile, 1.0, 0.0, 0, 0, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, FieldTab(), ld);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }
 
 template <bool SWZ>
 static int launch_typed_types(mpg_handle_s *h, const void *src, int sf32, int layout, int nlev, int nfields, void *dst, int df32, double scale,
-                              double offset, int sbe, int dbe, hipStream_t s, const FieldTab &tab) {
-  if (sf32 && df32) return launch_typed<float, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  if (sf32) return launch_typed<float, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  if (df32) return launch_typed<double, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
-  return launch_typed<double, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab);
+                              double offset, int sbe, int dbe, hipStream_t s, const FieldTab &tab, int64_t ld) {
+  if (sf32 && df32) return launch_typed<float, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (sf32) return launch_typed<float, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (df32) return launch_typed<double, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  return launch_typed<double, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
 }
 
 int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
-                      double scale, double offset, hipStream_t s, const FieldTab &tab) {
+                      double scale, double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
   if (h->n_dst == 0 || nlev == 0 || nfields == 0) return MPG_SUCCESS;
+  if (ld == 0) ld = h->n_dst;
   const int sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
   const int sbe = (src_type & MPG_TYPE_BE) != 0, dbe = (dst_type & MPG_TYPE_BE) != 0;
   if (h->n_src == 0) {  // nothing mapped: the destination is the epilogue of 0.0
@@ -465,13 +467,13 @@ int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout
       return MPG_ERR_UNSUPPORTED;
     }
     if (tab.n) return MPG_ERR_UNSUPPORTED;   // (mpg_regrid_bundle_typed_dev serves such a handle field by field)
-    MPG_HIP(hipMemsetAsync(dst, 0, (df32 ? 4 : 8) * (size_t)h->n_dst * nlev * nfields, s));
-    return MPG_SUCCESS;
+    return mpg_zero_planes(dst, df32 ? 4 : 8, h->n_dst, (int64_t)nlev * nfields, ld, s);
   }
   const bool three = h->kind == MPG_KIND_FIXED && h->nnz_per_row == 3;
   const bool lev_fast = layout == MPG_LAYOUT_LEV_FAST && nlev > 1;
   const bool long_bundle = nlev * nfields >= MPG_STAGE_MIN_LEVELS;
-  if (three && nlev == 1 && tab.n > 1) {   // 2-D fields in separate arrays: the bundle's fields are walked like levels
+  if (three && nlev == 1 && tab.n > 1) {   // 2-D fields in separate arrays: the bundle's fields are walked like levels (one plane each, at
+                                           // tab.dst[f] + 0 * ld: the level stride cannot matter to k_apply3_cf_fields)
     const int ntx = mpg_tile_ntx(h->nx_dst, 64), nty = (h->ny_dst + 7) / 8;
     const unsigned nwg = (unsigned)ntx * nty;
 #define CF_FIELDS(TS, TD)                                                                                                                                        \
@@ -500,7 +502,7 @@ int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout
       if (!fits) staged = -2;
     }
     if (staged >= 0) {
-      rc = mpg_k_apply3_cfu(h, staged, src, sf32, nlev, nfields, dst, df32, true, scale, offset, s, tab);
+      rc = mpg_k_apply3_cfu(h, staged, src, sf32, nlev, nfields, dst, df32, true, scale, offset, s, tab, ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
   }
@@ -511,13 +513,13 @@ int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout
       if (long_bundle && (rc = mpg_lfu_auto(h, s, &lfv))) return rc;
     }
     if (lfv == MPG_LF_STAGED) {
-      rc = mpg_k_apply3_lfu_typed(h, src, src_type, nlev, nfields, dst, dst_type, scale, offset, s, tab);
+      rc = mpg_k_apply3_lfu_typed(h, src, src_type, nlev, nfields, dst, dst_type, scale, offset, s, tab, ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
   }
-  int rc = (sbe || dbe) ? launch_typed_types<true>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, sbe, dbe, s, tab)
-                        : launch_typed_types<false>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, 0, 0, s, tab);
-  if (rc == MPG_SUCCESS && h->n_pole) rc = mpg_k_pole_fix(h, src, src_type, layout, nlev, nfields, dst, dst_type, scale, offset, s, tab);
+  int rc = (sbe || dbe) ? launch_typed_types<true>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, sbe, dbe, s, tab, ld)
+                        : launch_typed_types<false>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, 0, 0, s, tab, ld);
+  if (rc == MPG_SUCCESS && h->n_pole) rc = mpg_k_pole_fix(h, src, src_type, layout, nlev, nfields, dst, dst_type, scale, offset, s, tab, ld);
   return rc;
 }
 

@@ -46,7 +46,8 @@ struct WindArgs {
   const double *w1, *w2;
   const double *cosa, *sina;    // [ny][nx] (ROT only)
   const double *um, *vm;        // [nlev][ny][nx]
-  void *u, *v;                  // [nlev][ny][nx+1], [nlev][ny+1][nx]
+  void *u, *v;                  // [nlev][ny][nx+1], [nlev][ny+1][nx]: level k of U / V starts at k * ldu / k * ldv elements
+  int64_t ld;                   // 0: each dense (ldu = ny * (nx+1), ldv = (ny+1) * nx); else a pitched caller's one stride for both
   double *um_rot, *vm_rot;      // optional: the rotated mass winds [nlev][ny][nx] (never the inputs themselves)
   int nx, ny, nlev, periodic, mode, ntx;
   double scale, offset;
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(WD_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   uint32_t pu[WD_RPT], pv[WD_RPT];     // byte offset inside a level plane of U / V; MPG_BUF_NONE: nothing to store in the level loop
   const int nxu = nx + 1;
   const int64_t P1 = (int64_t)nxu * ny, P2 = (int64_t)nx * (ny + 1);
+  const int64_t ldu = a.ld ? a.ld : P1, ldv = a.ld ? a.ld : P2;
   auto locate = [&](int32_t c, bool &far) -> int {   // global CENTER index -> slot of the window
     const int cj = c / nx, ci = c - cj * nx;
     int lx = ci - wi0;
@@ -244,8 +246,8 @@ __global__ __launch_bounds__(WD_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         buf_store_lane(finish(acc, mapv[r]), ov, vplane, pv[r], lane_bytes);
       }
     }
-    uplane += P1;
-    vplane += P2;
+    uplane += ldu;
+    vplane += ldv;
   }
 
   // ---- points with a source outside the window: straight from global memory ---------------------------------
@@ -253,7 +255,7 @@ __global__ __launch_bounds__(WD_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 #pragma unroll
   for (int r = 0; r < WD_RPT; ++r) any_far = any_far || faru[r] || farv[r];
   if (!any_far) return;
-  auto far_point = [&](const int32_t *idx, int64_t P, int64_t p, const double *w4, bool want_v, TD *out) {
+  auto far_point = [&](const int32_t *idx, int64_t P, int64_t p, const double *w4, bool want_v, TD *out, int64_t ld) {
     int32_t c[4];
     double ca[4], sa[4], tn[4], dn[4];
 #pragma unroll
@@ -277,14 +279,14 @@ __global__ __launch_bounds__(WD_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         if constexpr (ROT) wd_rotate(uo, vo, ca[q], sa[q], tn[q], dn[q], un, vn);
         acc = fma(w4[q], want_v ? vn : un, acc);
       }
-      out[(int64_t)k * P + p] = finish(acc, true);
+      out[(int64_t)k * ld + p] = finish(acc, true);
     }
   };
 #pragma unroll
   for (int r = 0; r < WD_RPT; ++r) {
     const int j = j0 + wave + (WD_NT / 64) * r;
-    if (faru[r]) far_point(a.idx1, P1, (int64_t)j * nxu + (i0 + lane - (int)(((long long)j * nxu) % WD_A)), wu[r], false, (TD *)a.u);
-    if (farv[r]) far_point(a.idx2, P2, (int64_t)j * nx + (i0 + lane - (int)(((long long)j * nx) % WD_A)), wv[r], true, (TD *)a.v);
+    if (faru[r]) far_point(a.idx1, P1, (int64_t)j * nxu + (i0 + lane - (int)(((long long)j * nxu) % WD_A)), wu[r], false, (TD *)a.u, ldu);
+    if (farv[r]) far_point(a.idx2, P2, (int64_t)j * nx + (i0 + lane - (int)(((long long)j * nx) % WD_A)), wv[r], true, (TD *)a.v, ldv);
   }
 }
 
@@ -301,7 +303,7 @@ static int launch_wind(const WindArgs &a, bool rot, unsigned nwg, hipStream_t s)
 // produced); cosa / sina NULL: no rotation.  -> MPG_ERR_UNSUPPORTED when the handles are not such a pair (the caller
 // keeps the three-call chain).
 int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const double *um, const double *vm, int nlev,
-                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s) {
+                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s, int64_t ld) {
   int nx, ny;
   if (h2) {
     nx = h2->nx_dst;
@@ -334,6 +336,7 @@ int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa,
   a.vm = vm;
   a.u = u;
   a.v = v;
+  a.ld = ld;   // the level planes' descriptors stay per plane (u_bytes / v_bytes): the stride only moves their base
   a.um_rot = um_rot;
   a.vm_rot = vm_rot;
   a.nx = nx;
@@ -354,8 +357,8 @@ int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa,
   else rc = launch_wind<double, true>(a, rot, nwg, s);
   if (rc) return rc;
   // pole caps of a periodic grid: rewritten from the (unrotated) mass field exactly as after k_applyN
-  if (h1 && h1->n_pole && (rc = mpg_k_pole_fix(h1, um, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, u, dst_type, 1.0, 0.0, s))) return rc;
-  if (h2 && h2->n_pole && (rc = mpg_k_pole_fix(h2, vm, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, v, dst_type, 1.0, 0.0, s))) return rc;
+  if (h1 && h1->n_pole && (rc = mpg_k_pole_fix(h1, um, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, u, dst_type, 1.0, 0.0, s, FieldTab(), ld))) return rc;
+  if (h2 && h2->n_pole && (rc = mpg_k_pole_fix(h2, vm, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, v, dst_type, 1.0, 0.0, s, FieldTab(), ld))) return rc;
   return MPG_SUCCESS;
 }
 

@@ -921,36 +921,87 @@ int mpg_handle_release(mpg_handle h) {
 }
 
 // ---- Regrid ---------------------------------------------------------------------------------------
+// The destination level stride of the _pitched_ calls: 0 = dense (the plane size); otherwise at least the plane, and every byte of
+// nplanes planes of it must be addressable with 64-bit offsets (the kernels add k * ld to 64-bit plane bases; their buffer
+// descriptors cover one plane each, so no 32-bit range grows with the stride).  -> the stride to launch with in *out
+static int dst_stride(const char *who, int64_t plane, int64_t nplanes, int esz, int64_t ld, int64_t *out) {
+  if (ld == 0) ld = plane;
+  if (ld < plane) {
+    mpg_set_error("%s: dst_level_stride %lld is below the plane size %lld", who, (long long)ld, (long long)plane);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (ld > 0 && nplanes > 0 && nplanes > (INT64_MAX / esz) / ld) {
+    mpg_set_error("%s: %lld planes of stride %lld cannot be addressed", who, (long long)nplanes, (long long)ld);
+    return MPG_ERR_INVALID_ARG;
+  }
+  *out = ld;
+  return MPG_SUCCESS;
+}
+
+int mpg_dst_level_stride(int64_t plane_points, int dst_type, int64_t *ld) {   // pure arithmetic: no mpg_init needed
+  MPG_ARG(ld && plane_points >= 1, "mpg_dst_level_stride: NULL output or no points");
+  MPG_ARG(dst_type >= 0 && dst_type <= 3, "mpg_dst_level_stride: dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32, optionally | MPG_TYPE_BE");
+  const int64_t q = (dst_type & MPG_TYPE_F32) ? 32 : 16;   // elements per 128-byte line
+  MPG_ARG(plane_points <= INT64_MAX - q, "mpg_dst_level_stride: plane too large");
+  *ld = (plane_points + q - 1) / q * q;
+  return MPG_SUCCESS;
+}
+
 int mpg_regrid_dev(mpg_handle h, const double *src_dev, int src_layout, int nlev, int nfields, double *dst_dev, void *hip_stream) {
+  return mpg_regrid_pitched_dev(h, src_dev, src_layout, nlev, nfields, dst_dev, 0, hip_stream);
+}
+
+int mpg_regrid_pitched_dev(mpg_handle h, const double *src_dev, int src_layout, int nlev, int nfields, double *dst_dev, int64_t dst_level_stride,
+                           void *hip_stream) {
   MPG_CHECK_INIT();
   MPG_ARG(h && dst_dev && (src_dev || h->n_src == 0), "mpg_regrid: NULL argument");
   MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid: nlev and nfields must be >= 1");
   MPG_ARG(src_layout == MPG_LAYOUT_CELL_FAST || src_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid: bad src_layout");
-  return mpg_k_apply(h, src_dev, src_layout, nlev, nfields, dst_dev, (hipStream_t)hip_stream);
+  int64_t ld;
+  int rc = dst_stride("mpg_regrid", h->n_dst, (int64_t)nlev * nfields, 8, dst_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_apply(h, src_dev, src_layout, nlev, nfields, dst_dev, (hipStream_t)hip_stream, ld);
 }
 
 int mpg_regrid_typed_dev(mpg_handle h, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev,
                          int dst_type, double scale, double offset, void *hip_stream) {
+  return mpg_regrid_typed_pitched_dev(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, scale, offset, 0, hip_stream);
+}
+
+int mpg_regrid_typed_pitched_dev(mpg_handle h, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev,
+                                 int dst_type, double scale, double offset, int64_t dst_level_stride, void *hip_stream) {
   MPG_CHECK_INIT();
   MPG_ARG(h && dst_dev && (src_dev || h->n_src == 0), "mpg_regrid_typed: NULL argument");
   MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_typed: nlev and nfields must be >= 1");
   MPG_ARG(src_layout == MPG_LAYOUT_CELL_FAST || src_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_typed: bad src_layout");
   MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_typed: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32, optionally | MPG_TYPE_BE");
-  return mpg_k_apply_typed(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
+  int64_t ld;
+  int rc = dst_stride("mpg_regrid_typed", h->n_dst, (int64_t)nlev * nfields, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_apply_typed(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream, FieldTab(), ld);
 }
 
 int mpg_regrid_bundle_typed_dev(mpg_handle h, int nfields, const void *const *src_dev, int src_type, int src_layout, int nlev,
                                 void *const *dst_dev, int dst_type, double scale, const double *offsets, void *hip_stream) {
+  return mpg_regrid_bundle_typed_pitched_dev(h, nfields, src_dev, src_type, src_layout, nlev, dst_dev, dst_type, scale, offsets, 0, hip_stream);
+}
+
+int mpg_regrid_bundle_typed_pitched_dev(mpg_handle h, int nfields, const void *const *src_dev, int src_type, int src_layout, int nlev,
+                                        void *const *dst_dev, int dst_type, double scale, const double *offsets, int64_t dst_level_stride,
+                                        void *hip_stream) {
   MPG_CHECK_INIT();
   MPG_ARG(h && src_dev && dst_dev, "mpg_regrid_bundle_typed: NULL argument");
   MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_bundle_typed: nlev and nfields must be >= 1");
   MPG_ARG(src_layout == MPG_LAYOUT_CELL_FAST || src_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_bundle_typed: bad src_layout");
   MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_bundle_typed: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32, optionally | MPG_TYPE_BE");
   for (int f = 0; f < nfields; ++f) MPG_ARG(dst_dev[f] && (src_dev[f] || h->n_src == 0), "mpg_regrid_bundle_typed: NULL field pointer");
+  int64_t ld;   // every field is its own array of nlev planes
+  int rc = dst_stride("mpg_regrid_bundle_typed", h->n_dst, nlev, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (nfields == 1 || h->n_src == 0 || h->n_dst == 0) {   // nothing to share between fields: the plain call, field by field
     for (int f = 0; f < nfields; ++f) {
-      int rc = mpg_k_apply_typed(h, src_dev[f], src_type, src_layout, nlev, 1, dst_dev[f], dst_type, scale, offsets ? offsets[f] : 0.0, s);
+      rc = mpg_k_apply_typed(h, src_dev[f], src_type, src_layout, nlev, 1, dst_dev[f], dst_type, scale, offsets ? offsets[f] : 0.0, s, FieldTab(), ld);
       if (rc) return rc;
     }
     return MPG_SUCCESS;
@@ -963,7 +1014,7 @@ int mpg_regrid_bundle_typed_dev(mpg_handle h, int nfields, const void *const *sr
       tab.dst[k] = dst_dev[f0 + k];
       tab.off[k] = offsets ? offsets[f0 + k] : 0.0;
     }
-    int rc = mpg_k_apply_typed(h, nullptr, src_type, src_layout, nlev, tab.n, nullptr, dst_type, scale, 0.0, s, tab);
+    rc = mpg_k_apply_typed(h, nullptr, src_type, src_layout, nlev, tab.n, nullptr, dst_type, scale, 0.0, s, tab, ld);
     if (rc) return rc;
   }
   return MPG_SUCCESS;
@@ -989,6 +1040,13 @@ int mpg_rotate_winds_dev(int64_t npts, int nlev, const double *cosa_dev, const d
 int mpg_wind_destagger_dev(mpg_handle h1, mpg_handle h2, const double *cosa_dev, const double *sina_dev, const double *umass_dev,
                            const double *vmass_dev, int nlev, void *u_dev, void *v_dev, int dst_type, double *umass_rot_dev, double *vmass_rot_dev,
                            void *hip_stream) {
+  return mpg_wind_destagger_pitched_dev(h1, h2, cosa_dev, sina_dev, umass_dev, vmass_dev, nlev, u_dev, v_dev, dst_type, umass_rot_dev, vmass_rot_dev, 0,
+                                        hip_stream);
+}
+
+int mpg_wind_destagger_pitched_dev(mpg_handle h1, mpg_handle h2, const double *cosa_dev, const double *sina_dev, const double *umass_dev,
+                                   const double *vmass_dev, int nlev, void *u_dev, void *v_dev, int dst_type, double *umass_rot_dev,
+                                   double *vmass_rot_dev, int64_t dst_level_stride, void *hip_stream) {
   MPG_CHECK_INIT();
   MPG_ARG(h1 || h2, "mpg_wind_destagger: no handle");
   MPG_ARG((cosa_dev == nullptr) == (sina_dev == nullptr), "mpg_wind_destagger: cosa and sina come together");
@@ -1001,8 +1059,14 @@ int mpg_wind_destagger_dev(mpg_handle h1, mpg_handle h2, const double *cosa_dev,
   MPG_ARG((!umass_rot_dev || umass_rot_dev != umass_dev) && (!vmass_rot_dev || vmass_rot_dev != vmass_dev),
           "mpg_wind_destagger: the rotated mass winds cannot replace the inputs (neighbouring tiles read them)");
   MPG_ARG(rot || (!umass_rot_dev && !vmass_rot_dev), "mpg_wind_destagger: rotated mass winds asked for without a rotation");
-  int rc = mpg_k_wind_destagger(h1, h2, cosa_dev, sina_dev, umass_dev, vmass_dev, nlev, u_dev, v_dev, dst_type, umass_rot_dev, vmass_rot_dev,
-                                (hipStream_t)hip_stream);
+  int rc;
+  if (dst_level_stride != 0) {   // one stride for U [ny][nx+1] and V [ny+1][nx]: at least the plane of each component produced
+    const int64_t plane = std::max(h1 ? h1->n_dst : 0, h2 ? h2->n_dst : 0);
+    int64_t ld;
+    if ((rc = dst_stride("mpg_wind_destagger", plane, nlev, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld))) return rc;
+  }
+  rc = mpg_k_wind_destagger(h1, h2, cosa_dev, sina_dev, umass_dev, vmass_dev, nlev, u_dev, v_dev, dst_type, umass_rot_dev, vmass_rot_dev,
+                            (hipStream_t)hip_stream, dst_level_stride);
   if (rc == MPG_ERR_UNSUPPORTED) mpg_set_error("mpg_wind_destagger: the handles are not the CENTER -> EDGE1 / EDGE2 pair of one grid");
   return rc;
 }

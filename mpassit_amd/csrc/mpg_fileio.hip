@@ -85,8 +85,33 @@ int xfer_full(int fd, bool writing, char *p, size_t n, off_t off) {
   return 0;
 }
 
-// error codes of a worker: 0 ok, 1 file I/O, 2 HIP
-int transfer(Lane &L, int device, int fd, bool to_dev, int64_t offset, int64_t nbytes, char *dev) {
+// Device side of a chunk written to the file: bytes [lo, lo + n) of the DENSE range, gathered from planes of `plane` bytes that lie
+// `pitch` bytes apart in device memory (pitch == plane: one contiguous copy) -- the partial planes at the chunk's two ends one copy
+// each, the whole planes between them one 2-D copy.
+hipError_t gather_d2h(char *host, const char *dev, size_t lo, size_t n, size_t plane, size_t pitch, hipStream_t s) {
+  if (pitch == plane) return hipMemcpyAsync(host, dev + lo, n, hipMemcpyDeviceToHost, s);
+  size_t k = lo / plane, in = lo % plane;
+  hipError_t e = hipSuccess;
+  if (in) {
+    const size_t m = n < plane - in ? n : plane - in;
+    if ((e = hipMemcpyAsync(host, dev + k * pitch + in, m, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    host += m;
+    n -= m;
+    ++k;
+  }
+  const size_t whole = n / plane;
+  if (whole) {
+    if ((e = hipMemcpy2DAsync(host, plane, dev + k * pitch, pitch, plane, whole, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    host += whole * plane;
+    n -= whole * plane;
+    k += whole;
+  }
+  if (n) e = hipMemcpyAsync(host, dev + k * pitch, n, hipMemcpyDeviceToHost, s);
+  return e;
+}
+
+// error codes of a worker: 0 ok, 1 file I/O, 2 HIP.  plane / pitch: see gather_d2h (to_dev: always dense)
+int transfer(Lane &L, int device, int fd, bool to_dev, int64_t offset, int64_t nbytes, char *dev, size_t plane, size_t pitch) {
   const size_t chunk = CHUNK;
   const int64_t nchunk = (nbytes + (int64_t)chunk - 1) / (int64_t)chunk;
   std::atomic<int64_t> next(0);
@@ -109,7 +134,7 @@ int transfer(Lane &L, int device, int fd, bool to_dev, int64_t offset, int64_t n
             hipEventRecord(L.done[t][b], L.stream[t]) != hipSuccess) { err = 2; break; }
         used[b] = true;
       } else {
-        if (hipMemcpyAsync(L.buf[t][b], dev + lo, n, hipMemcpyDeviceToHost, L.stream[t]) != hipSuccess ||
+        if (gather_d2h((char *)L.buf[t][b], dev, lo, n, plane, pitch, L.stream[t]) != hipSuccess ||
             hipStreamSynchronize(L.stream[t]) != hipSuccess) { err = 2; break; }
         if (xfer_full(fd, true, (char *)L.buf[t][b], n, (off_t)(offset + (int64_t)lo))) { err = 1; break; }
       }
@@ -124,7 +149,8 @@ int transfer(Lane &L, int device, int fd, bool to_dev, int64_t offset, int64_t n
   return err.load();
 }
 
-int run(bool to_dev, const char *path, int64_t offset, int64_t nbytes, void *dev, hipStream_t s) {
+int run(bool to_dev, const char *path, int64_t offset, int64_t nbytes, void *dev, hipStream_t s, int64_t plane = 0, int64_t pitch = 0) {
+  const char *who = to_dev ? "mpg_file_to_dev" : plane ? "mpg_dev_to_file_planes" : "mpg_dev_to_file";   // (the caller's name in errors)
   if (nbytes == 0) return MPG_SUCCESS;
   Lane &L = to_dev ? g_read : g_write;
   std::lock_guard<std::mutex> lock(L.mu);
@@ -133,20 +159,21 @@ int run(bool to_dev, const char *path, int64_t offset, int64_t nbytes, void *dev
   MPG_HIP(hipStreamSynchronize(s));  // to_dev: earlier readers of the buffer are done; to file: its producer is
   const int fd = open(path, to_dev ? O_RDONLY : O_WRONLY);
   if (fd < 0) {
-    mpg_set_error("%s: cannot open %s", to_dev ? "mpg_file_to_dev" : "mpg_dev_to_file", path);
+    mpg_set_error("%s: cannot open %s", who, path);
     return MPG_ERR_INVALID_ARG;
   }
   int device = 0;
   (void)hipGetDevice(&device);
-  const int e = transfer(L, device, fd, to_dev, offset, nbytes, (char *)dev);
+  if (plane == 0) plane = pitch = nbytes;
+  const int e = transfer(L, device, fd, to_dev, offset, nbytes, (char *)dev, (size_t)plane, (size_t)pitch);
   close(fd);
   if (e == 1) {
-    mpg_set_error("%s: short %s on %s (offset %lld, %lld bytes)", to_dev ? "mpg_file_to_dev" : "mpg_dev_to_file", to_dev ? "read" : "write", path,
+    mpg_set_error("%s: short %s on %s (offset %lld, %lld bytes)", who, to_dev ? "read" : "write", path,
                   (long long)offset, (long long)nbytes);
     return MPG_ERR_INVALID_ARG;
   }
   if (e == 2) {
-    mpg_set_error("%s: HIP transfer failed", to_dev ? "mpg_file_to_dev" : "mpg_dev_to_file");
+    mpg_set_error("%s: HIP transfer failed", who);
     return MPG_ERR_HIP;
   }
   return MPG_SUCCESS;
@@ -169,4 +196,16 @@ extern "C" int mpg_dev_to_file(const char *path, int64_t offset, int64_t nbytes,
   MPG_CHECK_INIT();
   MPG_ARG(path && offset >= 0 && nbytes >= 0 && (src_dev || nbytes == 0), "mpg_dev_to_file: bad argument");
   return run(false, path, offset, nbytes, (void *)src_dev, (hipStream_t)hip_stream);
+}
+
+// Pitched level planes (mpg_regrid_*_pitched_dev results) -> one dense byte range of the file: the chunks are cut over the dense
+// range as for mpg_dev_to_file, so a large plane is still written by every writer thread, and each chunk is gathered from the planes.
+extern "C" int mpg_dev_to_file_planes(const char *path, int64_t offset, int64_t plane_bytes, int64_t nplanes, const void *src_dev,
+                                      int64_t src_pitch_bytes, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(path && offset >= 0 && plane_bytes >= 0 && nplanes >= 0 && src_pitch_bytes >= plane_bytes, "mpg_dev_to_file_planes: bad argument");
+  MPG_ARG(src_dev || plane_bytes == 0 || nplanes == 0, "mpg_dev_to_file_planes: NULL source");
+  if (plane_bytes == 0 || nplanes == 0) return MPG_SUCCESS;
+  MPG_ARG(nplanes <= INT64_MAX / src_pitch_bytes && offset <= INT64_MAX - plane_bytes * nplanes, "mpg_dev_to_file_planes: range too large");
+  return run(false, path, offset, plane_bytes * nplanes, (void *)src_dev, (hipStream_t)hip_stream, plane_bytes, src_pitch_bytes);
 }

@@ -365,7 +365,12 @@ int mpg_k_store_nearest(mpg_mesh_s *m, mpg_grid_s *g, int stagger, mpg_handle_s 
 int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s);
 int mpg_k_store_grid_bilinear(mpg_grid_s *g, int dst_stagger, mpg_handle_s *h, hipStream_t s);
 int mpg_k_build_bvh(mpg_mesh_s *m, hipStream_t s, bool whole = true);
-int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nfields, double *dst, hipStream_t s);
+// Destination level stride `ld` of the Regrid launchers below: level plane k of field f starts at (f * nlev + k) * ld elements (a bundle
+// given as a FieldTab: plane k of field f at tab.dst[f] + k * ld).  0 = dense (ld = n_dst); elements [n_dst, ld) of a plane are
+// never written.  The API entry points check ld >= n_dst and that nfields * nlev * ld bytes are addressable.
+int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
+// nplanes planes of P elements of esz bytes, ld elements apart, set to zero (a handle that maps nothing); the pad stays as it is
+int mpg_zero_planes(void *dst, size_t esz, int64_t P, int64_t nplanes, int64_t ld, hipStream_t s);
 // The fields of a bundle as separate allocations (mpg_regrid_bundle_typed_dev: an ESMF field bundle holds separate arrays): up
 // to MPG_TAB_MAX device pointers on either side and one epilogue offset per field, handed to the Regrid kernels BY VALUE -- in
 // their argument block, so there is no table in device memory to allocate, to keep alive or to race on, and a launch can be
@@ -391,7 +396,7 @@ __device__ __forceinline__ TD *mpg_field_dst(const FieldTab &t, TD *dst, int f, 
 __device__ __forceinline__ double mpg_field_off(const FieldTab &t, int f, double offset) { return t.n ? t.off[f] : offset; }
 // src_type / dst_type below: MPG_TYPE_F64 / MPG_TYPE_F32, optionally | MPG_TYPE_BE (include/mpassit_amd.h)
 int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
-                      double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab());
+                      double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
 // "lf_variant" numbering of the level-fast 3-point Regrid
 enum { MPG_LF_ROWS = 0, MPG_LF_STAGED = 1, MPG_LF_ROWTILES = 2 };
 #ifndef MPG_LF_STAGED_DEFAULT
@@ -403,11 +408,11 @@ enum { MPG_LF_ROWS = 0, MPG_LF_STAGED = 1, MPG_LF_ROWTILES = 2 };
 #define MPG_STAGE_MIN_LEVELS 8
 int mpg_cfu_num_variants();
 int mpg_k_apply3_cfu(mpg_handle_s *h, int variant, const void *src, int src_f32, int nlev, int nfields, void *dst, int dst_f32, bool epi,
-                     double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab());
-int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s);
+                     double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
+int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
 int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
-                           double offset, hipStream_t s, const FieldTab &tab = FieldTab());
-int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s);
+                           double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
+int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
 int mpg_a3_staged();  // current "a3_staged" knob
 int mpg_lf_variant(); // current "lf_variant" knob
 int mpg_lfu_build_shape(mpg_handle_s *h, int txu, int tyu, hipStream_t s);  // tile lists for txu x tyu-point tiles (cached per handle)
@@ -415,7 +420,7 @@ int mpg_cfu_fits(mpg_handle_s *h, int variant, hipStream_t s, int *fits);
 int mpg_cfu_auto(mpg_handle_s *h, hipStream_t s, int *cfu_variant);  // -> variant index or -1 (use k_apply3_cf)
 int mpg_lfu_auto(mpg_handle_s *h, hipStream_t s, int *lf_variant);   // -> MPG_LF_ROWS or the staged default
 int mpg_k_pole_fix(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
-                   double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab());
+                   double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);
@@ -423,7 +428,7 @@ int mpg_k_post_ptop(const double *src, int nlev, int64_t P, double *ptop_host, h
 int mpg_k_post_ptop_parts(const double *src, int nlev, int64_t P, double *vmax_host, double *candmin_host, int *has_cand_host, hipStream_t s);
 int mpg_k_rotate(int64_t npts, int nlev, const double *cosa, const double *sina, double *u, double *v, hipStream_t s);
 int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const double *um, const double *vm, int nlev,
-                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s);   // k_wind.hip
+                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s, int64_t ld = 0);   // k_wind.hip; ld: U's and V's (0: each dense)
 int mpg_k_pack(const double *src, int64_t n_src, int nlev, const int32_t *ids, int64_t n_ids, double *dst, hipStream_t s);
 int mpg_k_tune(const char *key, int value);
 int mpg_store_boxes();         // "store_boxes" knob: 1 (default) index-space candidate boxes on projection-built grids, 0 pyramid walk only

@@ -5,6 +5,7 @@
 module model_data
   use, intrinsic :: iso_c_binding
   use program_setup, only: dp
+  use mpg, only: mpg_dst_level_stride, MPG_TYPE_F32, MPG_TYPE_BE, MPG_SUCCESS
   implicit none
   public
   type field_t
@@ -22,6 +23,8 @@ module model_data
     !> the device buffer holds the file's big-endian bytes as they are (NetCDF classic): the Regrid reads / writes them so
     logical :: src_is_be = .false., dst_is_be = .false.
     integer(c_int64_t) :: n_dst_elems = 0
+    !> level stride of dst_dev in elements: 0 = dense; else the planes start dst_ld apart, each on a 128-byte line (pitched_ld)
+    integer(c_int64_t) :: dst_ld = 0
   end type field_t
   type bundle_t
     integer :: n = 0
@@ -44,8 +47,32 @@ module model_data
   !> device flow: the source window of this image (mpg_mesh_set_source_window) -- the cell / vertex ids [win0, win0 + winn)
   !! its target rows reference; only those rows of every variable are read from the input files.  winn < 0: whole mesh
   integer(c_int64_t) :: win0_cell = 0, winn_cell = -1, win0_vert = 0, winn_vert = -1
+  !> device flow: float32 big-endian results whose only reader is the file writer (put_dev) get level planes on whole 128-byte lines
+  !! (mpg_dst_level_stride); MPASSIT_DST_PITCH=0 in the environment keeps them dense, =1 pitches them (A/B runs: profiles/r07_dst_pitch.md)
+  integer, parameter :: DST_PITCH_DEFAULT = 1
+  integer :: dst_pitch = -1
 
 contains
+
+  !> the level stride for float32 big-endian results of n_dst points per level: 0 (dense) when pitching is off
+  integer(c_int64_t) function pitched_ld(n_dst)
+    integer(c_int64_t), intent(in) :: n_dst
+    character(len=8) :: buf
+    integer :: st
+    if (dst_pitch < 0) then
+      call get_environment_variable("MPASSIT_DST_PITCH", buf, status=st)
+      dst_pitch = DST_PITCH_DEFAULT
+      if (st == 0 .and. trim(buf) == '0') dst_pitch = 0
+      if (st == 0 .and. trim(buf) == '1') dst_pitch = 1
+    end if
+    pitched_ld = 0
+    if (dst_pitch == 0 .or. n_dst < 1) return
+    if (mpg_dst_level_stride(n_dst, MPG_TYPE_F32 + MPG_TYPE_BE, pitched_ld) /= MPG_SUCCESS) pitched_ld = 0
+    if (pitched_ld > n_dst .and. dst_pitch == 1) then      ! said once: the run pads level planes (tests look for it)
+      print *, "- FLOAT32 RESULTS ON PITCHED LEVEL PLANES (128-BYTE LINES)"
+      dst_pitch = 2
+    end if
+  end function pitched_ld
 
   !> fields the host still works on in float64 after the Regrid: rotated winds (interp.F90:138-140,291-293),
   !! PHB (Z_C and PHB*9.81, write_data.F90:1406-1418), P_HYD (P_TOP, :1362-1371)
@@ -69,7 +96,7 @@ contains
     if (allocated(a%dst)) call move_alloc(a%dst, b%dst)
     if (allocated(a%dst4)) call move_alloc(a%dst4, b%dst4)
     b%src_dev = a%src_dev; b%dst_dev = a%dst_dev; a%src_dev = c_null_ptr; a%dst_dev = c_null_ptr
-    b%src_is_f32 = a%src_is_f32; b%dst_is_f32 = a%dst_is_f32; b%n_dst_elems = a%n_dst_elems
+    b%src_is_f32 = a%src_is_f32; b%dst_is_f32 = a%dst_is_f32; b%n_dst_elems = a%n_dst_elems; b%dst_ld = a%dst_ld
     b%src_is_be = a%src_is_be; b%dst_is_be = a%dst_is_be
   end subroutine move_field
 end module model_data
@@ -212,7 +239,10 @@ contains
       f%dst_is_f32 = .not. keeps_r8(f)
       f%dst_is_be = f%dst_is_f32
       f%n_dst_elems = n_dst*f%nlev
-      call mpg_check(mpg_dev_alloc(f%n_dst_elems*merge(4, 8, f%dst_is_f32), f%dst_dev), "IN dev_alloc "//trim(f%name))
+      f%dst_ld = 0
+      if (f%dst_is_f32) f%dst_ld = pitched_ld(n_dst)   ! read only by put_dev: planes on whole lines
+      call mpg_check(mpg_dev_alloc(merge(f%dst_ld*f%nlev, f%n_dst_elems, f%dst_ld > 0)*merge(4, 8, f%dst_is_f32), f%dst_dev), &
+                     "IN dev_alloc "//trim(f%name))
     end do
     done = .false.
     do i = 1, b%n
@@ -232,9 +262,10 @@ contains
       end do
       layout = MPG_LAYOUT_LEV_FAST
       if (f%nlev == 1) layout = MPG_LAYOUT_CELL_FAST
-      call mpg_check(mpg_regrid_bundle_typed_dev(rh, int(ng, c_int), sp, elem_type(f%src_is_f32, f%src_is_be), layout, int(f%nlev, c_int), &
-                                                 dp, elem_type(f%dst_is_f32, f%dst_is_be), 1.0_c_double, offs, c_null_ptr), &
-                     "IN FieldBundleRegrid "//trim(f%name))
+      ! (a group shares the handle and the destination type, hence the level stride)
+      call mpg_check(mpg_regrid_bundle_typed_pitched_dev(rh, int(ng, c_int), sp, elem_type(f%src_is_f32, f%src_is_be), layout, &
+                                                         int(f%nlev, c_int), dp, elem_type(f%dst_is_f32, f%dst_is_be), 1.0_c_double, offs, &
+                                                         f%dst_ld, c_null_ptr), "IN FieldBundleRegrid "//trim(f%name))
     end do
     do i = 1, b%n                                   ! the sources are not needed again
       call mpg_check(mpg_dev_free(b%f(i)%src_dev), "IN dev_free")
@@ -259,11 +290,14 @@ contains
       f%dst_is_f32 = .not. keeps_r8(f)
       f%dst_is_be = f%dst_is_f32                 ! NF90_FLOAT results go straight to the file: produced as the file stores them
       f%n_dst_elems = n_dst*f%nlev
-      call mpg_check(mpg_dev_alloc(f%n_dst_elems*merge(4, 8, f%dst_is_f32), f%dst_dev), "IN dev_alloc "//trim(f%name))
+      f%dst_ld = 0
+      if (f%dst_is_f32) f%dst_ld = pitched_ld(n_dst)   ! read only by put_dev: planes on whole lines
+      call mpg_check(mpg_dev_alloc(merge(f%dst_ld*f%nlev, f%n_dst_elems, f%dst_ld > 0)*merge(4, 8, f%dst_is_f32), f%dst_dev), &
+                     "IN dev_alloc "//trim(f%name))
       offset = 0.0_c_double
       if (f%dst_is_f32 .and. wrf_mod_vars .and. trim(f%tname) == 'T') offset = -300.0_c_double
-      call mpg_check(mpg_regrid_typed_dev(rh, f%src_dev, elem_type(f%src_is_f32, f%src_is_be), layout, int(f%nlev, c_int), 1_c_int, &
-                                          f%dst_dev, elem_type(f%dst_is_f32, f%dst_is_be), 1.0_c_double, offset, c_null_ptr), &
+      call mpg_check(mpg_regrid_typed_pitched_dev(rh, f%src_dev, elem_type(f%src_is_f32, f%src_is_be), layout, int(f%nlev, c_int), 1_c_int, &
+                                                  f%dst_dev, elem_type(f%dst_is_f32, f%dst_is_be), 1.0_c_double, offset, f%dst_ld, c_null_ptr), &
                      "IN FieldRegrid "//trim(f%name))
       call mpg_check(mpg_dev_free(f%src_dev), "IN dev_free")      ! the source is not needed again
       f%src_dev = c_null_ptr
@@ -409,7 +443,7 @@ contains
   !! the three calls.  .false.: the library does not take this pair of handles -- nothing has been done.
   logical function wind_chain_fused()
     type(c_ptr) :: rh_u, rh_v, ca, sa
-    integer(c_int64_t) :: n_src, n_dst, nnz, npts
+    integer(c_int64_t) :: n_src, n_dst, nnz, npts, ld, n_u, n_v
     integer(c_int) :: nxd, nyd, npr, rc, nlev
     logical :: rot
     wind_chain_fused = .false.
@@ -434,20 +468,23 @@ contains
       call rotang_on_device()
       ca = cosa_dev; sa = sina_dev
     end if
+    ! U and V go only to the file (put_dev): one level stride for both, on whole lines for the larger plane
+    n_u = 0; n_v = 0
+    if (do_u_interp == 1) call mpg_check(mpg_handle_info(rh_u, n_src, n_u, nxd, nyd, npr, nnz), "IN HandleInfo")
+    if (do_v_interp == 1) call mpg_check(mpg_handle_info(rh_v, n_src, n_v, nxd, nyd, npr, nnz), "IN HandleInfo")
+    ld = pitched_ld(max(n_u, n_v))
     if (do_u_interp == 1) then
-      call mpg_check(mpg_handle_info(rh_u, n_src, n_dst, nxd, nyd, npr, nnz), "IN HandleInfo")
       if (c_associated(u_field%dst_dev)) call mpg_check(mpg_dev_free(u_field%dst_dev), "IN dev_free")
-      u_field%dst_is_f32 = .true.; u_field%dst_is_be = .true.; u_field%n_dst_elems = n_dst*nlev
-      call mpg_check(mpg_dev_alloc(u_field%n_dst_elems*4, u_field%dst_dev), "IN dev_alloc")
+      u_field%dst_is_f32 = .true.; u_field%dst_is_be = .true.; u_field%n_dst_elems = n_u*nlev; u_field%dst_ld = ld
+      call mpg_check(mpg_dev_alloc(merge(ld*nlev, u_field%n_dst_elems, ld > 0)*4, u_field%dst_dev), "IN dev_alloc")
     end if
     if (do_v_interp == 1) then
-      call mpg_check(mpg_handle_info(rh_v, n_src, n_dst, nxd, nyd, npr, nnz), "IN HandleInfo")
       if (c_associated(v_field%dst_dev)) call mpg_check(mpg_dev_free(v_field%dst_dev), "IN dev_free")
-      v_field%dst_is_f32 = .true.; v_field%dst_is_be = .true.; v_field%n_dst_elems = n_dst*nlev
-      call mpg_check(mpg_dev_alloc(v_field%n_dst_elems*4, v_field%dst_dev), "IN dev_alloc")
+      v_field%dst_is_f32 = .true.; v_field%dst_is_be = .true.; v_field%n_dst_elems = n_v*nlev; v_field%dst_ld = ld
+      call mpg_check(mpg_dev_alloc(merge(ld*nlev, v_field%n_dst_elems, ld > 0)*4, v_field%dst_dev), "IN dev_alloc")
     end if
-    rc = mpg_wind_destagger_dev(rh_u, rh_v, ca, sa, umass%dst_dev, vmass%dst_dev, nlev, u_field%dst_dev, v_field%dst_dev, &
-                                MPG_TYPE_F32 + MPG_TYPE_BE, c_null_ptr, c_null_ptr, c_null_ptr)
+    rc = mpg_wind_destagger_pitched_dev(rh_u, rh_v, ca, sa, umass%dst_dev, vmass%dst_dev, nlev, u_field%dst_dev, v_field%dst_dev, &
+                                        MPG_TYPE_F32 + MPG_TYPE_BE, c_null_ptr, c_null_ptr, ld, c_null_ptr)
     if (c_associated(rh_u)) call mpg_check(mpg_handle_release(rh_u), "IN FieldRegridRelease")
     if (c_associated(rh_v)) call mpg_check(mpg_handle_release(rh_v), "IN FieldRegridRelease")
     if (rc == MPG_ERR_UNSUPPORTED) return
@@ -524,7 +561,7 @@ contains
     dst%nlev = src%nlev
     if (dev_flow) then
       dst%dst_dev = src%dst_dev; src%dst_dev = c_null_ptr
-      dst%dst_is_f32 = src%dst_is_f32; dst%dst_is_be = src%dst_is_be; dst%n_dst_elems = src%n_dst_elems
+      dst%dst_is_f32 = src%dst_is_f32; dst%dst_is_be = src%dst_is_be; dst%n_dst_elems = src%n_dst_elems; dst%dst_ld = src%dst_ld
       return
     end if
     call move_alloc(src%dst, dst%dst)
@@ -543,7 +580,7 @@ contains
     if (dev_flow) then
       if (c_associated(stag%dst_dev)) call mpg_check(mpg_dev_free(stag%dst_dev), "IN dev_free")
       stag%dst_is_f32 = .true.; stag%dst_is_be = .true.
-      stag%n_dst_elems = n_dst*mass%nlev
+      stag%n_dst_elems = n_dst*mass%nlev; stag%dst_ld = 0
       call mpg_check(mpg_dev_alloc(stag%n_dst_elems*4, stag%dst_dev), "IN dev_alloc")
       call mpg_check(mpg_regrid_typed_dev(rh, mass%dst_dev, elem_type(mass%dst_is_f32, mass%dst_is_be), MPG_LAYOUT_CELL_FAST, &
                                           int(mass%nlev, c_int), 1_c_int, stag%dst_dev, MPG_TYPE_F32 + MPG_TYPE_BE, 1.0_c_double, 0.0_c_double, &

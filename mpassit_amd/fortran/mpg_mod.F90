@@ -196,6 +196,43 @@ module mpg
       real(c_double), intent(in) :: offsets(*)
       integer(c_int) :: rc
     end function mpg_regrid_bundle_typed_dev
+    !> pitched destinations (include/mpassit_amd.h): level planes dst_level_stride elements apart (0 = dense); the stride at which
+    !! every plane of dst_type starts on a 128-byte line
+    function mpg_dst_level_stride(plane_points, dst_type, ld) bind(C, name="mpg_dst_level_stride") result(rc)
+      import :: c_int, c_int64_t
+      integer(c_int64_t), value :: plane_points
+      integer(c_int), value :: dst_type
+      integer(c_int64_t), intent(out) :: ld
+      integer(c_int) :: rc
+    end function mpg_dst_level_stride
+    function mpg_regrid_pitched_dev(rh, src, src_layout, nlev, nfields, dst, dst_level_stride, stream) &
+      bind(C, name="mpg_regrid_pitched_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh, src, dst, stream
+      integer(c_int), value :: src_layout, nlev, nfields
+      integer(c_int64_t), value :: dst_level_stride
+      integer(c_int) :: rc
+    end function mpg_regrid_pitched_dev
+    function mpg_regrid_typed_pitched_dev(rh, src, src_f32, src_layout, nlev, nfields, dst, dst_f32, scale, offset, dst_level_stride, stream) &
+      bind(C, name="mpg_regrid_typed_pitched_dev") result(rc)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: rh, src, dst, stream
+      integer(c_int), value :: src_f32, src_layout, nlev, nfields, dst_f32
+      real(c_double), value :: scale, offset
+      integer(c_int64_t), value :: dst_level_stride
+      integer(c_int) :: rc
+    end function mpg_regrid_typed_pitched_dev
+    function mpg_regrid_bundle_typed_pitched_dev(rh, nfields, src, src_f32, src_layout, nlev, dst, dst_f32, scale, offsets, &
+                                                 dst_level_stride, stream) bind(C, name="mpg_regrid_bundle_typed_pitched_dev") result(rc)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: rh, stream
+      integer(c_int), value :: nfields, src_f32, src_layout, nlev, dst_f32
+      type(c_ptr), intent(in) :: src(*), dst(*)
+      real(c_double), value :: scale
+      real(c_double), intent(in) :: offsets(*)
+      integer(c_int64_t), value :: dst_level_stride
+      integer(c_int) :: rc
+    end function mpg_regrid_bundle_typed_pitched_dev
 
     !> the same on separate HOST arrays: every field of the bundle through one upload / Regrid / download pipeline
     function mpg_regrid_bundle_typed(rh, nfields, src, src_f32, src_layout, nlev, dst, dst_f32, scale, offsets) &
@@ -225,6 +262,15 @@ module mpg
       integer(c_int), value :: nlev, dst_type
       integer(c_int) :: rc
     end function mpg_wind_destagger_dev
+    !> ... with U's and V's level planes dst_level_stride elements apart (one stride for both, at least the larger plane)
+    function mpg_wind_destagger_pitched_dev(rh_edge1, rh_edge2, cosa, sina, umass, vmass, nlev, u, v, dst_type, umass_rot, vmass_rot, &
+                                            dst_level_stride, stream) bind(C, name="mpg_wind_destagger_pitched_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_edge1, rh_edge2, cosa, sina, umass, vmass, u, v, umass_rot, vmass_rot, stream
+      integer(c_int), value :: nlev, dst_type
+      integer(c_int64_t), value :: dst_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_destagger_pitched_dev
     !> the same chain on HOST arrays: the mass winds cross the link once, only U and V (and, on request, the rotated mass winds -- which
     !! may be the input arrays: rotate_winds_cgrid's in-place result) come back (include/mpassit_amd.h)
     function mpg_wind_destagger(rh_edge1, rh_edge2, cosa, sina, umass, vmass, nlev, u, v, dst_type, umass_rot, vmass_rot) &
@@ -270,6 +316,14 @@ module mpg
       type(c_ptr), value :: src_dev, stream
       integer(c_int) :: rc
     end function mpg_dev_to_file_c
+    function mpg_dev_to_file_planes_c(path, offset, plane_bytes, nplanes, src_dev, src_pitch_bytes, stream) &
+      bind(C, name="mpg_dev_to_file_planes") result(rc)
+      import :: c_int, c_int64_t, c_ptr, c_char
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int64_t), value :: offset, plane_bytes, nplanes, src_pitch_bytes
+      type(c_ptr), value :: src_dev, stream
+      integer(c_int) :: rc
+    end function mpg_dev_to_file_planes_c
     !> global source ids [first, last) a Mesh -> Grid handle references; source window of a mesh location
     function mpg_handle_source_range(rh, first, last) bind(C, name="mpg_handle_source_range") result(rc)
       import :: c_int, c_int64_t, c_ptr
@@ -507,6 +561,14 @@ contains
     type(c_ptr), intent(in) :: src_dev
     rc = mpg_dev_to_file_c(trim(path)//c_null_char, offset, nbytes, src_dev, c_null_ptr)
   end function mpg_dev_to_file
+
+  !> nplanes planes of plane_bytes, src_pitch_bytes apart in HBM -> one contiguous byte range of the file
+  integer(c_int) function mpg_dev_to_file_planes(path, offset, plane_bytes, nplanes, src_dev, src_pitch_bytes) result(rc)
+    character(len=*), intent(in) :: path
+    integer(c_int64_t), intent(in) :: offset, plane_bytes, nplanes, src_pitch_bytes
+    type(c_ptr), intent(in) :: src_dev
+    rc = mpg_dev_to_file_planes_c(trim(path)//c_null_char, offset, plane_bytes, nplanes, src_dev, src_pitch_bytes, c_null_ptr)
+  end function mpg_dev_to_file_planes
 
   !> MPASSIT_TUNE="key=value[,key=value...]": the library's run-time choices for a site whose ESMF comparison (tools/esmf_pin.py compare)
   !! named another setting than the default -- e.g. MPASSIT_TUNE="bilinear_linetype=1,node_fan_origin=-1".  Called once after mpg_init.

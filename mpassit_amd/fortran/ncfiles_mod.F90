@@ -325,21 +325,31 @@ contains
   !> device flow: a float32 field [nlev][rows][nxv] in HBM, big-endian as the Regrid / post-op kernels left it -> the
   !! variable's byte range.  With one image the buffer IS the variable; with
   !! several it holds this image's row block je_lo..je_hi (+1 row on the V stagger) and the owned rows j_lo..j_hi of every
-  !! level go to their place in the variable (the last image also owns the top V row).
-  subroutine put_dev(id, ptr, nlev, stag)
+  !! level go to their place in the variable (the last image also owns the top V row).  ld (optional, > 0): the buffer's level planes
+  !! lie ld elements apart (a pitched Regrid result, interp_mod pitched_ld) instead of ny_buf * nxv.
+  subroutine put_dev(id, ptr, nlev, stag, ld)
     integer(c_int), intent(in) :: id
     type(c_ptr), intent(in) :: ptr
     integer, intent(in) :: nlev, stag
-    integer(c_int64_t) :: off, nb, n, nxv, ny_buf, ny_glob, jb0, jg0, nrows, k
+    integer(c_int64_t), intent(in), optional :: ld
+    integer(c_int64_t) :: off, nb, n, nxv, ny_buf, ny_glob, jb0, jg0, nrows, k, pitch
     integer(int64) :: c0, c1, cr
     call system_clock(c0, cr)
     nxv = i_target + merge(1, 0, stag == 1)
     ny_buf = ny_ext + merge(1, 0, stag == 2)
     n = int(nlev, c_int64_t)*ny_buf*nxv
+    pitch = ny_buf*nxv
+    if (present(ld)) then
+      if (ld > 0) pitch = ld
+    end if
     call ncio_check(ncio_var_extent(nf_out, id, 0_c_int64_t, off, nb), "WRITING RECORD")
     if (nranks == 1) then
       if (n*4 > nb) call fatal("put_dev: field larger than its variable", int(id))
-      call mpg_check(mpg_dev_to_file(trim(out_path), off, n*4, ptr), "WRITING RECORD")
+      if (pitch == ny_buf*nxv) then
+        call mpg_check(mpg_dev_to_file(trim(out_path), off, n*4, ptr), "WRITING RECORD")
+      else
+        call mpg_check(mpg_dev_to_file_planes(trim(out_path), off, ny_buf*nxv*4, int(nlev, c_int64_t), ptr, pitch*4), "WRITING RECORD")
+      end if
     else
       ny_glob = j_target + merge(1, 0, stag == 2)
       jb0 = j_lo - je_lo
@@ -349,7 +359,7 @@ contains
       if (((nlev - 1)*ny_glob + jg0 + nrows)*nxv*4 > nb) call fatal("put_dev: rows beyond the variable", int(id))
       do k = 0, nlev - 1
         call mpg_check(mpg_dev_to_file(trim(out_path), off + ((k*ny_glob + jg0)*nxv)*4, nrows*nxv*4, &
-                                       ptr_add(ptr, ((k*ny_buf + jb0)*nxv)*4)), "WRITING RECORD")
+                                       ptr_add(ptr, (k*pitch + jb0*nxv)*4)), "WRITING RECORD")
       end do
     end if
     call system_clock(c1)
@@ -373,7 +383,7 @@ contains
     n = p%n_dst_elems
     if (p%dst_is_f32) then
       if (.not. p%dst_is_be) call fatal("write_field_dev: float32 field in host byte order - "//trim(p%tname), -1)
-      call put_dev(id, p%dst_dev, p%nlev, p%stagger)
+      call put_dev(id, p%dst_dev, p%nlev, p%stagger, p%dst_ld)
     else
       call mpg_check(mpg_dev_alloc(n*4, tmp), "IN dev_alloc")
       if (trim(p%tname) == 'PHB') then
@@ -402,6 +412,7 @@ contains
     if (wrf_mod_vars .and. trim(p%tname) == 'MUB') call put_zero(id_extra(1))
     call mpg_check(mpg_dev_free(p%dst_dev), "IN dev_free")
     p%dst_dev = c_null_ptr
+    p%dst_ld = 0
   end subroutine write_field_dev
 
   ! ---- several driver images, one output file -----------------------------------------------------------------------

@@ -35,6 +35,10 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _dtype_f32(dtype):
+    return str(dtype) in ("torch.float32", "float32")
+
+
 def _stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -57,6 +61,35 @@ def _account_regrid(rh, nlev, nfields, src_elem, dst_elem):
             rh._acc_U = int(rh.n_src)
     wbytes = (rh.nnz * 12 + (rh.n_dst + 1) * 4) if rh.nnz_per_row == 0 else rh.n_dst * (4 if rh.nnz_per_row == 1 else 12 * rh.nnz_per_row)
     ACCOUNT.append(("regrid nnz%d L%d x%d" % (rh.nnz_per_row, nlev, nfields), nfields * nlev * (rh._acc_U * src_elem + rh.n_dst * dst_elem) + wbytes))
+
+
+def _level_stride(out, lead, ny, nx, who):
+    """The destination level stride of a device `out` (elements): 0 for a contiguous one (dense), else the stride of a view whose
+    level planes lie a uniform `ld` >= ny * nx apart (Handle.empty_pitched: strides (nlev * ld, ld, nx, 1)).  lead: the leading
+    sizes, (nfields, nlev) or (nlev,).  Any other layout -- rows not contiguous, transposed, a field stride that is not nlev
+    times the level stride -- raises ValueError."""
+    if out.is_contiguous():
+        return 0
+    shape = tuple(lead) + (ny, nx)
+    if tuple(out.shape) != shape:
+        raise ValueError("%s: a strided out must have the shape %s, not %s" % (who, shape, tuple(out.shape)))
+    st = out.stride()
+    if (nx > 1 and st[-1] != 1) or (ny > 1 and st[-2] != nx):
+        raise ValueError("%s: out's rows must be contiguous (strides %s)" % (who, st))
+    ld, inner = None, 1
+    for size, stride in reversed(list(zip(lead, st[:len(lead)]))):
+        if size == 1:
+            continue
+        if ld is None:
+            ld = stride // inner if stride % inner == 0 else -1
+        if ld < 0 or stride != ld * inner:
+            raise ValueError("%s: out's level planes must lie one uniform stride apart (strides %s)" % (who, st))
+        inner *= size
+    if ld is None:        # a single plane: nothing to pitch
+        return 0
+    if ld < ny * nx:
+        raise ValueError("%s: out's level stride %d is below the plane size %d" % (who, ld, ny * nx))
+    return ld
 
 
 class Mesh:
@@ -257,6 +290,23 @@ class RouteHandle:
     def _refresh(self):
         self.__init__(self._h)
 
+    # -- pitched destinations ---------------------------------------------------------------------------
+    def level_stride(self, dtype):
+        """mpg_dst_level_stride: the smallest level stride (elements) >= ny_dst * nx_dst at which every level plane of this
+        handle's results in `dtype` (torch / numpy float32 or float64) starts on a 128-byte line."""
+        ld = C.c_int64()
+        check(L.load().mpg_dst_level_stride(C.c_int64(self.n_dst), C.c_int(1 if _dtype_f32(dtype) else 0), C.byref(ld)))
+        return ld.value
+
+    def empty_pitched(self, nlev, nfields=1, dtype=None, device=None):
+        """An uninitialised device result (nfields, nlev, ny_dst, nx_dst) whose level planes lie level_stride(dtype) elements apart:
+        strides (nlev * ld, ld, nx_dst, 1).  Every device regrid / wind call takes it as `out`; the pad of each plane is never written."""
+        import torch
+        dtype = dtype or torch.float64
+        ld = self.level_stride(dtype)
+        buf = torch.empty(nfields * nlev * ld, dtype=dtype, device=device or "cuda")
+        return buf.as_strided((nfields, nlev, self.ny_dst, self.nx_dst), (nlev * ld, ld, self.nx_dst, 1))
+
     # -- ESMF_FieldRegrid / ESMF_FieldBundleRegrid ---------------------------------------------------
     def regrid(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, out=None, src_be=False):
         """src: nfields slabs of nlev*n_src float64 (numpy on host or torch on the GPU).
@@ -276,9 +326,10 @@ class RouteHandle:
                 raise ValueError("source has %d elements, handle expects %d" % (src.numel(), need))
             if out is None:
                 out = torch.empty(shape, dtype=torch.float64, device=src.device)
+            ld = _level_stride(out, (nfields, nlev), self.ny_dst, self.nx_dst, "regrid")
             _account_regrid(self, nlev, nfields, 8, 8)
-            check(L.load().mpg_regrid_dev(self._h, C.c_void_p(src.data_ptr()), C.c_int(layout), C.c_int(nlev), C.c_int(nfields),
-                                          C.c_void_p(out.data_ptr()), _stream_ptr()))
+            check(L.load().mpg_regrid_pitched_dev(self._h, C.c_void_p(src.data_ptr()), C.c_int(layout), C.c_int(nlev), C.c_int(nfields),
+                                                  C.c_void_p(out.data_ptr()), C.c_int64(ld), _stream_ptr()))
             return out
         if isinstance(src, np.ndarray) and src.dtype == np.float32:
             return self.regrid_typed_host(src, nlev=nlev, nfields=nfields, layout=layout, out_dtype=np.float64, out=out)
@@ -303,11 +354,12 @@ class RouteHandle:
         out_dtype = out_dtype or src.dtype
         if out is None:
             out = torch.empty((nfields, nlev, self.ny_dst, self.nx_dst), dtype=out_dtype, device=src.device)
+        ld = _level_stride(out, (nfields, nlev), self.ny_dst, self.nx_dst, "regrid_typed")
         _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
-        check(L.load().mpg_regrid_typed_dev(self._h, C.c_void_p(src.data_ptr()), C.c_int(int(src.dtype == torch.float32) | (2 if src_be else 0)),
-                                            C.c_int(layout), C.c_int(nlev), C.c_int(nfields), C.c_void_p(out.data_ptr()),
-                                            C.c_int(int(out.dtype == torch.float32) | (2 if dst_be else 0)), C.c_double(scale), C.c_double(offset),
-                                            _stream_ptr()))
+        check(L.load().mpg_regrid_typed_pitched_dev(self._h, C.c_void_p(src.data_ptr()), C.c_int(int(src.dtype == torch.float32) | (2 if src_be else 0)),
+                                                    C.c_int(layout), C.c_int(nlev), C.c_int(nfields), C.c_void_p(out.data_ptr()),
+                                                    C.c_int(int(out.dtype == torch.float32) | (2 if dst_be else 0)), C.c_double(scale), C.c_double(offset),
+                                                    C.c_int64(ld), _stream_ptr()))
         return out
 
     def regrid_bundle(self, srcs, nlev=1, layout=LAYOUT_CELL_FAST, out_dtype=None, scale=1.0, offsets=None, outs=None, src_be=False, dst_be=False):
@@ -327,16 +379,26 @@ class RouteHandle:
         out_dtype = out_dtype or dt
         if outs is None:
             outs = [torch.empty((nlev, self.ny_dst, self.nx_dst), dtype=out_dtype, device=srcs[0].device) for _ in range(nf)]
+        lds = set()
         for t in outs:
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == outs[0].dtype and t.numel() == nlev * self.n_dst):
+            if not (t.is_cuda and t.dtype == outs[0].dtype and t.numel() == nlev * self.n_dst):
                 raise ValueError("regrid_bundle: bad destination tensor")
+            if t.is_contiguous():
+                lds.add(0)
+            else:   # a pitched result, (nlev, ny, nx) or empty_pitched's (1, nlev, ny, nx)
+                lead = tuple(t.shape[:-2]) if t.dim() == 4 else (nlev,)
+                lds.add(_level_stride(t, lead, self.ny_dst, self.nx_dst, "regrid_bundle"))
+        if len(lds) > 1:
+            raise ValueError("regrid_bundle: the destinations must share one level stride (or all be dense)")
+        ld = lds.pop()
         _account_regrid(self, nlev, nf, srcs[0].element_size(), outs[0].element_size())
         sp = (C.c_void_p * nf)(*[t.data_ptr() for t in srcs])
         dp = (C.c_void_p * nf)(*[t.data_ptr() for t in outs])
         op = None if offsets is None else (C.c_double * nf)(*[float(o) for o in offsets])
-        check(L.load().mpg_regrid_bundle_typed_dev(self._h, C.c_int(nf), sp, C.c_int(int(dt == torch.float32) | (2 if src_be else 0)), C.c_int(layout),
-                                                   C.c_int(nlev), dp, C.c_int(int(outs[0].dtype == torch.float32) | (2 if dst_be else 0)),
-                                                   C.c_double(scale), op, _stream_ptr()))
+        check(L.load().mpg_regrid_bundle_typed_pitched_dev(self._h, C.c_int(nf), sp, C.c_int(int(dt == torch.float32) | (2 if src_be else 0)),
+                                                           C.c_int(layout), C.c_int(nlev), dp,
+                                                           C.c_int(int(outs[0].dtype == torch.float32) | (2 if dst_be else 0)),
+                                                           C.c_double(scale), op, C.c_int64(ld), _stream_ptr()))
         return outs
 
     def regrid_typed_host(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, out_dtype=None, scale=1.0, offset=0.0, out=None):
@@ -526,16 +588,20 @@ def rotate_winds_cgrid(cosa, sina, u, v):
     return u, v
 
 
-def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, dst_be=False, keep_mass=False):
+def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, dst_be=False, keep_mass=False, outs=None):
     """interp.F90:291-328 in one pass (mpg_wind_destagger_dev; numpy arrays: mpg_wind_destagger): rotate_winds_cgrid on the CENTER-stagger winds (cosa / sina
     None: no rotation) + UMASS -> U(EDGE1) + VMASS -> V(EDGE2).  rh_u / rh_v: the regrid_store_grid handles of ONE grid (either
     may be None); umass / vmass: float64 CUDA tensors (or numpy arrays) [nlev][ny][nx], not modified.  Returns (U, V, UMASS', VMASS'): U
     [nlev][ny][nx+1], V [nlev][ny+1][nx] of out_dtype (float64), the rotated mass winds only with keep_mass (else None).
     Bit-identical to rotate_winds_cgrid followed by the two handles' regrid().  Raises MpgError(rc = MPG_ERR_UNSUPPORTED) for
-    handles that are not such a pair (re-indexed ones)."""
+    handles that are not such a pair (re-indexed ones).  outs=(U, V) (device only): tensors to write into, dense or plane-pitched
+    (rh_u.empty_pitched / rh_v.empty_pitched) with ONE level stride for both (at least the larger plane: use the larger of the two
+    handles' level_stride)."""
     ref = umass if umass is not None else vmass
     rot = cosa is not None
     if not _is_torch(ref):
+        if outs is not None:
+            raise ValueError("wind_destagger: outs= takes device tensors; the host-array chain returns new arrays")
         # HOST arrays (mpg_wind_destagger): the mass winds cross the link once, U and V come back -- 2 fields up, 2 down, where
         # rotate_winds_cgrid + two regrid() calls move 4 up and 4 down.  keep_mass: the rotated mass winds are returned as new arrays.
         out_np = np.dtype(out_dtype or np.float64)
@@ -555,12 +621,27 @@ def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, d
                                           C.c_int(nlev), hp(u), hp(v), C.c_int(int(out_np == np.dtype(np.float32)) | (2 if dst_be else 0)), hp(ur), hp(vr)))
         return u, v, ur, vr
     import torch
-    out_dtype = out_dtype or torch.float64
+    given = [t for t in (outs or ()) if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else torch.float64)
     for t in (umass, vmass):
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64):
             raise ValueError("wind_destagger needs contiguous float64 CUDA tensors")
-    u = torch.empty((nlev, rh_u.ny_dst, rh_u.nx_dst), dtype=out_dtype, device=ref.device) if rh_u is not None else None
-    v = torch.empty((nlev, rh_v.ny_dst, rh_v.nx_dst), dtype=out_dtype, device=ref.device) if rh_v is not None else None
+    u, v = outs if outs is not None else (None, None)
+    if u is None and rh_u is not None:
+        u = torch.empty((nlev, rh_u.ny_dst, rh_u.nx_dst), dtype=out_dtype, device=ref.device)
+    if v is None and rh_v is not None:
+        v = torch.empty((nlev, rh_v.ny_dst, rh_v.nx_dst), dtype=out_dtype, device=ref.device)
+    lds = set()
+    for t, rh in ((u, rh_u), (v, rh_v)):
+        if t is None or rh is None:
+            continue
+        if not (t.is_cuda and t.dtype == out_dtype and t.numel() == nlev * rh.n_dst):
+            raise ValueError("wind_destagger: bad destination tensor")
+        lead = tuple(t.shape[:-2]) if t.dim() == 4 else (nlev,)
+        lds.add(_level_stride(t, lead, rh.ny_dst, rh.nx_dst, "wind_destagger"))
+    if len(lds) > 1:
+        raise ValueError("wind_destagger: U and V must share one level stride (or both be dense)")
+    ld = lds.pop() if lds else 0
     ur = torch.empty_like(umass) if (keep_mass and rot) else None
     vr = torch.empty_like(vmass) if (keep_mass and rot) else None
     if ACCOUNT is not None:     # both mass fields read once, U and V written once, indices + weights of both handles and the angles once
@@ -575,7 +656,8 @@ def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, d
 
     def p(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
-    check(L.load().mpg_wind_destagger_dev(rh_u._h if rh_u is not None else None, rh_v._h if rh_v is not None else None, p(cosa), p(sina),
-                                          p(umass), p(vmass), C.c_int(nlev), p(u), p(v),
-                                          C.c_int(int(out_dtype == torch.float32) | (2 if dst_be else 0)), p(ur), p(vr), _stream_ptr()))
+    check(L.load().mpg_wind_destagger_pitched_dev(rh_u._h if rh_u is not None else None, rh_v._h if rh_v is not None else None, p(cosa), p(sina),
+                                                  p(umass), p(vmass), C.c_int(nlev), p(u), p(v),
+                                                  C.c_int(int(out_dtype == torch.float32) | (2 if dst_be else 0)), p(ur), p(vr), C.c_int64(ld),
+                                                  _stream_ptr()))
     return u, v, ur, vr

@@ -142,6 +142,39 @@ def main():
     print("fortran, device flow:  %.2f s wall (process start to exit; %.2f GB out)" % (t_f, gb_out), flush=True)
     print("    " + "  ".join(ln.strip() for ln in r.stdout.splitlines() if ln.lstrip().startswith("[")), flush=True)
 
+    nab = int(os.environ.get("C4JOB_PITCH_AB", "0"))   # C4JOB_PITCH_AB=N: the device flow with dense / pitched results (MPASSIT_DST_PITCH=0 / 1),
+    if nab > 0 and not c5:                             # alternating, N runs each, on this grid and on HRRR's 1799 x 1059 (namelist 1800 x 1060); then stop
+        txt = open(os.path.join(d, "namelist.input")).read()
+        grids = (("1800x1060", txt), ("1799x1059", txt.replace("nx = 1801", "nx = 1800").replace("ny = 1061", "ny = 1060")))
+        ok = True
+        for gname, nml_txt in grids:
+            walls = {"0": [], "1": []}
+            outs = {}
+            for rep in range(nab):
+                for pitch in ("0", "1"):
+                    out = "out_pitch%s.nc" % pitch
+                    open(os.path.join(d, "namelist.ab"), "w").write(nml_txt.replace("out_fortran.nc", out))
+                    t0 = time.perf_counter()
+                    r = subprocess.run([exe, "namelist.ab"], cwd=d, capture_output=True, text=True, timeout=900, env=dict(os.environ, MPASSIT_DST_PITCH=pitch))
+                    walls[pitch].append(time.perf_counter() - t0)
+                    if r.returncode != 0:
+                        print(r.stdout[-3000:], r.stderr[-3000:])
+                        return 1
+                    print("%s MPASSIT_DST_PITCH=%s run %d: %.2f s wall   %s" % (gname, pitch, rep, walls[pitch][-1], "  ".join(
+                        ln.strip() for ln in r.stdout.splitlines() if ln.lstrip().startswith("[") or "PITCH" in ln)), flush=True)
+                    outs[pitch] = os.path.join(d, out)
+            same_ab = open(outs["0"], "rb").read() == open(outs["1"], "rb").read()
+            ok = ok and same_ab
+            print("%s: dense median %.3f s, pitched median %.3f s (%d runs each); outputs identical byte for byte: %s" % (
+                gname, float(np.median(walls["0"])), float(np.median(walls["1"])), nab, same_ab), flush=True)
+            for p in outs.values():
+                os.remove(p)
+        if not os.environ.get("C4JOB_KEEP"):
+            for f in os.listdir(d):
+                os.remove(os.path.join(d, f))
+            os.rmdir(d)
+        return 0 if ok else 1
+
     if os.environ.get("C4JOB_NC4"):                   # C4JOB_NC4=1: the same job with a NetCDF-4 output (what the reference creates): host arrays, libhdf5
         from mpassit_amd import ncio
         if not ncio.has_netcdf4():
