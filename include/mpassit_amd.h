@@ -214,6 +214,28 @@ int mpg_regrid_typed_dev(mpg_handle rh, const void *src_dev, int src_type, int s
 /* ... with the destination's level planes dst_level_stride elements apart (mpg_regrid_pitched_dev) */
 int mpg_regrid_typed_pitched_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev,
                                  int dst_type, double scale, double offset, int64_t dst_level_stride, void *hip_stream);
+/* Transpose Regrid: ESMF_FieldRegridStore(..., transposeRoutehandle=) applied with ESMF_FieldRegrid, mesh_out = A^T grid_in.
+ * A is exactly the operator the forward Regrid of this handle applies: every stored entry with idx >= 0 (weight 1 for nearest
+ * neighbour), every CSR entry (mpg_handle_from_weights duplicates included) and the pole caps of a periodic Grid -> Grid handle,
+ * whose forward adds w_pole * mean(row): the transpose adds (sum_q w_pole[q] * g[pole_dst[q]]) / row_len to every source of that
+ * row.  It is the ADJOINT of the Regrid, not an inverse (A^T A != I): it does not "regrid back".
+ * src_dev: grid values [nfields][nlev][plane], plane = n_dst of mpg_handle_info, planes src_level_stride elements apart (0 = dense;
+ * below n_dst -> MPG_ERR_INVALID_ARG); a pitched result of the *_pitched_dev calls can be fed back as it is, its pad is never read.
+ * dst_dev: nfields slabs of nlev * n_src in dst_layout (MPG_LAYOUT_CELL_FAST [lev][cell], MPG_LAYOUT_LEV_FAST [cell][lev]), n_src
+ * the handle's current index space (the window count after mpg_mesh_set_source_window, the local extent after mpg_handle_localize /
+ * rebase).  dst is fully overwritten; a source no entry references gets exactly 0.0 (zeroregion=TOTAL).
+ * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, float32 rounded once at the store; MPG_TYPE_BE ->
+ * MPG_ERR_UNSUPPORTED.  The linear part only: no scale / offset (the transpose of an affine epilogue is not defined).
+ * Determinism: a source's sum runs in ascending (destination point, slot) order, the pole term last, without floating-point
+ * atomics: the bits are the same across calls, nfields batching, float32 / float64 inputs that hold the same values and the two
+ * layouts.  Stream as mpg_regrid_dev: the first call on a handle builds the transposed index (allocates and synchronises; it is
+ * dropped whenever the handle is re-indexed); every later call only enqueues and can be captured in a hipGraph. */
+int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
+                             void *dst_dev, int dst_type, int dst_layout, void *hip_stream);
+/* diagnostics: sources with at least one entry, and the longest transposed row (builds the transposed index if needed) */
+int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
+/* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */
+int mpg_handle_transpose_build_ms(mpg_handle rh, float *ms);
 /* ESMF_FieldBundleRegrid as interp.F90:240-254 issues it: ONE Regrid over every field of a bundle whose fields are SEPARATE
  * arrays (an ESMF bundle holds independent fields; here: nfields device pointers on either side, host arrays of pointers).
  * All fields share the handle, the layout, nlev and the element types; offsets (nfields values, or NULL for 0) is the

@@ -22,7 +22,8 @@ SYMBOLS = [
     "mpg_halo_destroy", "mpg_gather_rows", "mpg_halo_plan_host", "mpg_comm_idfile_verdict", "mpg_pack_rows_dev", "mpg_comm_virtual",
     "mpg_comm_virtual_stats", "mpg_handle_store_stats", "mpg_debug_scan_i32", "mpg_device_count", "mpg_warmup_wait", "mpg_halo_build_owned", "mpg_halo_plan_owned_host",
     "mpg_dst_level_stride", "mpg_regrid_pitched_dev", "mpg_regrid_typed_pitched_dev", "mpg_regrid_bundle_typed_pitched_dev",
-    "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes",
+    "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes", "mpg_regrid_transpose_dev", "mpg_handle_transpose_stats",
+    "mpg_handle_transpose_build_ms",
 ]
 
 MPG_SUCCESS = 0

@@ -132,7 +132,8 @@ void mpg_pool_release() {
 // creates the pinned staging of the host-array upload path, while the caller goes on (reading its namelist, opening its
 // files); a call that needs a module before the helper got to it simply loads it itself (the runtime serialises that).
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
-  X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort)
+  X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
+  X(k_transpose)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -979,6 +980,40 @@ int mpg_regrid_typed_pitched_dev(mpg_handle h, const void *src_dev, int src_type
   int rc = dst_stride("mpg_regrid_typed", h->n_dst, (int64_t)nlev * nfields, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_apply_typed(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream, FieldTab(), ld);
+}
+
+// ---- transpose Regrid (ESMF's transposeRoutehandle): mesh_out = A^T grid_in ---------------------------------------------
+int mpg_regrid_transpose_dev(mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields, void *dst_dev,
+                             int dst_type, int dst_layout, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && (dst_dev || h->n_src == 0) && (src_dev || h->n_dst == 0), "mpg_regrid_transpose: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_transpose: nlev and nfields must be >= 1");
+  MPG_ARG(dst_layout == MPG_LAYOUT_CELL_FAST || dst_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_transpose: bad dst_layout");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_transpose: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_transpose: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  int64_t ld;   // the source's level stride, checked as a destination stride is
+  int rc = dst_stride("mpg_regrid_transpose: source", h->n_dst, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_transpose(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
+}
+
+int mpg_handle_transpose_stats(mpg_handle h, int64_t *n_referenced, int64_t *max_per_source) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h, "mpg_handle_transpose_stats: NULL handle");
+  int rc = mpg_k_transpose_build(h, g_stream);
+  if (rc) return rc;
+  if (n_referenced) *n_referenced = h->tr_nref;
+  if (max_per_source) *max_per_source = h->tr_max;
+  return MPG_SUCCESS;
+}
+
+int mpg_handle_transpose_build_ms(mpg_handle h, float *ms) {
+  MPG_ARG(h && ms, "mpg_handle_transpose_build_ms: NULL argument");
+  *ms = h->tr_built ? h->tr_build_ms : 0.f;
+  return MPG_SUCCESS;
 }
 
 int mpg_regrid_bundle_typed_dev(mpg_handle h, int nfields, const void *const *src_dev, int src_type, int src_layout, int nlev,

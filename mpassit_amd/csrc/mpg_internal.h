@@ -313,9 +313,25 @@ struct mpg_handle_s {
   int64_t ut2_total = 0;
   DevBuf<int32_t> ut2_cnt, ut2_cells;
   DevBuf<uint16_t> lidx2;
+  // transposed index of the transpose Regrid (k_transpose.hip), built on its first call: segment of source c at
+  // [tr_ptr[c], tr_ptr[c + 1]) of tr_row (destination points, ascending) / tr_w; tr_long lists the sources whose segment is
+  // too long for one lane.  It holds source ids, so it goes with the tile lists whenever the indices are rewritten.
+  bool tr_built = false;
+  DevBuf<int32_t> tr_ptr, tr_row, tr_long;
+  DevBuf<double> tr_w;
+  int64_t tr_nnz = 0, tr_nref = 0, tr_max = 0;
+  int tr_nlong = 0;
+  float tr_build_ms = 0.f;
+  void free_transpose() {
+    tr_ptr.free(); tr_row.free(); tr_long.free(); tr_w.free();
+    tr_built = false;
+    tr_nnz = tr_nref = tr_max = 0;
+    tr_nlong = 0;
+  }
   void free_tile_lists() {
     ut_cnt.free(); ut_cells.free(); lidx.free(); ut2_cnt.free(); ut2_cells.free(); lidx2.free(); ut_order.free(); ut2_order.free();
     ut_rpt = ut2_rpt = 0;
+    free_transpose();
   }
 };
 
@@ -421,6 +437,11 @@ int mpg_cfu_auto(mpg_handle_s *h, hipStream_t s, int *cfu_variant);  // -> varia
 int mpg_lfu_auto(mpg_handle_s *h, hipStream_t s, int *lf_variant);   // -> MPG_LF_ROWS or the staged default
 int mpg_k_pole_fix(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
                    double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
+// k_transpose.hip: dst (n_src per plane, `layout`) = A^T src ([nfields][nlev] planes ld elements apart, 0 = n_dst); builds the transposed
+// index on the first call (allocates, synchronises)
+int mpg_k_transpose_build(mpg_handle_s *h, hipStream_t s);
+int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
+                    hipStream_t s);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);

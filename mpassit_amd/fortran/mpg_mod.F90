@@ -222,6 +222,21 @@ module mpg
       integer(c_int64_t), value :: dst_level_stride
       integer(c_int) :: rc
     end function mpg_regrid_typed_pitched_dev
+    ! transpose Regrid (ESMF's transposeRoutehandle): mesh_out = A^T grid_in, the adjoint of the Regrid, not an inverse
+    function mpg_regrid_transpose_dev(rh, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, hip_stream) &
+      bind(C, name="mpg_regrid_transpose_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, nfields, dst_type, dst_layout
+      integer(c_int64_t), value :: src_level_stride
+      integer(c_int) :: rc
+    end function mpg_regrid_transpose_dev
+    function mpg_handle_transpose_stats(rh, n_referenced, max_per_source) bind(C, name="mpg_handle_transpose_stats") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh
+      integer(c_int64_t) :: n_referenced, max_per_source
+      integer(c_int) :: rc
+    end function mpg_handle_transpose_stats
     function mpg_regrid_bundle_typed_pitched_dev(rh, nfields, src, src_f32, src_layout, nlev, dst, dst_f32, scale, offsets, &
                                                  dst_level_stride, stream) bind(C, name="mpg_regrid_bundle_typed_pitched_dev") result(rc)
       import :: c_int, c_int64_t, c_double, c_ptr

@@ -18,7 +18,7 @@ from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_N
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
                    check)
 
-__all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger",
+__all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST"]
 
@@ -440,6 +440,55 @@ class RouteHandle:
                                                C.c_int(int(out_dtype == np.float32)), C.c_double(scale), op))
         return outs
 
+    # -- transposeRoutehandle: the adjoint A^T (not an inverse) ------------------------------------------
+    def regrid_transpose(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, out_dtype=None, out=None):
+        """mpg_regrid_transpose_dev: mesh_out = A^T grid_in with the operator regrid() applies (ESMF's transposeRoutehandle).  The
+        ADJOINT of the Regrid, not an inverse (A^T A != I): it takes gradients, increments and residuals back to the mesh.
+        src: grid values [nfields][nlev][ny_dst][nx_dst], float32 / float64, a CUDA tensor (contiguous, or a plane-pitched view as
+        empty_pitched makes) or a numpy array (uploaded, and the result comes back as numpy).  Returns nfields slabs of nlev * n_src
+        values of out_dtype (default: src's): (nfields, nlev, n_src) for LAYOUT_CELL_FAST, (nfields, n_src, nlev) for LAYOUT_LEV_FAST.
+        Sources no entry references are exactly 0."""
+        import torch
+        host = isinstance(src, np.ndarray)
+        if host:
+            src = torch.from_numpy(np.ascontiguousarray(src)).cuda()
+        if not (_is_torch(src) and src.is_cuda and src.dtype in (torch.float32, torch.float64)):
+            raise ValueError("regrid_transpose needs a float32/float64 CUDA tensor or numpy array")
+        if src.is_contiguous():
+            if src.numel() != nfields * nlev * self.n_dst:
+                raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_dst))
+            ld = 0
+        else:
+            lead = (nfields, nlev) if src.dim() == 4 else (nlev,)
+            if src.dim() not in (3, 4) or (src.dim() == 3 and nfields != 1):
+                raise ValueError("regrid_transpose: a strided source must be (nfields, nlev, ny, nx) or (nlev, ny, nx) with plane-pitched levels")
+            ld = _level_stride(src, lead, self.ny_dst, self.nx_dst, "regrid_transpose")
+        out_dtype = out_dtype or src.dtype
+        if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+            out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+        shape = (nfields, nlev, self.n_src) if layout == LAYOUT_CELL_FAST else (nfields, self.n_src, nlev)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=src.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64) and out.numel() == nfields * nlev * self.n_src):
+            raise ValueError("regrid_transpose: out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_src))
+        check(L.load().mpg_regrid_transpose_dev(self._h, C.c_void_p(src.data_ptr()), C.c_int(int(src.dtype == torch.float32)), C.c_int64(ld),
+                                                C.c_int(nlev), C.c_int(nfields), C.c_void_p(out.data_ptr()),
+                                                C.c_int(int(out.dtype == torch.float32)), C.c_int(layout), _stream_ptr()))
+        return out.cpu().numpy() if host else out
+
+    def transpose_stats(self):
+        """(n_referenced, max_per_source): sources with at least one entry and the longest transposed row
+        (mpg_handle_transpose_stats; builds the transposed index if needed)."""
+        a, b = C.c_int64(), C.c_int64()
+        check(L.load().mpg_handle_transpose_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def transpose_build_ms(self):
+        """GPU time of the transposed index build (mpg_handle_transpose_build_ms); 0.0 while none is built."""
+        ms = C.c_float()
+        check(L.load().mpg_handle_transpose_build_ms(self._h, C.byref(ms)))
+        return ms.value
+
     @classmethod
     def from_weights(cls, n_src, nx_dst, ny_dst, row, col, S):
         """Route handle from externally computed weights in ESMF's factorList / factorIndexList form (1-based
@@ -541,6 +590,34 @@ class RouteHandle:
         if self._h:
             check(L.load().mpg_handle_release(self._h))
             self._h = None
+
+
+try:   # the differentiable Regrid needs torch; the rest of this module does not
+    import torch as _torch
+except ImportError:
+    _torch = None
+
+if _torch is not None:
+    class RegridFunction(_torch.autograd.Function):
+        """Regrid with a gradient: forward is regrid_typed (scale 1, offset 0) in src's dtype, backward is regrid_transpose into
+        src's layout and dtype.  Use regrid_autograd()."""
+
+        @staticmethod
+        def forward(ctx, src, rh, nlev, nfields, layout):
+            ctx.rh, ctx.nlev, ctx.nfields, ctx.layout = rh, nlev, nfields, layout
+            ctx.src_shape, ctx.src_dtype = src.shape, src.dtype
+            return rh.regrid_typed(src.contiguous(), nlev=nlev, nfields=nfields, layout=layout, out_dtype=src.dtype)
+
+        @staticmethod
+        def backward(ctx, grad):
+            g = ctx.rh.regrid_transpose(grad.contiguous(), nlev=ctx.nlev, nfields=ctx.nfields, layout=ctx.layout, out_dtype=ctx.src_dtype)
+            return g.reshape(ctx.src_shape), None, None, None, None
+
+
+def regrid_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST):
+    """rh.regrid_typed(src) (float32 or float64 CUDA tensor, scale 1, offset 0) as a differentiable torch op: the gradient with
+    respect to src is rh.regrid_transpose of the incoming gradient, in src's layout and dtype."""
+    return RegridFunction.apply(src, rh, nlev, nfields, layout)
 
 
 def regrid_store(src_mesh, dst_grid, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER,
