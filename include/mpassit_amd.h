@@ -236,6 +236,47 @@ int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, i
 int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */
 int mpg_handle_transpose_build_ms(mpg_handle rh, float *ms);
+/* Masked Regrid: missing sources are skipped, the valid ones stand in for them above a threshold, everything else is filled.
+ * What ESMF calls dynamic masking (dynamicSrcMaskValue) and xESMF skipna / na_thres -- NOT ESMF's Store-time srcMaskValues: the
+ * weights are those of the unmasked Store of this handle, only their use changes per call.
+ * For a destination point p and level k take the stored entries q in stored order (slot order of a fixed-nnz handle, CSR order of
+ * a conservative or a from-weights handle, duplicates included).  All arithmetic is float64.
+ *   valid(q)   idx_q >= 0, its source is not statically masked (src_mask_dev), and its value at level k is not missing under
+ *              `flags`: MPG_MISSING_NAN -> a NaN is missing; MPG_MISSING_VALUE -> an element is missing when
+ *              (double)element == missing_value.  flags may be 0 (static mask only).
+ *   Wt         the plain left-to-right sum of the point's stored weights (1 for nearest neighbour)
+ *   Wv         the same sum with the weight of every invalid entry replaced by 0.0
+ *   N          the unmasked Regrid's own expression with weight AND value of every invalid entry replaced by 0.0 (a missing NaN never
+ *              enters a product)
+ *   defined    the point has at least one stored entry, Wv > 0 and Wv >= min_valid_frac * Wt
+ *   result     defined: dst = (dst type)( N * (Wt / Wv) * scale + offset );  undefined -- unmapped points included --:
+ *              dst = (dst type) fill_value, whatever scale and offset are (fill_value for unmapped points: a result can tell
+ *              "no data" from 0).  Wt / Wv keeps a partly covered conservative cell scaled as the unmasked Regrid scales it; for
+ *              bilinear weights (Wt = 1 up to rounding) it is the usual renormalisation.
+ * Bit identity with the unmasked Regrid when nothing is missing: a point none of whose entries is invalid has Wv and Wt of the same
+ * bits, Wt / Wv == 1.0, and stores exactly what the typed, pitched unmasked call with scale 1, offset 0 stores for it -- switching the
+ * call on for a field that happens to have no gaps changes nothing.  Nearest-neighbour handles copy when valid and fill when not
+ * (no search for the next valid neighbour).
+ * src_mask_dev: optional [n_src] bytes on the device, in the handle's CURRENT index space (the window after
+ * mpg_mesh_set_source_window, the local ids after a localize / rebase of the handle): non-zero = never use this source.
+ * The destination is fully overwritten; dst_level_stride as in the _pitched_dev calls (0 = dense, below the plane size ->
+ * MPG_ERR_INVALID_ARG), the pad of pitched planes is never written.  Both source layouts, MPG_TYPE_F64 / MPG_TYPE_F32 on either
+ * side, every handle kind.  Refused with MPG_ERR_UNSUPPORTED: MPG_TYPE_BE on either side, and handles with pole caps (pole-cap
+ * count > 0: winds are never masked).  Refused with MPG_ERR_INVALID_ARG: rh or opts NULL, min_valid_frac outside [0, 1] or NaN,
+ * MPG_MISSING_VALUE with a NaN missing_value, unknown flag bits.
+ * Stream as mpg_regrid_dev; the call allocates nothing and synchronises nothing, so it can be captured in a hipGraph from the first
+ * call.  No atomics: the same bits across calls, across nfields batching and for the two source layouts holding the same values. */
+enum { MPG_MISSING_NAN = 1, MPG_MISSING_VALUE = 2 };
+typedef struct mpg_mask_opts {
+  int flags;                    /* MPG_MISSING_NAN | MPG_MISSING_VALUE, may be 0 (static mask only) */
+  double missing_value;         /* with MPG_MISSING_VALUE: an element is missing when (double)element == missing_value */
+  const uint8_t *src_mask_dev;  /* optional [n_src] in the handle's CURRENT index space: non-zero = never use this source (every level, every field) */
+  double min_valid_frac;        /* in [0, 1] */
+  double fill_value;            /* any double, NaN allowed */
+  double scale, offset;         /* writer's epilogue, applied to DEFINED points only */
+} mpg_mask_opts;
+int mpg_regrid_masked_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields,
+                          void *dst_dev, int dst_type, int64_t dst_level_stride, const mpg_mask_opts *opts, void *hip_stream);
 /* ESMF_FieldBundleRegrid as interp.F90:240-254 issues it: ONE Regrid over every field of a bundle whose fields are SEPARATE
  * arrays (an ESMF bundle holds independent fields; here: nfields device pointers on either side, host arrays of pointers).
  * All fields share the handle, the layout, nlev and the element types; offsets (nfields values, or NULL for 0) is the

@@ -23,7 +23,7 @@ SYMBOLS = [
     "mpg_comm_virtual_stats", "mpg_handle_store_stats", "mpg_debug_scan_i32", "mpg_device_count", "mpg_warmup_wait", "mpg_halo_build_owned", "mpg_halo_plan_owned_host",
     "mpg_dst_level_stride", "mpg_regrid_pitched_dev", "mpg_regrid_typed_pitched_dev", "mpg_regrid_bundle_typed_pitched_dev",
     "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes", "mpg_regrid_transpose_dev", "mpg_handle_transpose_stats",
-    "mpg_handle_transpose_build_ms",
+    "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -33,6 +33,30 @@ MESHLOC_ELEMENT, MESHLOC_NODE = 0, 1
 STAGGERLOC_CENTER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2, STAGGERLOC_CORNER = 0, 1, 2, 3
 LAYOUT_CELL_FAST, LAYOUT_LEV_FAST = 0, 1
 GRID_PERIODIC_I, GRID_NO_SOUTH_POLE, GRID_NO_NORTH_POLE = 1, 2, 4
+
+MISSING_NAN, MISSING_VALUE = 1, 2
+
+
+class MaskOpts(C.Structure):
+    """mpg_mask_opts of include/mpassit_amd.h (mpg_regrid_masked_dev)."""
+    _fields_ = [("flags", C.c_int), ("missing_value", C.c_double), ("src_mask_dev", C.c_void_p), ("min_valid_frac", C.c_double),
+                ("fill_value", C.c_double), ("scale", C.c_double), ("offset", C.c_double)]
+
+
+# mpg_regrid_masked_dev with its argument types (rh, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, dst_level_stride,
+# opts, hip_stream).  A prototype of its own: the attribute of the loaded library stays untyped like every other entry point.
+_MASKED_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64,
+                            C.POINTER(MaskOpts), C.c_void_p)
+_masked_fn = None
+
+
+def regrid_masked_dev(*args):
+    """The typed binding of mpg_regrid_masked_dev; returns the call's status code."""
+    global _masked_fn
+    if _masked_fn is None:
+        _masked_fn = _MASKED_PROTO(("mpg_regrid_masked_dev", load()))
+    return _masked_fn(*args)
+
 
 _lib = None
 _initialized = False

@@ -133,7 +133,7 @@ void mpg_pool_release() {
 // files); a call that needs a module before the helper got to it simply loads it itself (the runtime serialises that).
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
-  X(k_transpose)
+  X(k_transpose) X(k_apply_masked)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -998,6 +998,33 @@ int mpg_regrid_transpose_dev(mpg_handle h, const void *src_dev, int src_type, in
   int rc = dst_stride("mpg_regrid_transpose: source", h->n_dst, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_transpose(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
+}
+
+// ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------
+int mpg_regrid_masked_dev(mpg_handle h, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev, int dst_type,
+                          int64_t dst_level_stride, const mpg_mask_opts *opts, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h, "mpg_regrid_masked: NULL handle");
+  MPG_ARG(opts, "mpg_regrid_masked: NULL options");
+  MPG_ARG(dst_dev && (src_dev || h->n_src == 0), "mpg_regrid_masked: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_masked: nlev and nfields must be >= 1");
+  MPG_ARG(src_layout == MPG_LAYOUT_CELL_FAST || src_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_masked: bad src_layout");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_masked: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_masked: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_masked: handles with pole-cap terms (periodic Grid -> Grid) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  MPG_ARG((opts->flags & ~(MPG_MISSING_NAN | MPG_MISSING_VALUE)) == 0, "mpg_regrid_masked: unknown flag bits");
+  MPG_ARG(opts->min_valid_frac >= 0.0 && opts->min_valid_frac <= 1.0, "mpg_regrid_masked: min_valid_frac must lie in [0, 1]");   // (false for NaN)
+  MPG_ARG(!(opts->flags & MPG_MISSING_VALUE) || opts->missing_value == opts->missing_value, "mpg_regrid_masked: MPG_MISSING_VALUE with a NaN missing_value (use MPG_MISSING_NAN)");
+  int64_t ld;
+  int rc = dst_stride("mpg_regrid_masked", h->n_dst, (int64_t)nlev * nfields, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_apply_masked(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, ld, opts, (hipStream_t)hip_stream);
 }
 
 int mpg_handle_transpose_stats(mpg_handle h, int64_t *n_referenced, int64_t *max_per_source) {

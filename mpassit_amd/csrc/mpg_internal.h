@@ -442,6 +442,9 @@ int mpg_k_pole_fix(mpg_handle_s *h, const void *src, int src_type, int layout, i
 int mpg_k_transpose_build(mpg_handle_s *h, hipStream_t s);
 int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                     hipStream_t s);
+// k_apply_masked.hip: the masked Regrid (include/mpassit_amd.h mpg_regrid_masked_dev; arguments checked by the API entry point); ld as above
+int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type, int64_t ld,
+                       const mpg_mask_opts *opts, hipStream_t s);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);

@@ -34,6 +34,16 @@ module mpg
     real(c_double) :: stand_lon, truelat1, truelat2
     real(c_double) :: dlat_deg, dlon_deg
   end type mpg_proj
+  !> struct mpg_mask_opts (include/mpassit_amd.h): the options of the masked Regrid, mpg_regrid_masked_dev
+  integer(c_int), parameter :: MPG_MISSING_NAN = 1, MPG_MISSING_VALUE = 2
+  type, bind(C) :: mpg_mask_opts
+    integer(c_int) :: flags            !< MPG_MISSING_NAN + MPG_MISSING_VALUE, or 0 (static mask only)
+    real(c_double) :: missing_value    !< with MPG_MISSING_VALUE: an element equal to it is missing
+    type(c_ptr) :: src_mask_dev        !< optional device bytes [n_src], non-zero = never use this source; c_null_ptr: none
+    real(c_double) :: min_valid_frac   !< in [0, 1]
+    real(c_double) :: fill_value       !< what undefined points (unmapped ones included) get
+    real(c_double) :: scale, offset    !< the writer's epilogue, defined points only
+  end type mpg_mask_opts
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -237,6 +247,16 @@ module mpg
       integer(c_int64_t) :: n_referenced, max_per_source
       integer(c_int) :: rc
     end function mpg_handle_transpose_stats
+    ! masked Regrid: missing sources skipped, the valid ones renormalised by Wt / Wv, fill_value elsewhere (weights of the unmasked Store)
+    function mpg_regrid_masked_dev(rh, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, dst_level_stride, opts, hip_stream) &
+      bind(C, name="mpg_regrid_masked_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr, mpg_mask_opts
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, src_layout, nlev, nfields, dst_type
+      integer(c_int64_t), value :: dst_level_stride
+      type(mpg_mask_opts), intent(in) :: opts
+      integer(c_int) :: rc
+    end function mpg_regrid_masked_dev
     function mpg_regrid_bundle_typed_pitched_dev(rh, nfields, src, src_f32, src_layout, nlev, dst, dst_f32, scale, offsets, &
                                                  dst_level_stride, stream) bind(C, name="mpg_regrid_bundle_typed_pitched_dev") result(rc)
       import :: c_int, c_int64_t, c_double, c_ptr

@@ -489,6 +489,57 @@ class RouteHandle:
         check(L.load().mpg_handle_transpose_build_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- masked Regrid: dynamic masking / skipna + na_thres on the unmasked Store's weights ----------------
+    def regrid_masked(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, missing="nan", src_mask=None, min_valid_frac=0.5,
+                      fill_value=float("nan"), out_dtype=None, scale=1.0, offset=0.0, out=None):
+        """mpg_regrid_masked_dev: Regrid from the valid sources only.  A source is invalid when it is statically masked (src_mask:
+        bool / uint8 CUDA tensor of n_src, non-zero = never use) or its value is missing: missing = "nan", a number (a sentinel such
+        as a file's _FillValue), a tuple of both, or None.  With a float32 source a numeric `missing` is rounded to float32 first,
+        so that the file's sentinel compares equal.  A point whose valid weight Wv reaches min_valid_frac of its total weight Wt gets
+        regrid_valid * Wt / Wv (then * scale + offset); every other point, unmapped ones included, gets fill_value.  With nothing
+        missing the result equals regrid_typed's bit for bit on mapped points.
+        src: contiguous float32 / float64 CUDA tensor of nfields * nlev * n_src elements; out may come from empty_pitched."""
+        import torch
+        if not (_is_torch(src) and src.is_cuda and src.is_contiguous() and src.dtype in (torch.float32, torch.float64)):
+            raise ValueError("regrid_masked needs a contiguous float32/float64 CUDA tensor")
+        if src.numel() != nfields * nlev * self.n_src:
+            raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
+        flags, mv = 0, 0.0
+        for item in (missing if isinstance(missing, (tuple, list)) else (missing,)):
+            if item is None:
+                continue
+            if isinstance(item, str):
+                if item.lower() != "nan":
+                    raise ValueError("regrid_masked: missing must be \"nan\", a number, a tuple of both, or None")
+                flags |= L.MISSING_NAN
+            elif np.isnan(float(item)):
+                flags |= L.MISSING_NAN
+            else:
+                if flags & L.MISSING_VALUE:
+                    raise ValueError("regrid_masked: one numeric missing value at most")
+                flags |= L.MISSING_VALUE
+                mv = float(np.float32(item)) if src.dtype == torch.float32 else float(item)
+        mask_ptr = None
+        if src_mask is not None:
+            if not (_is_torch(src_mask) and src_mask.is_cuda and src_mask.is_contiguous() and src_mask.dtype in (torch.bool, torch.uint8)):
+                raise ValueError("regrid_masked: src_mask must be a contiguous bool/uint8 CUDA tensor")
+            if src_mask.numel() != self.n_src:
+                raise ValueError("src_mask has %d elements, handle expects %d" % (src_mask.numel(), self.n_src))
+            mask_ptr = src_mask.data_ptr()
+        out_dtype = out_dtype or src.dtype
+        if out is None:
+            out = torch.empty((nfields, nlev, self.ny_dst, self.nx_dst), dtype=out_dtype, device=src.device)
+        elif not (out.is_cuda and out.dtype in (torch.float32, torch.float64)):
+            raise ValueError("regrid_masked: out must be a float32/float64 CUDA tensor")
+        ld = _level_stride(out, (nfields, nlev), self.ny_dst, self.nx_dst, "regrid_masked")
+        if ld == 0 and out.numel() != nfields * nlev * self.n_dst:
+            raise ValueError("out has %d elements, handle produces %d" % (out.numel(), nfields * nlev * self.n_dst))
+        opts = L.MaskOpts(flags, mv, mask_ptr, float(min_valid_frac), float(fill_value), float(scale), float(offset))
+        _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
+        check(L.regrid_masked_dev(self._h, src.data_ptr(), int(src.dtype == torch.float32), int(layout), int(nlev), int(nfields),
+                                  out.data_ptr(), int(out.dtype == torch.float32), ld, C.byref(opts), torch.cuda.current_stream().cuda_stream))
+        return out
+
     @classmethod
     def from_weights(cls, n_src, nx_dst, ny_dst, row, col, S):
         """Route handle from externally computed weights in ESMF's factorList / factorIndexList form (1-based
