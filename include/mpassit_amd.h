@@ -164,6 +164,37 @@ int mpg_regrid_store(mpg_mesh src, int src_meshloc, mpg_grid dst, int dst_stagge
 /* Grid -> Grid on the same grid, CENTER -> EDGE1/EDGE2 bilinear (interp.F90:298,316). */
 int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc, int regridmethod,
                           mpg_handle *out);
+/* Grid -> Mesh: ESMF_FieldRegridStore(srcField on a Grid stagger, dstField on a Mesh location) -- the call that regrids BACK: a gridded
+ * analysis, a grid-space increment or a model's output on the structured grid interpolated onto the MPAS cells.  (The transpose
+ * Regrid below is the adjoint of a Mesh -> Grid handle and does not regrid back; this Store builds the interpolation itself.)
+ * Source points: the grid's points of src_staggerloc, snx x sny of them (CENTER nx x ny, EDGE1 (nx+1) x ny, EDGE2 nx x (ny+1), CORNER
+ *   (nx+1) x (ny+1)), source index = j * snx + i; any stagger whose coordinates the grid holds (a stagger without coordinates ->
+ *   MPG_ERR_INVALID_ARG).  Destinations: the mesh's cell centres (MPG_MESHLOC_ELEMENT) or vertices (MPG_MESHLOC_NODE).  The handle is
+ *   an ordinary fixed one (MPG_KIND_FIXED), nnz_per_row 4 (bilinear) or 1 (nearest); mpg_handle_info reports n_src = snx * sny,
+ *   n_dst = nx_dst = the mesh count, ny_dst = 1.
+ * MPG_REGRIDMETHOD_BILINEAR: source cells are the quads of four neighbouring stagger points A = (b, a), B = (b, a+1), C = (b+1, a+1),
+ *   D = (b+1, a).  A mesh point belongs to the quad with the lowest quad id b * (snx - 1) + a for which the bilinear map X(xi, eta) = t * P
+ *   has a solution on the point's side of the sphere with xi, eta in [-tol, 1 + tol]; tol = 10^-grid_inside_tol_exp (mpg_tune; default
+ *   1e-10, the Grid -> Grid Store's).  Slots and weights are the Grid -> Grid Store's: A, B, C, D with (1-xi)(1-eta), xi (1-eta), xi eta,
+ *   (1-xi) eta.  A point in no quad is unmapped: idx -1, weights 0, Regrid gives 0.0 (mpg_regrid_masked_dev: fill_value).
+ *   Candidate search, two routes with identical results: on a grid with a usable inverse projection (mpg_grid_create_proj,
+ *   mpg_grid_attach_proj) the quads around the point's own (i, j), within the pad of the other Stores' index boxes; where the inverse
+ *   gives no index, and on every other grid, a descent of a box pyramid over the stagger's quads that tests every leaf quad whose box
+ *   holds the point.  mpg_tune("store_boxes", 0) selects the pyramid everywhere; mpg_handle_store_path reports 1 (index space) or 0.
+ * MPG_REGRIDMETHOD_NEAREST_STOD: the stagger point at the smallest chord distance, the lowest source index on ties; every mesh point
+ *   is mapped.  A pyramid descent, seeded from the inverse projection where there is one.
+ * Refusals.  MPG_ERR_UNSUPPORTED: MPG_REGRIDMETHOD_CONSERVE; bilinear on a grid created with MPG_GRID_PERIODIC_I (pole caps and the i-wrap
+ *   towards a mesh are not built; nearest on such a grid is accepted); a mesh of mpg_mesh_create_window (its resident cells are a window:
+ *   the result would be a partial mesh).  MPG_ERR_OVERFLOW: snx * sny or the mesh count beyond int32.  MPG_ERR_INVALID_ARG: NULL
+ *   objects, unknown enums.
+ * Cached like every Store -- the key carries the direction, so (mesh, loc, grid, stagger, method) of the two directions never collide --
+ *   and paired with one mpg_handle_release; parked entries go when their mesh or grid is destroyed.  mpg_mesh_set_source_window passes
+ *   these handles by: the mesh is their destination, their sources are grid points.  There is no _begin variant.
+ * Everything that takes a fixed handle takes this one: mpg_regrid_dev / _typed[_pitched]_dev / _bundle_typed_dev give [nlev][n_dst] (the
+ *   source layout MPG_LAYOUT_CELL_FAST is the grid's [lev][plane]), mpg_regrid_masked_dev fills mesh points outside the grid and skips
+ *   missing grid values, mpg_regrid_transpose_dev is then the Mesh -> Grid adjoint, and the weight getters, mpg_handle_unique_sources,
+ *   _localize and _rebase work.  mpg_regrid_to_mesh_dev below adds the mesh's own memory order. */
+int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out);
 /* The same two Stores STARTED and not waited for.  interp.F90:207-437 stores its weight sets one after the other, each in front of
  * the Regrids that use it; they are independent of each other and of every Regrid that does not use them.  A _begin call queues
  * the Store on the library's worker thread (own stream, one Store at a time) and returns; the matching mpg_regrid_store[_grid]
@@ -218,7 +249,7 @@ int mpg_regrid_typed_pitched_dev(mpg_handle rh, const void *src_dev, int src_typ
  * A is exactly the operator the forward Regrid of this handle applies: every stored entry with idx >= 0 (weight 1 for nearest
  * neighbour), every CSR entry (mpg_handle_from_weights duplicates included) and the pole caps of a periodic Grid -> Grid handle,
  * whose forward adds w_pole * mean(row): the transpose adds (sum_q w_pole[q] * g[pole_dst[q]]) / row_len to every source of that
- * row.  It is the ADJOINT of the Regrid, not an inverse (A^T A != I): it does not "regrid back".
+ * row.  It is the ADJOINT of the Regrid, not an inverse (A^T A != I): it does not "regrid back" (mpg_regrid_store_to_mesh does).
  * src_dev: grid values [nfields][nlev][plane], plane = n_dst of mpg_handle_info, planes src_level_stride elements apart (0 = dense;
  * below n_dst -> MPG_ERR_INVALID_ARG); a pitched result of the *_pitched_dev calls can be fed back as it is, its pad is never read.
  * dst_dev: nfields slabs of nlev * n_src in dst_layout (MPG_LAYOUT_CELL_FAST [lev][cell], MPG_LAYOUT_LEV_FAST [cell][lev]), n_src
@@ -232,6 +263,23 @@ int mpg_regrid_typed_pitched_dev(mpg_handle rh, const void *src_dev, int src_typ
  * dropped whenever the handle is re-indexed); every later call only enqueues and can be captured in a hipGraph. */
 int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
                              void *dst_dev, int dst_type, int dst_layout, void *hip_stream);
+/* Regrid onto a mesh, in either memory order of a mesh field: grid planes in, a mesh slab out -- the argument order of
+ * mpg_regrid_transpose_dev, plus the typed calls' scale and offset.  The hot path of a Grid -> Mesh handle (mpg_regrid_store_to_mesh); it
+ * is not tied to how the handle was stored: fixed 4-, 3- and 1-slot handles are all accepted.
+ * src_dev: [nfields][nlev][plane], plane = n_src of mpg_handle_info, planes src_level_stride elements apart (0 = dense; below n_src ->
+ * MPG_ERR_INVALID_ARG); a pitched result of the *_pitched_dev calls is accepted as it is, its pad is never read.
+ * dst_dev: nfields slabs of nlev * n_dst in dst_layout: MPG_LAYOUT_CELL_FAST [lev][cell] or MPG_LAYOUT_LEV_FAST [cell][lev] (MPAS file
+ * order: the slab can go into an init or restart file as it is).  Fully overwritten; unmapped points get (dst type)(0.0 * scale + offset).
+ * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type)( regrid(src) * scale + offset ) rounded once
+ * at the store; MPG_TYPE_BE -> MPG_ERR_UNSUPPORTED.  MPG_ERR_UNSUPPORTED too for CSR handles (conservative, from-weights) and for handles
+ * with pole caps.
+ * Contract by identity, no tolerance: with MPG_LAYOUT_CELL_FAST the bytes equal what mpg_regrid_typed_dev(rh, src, src_type,
+ * MPG_LAYOUT_CELL_FAST, nlev, nfields, dst, dst_type, scale, offset, stream) writes on the same handle from a dense source -- slot order,
+ * accumulate expression, unmapped rule and epilogue are the same code; with MPG_LAYOUT_LEV_FAST element [c][k] has the bits of element
+ * [k][c] of that result.  The same bits across calls, across nfields batching and between a pitched and a dense source.  No atomics.
+ * Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a hipGraph from the first call. */
+int mpg_regrid_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
+                           void *dst_dev, int dst_type, int dst_layout, double scale, double offset, void *hip_stream);
 /* diagnostics: sources with at least one entry, and the longest transposed row (builds the transposed index if needed) */
 int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */
@@ -441,7 +489,8 @@ int mpg_handle_unique_sources(mpg_handle rh, int64_t *n_unique, int32_t *ids_hos
  * handle references (first == end: none).  mpg_mesh_set_source_window then declares the window for one mesh location:
  * every handle of that mesh and location -- existing (in use or parked in the cache) and future -- indexes its sources
  * relative to `first`, and Regrid reads source slabs of `count` ids ([nlev][count] / [count][nlev]); mpg_handle_info
- * reports n_src = count.  A handle that references a source outside the window fails the call.  Unlike the two calls
+ * reports n_src = count.  A handle that references a source outside the window fails the call.  Grid -> Mesh handles
+ * (mpg_regrid_store_to_mesh) are not touched: the mesh is their destination.  Unlike the two calls
  * below the handles stay in the Store cache.  The whole mesh (first 0, count nCells / nVertices) resets it. */
 int mpg_handle_source_range(mpg_handle rh, int64_t *first, int64_t *end);
 int mpg_mesh_set_source_window(mpg_mesh mesh, int meshloc, int64_t first, int64_t count);

@@ -23,11 +23,11 @@ SYMBOLS = [
     "mpg_comm_virtual_stats", "mpg_handle_store_stats", "mpg_debug_scan_i32", "mpg_device_count", "mpg_warmup_wait", "mpg_halo_build_owned", "mpg_halo_plan_owned_host",
     "mpg_dst_level_stride", "mpg_regrid_pitched_dev", "mpg_regrid_typed_pitched_dev", "mpg_regrid_bundle_typed_pitched_dev",
     "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes", "mpg_regrid_transpose_dev", "mpg_handle_transpose_stats",
-    "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev",
+    "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev", "mpg_regrid_store_to_mesh", "mpg_regrid_to_mesh_dev",
 ]
 
 MPG_SUCCESS = 0
-MPG_ERR_INVALID_ARG, MPG_ERR_UNSUPPORTED = 2, 4
+MPG_ERR_INVALID_ARG, MPG_ERR_UNSUPPORTED, MPG_ERR_OVERFLOW = 2, 4, 5
 REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE, REGRIDMETHOD_NEAREST_STOD = 0, 1, 2
 MESHLOC_ELEMENT, MESHLOC_NODE = 0, 1
 STAGGERLOC_CENTER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2, STAGGERLOC_CORNER = 0, 1, 2, 3
@@ -56,6 +56,29 @@ def regrid_masked_dev(*args):
     if _masked_fn is None:
         _masked_fn = _MASKED_PROTO(("mpg_regrid_masked_dev", load()))
     return _masked_fn(*args)
+
+
+# The Grid -> Mesh calls with their argument types, bound like the masked Regrid above.
+#   mpg_regrid_store_to_mesh(src grid, src_staggerloc, dst mesh, dst_meshloc, regridmethod, out)
+#   mpg_regrid_to_mesh_dev(rh, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, hip_stream)
+_STORE_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p))
+_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                             C.c_double, C.c_void_p)
+_to_mesh_fns = {}
+
+
+def regrid_store_to_mesh(*args):
+    """The typed binding of mpg_regrid_store_to_mesh; returns the call's status code."""
+    if "store" not in _to_mesh_fns:
+        _to_mesh_fns["store"] = _STORE_TO_MESH_PROTO(("mpg_regrid_store_to_mesh", load()))
+    return _to_mesh_fns["store"](*args)
+
+
+def regrid_to_mesh_dev(*args):
+    """The typed binding of mpg_regrid_to_mesh_dev; returns the call's status code."""
+    if "apply" not in _to_mesh_fns:
+        _to_mesh_fns["apply"] = _TO_MESH_PROTO(("mpg_regrid_to_mesh_dev", load()))
+    return _to_mesh_fns["apply"](*args)
 
 
 _lib = None

@@ -92,6 +92,21 @@ __device__ __forceinline__ double wsum3(double w0, double a, double w1, double b
   return fma(w2, e, fma(w1, b, w0 * a));
 }
 
+// The weighted sum of one point of a fixed-nnz handle in slot order, as every kernel that serves such handles forms it: a copy for
+// nearest neighbour (NNZ 1), wsum3 for the three bilinear weights of a Mesh -> Grid handle, else the fma chain from 0.0 of k_applyN /
+// k_apply_generic_t (four weights of a Grid -> Grid or Grid -> Mesh handle); an unmapped point is +0.0 whatever was loaded for it.
+template <int NNZ>
+__device__ __forceinline__ double wsum_fixed(const double *w, const double *v, bool mapped) {
+  double acc = 0.0;
+  if (NNZ == 1) acc = v[0];
+  else if (NNZ == 3) acc = wsum3(w[0], v[0], w[1], v[1], w[2], v[2]);
+  else {
+#pragma unroll
+    for (int q = 0; q < NNZ; ++q) acc = fma(w[q], v[q], acc);
+  }
+  return mapped ? acc : 0.0;
+}
+
 // A5: signed spherical triangle area (Van Oosterom-Strackee), difference form
 __device__ __forceinline__ double sph_tri_area(dv3 a, dv3 b, dv3 c) {
   double num = det3_from(a, b, c);

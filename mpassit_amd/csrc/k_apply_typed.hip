@@ -333,15 +333,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
 #pragma unroll
       for (int q = 0; q < NNZ; ++q) v[q] = (double)swz<SWZ>(sf[base[q] + k * step], zs);
     };
-    auto combine = [&](const double *v) -> double {
-      double acc = 0.0;
-      if (NNZ == 1) acc = v[0];
-      else {
-#pragma unroll
-        for (int q = 0; q < NNZ; ++q) acc = fma(ww[q], v[q], acc);
-      }
-      return mapped ? acc : 0.0;
-    };
+    auto combine = [&](const double *v) -> double { return wsum_fixed<NNZ>(ww, v, mapped); };   // geom.h: shared with k_apply_to_mesh.hip
     // Two levels per step, and the loads of the NEXT two are issued before the stores of the current two: loads and stores
     // share one in-order counter on gfx950, so a load issued after a store cannot be consumed before that store has been
     // acknowledged -- with the loads in front, a step waits for its own data only (s_waitcnt vmcnt(2): the two stores stay

@@ -133,7 +133,7 @@ void mpg_pool_release() {
 // files); a call that needs a module before the helper got to it simply loads it itself (the runtime serialises that).
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
-  X(k_transpose) X(k_apply_masked)
+  X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -468,6 +468,7 @@ int mpg_grid_destroy(mpg_grid g) {
     g->pyr[st].free();
   }
   g->cellpyr.free();
+  for (int st = 0; st < 4; ++st) g->quadpyr[st].free();
   for (int st = 0; st < 4; ++st) {
     g->lon[st].free();
     g->lat[st].free();
@@ -898,6 +899,55 @@ int mpg_regrid_store_grid_begin(mpg_grid grid, int src_staggerloc, int dst_stagg
   return store_grid_entry(grid, src_staggerloc, dst_staggerloc, regridmethod, nullptr);
 }
 
+// ---- Grid -> Mesh Store (k_store_to_mesh.hip) --------------------------------------------------------------------------------
+// Cache key: (grid, 200 + stagger, mesh, meshloc, method | tolerance | direction bit).  The source object comes first, as in the other
+// keys, so everything that looks for "the handles whose SOURCE is this mesh" -- mpg_mesh_set_source_window, the window offset of
+// mpg_handle_source_range / _unique_sources -- passes these handles by: the mesh is their destination, their sources are grid points.
+// The direction bit keeps the key apart from a Mesh -> Grid key even if a grid and a mesh should ever share an address.
+#define MPG_KEY_TO_MESH (1 << 20)
+static int store_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
+  StoreCtx *x = (StoreCtx *)c;
+  h->method = x->method;
+  return mpg_k_store_to_mesh(x->g, x->stagger, x->m, x->meshloc, x->method, h, s);
+}
+
+int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_to_mesh: NULL argument");
+  MPG_ARG(src_staggerloc >= MPG_STAGGERLOC_CENTER && src_staggerloc <= MPG_STAGGERLOC_CORNER, "mpg_regrid_store_to_mesh: unknown stagger location");
+  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE, "mpg_regrid_store_to_mesh: unknown mesh location");
+  MPG_ARG(regridmethod >= 0 && regridmethod <= 2, "mpg_regrid_store_to_mesh: unknown regrid method");
+  if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
+    mpg_set_error("mpg_regrid_store_to_mesh: conservative Grid -> Mesh regridding is not supported (bilinear and nearest are)");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (regridmethod == MPG_REGRIDMETHOD_BILINEAR && (src->periodic & MPG_GRID_PERIODIC_I)) {
+    mpg_set_error("mpg_regrid_store_to_mesh: bilinear from a periodic grid (MPG_GRID_PERIODIC_I: the i-wrap and the pole caps) is not supported; "
+                  "nearest is");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->geo_grid) {
+    mpg_set_error("mpg_regrid_store_to_mesh: the mesh was cut to a grid (mpg_mesh_create_window): its resident cells are a window and the result "
+                  "would be a partial mesh");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  const int64_t n_src = (int64_t)src->snx[src_staggerloc] * src->sny[src_staggerloc];
+  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
+  if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_to_mesh: %lld source points / %lld mesh points exceed int32 ids", (long long)n_src, (long long)n_dst);
+    return MPG_ERR_OVERFLOW;
+  }
+  if (src->pts[src_staggerloc].n != n_src) {
+    mpg_set_error("mpg_regrid_store_to_mesh: the grid holds no coordinates of stagger %d", src_staggerloc);
+    return MPG_ERR_INVALID_ARG;
+  }
+  StoreCtx ctx{dst, src, src_staggerloc, regridmethod, dst_meshloc};
+  // the inside tolerance in force is part of what a bilinear handle is (as for the Grid -> Grid Store)
+  HandleKey key(src, 200 + src_staggerloc, dst, dst_meshloc,
+                regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 256 * mpg_grid_inside_tol_exp() : 0) + MPG_KEY_TO_MESH);
+  return store_common(key, out, store_to_mesh_build, ctx);
+}
+
 int mpg_handle_release(mpg_handle h) {
   if (!h) return MPG_SUCCESS;
   CACHE_LOCK();
@@ -998,6 +1048,32 @@ int mpg_regrid_transpose_dev(mpg_handle h, const void *src_dev, int src_type, in
   int rc = dst_stride("mpg_regrid_transpose: source", h->n_dst, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_transpose(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
+}
+
+// ---- Regrid onto a mesh in either memory order of a mesh field (k_apply_to_mesh.hip) ------------------------------------------
+int mpg_regrid_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields, void *dst_dev,
+                           int dst_type, int dst_layout, double scale, double offset, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_to_mesh: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_to_mesh: nlev and nfields must be >= 1");
+  MPG_ARG(dst_layout == MPG_LAYOUT_CELL_FAST || dst_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_to_mesh: bad dst_layout");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_to_mesh: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_to_mesh: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->kind != MPG_KIND_FIXED || (h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4)) {
+    mpg_set_error("mpg_regrid_to_mesh: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_to_mesh: handles with pole-cap terms (periodic Grid -> Grid) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  int64_t ld;   // the source's level stride, checked as a destination stride is
+  int rc = dst_stride("mpg_regrid_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_apply_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

@@ -245,6 +245,7 @@ struct mpg_grid_s {
   int snx[4], sny[4];
   Pyramid pyr[4];   // point pyramids (per stagger), built lazily
   Pyramid cellpyr;  // pyramid over CENTER cells bounded by CORNER points (conservative)
+  Pyramid quadpyr[4];   // pyramids over the quads of four neighbouring points of one stagger (Grid -> Mesh bilinear Store), built lazily
   // grids created from a projection (mpg_grid_create_proj) also keep what the output file needs
   bool from_proj = false;
   int proj_code = 0;
@@ -445,6 +446,11 @@ int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, 
 // k_apply_masked.hip: the masked Regrid (include/mpassit_amd.h mpg_regrid_masked_dev; arguments checked by the API entry point); ld as above
 int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type, int64_t ld,
                        const mpg_mask_opts *opts, hipStream_t s);
+// k_store_to_mesh.hip: Grid -> Mesh Store (bilinear: 4 slots, nearest: 1) of the grid's `stagger` points onto the mesh's cells / vertices
+int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s);
+// k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
+int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
+                        double scale, double offset, hipStream_t s);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);

@@ -241,6 +241,25 @@ module mpg
       integer(c_int64_t), value :: src_level_stride
       integer(c_int) :: rc
     end function mpg_regrid_transpose_dev
+    ! Grid -> Mesh: ESMF_FieldRegridStore(srcField on a Grid stagger, dstField on a Mesh location), the Store that regrids back
+    function mpg_regrid_store_to_mesh(src, src_staggerloc, dst, dst_meshloc, regridmethod, rh) &
+        bind(C, name="mpg_regrid_store_to_mesh") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: src_staggerloc, dst_meshloc, regridmethod
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_to_mesh
+    ! ... and its Regrid onto the mesh in either memory order of a mesh field ([lev][cell] or MPAS file order [cell][lev])
+    function mpg_regrid_to_mesh_dev(rh, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, &
+                                    hip_stream) bind(C, name="mpg_regrid_to_mesh_dev") result(rc)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, nfields, dst_type, dst_layout
+      integer(c_int64_t), value :: src_level_stride
+      real(c_double), value :: scale, offset
+      integer(c_int) :: rc
+    end function mpg_regrid_to_mesh_dev
     function mpg_handle_transpose_stats(rh, n_referenced, max_per_source) bind(C, name="mpg_handle_transpose_stats") result(rc)
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: rh

@@ -19,6 +19,7 @@ from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_N
                    check)
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
+           "regrid_store_to_mesh", "regrid_to_mesh_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST"]
 
@@ -476,6 +477,42 @@ class RouteHandle:
                                                 C.c_int(int(out.dtype == torch.float32)), C.c_int(layout), _stream_ptr()))
         return out.cpu().numpy() if host else out
 
+    # -- Grid -> Mesh: the mesh's own memory orders ---------------------------------------------------
+    def regrid_to_mesh(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, out_dtype=None, scale=1.0, offset=0.0, out=None):
+        """mpg_regrid_to_mesh_dev: Regrid of a fixed-nnz handle (regrid_store_to_mesh's, but any 4-, 3- or 1-slot handle) onto its
+        n_dst points in either memory order of a mesh field.  `layout` is the DESTINATION layout: LAYOUT_CELL_FAST returns
+        (nfields, nlev, n_dst) with the bytes of regrid_typed, LAYOUT_LEV_FAST (nfields, n_dst, nlev) -- MPAS file order -- with the
+        same bits transposed.  src: grid values [nfields][nlev][plane of n_src], float32 / float64, a contiguous CUDA tensor or a
+        plane-pitched view (nfields, nlev, ny, nx) / (nlev, ny, nx) as empty_pitched of the handle that produced it makes.
+        dst = cast(regrid(src) * scale + offset), float64 arithmetic."""
+        import torch
+        if not (_is_torch(src) and src.is_cuda and src.dtype in (torch.float32, torch.float64)):
+            raise ValueError("regrid_to_mesh needs a float32/float64 CUDA tensor")
+        if src.is_contiguous():
+            if src.numel() != nfields * nlev * self.n_src:
+                raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
+            ld = 0
+        else:
+            if src.dim() not in (3, 4) or (src.dim() == 3 and nfields != 1):
+                raise ValueError("regrid_to_mesh: a strided source must be (nfields, nlev, ny, nx) or (nlev, ny, nx) with plane-pitched levels")
+            ny, nx = int(src.shape[-2]), int(src.shape[-1])
+            if ny * nx != self.n_src:
+                raise ValueError("source planes have %d points, handle expects %d" % (ny * nx, self.n_src))
+            ld = _level_stride(src, (nfields, nlev) if src.dim() == 4 else (nlev,), ny, nx, "regrid_to_mesh")
+        out_dtype = out_dtype or src.dtype
+        if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+            out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+        shape = (nfields, nlev, self.n_dst) if layout == LAYOUT_CELL_FAST else (nfields, self.n_dst, nlev)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=src.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64) and out.numel() == nfields * nlev * self.n_dst):
+            raise ValueError("regrid_to_mesh: out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_dst))
+        _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
+        check(L.regrid_to_mesh_dev(self._h, src.data_ptr(), int(src.dtype == torch.float32), ld, int(nlev), int(nfields), out.data_ptr(),
+                                   int(out.dtype == torch.float32), int(layout), float(scale), float(offset),
+                                   torch.cuda.current_stream().cuda_stream))
+        return out
+
     def transpose_stats(self):
         """(n_referenced, max_per_source): sources with at least one entry and the longest transposed row
         (mpg_handle_transpose_stats; builds the transposed index if needed)."""
@@ -669,6 +706,42 @@ def regrid_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST):
     """rh.regrid_typed(src) (float32 or float64 CUDA tensor, scale 1, offset 0) as a differentiable torch op: the gradient with
     respect to src is rh.regrid_transpose of the incoming gradient, in src's layout and dtype."""
     return RegridFunction.apply(src, rh, nlev, nfields, layout)
+
+
+if _torch is not None:
+    class RegridToMeshFunction(_torch.autograd.Function):
+        """regrid_to_mesh with a gradient: forward is regrid_to_mesh (scale 1, offset 0) in src's dtype, backward is regrid_transpose
+        of the same handle, fed the incoming gradient in the forward's destination layout.  Use regrid_to_mesh_autograd()."""
+
+        @staticmethod
+        def forward(ctx, src, rh, nlev, nfields, layout):
+            ctx.rh, ctx.nlev, ctx.nfields, ctx.layout = rh, nlev, nfields, layout
+            ctx.src_shape, ctx.src_dtype = src.shape, src.dtype
+            return rh.regrid_to_mesh(src.contiguous(), nlev=nlev, nfields=nfields, layout=layout, out_dtype=src.dtype)
+
+        @staticmethod
+        def backward(ctx, grad):
+            # regrid_transpose reads [nfields][nlev][n_dst] planes: a gradient in [cell][lev] order goes back to [lev][cell] first
+            if ctx.layout == LAYOUT_LEV_FAST:
+                grad = grad.reshape(ctx.nfields, ctx.rh.n_dst, ctx.nlev).transpose(1, 2)
+            g = ctx.rh.regrid_transpose(grad.contiguous(), nlev=ctx.nlev, nfields=ctx.nfields, layout=LAYOUT_CELL_FAST, out_dtype=ctx.src_dtype)
+            return g.reshape(ctx.src_shape), None, None, None, None
+
+
+def regrid_to_mesh_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST):
+    """rh.regrid_to_mesh(src) (float32 or float64 CUDA tensor of [nfields][nlev][n_src] grid values, scale 1, offset 0) as a
+    differentiable torch op; `layout` is the destination layout.  The gradient with respect to src is rh.regrid_transpose of the
+    incoming gradient, in src's shape and dtype."""
+    return RegridToMeshFunction.apply(src, rh, nlev, nfields, layout)
+
+
+def regrid_store_to_mesh(src_grid, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER, meshloc=MESHLOC_ELEMENT):
+    """ESMF_FieldRegridStore(grid field -> mesh field): the grid's `staggerloc` points onto the mesh's cells (MESHLOC_ELEMENT) or
+    vertices (MESHLOC_NODE), bilinear or nearest.  The handle is an ordinary fixed one (n_dst = the mesh count): regrid_typed,
+    regrid_masked, regrid_transpose and the getters work on it, regrid_to_mesh writes the mesh's own memory orders."""
+    h = C.c_void_p()
+    check(L.regrid_store_to_mesh(src_grid._h, int(staggerloc), dst_mesh._h, int(meshloc), int(regridmethod), C.byref(h)))
+    return RouteHandle(h)
 
 
 def regrid_store(src_mesh, dst_grid, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER,
