@@ -93,7 +93,7 @@ __device__ __forceinline__ double wsum3(double w0, double a, double w1, double b
 }
 
 // The weighted sum of one point of a fixed-nnz handle in slot order, as every kernel that serves such handles forms it: a copy for
-// nearest neighbour (NNZ 1), wsum3 for the three bilinear weights of a Mesh -> Grid handle, else the fma chain from 0.0 of k_applyN /
+// nearest neighbour (NNZ 1), wsum3 for the three bilinear weights of a Mesh -> Grid handle, else the fma chain from 0.0 of
 // k_apply_generic_t (four weights of a Grid -> Grid or Grid -> Mesh handle); an unmapped point is +0.0 whatever was loaded for it.
 template <int NNZ>
 __device__ __forceinline__ double wsum_fixed(const double *w, const double *v, bool mapped) {

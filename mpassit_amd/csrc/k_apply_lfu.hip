@@ -716,23 +716,19 @@ static int launch_lfu(mpg_handle_s *h, const void *src, int nlev, int nfields, v
 #endif
 // LFU_NT 512: 64 x 8-point tiles; float32 rows: 35 KB of LDS, four workgroups of eight waves per CU; float64: 70 KB, two
 
-// -> MPG_ERR_UNSUPPORTED when a tile's list does not fit the slab (the caller takes the row gather)
-int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
+// -> MPG_ERR_UNSUPPORTED when a tile's list does not fit the slab (the caller takes the row gather).  epi = false: mpg_regrid_dev
+// (float64 both sides, the result as it stands, sign of zero included), as for mpg_k_apply3_cfu.
+int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, bool epi, double scale,
                            double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
   if (ld == 0) ld = h->n_dst;
   const int sbe = (src_type & MPG_TYPE_BE) != 0, dbe = (dst_type & MPG_TYPE_BE) != 0, sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
   int rc = lfu_build_shape(h, 64, LFU_NT / 64, s, LFU_LIST_PAD);
   if (rc) return rc;
+  if (!epi) return launch_lfu<double, double, LFU_NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, 0, 0, s, tab, ld);
   if (sf32 && df32) return launch_lfu<float, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
   if (sf32) return launch_lfu<float, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
   if (df32) return launch_lfu<double, float, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
   return launch_lfu<double, double, LFU_NT, true>(h, src, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
-}
-int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld) {
-  if (ld == 0) ld = h->n_dst;
-  int rc = lfu_build_shape(h, 64, LFU_NT / 64, s, LFU_LIST_PAD);
-  if (rc) return rc;
-  return launch_lfu<double, double, LFU_NT, false>(h, src, nlev, nfields, dst, 1.0, 0.0, 0, 0, s, FieldTab(), ld);
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

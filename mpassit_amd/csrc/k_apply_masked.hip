@@ -4,7 +4,7 @@
 //     valid(q)  = idx_q >= 0  and  not src_mask[idx_q]  and  src(idx_q, k) not missing
 //     Wt        = w_0 + w_1 + ...                       (stored order, every stored weight)
 //     Wv        = the same sum, 0.0 for every invalid entry
-//     N         = the unmasked kernels' own expression (wsum3 / the fma chains of k_applyN, k_apply1, k_apply_csr) with weight AND
+//     N         = the unmasked kernels' own expression (wsum3 / the fma chains of k_apply_generic_t) with weight AND
 //                 value of every invalid entry replaced by 0.0 -- a missing NaN never enters a product
 //     defined   = Wv > 0 and Wv >= min_valid_frac * Wt
 //     dst       = defined ? (TD) fma(N * (Wt / Wv), scale, offset) : (TD) fill_value
@@ -56,7 +56,7 @@ __device__ __forceinline__ double mk_point(const double (&w)[NNZ], const double 
   else {
     N = 0.0;
 #pragma unroll
-    for (int q = 0; q < NNZ; ++q) N = fma(wk[q], xk[q], N);                        // k_applyN
+    for (int q = 0; q < NNZ; ++q) N = fma(wk[q], xk[q], N);                        // k_apply_generic_t (wsum_fixed)
   }
   return mk_resolve(N, Wt, Wv, m);
 }
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_masked_csr(const int32_t *__restrict__ 
       const double x1 = (double)(LEVF ? sf[cc * nlev + k1] : sf[(int64_t)k1 * nsrc + cc]);
       const bool ok0 = v0 && !mk_missing(x0, m), ok1 = v0 && !mk_missing(x1, m);
       const double w0 = ok0 ? wq : 0.0, w1 = ok1 ? wq : 0.0;
-      a0 = fma(w0, ok0 ? x0 : 0.0, a0);   // k_apply_csr's product and sum pattern
+      a0 = fma(w0, ok0 ? x0 : 0.0, a0);   // the CSR form of k_apply_generic_t: its product and sum pattern
       a1 = fma(w1, ok1 ? x1 : 0.0, a1);
       wv0 += w0;
       wv1 += w1;

@@ -9,20 +9,40 @@
 // HBM traffic per 3-D field drops from 8+8 to 4+4 bytes per source/destination element.  Either side may be
 // big-endian (MPG_TYPE_BE): a NetCDF classic variable is consumed and produced as the file stores it, the byte
 // reversal is a v_perm_b32 in the load / store path (geom.h swz), no swap pass exists.
-//   k_apply3_cf_t     lane gather, cell-fast source (structure of k_apply3_cf, k_apply.hip)
-//   k_apply3_lf_rows  the level-fast row gather on LINEAR tiles -- the default of both entry points for file-order
-//                     sources whose target points share few cells (configuration 4), float32 and float64 rows
-//   k_apply3_lf_t     row gather on grid-row tiles: the capacity fallback (structure of k_apply3_lf)
-//   k_apply_generic_t nearest / 4-point destagger / CSR, one thread per target point
+//   K2  k_apply3_cf       3-point lane gather, source cell-fastest [nlev][ncell] (reference memory order, input_data.F90:653-655),
+//                         destination [nlev][ny][nx]; the default for cell-fast bundles is the LDS-staged k_apply3_cfu of
+//                         k_apply_lfu.hip, this one serves short bundles (2-D fields) and handles whose tiles share no cells
+//   K2' k_apply3_lf_rows  3-point row gather from level-fastest [ncell][nlev] (MPAS file order, input_data.F90:630,645) on
+//                         LINEAR tiles: the reference's host transpose is fused away through an LDS tile transpose -- the
+//                         default for file-order sources whose target points share few cells (configuration 4), else k_apply3_lfu
+//       k_apply3_lf       the same on grid-row tiles: the capacity fallback
+//   K3 / K6 / K4  k_apply_generic_t  nearest-neighbour copy / 4-point destagger (CENTER -> EDGE1/EDGE2) / conservative CSR, one
+//                         thread per target point, two levels in flight
+//       k_apply1, k_applyN<4>  nearest / 4-point with one level in flight: the float64 entry on a cell-fast source (measured faster there)
+// ONE dispatcher, mpg_k_apply_typed at the end of this file, serves every entry point.  mpg_regrid_dev (float64 both sides, no
+// scale or offset) is one more caller of it with epi = false, which selects the EPI = false instances: they leave the epilogue
+// out instead of running it with scale 1 and offset 0, because fma(x, 1.0, 0.0) turns a -0.0 result into +0.0 and that entry
+// point has always stored the float64 result as it stands.  EPI = false exists for <double, double, SWZ = false> only.
+//
+// Roofline: no reuse beyond the ~1.9 target points that share a source value, 5 flop per 36-60 B -> HBM-bound; MFMA does not
+// apply.  Design for CDNA4: 64 consecutive i per wave (512 B coalesced, non-temporal stores so the write stream does not evict
+// the source lines from L2), 2-D target tiles so a workgroup's gather footprint is spatially compact, XCD-aware tile order so
+// neighbouring tiles share an L2, weights/indices SoA and read once per tile for all levels.
 #include <algorithm>
 
 #include "geom.h"
 #include "mpg_internal.h"
 
-template <typename TS, typename TD, bool SWZ>
-__global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__ idx, const double *__restrict__ w,
-                                                     const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
-                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
+// The lane-gather form: a 256-thread workgroup = 64 (i) x 8 (j) target points, two rows per thread; the waves are kept
+// in level lock-step by one barrier per level so that lines shared between neighbouring rows are still in L1/L2 when the
+// next wave asks for them.  Indices and weights are read once per tile and kept in registers for all levels; destination
+// stores are non-temporal.  (Shapes measured in round 1 and dropped from the library in round 3 -- more rows per thread,
+// 8 / 16 waves, level chunks, several fields per workgroup, banded tile order, 16 x 4 / 32 x 2 wave patches: all equal or
+// slower, profiles/r01_sweep_apply*.txt.)
+template <typename TS, typename TD, bool SWZ, bool EPI>
+__global__ __launch_bounds__(256) void k_apply3_cf(const int32_t *__restrict__ idx, const double *__restrict__ w,
+                                                   const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
+                                                   int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
   constexpr int RPT = 2, TY = 4 * RPT;
   const Swz zs = make_swz(sbe), zd = make_swz(dbe);
   int64_t P = (int64_t)nx * ny;
@@ -55,7 +75,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__
   }
   const TS *s = mpg_field_src(tab, src, fld, (int64_t)nlev * nsrc);
   TD *d = mpg_field_dst(tab, dst, fld, (int64_t)nlev * ld);
-  offset = mpg_field_off(tab, fld, offset);
+  if constexpr (EPI) offset = mpg_field_off(tab, fld, offset);
   for (int k = 0; k < nlev; ++k) {
     __syncthreads();
     double v[RPT];
@@ -65,8 +85,11 @@ __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__
       v[r] = wsum3(ww[r][0], a, ww[r][1], b, ww[r][2], e);
     }
 #pragma unroll
-    for (int r = 0; r < RPT; ++r)
-      if (act[r]) stream_store_lane(swz<SWZ>((TD)fma(mapped[r] ? v[r] : 0.0, scale, offset), zd), d + po[r], (unsigned)lane * (unsigned)sizeof(TD));   // geom.h: per lane
+    for (int r = 0; r < RPT; ++r) {
+      double x = mapped[r] ? v[r] : 0.0;
+      if constexpr (EPI) x = fma(x, scale, offset);
+      if (act[r]) stream_store_lane(swz<SWZ>((TD)x, zd), d + po[r], (unsigned)lane * (unsigned)sizeof(TD));   // geom.h: per lane
+    }
     s += nsrc;
     d += ld;
   }
@@ -76,7 +99,7 @@ __global__ __launch_bounds__(256) void k_apply3_cf_t(const int32_t *__restrict__
 // with nlev = 1): the fields take the place of the levels -- a workgroup keeps its 64 x 8 points' indices and weights in registers and
 // walks the bundle's fields, where one launch item per (field, tile) would load those 36 bytes per point once per FIELD to produce 8
 // (the staged kernel did, after building tile lists no 3-D Regrid of a file-order job ever uses: 0.47 + 0.95 ms of a cold
-// configuration-4 job for its 19 diag fields, round 6 timeline).  Arithmetic and epilogue of k_apply3_cf_t: the same bits.
+// configuration-4 job for its 19 diag fields, round 6 timeline).  Arithmetic and epilogue of k_apply3_cf: the same bits.
 template <typename TS, typename TD, bool SWZ>
 __global__ __launch_bounds__(256) void k_apply3_cf_fields(const int32_t *__restrict__ idx, const double *__restrict__ w, int nx, int ny, int ntx,
                                                           double scale, int sbe, int dbe, FieldTab tab) {
@@ -124,10 +147,18 @@ __global__ __launch_bounds__(256) void k_apply3_cf_fields(const int32_t *__restr
   }
 }
 
-template <typename TS, typename TD, bool SWZ>
-__global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__ idx, const double *__restrict__ w,
-                                                     const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
-                                                     int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
+// Level-fastest source ([ncell][nlev], MPAS file order) on tiles of 64 points of ONE grid row: the older row gather, kept as
+// the route for handles the default (k_apply3_lf_rows below: linear tiles, 32-bit row offsets) cannot take -- n_src * nlev >=
+// 2^32 -- and as its cross-check ("lf_variant" 2).
+// phase 0: the tile's 64 x 3 indices/weights are staged in LDS (coalesced);
+// phase 1: wave w serves points 16w..16w+15, lanes = levels: the cell id is wave-uniform (readfirstlane -> scalar row base),
+//          so each gather is one coalesced nlev*sizeof(TS)-byte row read; 4 points (12 loads) in flight;
+// phase 2: lanes = points: contiguous non-temporal stores per level.
+// LDS tile [nlev][65] (row pad 1: conflict-free column writes).
+template <typename TS, typename TD, bool SWZ, bool EPI>
+__global__ __launch_bounds__(256) void k_apply3_lf(const int32_t *__restrict__ idx, const double *__restrict__ w,
+                                                   const TS *__restrict__ src, TD *__restrict__ dst, int nx, int ny, int64_t nsrc,
+                                                   int nlev, int ntx, int nty, double scale, double offset, int sbe, int dbe, FieldTab tab, int64_t ld) {
   extern __shared__ double sw[];    // sw[3][64] | sidx[3][64] | tile[nlev][65] in the DESTINATION type (narrowing at the tile
   int32_t *sidx = (int32_t *)(sw + 192);            // write or at the store gives the same bits; float32 halves the LDS -> 8 WGs / CU)
   TD *tile = (TD *)(sidx + 192);
@@ -150,7 +181,7 @@ __global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__
   }
   __syncthreads();
   const TS *sf = mpg_field_src(tab, src, fld, (int64_t)nlev * nsrc);
-  offset = mpg_field_off(tab, fld, offset);
+  if constexpr (EPI) offset = mpg_field_off(tab, fld, offset);
   for (int kb = 0; kb < nlev; kb += 64) {
     int k = kb + lane;
     bool kact = k < nlev;
@@ -169,7 +200,8 @@ __global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__
         c0 = max(c0, 0); c1 = max(c1, 0); c2 = max(c2, 0);
         const TS *r0 = sf + (int64_t)c0 * nlev, *r1 = sf + (int64_t)c1 * nlev, *r2 = sf + (int64_t)c2 * nlev;
         double a = (double)swz<SWZ>(r0[kk], zs), b = (double)swz<SWZ>(r1[kk], zs), e = (double)swz<SWZ>(r2[kk], zs);
-        v[u] = fma(m ? wsum3(w0, a, w1, b, w2, e) : 0.0, scale, offset);
+        v[u] = m ? wsum3(w0, a, w1, b, w2, e) : 0.0;
+        if constexpr (EPI) v[u] = fma(v[u], scale, offset);
       }
       if (kact) {
 #pragma unroll
@@ -199,7 +231,7 @@ __global__ __launch_bounds__(256) void k_apply3_lf_t(const int32_t *__restrict__
 // hardware's unaligned access mode takes; the lane at the end of a row reads its last two levels and shifts), two points
 // per wavefront pass, results transposed through an LDS tile [nlev][65] in the DESTINATION type (8 workgroups per CU
 // with registers capped at 64); phase 2: lanes = points, non-temporal stores.  EPI = false leaves the affine epilogue
-// out (mpg_regrid_dev: the float64 result as it stands, sign of zero included).  Round 2 measurements behind the shape
+// out (mpg_regrid_dev: the float64 result as it stands, sign of zero included), as in the other gather kernels of this file.  Round 2 measurements behind the shape
 // (unroll, occupancy, fields per workgroup, 16-byte loads): profiles/r02_f32_row_gather.txt.
 typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 typedef double f64x2_u __attribute__((ext_vector_type(2), aligned(8)));
@@ -292,8 +324,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
 // nearest (NNZ = 1, weights implicit), 4-point destagger (NNZ = 4) and CSR (NNZ = 0): one thread per target point.  The
 // fixed forms keep the point's indices and weights in registers for all levels and work on two levels at a time (2 x NNZ
-// independent loads in flight); accumulation order per level as k_applyN / k_apply1 of k_apply.hip -> the same bits.
-template <typename TS, typename TD, bool SWZ, int NNZ, bool LEVF>
+// independent loads in flight); the weighted sum of a level is wsum_fixed (geom.h): a copy for NNZ = 1, the fma chain from 0.0
+// in slot order otherwise.  Stores are non-temporal per lane: a result is written once and never read by this kernel, it must
+// not push the gathered source lines out of L2 (round-5 review, item 6).
+template <typename TS, typename TD, bool SWZ, int NNZ, bool LEVF, bool EPI>
 __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restrict__ idx, const double *__restrict__ w,
                                                          const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                          const double *__restrict__ val, const TS *__restrict__ src,
@@ -307,7 +341,11 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
   if (p >= P) return;
   const TS *sf = mpg_field_src(tab, src, fld, (int64_t)nlev * nsrc);
   TD *df = mpg_field_dst(tab, dst, fld, (int64_t)nlev * ld);
-  offset = mpg_field_off(tab, fld, offset);
+  if constexpr (EPI) offset = mpg_field_off(tab, fld, offset);
+  auto store = [&](int k, double x) {
+    if constexpr (EPI) x = fma(x, scale, offset);
+    stream_store_lane(swz<SWZ>((TD)x, zd), df + (int64_t)k * ld + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD));
+  };
   if constexpr (NNZ == 0) {
     for (int k = 0; k < nlev; ++k) {
       double acc = 0.0;
@@ -315,7 +353,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
         int32_t c = col[q];
         acc = fma(val[q], (double)swz<SWZ>(lev_fast ? sf[(int64_t)c * nlev + k] : sf[(int64_t)k * nsrc + c], zs), acc);
       }
-      stream_store_lane(swz<SWZ>((TD)fma(acc, scale, offset), zd), df + (int64_t)k * ld + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD));
+      store(k, acc);
     }
   } else {
     int32_t c[NNZ];
@@ -338,7 +376,7 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
     // share one in-order counter on gfx950, so a load issued after a store cannot be consumed before that store has been
     // acknowledged -- with the loads in front, a step waits for its own data only (s_waitcnt vmcnt(2): the two stores stay
     // in flight).
-    auto put = [&](int k, const double *v) { stream_store_lane(swz<SWZ>((TD)fma(combine(v), scale, offset), zd), df + (int64_t)k * ld + p, (unsigned)(threadIdx.x & 63) * (unsigned)sizeof(TD)); };
+    auto put = [&](int k, const double *v) { store(k, combine(v)); };
     double a0[NNZ], a1[NNZ];
     level(0, a0);
     level(nlev > 1 ? 1 : 0, a1);
@@ -369,6 +407,54 @@ __global__ __launch_bounds__(256) void k_apply_generic_t(const int32_t *__restri
   }
 }
 
+// The float64 entry (EPI = false) on a CELL-FAST source keeps the plain per-level loop for nearest and 4-point handles: one level
+// in flight, 8 / 36 VGPRs.  Measured against the two-levels-in-flight form above on configuration 4, 13 x 55 levels: nearest
+// 4.51 against 4.93 ms, CENTER -> EDGE1 5.290 against 5.311 ms (profiles/r11_one_dispatcher.md); in file order the form above is
+// 1.4 - 1.9 times faster and serves both entries.  k_apply1 is a pure copy; k_applyN sums in slot order from 0.0 (wsum_fixed).
+__global__ __launch_bounds__(256) void k_apply1(const int32_t *__restrict__ idx, const double *__restrict__ src,
+                                                double *__restrict__ dst, int64_t P, int64_t nsrc, int nlev, int nblk, int64_t ld) {
+  unsigned blk = blockIdx.x % nblk;
+  int fld = blockIdx.x / nblk;
+  int64_t p = (int64_t)blk * 256 + threadIdx.x;
+  if (p >= P) return;
+  int32_t c = idx[p];
+  const double *sf = src + (int64_t)fld * nlev * nsrc + (c >= 0 ? (int64_t)c : 0);
+  double *df = dst + (int64_t)fld * nlev * ld + p;
+  for (int k = 0; k < nlev; ++k) {
+    double v = 0.0;
+    if (c >= 0) v = sf[k * nsrc];
+    stream_store_lane(v, df + (int64_t)k * ld, (unsigned)(threadIdx.x & 63) * 8u);
+  }
+}
+
+template <int NNZ>
+__global__ __launch_bounds__(256) void k_applyN(const int32_t *__restrict__ idx, const double *__restrict__ w,
+                                                const double *__restrict__ src, double *__restrict__ dst, int64_t P,
+                                                int64_t nsrc, int nlev, int nblk, int64_t ld) {
+  unsigned blk = blockIdx.x % nblk;
+  int fld = blockIdx.x / nblk;
+  int64_t p = (int64_t)blk * 256 + threadIdx.x;
+  if (p >= P) return;
+  int64_t c[NNZ];
+  double ww[NNZ];
+#pragma unroll
+  for (int q = 0; q < NNZ; ++q) {
+    c[q] = idx[q * P + p];
+    ww[q] = w[q * P + p];
+  }
+  bool mapped = c[0] >= 0;
+  const double *sf = src + (int64_t)fld * nlev * nsrc;
+  double *df = dst + (int64_t)fld * nlev * ld + p;
+  for (int k = 0; k < nlev; ++k) {
+    double acc = 0.0;
+    if (mapped) {
+#pragma unroll
+      for (int q = 0; q < NNZ; ++q) acc = fma(ww[q], sf[c[q] + k * nsrc], acc);
+    }
+    stream_store_lane(acc, df + (int64_t)k * ld, (unsigned)(threadIdx.x & 63) * 8u);
+  }
+}
+
 // the (field, tile) order of the row gather: bands of 1024 tiles (64 K points, 2.4 MB of indices + weights: they stay in the
 // XCD's L2 from one field of the bundle to the next), all fields of a band before the next band -- 4 % on configuration 4
 #define LF_ROWS_BAND 1024
@@ -379,7 +465,7 @@ static bool lf_rows_fits(const mpg_handle_s *h, size_t dst_size, int nlev) {
   return nlev >= 2 && (uint64_t)h->n_src * (uint64_t)nlev < 0xFFFFFFFFull && lf_rows_lds(dst_size, nlev) <= 160 * 1024;
 }
 
-template <typename TS, typename TD, bool SWZ>
+template <typename TS, typename TD, bool SWZ, bool EPI>
 static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, int nfields, void *dst, double scale, double offset, int sbe,
                         int dbe, hipStream_t s, const FieldTab &tab, int64_t ld) {
   int64_t P = h->n_dst;
@@ -388,7 +474,7 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
     if (lev_fast && mpg_lf_variant() != MPG_LF_ROWTILES && lf_rows_fits(h, sizeof(TD), nlev)) {
       const size_t lds = std::min<size_t>(lf_rows_lds(sizeof(TD), nlev) + (size_t)mpg_staged_lds_pad_kb() * 1024, 160 * 1024);   // the pad: A/B knob, 0 in production
       const unsigned ntile = (unsigned)((P + 63) / 64);
-      auto fn = k_apply3_lf_rows<TS, TD, sizeof(TS) == 4 ? 2 : 1, true, SWZ>;   // measured: unroll 2 for float32 rows, 1 for float64
+      auto fn = k_apply3_lf_rows<TS, TD, sizeof(TS) == 4 ? 2 : 1, EPI, SWZ>;   // measured: unroll 2 for float32 rows, 1 for float64
       if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, P, h->n_src, nlev, ntile, scale, offset, sbe, dbe, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, tab, ld);
     } else if (lev_fast) {
@@ -397,15 +483,15 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
         mpg_set_error("Regrid(LEV_FAST): %d levels exceed the LDS tile", nlev);
         return MPG_ERR_UNSUPPORTED;
       }
-      auto fn = k_apply3_lf_t<TS, TD, SWZ>;
+      auto fn = k_apply3_lf<TS, TD, SWZ, EPI>;
       if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int ntxs = mpg_tile_ntx(h->nx_dst, 64), nty = h->ny_dst;
       fn<<<(unsigned)ntxs * nty * nfields, 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst, h->ny_dst, h->n_src, nlev, ntxs, nty,
                                                          scale, offset, sbe, dbe, tab, ld);
     } else {
       int ntx = mpg_tile_ntx(h->nx_dst, 64), nty = (h->ny_dst + 7) / 8;
-      k_apply3_cf_t<TS, TD, SWZ><<<(unsigned)ntx * nty * nfields, 256, 0, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst, h->ny_dst,
-                                                                              h->n_src, nlev, ntx, nty, scale, offset, sbe, dbe, tab, ld);
+      k_apply3_cf<TS, TD, SWZ, EPI><<<(unsigned)ntx * nty * nfields, 256, 0, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, h->nx_dst, h->ny_dst,
+                                                                                 h->n_src, nlev, ntx, nty, scale, offset, sbe, dbe, tab, ld);
     }
   } else {
     int nblk = (int)((P + 255) / 256);
@@ -414,8 +500,16 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
       mpg_set_error("Regrid: unsupported handle (%d weights per row)", nnz);
       return MPG_ERR_UNSUPPORTED;
     }
-    auto fn = lev_fast ? (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, true> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, true> : k_apply_generic_t<TS, TD, SWZ, 4, true>))
-                       : (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, false> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, false> : k_apply_generic_t<TS, TD, SWZ, 4, false>));
+    if constexpr (!EPI) {   // float64 both sides (mpg_k_apply_typed checks it): the plain loops above on a cell-fast source
+      if (!lev_fast && nnz != 0) {
+        if (nnz == 1) k_apply1<<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, (const double *)src, (double *)dst, P, h->n_src, nlev, nblk, ld);
+        else k_applyN<4><<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, (const double *)src, (double *)dst, P, h->n_src, nlev, nblk, ld);
+        MPG_HIP(hipGetLastError());
+        return MPG_SUCCESS;
+      }
+    }
+    auto fn = lev_fast ? (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, true, EPI> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, true, EPI> : k_apply_generic_t<TS, TD, SWZ, 4, true, EPI>))
+                       : (nnz == 0 ? k_apply_generic_t<TS, TD, SWZ, 0, false, EPI> : (nnz == 1 ? k_apply_generic_t<TS, TD, SWZ, 1, false, EPI> : k_apply_generic_t<TS, TD, SWZ, 4, false, EPI>));
     fn<<<(unsigned)nblk * nfields, 256, 0, s>>>(h->idx.p, h->w.p, h->rowptr.p, h->col.p, h->val.p, (const TS *)src, (TD *)dst, P, h->n_src, nlev,
                                                nblk, scale, offset, sbe, dbe, tab, ld);
   }
@@ -423,32 +517,21 @@ static int launch_typed(mpg_handle_s *h, const void *src, int layout, int nlev, 
   return MPG_SUCCESS;
 }
 
-// float64 rows in, float64 out, no epilogue: the level-fast row gather of mpg_regrid_dev (k_apply.hip).
-// -> MPG_ERR_UNSUPPORTED when the 32-bit row offsets or the LDS tile do not fit (the caller keeps its older kernel).
-int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld) {
-  const int64_t P = h->n_dst;
-  if (ld == 0) ld = P;
-  if (!lf_rows_fits(h, sizeof(double), nlev)) return MPG_ERR_UNSUPPORTED;
-  const size_t lds = lf_rows_lds(sizeof(double), nlev);
-  const unsigned ntile = (unsigned)((P + 63) / 64);
-  auto fn = k_apply3_lf_rows<double, double, 1, false, false>;
-  if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  fn<<<ntile * (unsigned)nfields, 256, lds, s>>>(h->idx.p, h->w.p, src, dst, P, h->n_src, nlev, ntile, 1.0, 0.0, 0, 0, mpg_field_band(LF_ROWS_BAND), g_lf_rows_store, FieldTab(), ld);
-  MPG_HIP(hipGetLastError());
-  return MPG_SUCCESS;
-}
-
 template <bool SWZ>
 static int launch_typed_types(mpg_handle_s *h, const void *src, int sf32, int layout, int nlev, int nfields, void *dst, int df32, double scale,
                               double offset, int sbe, int dbe, hipStream_t s, const FieldTab &tab, int64_t ld) {
-  if (sf32 && df32) return launch_typed<float, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
-  if (sf32) return launch_typed<float, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
-  if (df32) return launch_typed<double, float, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
-  return launch_typed<double, double, SWZ>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (sf32 && df32) return launch_typed<float, float, SWZ, true>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (sf32) return launch_typed<float, double, SWZ, true>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  if (df32) return launch_typed<double, float, SWZ, true>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
+  return launch_typed<double, double, SWZ, true>(h, src, layout, nlev, nfields, dst, scale, offset, sbe, dbe, s, tab, ld);
 }
 
 int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
-                      double scale, double offset, hipStream_t s, const FieldTab &tab, int64_t ld) {
+                      double scale, double offset, hipStream_t s, const FieldTab &tab, int64_t ld, bool epi) {
+  if (!epi && (src_type != MPG_TYPE_F64 || dst_type != MPG_TYPE_F64 || tab.n || scale != 1.0 || offset != 0.0)) {
+    mpg_set_error("Regrid: the epilogue can be left out for float64 on both sides, scale 1, offset 0 and consecutive fields only");
+    return MPG_ERR_INVALID_ARG;
+  }
   if (h->n_dst == 0 || nlev == 0 || nfields == 0) return MPG_SUCCESS;
   if (ld == 0) ld = h->n_dst;
   const int sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
@@ -494,7 +577,7 @@ int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout
       if (!fits) staged = -2;
     }
     if (staged >= 0) {
-      rc = mpg_k_apply3_cfu(h, staged, src, sf32, nlev, nfields, dst, df32, true, scale, offset, s, tab, ld);
+      rc = mpg_k_apply3_cfu(h, staged, src, sf32, nlev, nfields, dst, df32, epi, scale, offset, s, tab, ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
   }
@@ -505,15 +588,16 @@ int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout
       if (long_bundle && (rc = mpg_lfu_auto(h, s, &lfv))) return rc;
     }
     if (lfv == MPG_LF_STAGED) {
-      rc = mpg_k_apply3_lfu_typed(h, src, src_type, nlev, nfields, dst, dst_type, scale, offset, s, tab, ld);
+      rc = mpg_k_apply3_lfu_typed(h, src, src_type, nlev, nfields, dst, dst_type, epi, scale, offset, s, tab, ld);
       if (rc != MPG_ERR_UNSUPPORTED) return rc;
     }
   }
-  int rc = (sbe || dbe) ? launch_typed_types<true>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, sbe, dbe, s, tab, ld)
-                        : launch_typed_types<false>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, 0, 0, s, tab, ld);
+  int rc = !epi         ? launch_typed<double, double, false, false>(h, src, layout, nlev, nfields, dst, scale, offset, 0, 0, s, tab, ld)
+           : (sbe || dbe) ? launch_typed_types<true>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, sbe, dbe, s, tab, ld)
+                          : launch_typed_types<false>(h, src, sf32, layout, nlev, nfields, dst, df32, scale, offset, 0, 0, s, tab, ld);
   if (rc == MPG_SUCCESS && h->n_pole) rc = mpg_k_pole_fix(h, src, src_type, layout, nlev, nfields, dst, dst_type, scale, offset, s, tab, ld);
   return rc;
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)
-const void *mpg_anchor_k_apply_typed() { return (const void *)&k_apply3_cf_t<float, float, false>; }
+const void *mpg_anchor_k_apply_typed() { return (const void *)&k_apply3_cf<float, float, false, true>; }

@@ -4,8 +4,8 @@
 // lat-lon target grid with a pole node whose value is the mean of the neighbouring CENTER row.  The CENTER ->
 // EDGE2 destaggering (interp.F90:316-327) therefore has destination points (the V rows at the poles) whose
 // factor list holds the whole source row.  Those few points are not worth a CSR route for the whole handle:
-// the handle stays 4-point (k_applyN<4>) and this kernel rewrites the cap points afterwards as
-//   dst = sum_k w_k * src[idx_k]  (k_applyN's accumulation order)  +  w_pole * mean(row).
+// the handle stays 4-point (k_apply_generic_t<..., 4, ...>) and this kernel rewrites the cap points afterwards as
+//   dst = sum_k w_k * src[idx_k]  (wsum_fixed<4>, geom.h: the accumulation order of k_apply_generic_t)  +  w_pole * mean(row).
 // One workgroup per (field, level): both row means are reduced in a fixed order (strided partial sums, then an
 // LDS tree), so the result does not depend on scheduling.
 #include "geom.h"

@@ -4,13 +4,13 @@
 //   ESMF_FieldRegridStore / Regrid  UMASS(CENTER) -> U(EDGE1)                 interp.F90:295-311
 //   ESMF_FieldRegridStore / Regrid  VMASS(CENTER) -> V(EDGE2)                 interp.F90:313-328
 //
-// The reference (and this library until round 5: k_rotate + 2 x k_applyN<4>) makes three passes: the rotation reads and
+// The reference (and this library until round 5: k_rotate + two 4-point Regrids) makes three passes: the rotation reads and
 // rewrites both mass fields, each destaggering reads one of them again.  u/v_target_grid_nostag are intermediates the
 // reference never writes to its file (write_data.F90 has no `nostag`), so here the earth-relative mass winds are read ONCE:
 // a workgroup owns 64 x 16 points of the (i, j) index space, stages the (64 + 2 + WD_A - 1) x (16 + 2) window of mass points
 // around them in LDS -- rotated on the way in, with the operation sequence of interp.F90:737-748 (no contraction, as
 // k_rotate: bit-identical) -- and combines every U point (EDGE1, nx + 1 columns) and every V point (EDGE2, ny + 1 rows) of
-// its tile from there with the 4-point weights of the two Grid -> Grid handles, in k_applyN's accumulation order (the same
+// its tile from there with the 4-point weights of the two Grid -> Grid handles, in the 4-point Regrid's accumulation order (wsum_fixed<4>, geom.h) (the same
 // bits as the three-pass chain).  Algorithmic bytes per level: 2 x 8 B read + 2 x e_dst written per mass point (+ 2 x 48 B
 // of indices and weights and 16 B of rotation angles per point, once per launch) against 4 x 8 + 2 x (8 + e_dst) before.
 //
@@ -22,7 +22,7 @@
 // Generality: the handles are ordinary Grid -> Grid handles (k_store_gridbil.hip); a point whose four sources do not all
 // lie in its tile's window (none on the grids of the Store above; kept for handles of other origin) is combined from global
 // memory after the level loop.  Periodic grids (global lat-lon, no rotation there: interp.F90:291 asks for PROJ_LC) wrap
-// the window's columns; their pole caps are rewritten afterwards by k_pole_fix exactly as after k_applyN.
+// the window's columns; their pole caps are rewritten afterwards by k_pole_fix exactly as after a 4-point Regrid.
 #pragma clang fp contract(off)
 #include "geom.h"
 #include "mpg_internal.h"
@@ -356,7 +356,7 @@ int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa,
   else if (dst_type & MPG_TYPE_F32) rc = launch_wind<float, true>(a, rot, nwg, s);
   else rc = launch_wind<double, true>(a, rot, nwg, s);
   if (rc) return rc;
-  // pole caps of a periodic grid: rewritten from the (unrotated) mass field exactly as after k_applyN
+  // pole caps of a periodic grid: rewritten from the (unrotated) mass field exactly as after a 4-point Regrid
   if (h1 && h1->n_pole && (rc = mpg_k_pole_fix(h1, um, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, u, dst_type, 1.0, 0.0, s, FieldTab(), ld))) return rc;
   if (h2 && h2->n_pole && (rc = mpg_k_pole_fix(h2, vm, MPG_TYPE_F64, MPG_LAYOUT_CELL_FAST, nlev, 1, v, dst_type, 1.0, 0.0, s, FieldTab(), ld))) return rc;
   return MPG_SUCCESS;

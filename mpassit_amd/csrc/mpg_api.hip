@@ -1011,7 +1011,8 @@ int mpg_regrid_pitched_dev(mpg_handle h, const double *src_dev, int src_layout, 
   int64_t ld;
   int rc = dst_stride("mpg_regrid", h->n_dst, (int64_t)nlev * nfields, 8, dst_level_stride, &ld);
   if (rc) return rc;
-  return mpg_k_apply(h, src_dev, src_layout, nlev, nfields, dst_dev, (hipStream_t)hip_stream, ld);
+  return mpg_k_apply_typed(h, src_dev, MPG_TYPE_F64, src_layout, nlev, nfields, dst_dev, MPG_TYPE_F64, 1.0, 0.0, (hipStream_t)hip_stream, FieldTab(), ld,
+                           /*epi=*/false);
 }
 
 int mpg_regrid_typed_dev(mpg_handle h, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev,
@@ -1162,8 +1163,9 @@ int mpg_regrid(mpg_handle h, const double *src_host, int src_layout, int nlev, i
   MPG_CHECK_INIT();
   MPG_ARG(h && src_host && dst_host, "mpg_regrid: NULL argument");
   MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid: nlev and nfields must be >= 1");
-  // float64 in, float64 out through the chunked upload / kernel / download pipeline (mpg_hostpipe.hip); same kernels and
-  // the same bits as mpg_regrid_dev
+  // float64 in, float64 out through the chunked upload / kernel / download pipeline (mpg_hostpipe.hip): the kernels of
+  // mpg_regrid_dev WITH the affine epilogue (scale 1, offset 0), so the same values, and the same bits but for the sign of a zero
+  // result: fma(-0.0, 1.0, 0.0) is +0.0, a -0.0 that mpg_regrid_dev stores as it stands comes back as +0.0 here
   return mpg_regrid_typed(h, src_host, 0, src_layout, nlev, nfields, dst_host, 0, 1.0, 0.0);
 }
 

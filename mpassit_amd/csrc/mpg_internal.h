@@ -382,10 +382,6 @@ int mpg_k_store_nearest(mpg_mesh_s *m, mpg_grid_s *g, int stagger, mpg_handle_s 
 int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s);
 int mpg_k_store_grid_bilinear(mpg_grid_s *g, int dst_stagger, mpg_handle_s *h, hipStream_t s);
 int mpg_k_build_bvh(mpg_mesh_s *m, hipStream_t s, bool whole = true);
-// Destination level stride `ld` of the Regrid launchers below: level plane k of field f starts at (f * nlev + k) * ld elements (a bundle
-// given as a FieldTab: plane k of field f at tab.dst[f] + k * ld).  0 = dense (ld = n_dst); elements [n_dst, ld) of a plane are
-// never written.  The API entry points check ld >= n_dst and that nfields * nlev * ld bytes are addressable.
-int mpg_k_apply(mpg_handle_s *h, const double *src, int layout, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
 // nplanes planes of P elements of esz bytes, ld elements apart, set to zero (a handle that maps nothing); the pad stays as it is
 int mpg_zero_planes(void *dst, size_t esz, int64_t P, int64_t nplanes, int64_t ld, hipStream_t s);
 // The fields of a bundle as separate allocations (mpg_regrid_bundle_typed_dev: an ESMF field bundle holds separate arrays): up
@@ -411,9 +407,14 @@ __device__ __forceinline__ TD *mpg_field_dst(const FieldTab &t, TD *dst, int f, 
   return t.n ? (TD *)t.dst[f] : dst + (int64_t)f * slab;
 }
 __device__ __forceinline__ double mpg_field_off(const FieldTab &t, int f, double offset) { return t.n ? t.off[f] : offset; }
-// src_type / dst_type below: MPG_TYPE_F64 / MPG_TYPE_F32, optionally | MPG_TYPE_BE (include/mpassit_amd.h)
+// Destination level stride `ld` of the Regrid launchers below: level plane k of field f starts at (f * nlev + k) * ld elements (a bundle
+// given as a FieldTab: plane k of field f at tab.dst[f] + k * ld).  0 = dense (ld = n_dst); elements [n_dst, ld) of a plane are
+// never written.  The API entry points check ld >= n_dst and that nfields * nlev * ld bytes are addressable.
+// The one Regrid dispatcher.  src_type / dst_type below: MPG_TYPE_F64 / MPG_TYPE_F32, optionally | MPG_TYPE_BE (include/mpassit_amd.h).
+// epi = false (mpg_regrid_dev; both types MPG_TYPE_F64, scale 1, offset 0, no FieldTab, else MPG_ERR_INVALID_ARG): the same choices,
+// kernels without the affine epilogue, so that the float64 result is stored as it stands (fma(x, 1, 0) would turn a -0.0 into +0.0).
 int mpg_k_apply_typed(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type,
-                      double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
+                      double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0, bool epi = true);
 // "lf_variant" numbering of the level-fast 3-point Regrid
 enum { MPG_LF_ROWS = 0, MPG_LF_STAGED = 1, MPG_LF_ROWTILES = 2 };
 #ifndef MPG_LF_STAGED_DEFAULT
@@ -426,10 +427,8 @@ enum { MPG_LF_ROWS = 0, MPG_LF_STAGED = 1, MPG_LF_ROWTILES = 2 };
 int mpg_cfu_num_variants();
 int mpg_k_apply3_cfu(mpg_handle_s *h, int variant, const void *src, int src_f32, int nlev, int nfields, void *dst, int dst_f32, bool epi,
                      double scale, double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
-int mpg_k_apply3_lfu(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
-int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
+int mpg_k_apply3_lfu_typed(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, bool epi, double scale,
                            double offset, hipStream_t s, const FieldTab &tab = FieldTab(), int64_t ld = 0);
-int mpg_k_apply3_lf_rows(mpg_handle_s *h, const double *src, int nlev, int nfields, double *dst, hipStream_t s, int64_t ld = 0);
 int mpg_a3_staged();  // current "a3_staged" knob
 int mpg_lf_variant(); // current "lf_variant" knob
 int mpg_lfu_build_shape(mpg_handle_s *h, int txu, int tyu, hipStream_t s);  // tile lists for txu x tyu-point tiles (cached per handle)

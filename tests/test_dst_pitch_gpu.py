@@ -101,7 +101,7 @@ def test_file_order_f32_every_kernel(case, gpu_lib, be):
     src = case["lf64"].to(torch.float32)
     src = _be(torch, src) if be else src
     try:
-        for lfv in (0, 2, 1):                # k_apply3_lf_rows, k_apply3_lf_t, the staged k_apply3_lfu
+        for lfv in (0, 2, 1):                # k_apply3_lf_rows, k_apply3_lf, the staged k_apply3_lfu
             gpu_lib.tune("lf_variant", lfv)
             _both(torch, rh, lambda o: rh.regrid_typed(src.view(-1), nlev=nlev, nfields=nf, layout=R.LAYOUT_LEV_FAST, out_dtype=torch.float32,
                                                        src_be=be, dst_be=be, out=o), (nf, nlev), torch.float32, "file order f32 be=%s lf_variant %d" % (be, lfv))
