@@ -193,7 +193,8 @@ int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc,
  * Everything that takes a fixed handle takes this one: mpg_regrid_dev / _typed[_pitched]_dev / _bundle_typed_dev give [nlev][n_dst] (the
  *   source layout MPG_LAYOUT_CELL_FAST is the grid's [lev][plane]), mpg_regrid_masked_dev fills mesh points outside the grid and skips
  *   missing grid values, mpg_regrid_transpose_dev is then the Mesh -> Grid adjoint, and the weight getters, mpg_handle_unique_sources,
- *   _localize and _rebase work.  mpg_regrid_to_mesh_dev below adds the mesh's own memory order. */
+ *   _localize and _rebase work.  mpg_regrid_to_mesh_dev below adds the mesh's own memory order.  The conservative method has a
+ *   Store of its own, with its normalisation argument: mpg_regrid_store_conserve_to_mesh. */
 int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out);
 /* The same two Stores STARTED and not waited for.  interp.F90:207-437 stores its weight sets one after the other, each in front of
  * the Regrids that use it; they are independent of each other and of every Regrid that does not use them.  A _begin call queues
@@ -277,9 +278,52 @@ int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, i
  * MPG_LAYOUT_CELL_FAST, nlev, nfields, dst, dst_type, scale, offset, stream) writes on the same handle from a dense source -- slot order,
  * accumulate expression, unmapped rule and epilogue are the same code; with MPG_LAYOUT_LEV_FAST element [c][k] has the bits of element
  * [k][c] of that result.  The same bits across calls, across nfields batching and between a pitched and a dense source.  No atomics.
- * Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a hipGraph from the first call. */
+ * Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a hipGraph from the first call.
+ * CSR handles are served by mpg_regrid_csr_to_mesh_dev. */
 int mpg_regrid_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
                            void *dst_dev, int dst_type, int dst_layout, double scale, double offset, void *hip_stream);
+/* Conservative Store onto a mesh: ESMF_FieldRegridStore(regridmethod=CONSERVE, normType=) with a Grid as the source and a Mesh's elements
+ * as the destination -- snow, precipitation, increments of extensive quantities taken back to the MPAS cells with their integral kept.
+ * Source polygons are the grid's cells, the four CORNER points around centre (i, j), source index = j * nx + i, n_src = nx * ny (a grid
+ *   without CORNER coordinates -> MPG_ERR_INVALID_ARG).  Destination polygons are the mesh's Voronoi cells from verticesOnCell;
+ *   mpg_handle_info reports n_dst = nx_dst = nCells, ny_dst = 1.  I(c, g), the area of cell c inside grid cell g, is the very number
+ *   the Mesh -> Grid conservative Store computes (great-circle sides, the same clip and the same area code, no floating-point
+ *   contraction); area(c) is the cell polygon's own area by the same triangle fan.
+ * Weights, rows keyed by mesh cell.  MPG_NORM_DSTAREA (ESMF's default normType): w = I / area(c) -- a partly covered cell gets coverage
+ *   times mean.  MPG_NORM_FRACAREA: w = I / sum_g I -- a partly covered cell gets the mean of its covered part.  An entry is dropped when
+ *   I <= 1e-14 * area(c) (the sliver rule of the Mesh -> Grid Store, applied to this destination).  An uncovered cell has an empty row:
+ *   Regrid gives 0.0.  The dst fraction frac(c) = sum_g I / area(c), summed in ascending g (0 for an uncovered cell), stays on the device
+ *   with the handle; mpg_handle_get_dst_frac copies its n_dst values to the host (MPG_ERR_INVALID_ARG on a handle that has none).
+ *   This is NOT the transpose of the Mesh -> Grid handle: with A[g][c] = I / area(g) this matrix is B = D_c^-1 A^T D_g.
+ * The handle is an ordinary CSR one (nnz_per_row 0, method conservative), columns ascending within a row, the same bytes from run to run.
+ *   Both candidate routes -- index boxes on a grid with an inverse projection, the pyramid walk otherwise or under
+ *   mpg_tune("store_boxes", 0) -- give identical handles; grids created with MPG_GRID_PERIODIC_I are accepted (collapsed pole sides
+ *   bound nothing).  mpg_handle_store_stats, _store_path and _store_ms are filled as for the Mesh -> Grid Store.
+ * Refusals.  MPG_ERR_UNSUPPORTED: a mesh of mpg_mesh_create_window; maxEdges > 12.  MPG_ERR_OVERFLOW: ids or entries beyond int32; a
+ *   clipped polygon that outgrew its vertex slots (a non-convex cell).  MPG_ERR_INVALID_ARG: NULL arguments, unknown norm_type.
+ * Cached like every Store, the key carrying the direction and norm_type (the two normalisations are two handles, and neither collides
+ *   with a Mesh -> Grid key of the same pair); parked entries go when their mesh or grid is destroyed; mpg_mesh_set_source_window
+ *   passes these handles by.  There is no _begin variant.  Everything that takes a CSR handle takes this one: mpg_regrid_typed[_pitched]_dev
+ *   ([lev][cell]), mpg_regrid_masked_dev, mpg_regrid_transpose_dev, mpg_handle_get_csr; mpg_regrid_csr_to_mesh_dev below adds the mesh's
+ *   own memory order. */
+enum { MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1 };
+int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type, mpg_handle *out);
+int mpg_handle_get_dst_frac(mpg_handle rh, double *frac_host);   /* [n_dst]; MPG_ERR_INVALID_ARG on a handle that has none */
+/* CSR Regrid in mesh order: the arguments of mpg_regrid_to_mesh_dev with the same meaning -- grid planes [nfields][nlev][plane], plane =
+ * n_src, src_level_stride elements apart (0 = dense; below n_src -> MPG_ERR_INVALID_ARG; the pad is never read), out a slab of
+ * nlev * n_dst per field in MPG_LAYOUT_CELL_FAST [lev][cell] or MPG_LAYOUT_LEV_FAST [cell][lev], MPG_TYPE_F64 / MPG_TYPE_F32 on either
+ * side, float64 arithmetic, dst = (dst type) fma(x, scale, offset) rounded once at the store.  Accepts ANY CSR handle without pole caps:
+ * mpg_regrid_store_conserve_to_mesh's, a Mesh -> Grid conservative one, one of mpg_handle_from_weights (an ESMF weight file).
+ * Refusals.  MPG_ERR_UNSUPPORTED: a fixed handle (mpg_regrid_to_mesh_dev serves those); MPG_TYPE_BE.  MPG_ERR_INVALID_ARG: a stride
+ * below the plane, a bad layout, nlev < 1, NULL.
+ * Contract by identity, no tolerance: a row's value is acc = fma(val[q], src[col[q]], acc) from 0.0 in stored order, then the epilogue
+ * -- the expression of the typed Regrid's CSR kernel -- so with MPG_LAYOUT_CELL_FAST the bytes equal what mpg_regrid_typed_dev writes on
+ * the same handle from a dense source, and with MPG_LAYOUT_LEV_FAST element [c][k] has the bits of element [k][c] of that result; an
+ * empty row gives (dst type)(0.0 * scale + offset).  The same bits across calls, across nfields batching and between a pitched and a
+ * dense source.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a
+ * hipGraph from the first call. */
+int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
+                               void *dst_dev, int dst_type, int dst_layout, double scale, double offset, void *hip_stream);
 /* diagnostics: sources with at least one entry, and the longest transposed row (builds the transposed index if needed) */
 int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */

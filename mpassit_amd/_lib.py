@@ -24,6 +24,7 @@ SYMBOLS = [
     "mpg_dst_level_stride", "mpg_regrid_pitched_dev", "mpg_regrid_typed_pitched_dev", "mpg_regrid_bundle_typed_pitched_dev",
     "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes", "mpg_regrid_transpose_dev", "mpg_handle_transpose_stats",
     "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev", "mpg_regrid_store_to_mesh", "mpg_regrid_to_mesh_dev",
+    "mpg_regrid_store_conserve_to_mesh", "mpg_handle_get_dst_frac", "mpg_regrid_csr_to_mesh_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -35,6 +36,8 @@ LAYOUT_CELL_FAST, LAYOUT_LEV_FAST = 0, 1
 GRID_PERIODIC_I, GRID_NO_SOUTH_POLE, GRID_NO_NORTH_POLE = 1, 2, 4
 
 MISSING_NAN, MISSING_VALUE = 1, 2
+MPG_NORM_DSTAREA, MPG_NORM_FRACAREA = 0, 1
+NORM_DSTAREA, NORM_FRACAREA = MPG_NORM_DSTAREA, MPG_NORM_FRACAREA
 
 
 class MaskOpts(C.Structure):
@@ -79,6 +82,37 @@ def regrid_to_mesh_dev(*args):
     if "apply" not in _to_mesh_fns:
         _to_mesh_fns["apply"] = _TO_MESH_PROTO(("mpg_regrid_to_mesh_dev", load()))
     return _to_mesh_fns["apply"](*args)
+
+
+# The conservative Grid -> Mesh calls, bound the same way.
+#   mpg_regrid_store_conserve_to_mesh(src grid, dst mesh, norm_type, out)
+#   mpg_handle_get_dst_frac(rh, frac_host)
+#   mpg_regrid_csr_to_mesh_dev(rh, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, hip_stream)
+_STORE_CONSERVE_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p))
+_DST_FRAC_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
+_CSR_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                 C.c_double, C.c_void_p)
+
+
+def regrid_store_conserve_to_mesh(*args):
+    """The typed binding of mpg_regrid_store_conserve_to_mesh; returns the call's status code."""
+    if "cstore" not in _to_mesh_fns:
+        _to_mesh_fns["cstore"] = _STORE_CONSERVE_TO_MESH_PROTO(("mpg_regrid_store_conserve_to_mesh", load()))
+    return _to_mesh_fns["cstore"](*args)
+
+
+def handle_get_dst_frac(*args):
+    """The typed binding of mpg_handle_get_dst_frac; returns the call's status code."""
+    if "frac" not in _to_mesh_fns:
+        _to_mesh_fns["frac"] = _DST_FRAC_PROTO(("mpg_handle_get_dst_frac", load()))
+    return _to_mesh_fns["frac"](*args)
+
+
+def regrid_csr_to_mesh_dev(*args):
+    """The typed binding of mpg_regrid_csr_to_mesh_dev; returns the call's status code."""
+    if "capply" not in _to_mesh_fns:
+        _to_mesh_fns["capply"] = _CSR_TO_MESH_PROTO(("mpg_regrid_csr_to_mesh_dev", load()))
+    return _to_mesh_fns["capply"](*args)
 
 
 _lib = None

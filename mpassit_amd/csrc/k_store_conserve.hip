@@ -509,6 +509,9 @@ __device__ __forceinline__ int clip_halfspace_lds(int n, const LdsPoly &L, dv3 n
   }
   return m;
 }
+// RAW = false: Mesh -> Grid, pair_val = I / area(grid cell) above the sliver threshold (else 0) and the grid cell's counter bumped.
+// RAW = true: Grid -> Mesh, pair_val = I itself -- the same polygon, the same area, the other direction normalises by the mesh cell.
+template <bool RAW>
 __global__ __launch_bounds__(CLIP_NT) void k_conserve_clip_pairs(int64_t npairs, const int32_t *__restrict__ pair_c, const int32_t *__restrict__ pair_p,
                                                                  int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
                                                                  const double *__restrict__ vy, const double *__restrict__ vz,
@@ -577,12 +580,16 @@ __global__ __launch_bounds__(CLIP_NT) void k_conserve_clip_pairs(int64_t npairs,
       ar = sa > 0.0 ? sa : 0.0;
     }
   }
-  double ratio = 0.0;
-  if (ar > 1e-14 * aq) {
-    ratio = ar / aq;
-    atomicAdd(&count[p], 1);
+  if constexpr (RAW) {
+    pair_val[t] = ar;
+  } else {
+    double ratio = 0.0;
+    if (ar > 1e-14 * aq) {
+      ratio = ar / aq;
+      atomicAdd(&count[p], 1);
+    }
+    pair_val[t] = ratio;
   }
-  pair_val[t] = ratio;
   if (trunc) atomicOr(truncated, 1);
 }
 __global__ __launch_bounds__(256) void k_conserve_scatter_pairs(int64_t npairs, const int32_t *__restrict__ pair_c, const int32_t *__restrict__ pair_p,
@@ -599,41 +606,29 @@ __global__ __launch_bounds__(256) void k_conserve_scatter_pairs(int64_t npairs, 
   val[rowptr[p] + slot] = r;
 }
 
-int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s) {
-  int rc;
-  PointSet &cor = g->pts[MPG_STAGGERLOC_CORNER];
-  int nx = g->nx, ny = g->ny;
-  int64_t P = (int64_t)nx * ny;
-  if (cor.n != (int64_t)(nx + 1) * (ny + 1)) {
-    mpg_set_error("conservative RegridStore needs CORNER-stagger coordinates on the destination grid");
-    return MPG_ERR_INVALID_ARG;
-  }
-  if (m->maxEdges > CONS_MAXV) {
-    mpg_set_error("conservative RegridStore: maxEdges %d > %d", m->maxEdges, CONS_MAXV);
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (!g->cellpyr.built && (rc = mpg_k_build_cell_pyramid(cor, nx, ny, g->cellpyr, s))) return rc;
-  h->kind = MPG_KIND_CSR;
-  h->nnz_per_row = 0;
-  h->n_src = m->nCells;
-  h->n_dst = P;
-  h->nx_dst = nx;
-  h->ny_dst = ny;
-  TmpBuf<int32_t> count, cnt_src, tmp_dst, ovf, n_ovf, npair, poff, pair_c, pair_p;
+// Everything the two directions share: the candidate passes, the pair list grouped by mesh cell (pairs of cell c at
+// [poff[c], poff[c + 1]) of pair_c / pair_p) and the clip.  raw = false: pair_val holds the Mesh -> Grid weights and `count` the entries
+// per grid cell; raw = true: pair_val holds the intersection areas.
+struct ConsPairs {
+  TmpBuf<int32_t> count, cnt_src, tmp_dst, ovf, n_ovf, npair, poff, pair_c, pair_p, spill, bigq, truncated;
   TmpBuf<double> qarea, qsph, pair_val;
   TmpBuf<uint8_t> flip;
-  // source cells = the rows of the mesh's geometry window (all of them unless the mesh was cut to this grid, mpg_mesh_create_window);
-  // the kernels number them 0 .. nC - 1, vertex coordinates are reached through pointers biased by the window's first vertex
+  TmpBuf<float> vij;
+  int32_t npairs = 0, novf = 0, nbig = 0;
+  int cb = 0;
+};
+static int conserve_pairs(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s, bool raw, ConsPairs &X) {
+  int rc;
+  PointSet &cor = g->pts[MPG_STAGGERLOC_CORNER];
+  const int nx = g->nx, ny = g->ny;
+  const int64_t P = (int64_t)nx * ny;
+  TmpBuf<int32_t> &count = X.count, &cnt_src = X.cnt_src, &tmp_dst = X.tmp_dst, &ovf = X.ovf, &n_ovf = X.n_ovf, &npair = X.npair, &poff = X.poff,
+                  &pair_c = X.pair_c, &pair_p = X.pair_p;
+  TmpBuf<double> &qarea = X.qarea, &qsph = X.qsph, &pair_val = X.pair_val;
+  TmpBuf<uint8_t> &flip = X.flip;
   const int64_t nC = m->cwn;
   const double *vx = m->vx_g(), *vy = m->vy_g(), *vz = m->vz_g();
-  if (nC == 0) {   // a window without cells (the grid lies off the mesh): the empty matrix
-    if ((rc = h->rowptr.alloc((size_t)P + 1)) || (rc = h->col.alloc(1)) || (rc = h->val.alloc(1))) return rc;
-    MPG_HIP(hipMemsetAsync(h->rowptr.p, 0, sizeof(int32_t) * (P + 1), s));
-    MPG_HIP(hipStreamSynchronize(s));
-    h->nnz = 0;
-    return MPG_SUCCESS;
-  }
-  if ((rc = count.alloc((size_t)P + 1, s)) || (rc = h->rowptr.alloc((size_t)P + 1)) || (rc = qarea.alloc((size_t)P, s)) || (rc = qsph.alloc(4 * (size_t)P, s)) ||
+  if ((!raw && (rc = count.alloc((size_t)P + 1, s))) || (rc = qarea.alloc((size_t)P, s)) || (rc = qsph.alloc(4 * (size_t)P, s)) ||
       (rc = cnt_src.alloc((size_t)nC, s)) || (rc = tmp_dst.alloc((size_t)nC * CAND_CAP, s)) || (rc = ovf.alloc((size_t)nC, s)) || (rc = n_ovf.alloc(5, s)) ||
       (rc = npair.alloc((size_t)nC + 1, s)) || (rc = poff.alloc((size_t)nC + 1, s)) || (rc = flip.alloc((size_t)nC, s)))
     return rc;
@@ -641,12 +636,12 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
                                                                   // [3] polygons the count pass walked for, [4] lists the list pass copied (statistics)
   MPG_HIP(hipMemsetAsync(cnt_src.p, 0, sizeof(int32_t) * (size_t)nC, s));  // degenerate cells leave early
   MPG_HIP(hipMemsetAsync(flip.p, 0, (size_t)nC, s));
-  MPG_HIP(hipMemsetAsync(count.p, 0, sizeof(int32_t) * (P + 1), s));
+  if (!raw) MPG_HIP(hipMemsetAsync(count.p, 0, sizeof(int32_t) * (P + 1), s));
   unsigned nb = (unsigned)((nC + 127) / 128);
   PyramidView pv = mpg_pyr_view(g->cellpyr);
   // a grid built from its projection: the vertices' places in its index space (one inverse projection per vertex, shared by the
   // three cells around it) give every polygon its candidate cells in O(1); "store_boxes" 0 keeps the pyramid walk (A/B)
-  TmpBuf<float> vij;
+  TmpBuf<float> &vij = X.vij;
   const float *vijp = nullptr;
   if (mpg_grid_has_inverse(g, MPG_STAGGERLOC_CORNER) && mpg_store_boxes() && m->vwn > 0) {
     if ((rc = vij.alloc(2 * (size_t)m->vwn, s))) return rc;
@@ -659,14 +654,14 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
   // the spill areas of the overflow list's first slots (CONS_SPILL candidates each): filled by the candidate pass for polygons it
   // can enumerate from their index boxes, by the cooperative count pass for the others
   const int spill_cap = (int)std::min<int64_t>(nC, 1 << 16);
-  TmpBuf<int32_t> spill, bigq;
+  TmpBuf<int32_t> &spill = X.spill, &bigq = X.bigq;
   if ((rc = spill.alloc((size_t)spill_cap * CONS_SPILL, s)) || (rc = bigq.alloc((size_t)spill_cap, s))) return rc;
   k_conserve_raster<3><<<nb, 128, 0, s>>>(nC, m->maxEdges, m->voc.p, vx, vy, vz, pv, nx, ny, cor.x.p, cor.y.p, cor.z.p,
                                         qarea.p, qsph.p, cnt_src.p, tmp_dst.p, ovf.p, n_ovf.p, flip.p, nullptr, vijp ? bigq.p : nullptr, nullptr, vijp,
                                         (float)mpg_grid_box_pad_coef(g), (float)mpg_grid_box_pad_latlon(g), (float)mpg_grid_box_emax(g), spill.p, spill_cap);
   if (m->max_valence < 0) k_max_valence<<<(unsigned)std::min<int64_t>((nC + 255) / 256, 2048), 256, 0, s>>>(nC, m->maxEdges, m->voc.p, n_ovf.p + 1);
   MPG_HIP(hipGetLastError());
-  int32_t novf = 0, hv[3] = {0, 0, 0};
+  int32_t &novf = X.novf, hv[3] = {0, 0, 0};
   MPG_HIP(hipMemcpyAsync(hv, n_ovf.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   MPG_HIP(hipStreamSynchronize(s));
   novf = hv[0];
@@ -689,7 +684,7 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
   k_conserve_clamp_counts<<<(unsigned)((nC + 256) / 256), 256, 0, s>>>(nC, cnt_src.p, npair.p);
   if ((rc = mpg_scan_excl_i32(npair.p, poff.p, nC + 1, s))) return rc;
   // the pair count twice -- the int32 scan's last entry and a 64-bit sum (the scan could wrap more than once) -- in ONE round trip
-  int32_t npairs = 0;
+  int32_t &npairs = X.npairs;
   long long total = 0;
   {
     TmpBuf<long long> tot;
@@ -715,18 +710,58 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
   // polygon otherwise), so the cells' largest vertex count + 4 is all that can be used; 24 bytes x 64 lanes each, and the slots
   // decide how many wavefronts a CU holds (10 slots: ten, 16: six -- configuration 4's clip 1.55 -> 1.3 ms from 12 to 10)
   const int nv = std::max(3, std::min(m->max_valence, m->maxEdges));
-  const int cb = nv + 4 < CONS_BUF ? nv + 4 : CONS_BUF;
+  const int cb = X.cb = nv + 4 < CONS_BUF ? nv + 4 : CONS_BUF;
   const size_t clip_lds_bytes = sizeof(double) * cb * 3 * CLIP_NT;
-  if (clip_lds_bytes > 48 * 1024)
-    MPG_HIP(hipFuncSetAttribute((const void *)k_conserve_clip_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clip_lds_bytes));
-  TmpBuf<int32_t> truncated;
+  auto clip = raw ? k_conserve_clip_pairs<true> : k_conserve_clip_pairs<false>;
+  if (clip_lds_bytes > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)clip, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clip_lds_bytes));
+  TmpBuf<int32_t> &truncated = X.truncated;
   if ((rc = truncated.alloc(1, s))) return rc;
   MPG_HIP(hipMemsetAsync(truncated.p, 0, sizeof(int32_t), s));
   if (npairs > 0)
-    k_conserve_clip_pairs<<<(unsigned)(((int64_t)npairs + CLIP_NT - 1) / CLIP_NT), CLIP_NT, clip_lds_bytes, s>>>(
+    clip<<<(unsigned)(((int64_t)npairs + CLIP_NT - 1) / CLIP_NT), CLIP_NT, clip_lds_bytes, s>>>(
         npairs, pair_c.p, pair_p.p, m->maxEdges, m->voc.p, vx, vy, vz, flip.p, nx, cor.x.p, cor.y.p, cor.z.p, qarea.p, cb,
-        pair_val.p, count.p, truncated.p);
+        pair_val.p, raw ? nullptr : count.p, truncated.p);
   MPG_HIP(hipGetLastError());
+  X.nbig = std::min(hv[2], spill_cap);
+  return MPG_SUCCESS;
+}
+
+int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s) {
+  int rc;
+  PointSet &cor = g->pts[MPG_STAGGERLOC_CORNER];
+  int nx = g->nx, ny = g->ny;
+  int64_t P = (int64_t)nx * ny;
+  if (cor.n != (int64_t)(nx + 1) * (ny + 1)) {
+    mpg_set_error("conservative RegridStore needs CORNER-stagger coordinates on the destination grid");
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (m->maxEdges > CONS_MAXV) {
+    mpg_set_error("conservative RegridStore: maxEdges %d > %d", m->maxEdges, CONS_MAXV);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (!g->cellpyr.built && (rc = mpg_k_build_cell_pyramid(cor, nx, ny, g->cellpyr, s))) return rc;
+  h->kind = MPG_KIND_CSR;
+  h->nnz_per_row = 0;
+  h->n_src = m->nCells;
+  h->n_dst = P;
+  h->nx_dst = nx;
+  h->ny_dst = ny;
+  // source cells = the rows of the mesh's geometry window (all of them unless the mesh was cut to this grid, mpg_mesh_create_window);
+  // the kernels number them 0 .. nC - 1, vertex coordinates are reached through pointers biased by the window's first vertex
+  const int64_t nC = m->cwn;
+  if (nC == 0) {   // a window without cells (the grid lies off the mesh): the empty matrix
+    if ((rc = h->rowptr.alloc((size_t)P + 1)) || (rc = h->col.alloc(1)) || (rc = h->val.alloc(1))) return rc;
+    MPG_HIP(hipMemsetAsync(h->rowptr.p, 0, sizeof(int32_t) * (P + 1), s));
+    MPG_HIP(hipStreamSynchronize(s));
+    h->nnz = 0;
+    return MPG_SUCCESS;
+  }
+  ConsPairs X;
+  if ((rc = h->rowptr.alloc((size_t)P + 1)) || (rc = conserve_pairs(m, g, h, s, false, X))) return rc;
+  TmpBuf<int32_t> &count = X.count, &n_ovf = X.n_ovf, &truncated = X.truncated, &pair_c = X.pair_c, &pair_p = X.pair_p;
+  TmpBuf<double> &pair_val = X.pair_val;
+  const int32_t npairs = X.npairs, novf = X.novf;
+  const int cb = X.cb;
   if ((rc = mpg_scan_excl_i32(count.p, h->rowptr.p, P + 1, s))) return rc;
   int32_t nnz = 0, was_truncated = 0, hs[5] = {0, 0, 0, 0, 0};
   MPG_HIP(hipMemcpyAsync(hs, n_ovf.p, sizeof(hs), hipMemcpyDeviceToHost, s));
@@ -744,7 +779,7 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
   h->nnz = nnz;
   // mpg_handle_store_stats: [1] pairs clipped, [2] polygons that outgrew their list, [3] polygons enumerated by a wavefront,
   // [4] polygons the cooperative count pass walked the pyramid for, [5] lists copied from the spill area, [6] polygon slots of the clip
-  h->store_stats[1] = npairs; h->store_stats[2] = novf; h->store_stats[3] = std::min(hv[2], spill_cap); h->store_stats[4] = hs[3];
+  h->store_stats[1] = npairs; h->store_stats[2] = novf; h->store_stats[3] = X.nbig; h->store_stats[4] = hs[3];
   h->store_stats[5] = hs[4]; h->store_stats[6] = cb;
   if ((rc = h->col.alloc((size_t)nnz + 1)) || (rc = h->val.alloc((size_t)nnz + 1))) return rc;
   MPG_HIP(hipMemsetAsync(count.p, 0, sizeof(int32_t) * (P + 1), s));
@@ -752,6 +787,141 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
     k_conserve_scatter_pairs<<<(unsigned)(((int64_t)npairs + 255) / 256), 256, 0, s>>>(npairs, pair_c.p, pair_p.p, pair_val.p, h->rowptr.p, count.p,
                                                                                       h->col.p, h->val.p, (int32_t)m->cw0);
   k_csr_sort_rows<<<(unsigned)((P + 255) / 256), 256, 0, s>>>(P, h->rowptr.p, h->col.p, h->val.p);
+  MPG_HIP(hipGetLastError());
+  MPG_HIP(hipStreamSynchronize(s));
+  return MPG_SUCCESS;
+}
+
+// ---- Grid -> Mesh (mpg_regrid_store_conserve_to_mesh) ------------------------------------------------------------------------
+// The same intersections I(c, g), rows keyed by mesh cell: w = I / area(c) (MPG_NORM_DSTAREA) or I / sum_g I (MPG_NORM_FRACAREA).
+// The pair list is grouped by mesh cell already, so a row is made by ONE thread from its own run of pairs: count the entries above the
+// sliver threshold, scan, then insert them in ascending grid index -- no atomics, and the stored bytes do not depend on the order in
+// which the cooperative passes happened to list a cell's pairs.
+// area(c): the fan of the cell's vertices in listed order, as the candidate pass forms it, its sign dropped
+__device__ __forceinline__ double cell_fan_area(int64_t c, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
+                                                const double *__restrict__ vy, const double *__restrict__ vz) {
+  dv3 first = dv3{0, 0, 0}, prev = first;
+  int n = 0;
+  double area = 0.0;
+  for (int j = 0; j < maxEdges && n < CONS_MAXV; ++j) {
+    const int32_t v = voc[c * maxEdges + j];
+    if (v <= 0) continue;
+    const dv3 x = dv3{vx[v - 1], vy[v - 1], vz[v - 1]};
+    if (n == 0) first = x;
+    else if (n >= 2) area += sph_tri_area(first, prev, x);
+    prev = x;
+    ++n;
+  }
+  return n < 3 ? 0.0 : fabs(area);
+}
+__global__ __launch_bounds__(256) void k_conserve_tm_count(int64_t nCells, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
+                                                           const double *__restrict__ vy, const double *__restrict__ vz,
+                                                           const int32_t *__restrict__ poff, const double *__restrict__ pair_val,
+                                                           double *__restrict__ carea, int32_t *__restrict__ cnt) {
+  const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (c > nCells) return;
+  if (c == nCells) {   // the scan's extra element
+    cnt[c] = 0;
+    return;
+  }
+  const double a = cell_fan_area(c, maxEdges, voc, vx, vy, vz);
+  carea[c] = a;
+  int n = 0;
+  if (a > 0.0)
+    for (int t = poff[c]; t < poff[c + 1]; ++t) n += pair_val[t] > 1e-14 * a;
+  cnt[c] = n;
+}
+__global__ __launch_bounds__(256) void k_conserve_tm_rows(int64_t nCells, const int32_t *__restrict__ poff, const int32_t *__restrict__ pair_p,
+                                                          const double *__restrict__ pair_val, const double *__restrict__ carea,
+                                                          const int32_t *__restrict__ rowptr, int norm_type, int32_t *__restrict__ col,
+                                                          double *__restrict__ val, double *__restrict__ frac) {
+  const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (c >= nCells) return;
+  const double a = carea[c];
+  const int b = rowptr[c], e = rowptr[c + 1];
+  if (e == b) {
+    frac[c] = 0.0;
+    return;
+  }
+  int n = 0;
+  for (int t = poff[c]; t < poff[c + 1]; ++t) {
+    const double I = pair_val[t];
+    if (!(I > 1e-14 * a)) continue;
+    const int32_t g = pair_p[t];
+    int j = b + n - 1;
+    while (j >= b && col[j] > g) {
+      col[j + 1] = col[j];
+      val[j + 1] = val[j];
+      --j;
+    }
+    col[j + 1] = g;
+    val[j + 1] = I;
+    ++n;
+  }
+  double sum = 0.0;
+  for (int q = b; q < e; ++q) sum += val[q];   // ascending grid index
+  frac[c] = sum / a;
+  const double d = norm_type == MPG_NORM_FRACAREA ? sum : a;
+  for (int q = b; q < e; ++q) val[q] = val[q] / d;
+}
+
+int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s) {
+  int rc;
+  PointSet &cor = g->pts[MPG_STAGGERLOC_CORNER];
+  const int nx = g->nx, ny = g->ny;
+  if (cor.n != (int64_t)(nx + 1) * (ny + 1)) {
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: a conservative Store needs CORNER-stagger coordinates on the source grid");
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (m->maxEdges > CONS_MAXV) {
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: maxEdges %d > %d", m->maxEdges, CONS_MAXV);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (!g->cellpyr.built && (rc = mpg_k_build_cell_pyramid(cor, nx, ny, g->cellpyr, s))) return rc;
+  const int64_t nC = m->nCells;   // (window meshes are refused by the entry point: every cell is resident)
+  h->kind = MPG_KIND_CSR;
+  h->nnz_per_row = 0;
+  h->n_src = (int64_t)nx * ny;
+  h->n_dst = nC;
+  h->nx_dst = (int)nC;
+  h->ny_dst = 1;
+  if ((rc = h->rowptr.alloc((size_t)nC + 1)) || (rc = h->dst_frac.alloc((size_t)std::max<int64_t>(nC, 1)))) return rc;
+  if (nC == 0) {
+    MPG_HIP(hipMemsetAsync(h->rowptr.p, 0, sizeof(int32_t), s));
+    MPG_HIP(hipStreamSynchronize(s));
+    if ((rc = h->col.alloc(1)) || (rc = h->val.alloc(1))) return rc;
+    h->nnz = 0;
+    return MPG_SUCCESS;
+  }
+  ConsPairs X;
+  if ((rc = conserve_pairs(m, g, h, s, true, X))) return rc;
+  TmpBuf<double> carea;
+  TmpBuf<int32_t> cnt;
+  if ((rc = carea.alloc((size_t)nC, s)) || (rc = cnt.alloc((size_t)nC + 1, s))) return rc;
+  const double *vx = m->vx_g(), *vy = m->vy_g(), *vz = m->vz_g();
+  k_conserve_tm_count<<<(unsigned)((nC + 256) / 256), 256, 0, s>>>(nC, m->maxEdges, m->voc.p, vx, vy, vz, X.poff.p, X.pair_val.p, carea.p, cnt.p);
+  MPG_HIP(hipGetLastError());
+  if ((rc = mpg_scan_excl_i32(cnt.p, h->rowptr.p, nC + 1, s))) return rc;
+  int32_t nnz = 0, was_truncated = 0, hs[5] = {0, 0, 0, 0, 0};
+  MPG_HIP(hipMemcpyAsync(hs, X.n_ovf.p, sizeof(hs), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipMemcpyAsync(&nnz, h->rowptr.p + nC, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipMemcpyAsync(&was_truncated, X.truncated.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipStreamSynchronize(s));
+  if (was_truncated) {
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: a clipped polygon outgrew its %d vertex slots (a non-convex mesh cell?)", X.cb);
+    return MPG_ERR_OVERFLOW;
+  }
+  if (nnz < 0) {   // (at most one entry per pair, and the pairs were counted in 64 bits)
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: the weight matrix exceeds 2^31 entries");
+    return MPG_ERR_OVERFLOW;
+  }
+  h->nnz = nnz;
+  // mpg_handle_store_stats: as the Mesh -> Grid Store's
+  h->store_stats[1] = X.npairs; h->store_stats[2] = X.novf; h->store_stats[3] = X.nbig; h->store_stats[4] = hs[3];
+  h->store_stats[5] = hs[4]; h->store_stats[6] = X.cb;
+  if ((rc = h->col.alloc((size_t)nnz + 1)) || (rc = h->val.alloc((size_t)nnz + 1))) return rc;
+  k_conserve_tm_rows<<<(unsigned)((nC + 255) / 256), 256, 0, s>>>(nC, X.poff.p, X.pair_p.p, X.pair_val.p, carea.p, h->rowptr.p, norm_type, h->col.p,
+                                                                  h->val.p, h->dst_frac.p);
   MPG_HIP(hipGetLastError());
   MPG_HIP(hipStreamSynchronize(s));
   return MPG_SUCCESS;

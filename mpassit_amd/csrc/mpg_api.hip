@@ -133,7 +133,7 @@ void mpg_pool_release() {
 // files); a call that needs a module before the helper got to it simply loads it itself (the runtime serialises that).
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
-  X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh)
+  X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -572,6 +572,7 @@ static void handle_free(mpg_handle_s *h) {
   h->rowptr.free();
   h->col.free();
   h->val.free();
+  h->dst_frac.free();
   h->pole_dst.free();
   h->pole_src0.free();
   h->pole_w.free();
@@ -918,7 +919,8 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
   MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE, "mpg_regrid_store_to_mesh: unknown mesh location");
   MPG_ARG(regridmethod >= 0 && regridmethod <= 2, "mpg_regrid_store_to_mesh: unknown regrid method");
   if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
-    mpg_set_error("mpg_regrid_store_to_mesh: conservative Grid -> Mesh regridding is not supported (bilinear and nearest are)");
+    mpg_set_error("mpg_regrid_store_to_mesh: conservative Grid -> Mesh regridding is not supported (bilinear and nearest are). "
+                  "mpg_regrid_store_conserve_to_mesh is the conservative Store, with its normalisation argument.");
     return MPG_ERR_UNSUPPORTED;
   }
   if (regridmethod == MPG_REGRIDMETHOD_BILINEAR && (src->periodic & MPG_GRID_PERIODIC_I)) {
@@ -946,6 +948,44 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
   HandleKey key(src, 200 + src_staggerloc, dst, dst_meshloc,
                 regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 256 * mpg_grid_inside_tol_exp() : 0) + MPG_KEY_TO_MESH);
   return store_common(key, out, store_to_mesh_build, ctx);
+}
+
+// ---- conservative Grid -> Mesh Store (k_store_conserve.hip) ---------------------------------------------------------------------
+// Cache key: the Grid -> Mesh key of the CENTER stagger and the element location with the method MPG_REGRIDMETHOD_CONSERVE -- which
+// mpg_regrid_store_to_mesh refuses, so no key of that call has it -- plus 256 * norm_type and the direction bit.
+static int store_conserve_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
+  StoreCtx *x = (StoreCtx *)c;
+  h->method = MPG_REGRIDMETHOD_CONSERVE;
+  return mpg_k_store_conserve_to_mesh(x->g, x->m, x->method, h, s);   // (ctx.method carries the normalisation)
+}
+
+int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_conserve_to_mesh: NULL argument");
+  MPG_ARG(norm_type == MPG_NORM_DSTAREA || norm_type == MPG_NORM_FRACAREA,
+          "mpg_regrid_store_conserve_to_mesh: norm_type must be MPG_NORM_DSTAREA or MPG_NORM_FRACAREA");
+  if (dst->geo_grid) {
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: the mesh was cut to a grid (mpg_mesh_create_window): its resident cells are a window and the "
+                  "result would be a partial mesh");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->nCells > 0x7fffffffLL || (int64_t)src->nx * src->ny > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_conserve_to_mesh: %lld grid cells / %lld mesh cells exceed int32 ids", (long long)src->nx * src->ny,
+                  (long long)dst->nCells);
+    return MPG_ERR_OVERFLOW;
+  }
+  StoreCtx ctx{dst, src, MPG_STAGGERLOC_CENTER, norm_type, MPG_MESHLOC_ELEMENT};
+  HandleKey key(src, 200 + MPG_STAGGERLOC_CENTER, dst, MPG_MESHLOC_ELEMENT, MPG_REGRIDMETHOD_CONSERVE + 256 * norm_type + MPG_KEY_TO_MESH);
+  return store_common(key, out, store_conserve_to_mesh_build, ctx);
+}
+
+int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && frac_host, "mpg_handle_get_dst_frac: NULL argument");
+  MPG_ARG(h->dst_frac.p, "mpg_handle_get_dst_frac: the handle has no destination fraction (mpg_regrid_store_conserve_to_mesh stores one)");
+  MPG_HIP(hipStreamSynchronize(g_stream));
+  if (h->n_dst > 0) MPG_HIP(hipMemcpy(frac_host, h->dst_frac.p, sizeof(double) * (size_t)h->n_dst, hipMemcpyDeviceToHost));
+  return MPG_SUCCESS;
 }
 
 int mpg_handle_release(mpg_handle h) {
@@ -1064,7 +1104,8 @@ int mpg_regrid_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int6
     return MPG_ERR_UNSUPPORTED;
   }
   if (h->kind != MPG_KIND_FIXED || (h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4)) {
-    mpg_set_error("mpg_regrid_to_mesh: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are");
+    mpg_set_error("mpg_regrid_to_mesh: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
+                  "mpg_regrid_csr_to_mesh_dev serves CSR handles.");
     return MPG_ERR_UNSUPPORTED;
   }
   if (h->n_pole > 0) {
@@ -1075,6 +1116,32 @@ int mpg_regrid_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int6
   int rc = dst_stride("mpg_regrid_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_apply_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
+}
+
+// ---- Regrid of a CSR handle onto a mesh in either memory order (k_apply_csr_to_mesh.hip) -------------------------------------------
+int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields, void *dst_dev,
+                               int dst_type, int dst_layout, double scale, double offset, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_csr_to_mesh: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_csr_to_mesh: nlev and nfields must be >= 1");
+  MPG_ARG(dst_layout == MPG_LAYOUT_CELL_FAST || dst_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_csr_to_mesh: bad dst_layout");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_csr_to_mesh: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_csr_to_mesh: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->kind != MPG_KIND_CSR) {
+    mpg_set_error("mpg_regrid_csr_to_mesh: fixed 1-, 3- and 4-slot handles are served by mpg_regrid_to_mesh_dev; this call takes CSR handles");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_csr_to_mesh: handles with pole-cap terms are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  int64_t ld;   // the source's level stride, checked as a destination stride is
+  int rc = dst_stride("mpg_regrid_csr_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+  if (rc) return rc;
+  return mpg_k_apply_csr_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

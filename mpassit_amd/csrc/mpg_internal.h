@@ -273,6 +273,7 @@ struct mpg_handle_s {
   DevBuf<int32_t> col;
   DevBuf<double> val;
   int64_t nnz = 0;
+  DevBuf<double> dst_frac;   // [n_dst] covered fraction of every destination cell (conservative Grid -> Mesh Store only; absent otherwise)
   int refcount = 1;
   bool cached = false;
   uint64_t parked_at = 0;   // release order of a handle waiting in the cache with refcount 0 (mpg_api.hip)
@@ -450,6 +451,11 @@ int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, 
 // k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                         double scale, double offset, hipStream_t s);
+// k_store_conserve.hip: conservative Grid -> Mesh Store (CSR rows keyed by mesh cell, h->dst_frac); norm_type MPG_NORM_*
+int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s);
+// k_apply_csr_to_mesh.hip: Regrid of a CSR handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
+int mpg_k_apply_csr_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
+                            double scale, double offset, hipStream_t s);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);

@@ -36,6 +36,7 @@ module mpg
   end type mpg_proj
   !> struct mpg_mask_opts (include/mpassit_amd.h): the options of the masked Regrid, mpg_regrid_masked_dev
   integer(c_int), parameter :: MPG_MISSING_NAN = 1, MPG_MISSING_VALUE = 2
+  integer(c_int), parameter :: MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1
   type, bind(C) :: mpg_mask_opts
     integer(c_int) :: flags            !< MPG_MISSING_NAN + MPG_MISSING_VALUE, or 0 (static mask only)
     real(c_double) :: missing_value    !< with MPG_MISSING_VALUE: an element equal to it is missing
@@ -260,6 +261,29 @@ module mpg
       real(c_double), value :: scale, offset
       integer(c_int) :: rc
     end function mpg_regrid_to_mesh_dev
+    ! conservative Grid -> Mesh Store (norm_type: MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1), its dst fraction and the CSR Regrid in mesh order
+    function mpg_regrid_store_conserve_to_mesh(src, dst, norm_type, rh) bind(C, name="mpg_regrid_store_conserve_to_mesh") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: norm_type
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_conserve_to_mesh
+    function mpg_handle_get_dst_frac(rh, frac_host) bind(C, name="mpg_handle_get_dst_frac") result(rc)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: rh
+      real(c_double), intent(out) :: frac_host(*)
+      integer(c_int) :: rc
+    end function mpg_handle_get_dst_frac
+    function mpg_regrid_csr_to_mesh_dev(rh, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, &
+                                        hip_stream) bind(C, name="mpg_regrid_csr_to_mesh_dev") result(rc)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, nfields, dst_type, dst_layout
+      integer(c_int64_t), value :: src_level_stride
+      real(c_double), value :: scale, offset
+      integer(c_int) :: rc
+    end function mpg_regrid_csr_to_mesh_dev
     function mpg_handle_transpose_stats(rh, n_referenced, max_per_source) bind(C, name="mpg_handle_transpose_stats") result(rc)
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: rh

@@ -16,10 +16,11 @@ import numpy as np
 from . import _lib as L
 from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
-                   check)
+                   NORM_DSTAREA, NORM_FRACAREA, check)
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
-           "regrid_store_to_mesh", "regrid_to_mesh_autograd",
+           "regrid_store_to_mesh", "regrid_to_mesh_autograd", "regrid_store_conserve_to_mesh", "regrid_csr_to_mesh_autograd", "NORM_DSTAREA",
+           "NORM_FRACAREA",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST"]
 
@@ -485,20 +486,29 @@ class RouteHandle:
         same bits transposed.  src: grid values [nfields][nlev][plane of n_src], float32 / float64, a contiguous CUDA tensor or a
         plane-pitched view (nfields, nlev, ny, nx) / (nlev, ny, nx) as empty_pitched of the handle that produced it makes.
         dst = cast(regrid(src) * scale + offset), float64 arithmetic."""
+        return self._to_mesh(L.regrid_to_mesh_dev, "regrid_to_mesh", src, nlev, nfields, layout, out_dtype, scale, offset, out)
+
+    def regrid_csr_to_mesh(self, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, out_dtype=None, scale=1.0, offset=0.0, out=None):
+        """mpg_regrid_csr_to_mesh_dev: regrid_to_mesh for CSR handles -- regrid_store_conserve_to_mesh's, a Mesh -> Grid conservative
+        one, a from_weights one.  Same source rules (contiguous, or a plane-pitched view), same layouts and epilogue; LAYOUT_CELL_FAST
+        has the bytes of regrid_typed on the same handle, LAYOUT_LEV_FAST the same bits transposed."""
+        return self._to_mesh(L.regrid_csr_to_mesh_dev, "regrid_csr_to_mesh", src, nlev, nfields, layout, out_dtype, scale, offset, out)
+
+    def _to_mesh(self, fn, who, src, nlev, nfields, layout, out_dtype, scale, offset, out):
         import torch
         if not (_is_torch(src) and src.is_cuda and src.dtype in (torch.float32, torch.float64)):
-            raise ValueError("regrid_to_mesh needs a float32/float64 CUDA tensor")
+            raise ValueError(who + " needs a float32/float64 CUDA tensor")
         if src.is_contiguous():
             if src.numel() != nfields * nlev * self.n_src:
                 raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
             ld = 0
         else:
             if src.dim() not in (3, 4) or (src.dim() == 3 and nfields != 1):
-                raise ValueError("regrid_to_mesh: a strided source must be (nfields, nlev, ny, nx) or (nlev, ny, nx) with plane-pitched levels")
+                raise ValueError(who + ": a strided source must be (nfields, nlev, ny, nx) or (nlev, ny, nx) with plane-pitched levels")
             ny, nx = int(src.shape[-2]), int(src.shape[-1])
             if ny * nx != self.n_src:
                 raise ValueError("source planes have %d points, handle expects %d" % (ny * nx, self.n_src))
-            ld = _level_stride(src, (nfields, nlev) if src.dim() == 4 else (nlev,), ny, nx, "regrid_to_mesh")
+            ld = _level_stride(src, (nfields, nlev) if src.dim() == 4 else (nlev,), ny, nx, who)
         out_dtype = out_dtype or src.dtype
         if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
             out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
@@ -506,12 +516,18 @@ class RouteHandle:
         if out is None:
             out = torch.empty(shape, dtype=out_dtype, device=src.device)
         elif not (out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64) and out.numel() == nfields * nlev * self.n_dst):
-            raise ValueError("regrid_to_mesh: out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_dst))
+            raise ValueError(who + ": out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_dst))
         _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
-        check(L.regrid_to_mesh_dev(self._h, src.data_ptr(), int(src.dtype == torch.float32), ld, int(nlev), int(nfields), out.data_ptr(),
+        check(fn(self._h, src.data_ptr(), int(src.dtype == torch.float32), ld, int(nlev), int(nfields), out.data_ptr(),
                                    int(out.dtype == torch.float32), int(layout), float(scale), float(offset),
                                    torch.cuda.current_stream().cuda_stream))
         return out
+
+    def dst_frac(self):
+        """mpg_handle_get_dst_frac: the covered fraction of every destination cell, [n_dst] float64 (conservative Grid -> Mesh handles)."""
+        frac = np.empty(self.n_dst, np.float64)
+        check(L.handle_get_dst_frac(self._h, _ptr(frac)))
+        return frac
 
     def transpose_stats(self):
         """(n_referenced, max_per_source): sources with at least one entry and the longest transposed row
@@ -733,6 +749,35 @@ def regrid_to_mesh_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST)
     differentiable torch op; `layout` is the destination layout.  The gradient with respect to src is rh.regrid_transpose of the
     incoming gradient, in src's shape and dtype."""
     return RegridToMeshFunction.apply(src, rh, nlev, nfields, layout)
+
+
+if _torch is not None:
+    class RegridCsrToMeshFunction(_torch.autograd.Function):
+        """regrid_csr_to_mesh with a gradient: RegridToMeshFunction for CSR handles.  Use regrid_csr_to_mesh_autograd()."""
+
+        @staticmethod
+        def forward(ctx, src, rh, nlev, nfields, layout):
+            ctx.rh, ctx.nlev, ctx.nfields, ctx.layout = rh, nlev, nfields, layout
+            ctx.src_shape, ctx.src_dtype = src.shape, src.dtype
+            return rh.regrid_csr_to_mesh(src.contiguous(), nlev=nlev, nfields=nfields, layout=layout, out_dtype=src.dtype)
+
+        backward = RegridToMeshFunction.backward
+
+
+def regrid_csr_to_mesh_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST):
+    """rh.regrid_csr_to_mesh(src) (scale 1, offset 0) as a differentiable torch op; `layout` is the destination layout.  The gradient
+    with respect to src is rh.regrid_transpose of the same handle applied to the incoming gradient, in src's shape and dtype."""
+    return RegridCsrToMeshFunction.apply(src, rh, nlev, nfields, layout)
+
+
+def regrid_store_conserve_to_mesh(src_grid, dst_mesh, norm=NORM_DSTAREA):
+    """ESMF_FieldRegridStore(grid field -> mesh field, regridmethod=CONSERVE, normType=norm): the grid's cells (CORNER polygons) onto the
+    mesh's Voronoi cells, first-order conservative.  NORM_DSTAREA: w = I / area(cell); NORM_FRACAREA: w = I / covered area.  A CSR
+    handle (n_dst = nCells): regrid_typed, regrid_masked, regrid_transpose, csr() and dst_frac() work on it, regrid_csr_to_mesh writes
+    the mesh's own memory orders."""
+    h = C.c_void_p()
+    check(L.regrid_store_conserve_to_mesh(src_grid._h, dst_mesh._h, int(norm), C.byref(h)))
+    return RouteHandle(h)
 
 
 def regrid_store_to_mesh(src_grid, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER, meshloc=MESHLOC_ELEMENT):
