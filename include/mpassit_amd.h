@@ -196,6 +196,37 @@ int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc,
  *   _localize and _rebase work.  mpg_regrid_to_mesh_dev below adds the mesh's own memory order.  The conservative method has a
  *   Store of its own, with its normalisation argument: mpg_regrid_store_conserve_to_mesh. */
 int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out);
+/* Mesh -> Mesh: ESMF_FieldRegridStore(srcField on a Mesh's elements, dstField on another Mesh's location) -- a global run feeding the
+ * boundary and initial fields of a limited-area mesh, a 15-km state moved onto a 3-km or variable-resolution mesh, a restart remapped
+ * after re-meshing -- in ONE interpolation instead of two hops through an intermediate grid.
+ * Source points: the source mesh's cell centres (src_meshloc = MPG_MESHLOC_ELEMENT), source index = cell id.  Destinations: the
+ *   destination mesh's cell centres (dst_meshloc = MPG_MESHLOC_ELEMENT) or vertices (MPG_MESHLOC_NODE).  The handle is an ordinary fixed
+ *   one (MPG_KIND_FIXED), nnz_per_row 3 (bilinear) or 1 (nearest); mpg_handle_info reports n_src = the source mesh's nCells, n_dst =
+ *   nx_dst = the destination count, ny_dst = 1 (the Grid -> Mesh convention).
+ * MPG_REGRIDMETHOD_BILINEAR: source cells are the source mesh's dual (Delaunay) triangles (mpg_mesh_get_triangles).  A destination point
+ *   belongs to the triangle with the lowest triangle id (= vertex id) for which the line type's weight function passes with the
+ *   tolerance 1e-10 -- mpg_tune("bilinear_linetype", 0): the ray from the sphere's centre; 1: along the triangle's normal.  Slots are
+ *   the triangle's cells in the stored order of mpg_mesh_get_triangles, weights dA / S, dB / S, dC / S.  A point in no triangle is
+ *   unmapped: idx -1, weights 0, Regrid gives 0.0 (mpg_regrid_masked_dev: fill_value) -- the points outside a regional source mesh and
+ *   the rim strip outside its outermost cell centres.  The result depends on the two meshes and the knob only: the search is a box
+ *   tree over the source mesh's triangles (built at the first such Store of a source mesh and kept on it) whose boxes remove no
+ *   triangle that would pass, and every passing triangle is compared by id.
+ * MPG_REGRIDMETHOD_NEAREST_STOD: the source cell centre at the smallest chord distance, the lowest cell id on ties; every destination
+ *   point is mapped.  The exact search of the Mesh -> Grid Store over the source mesh's site tree; the grid's index bins are not used.
+ * Refusals, each with a message that names the way out.  MPG_ERR_UNSUPPORTED: MPG_REGRIDMETHOD_CONSERVE (Voronoi cell against Voronoi
+ *   cell is not built); src_meshloc = MPG_MESHLOC_NODE; either mesh made by mpg_mesh_create_window.  MPG_ERR_OVERFLOW: counts beyond
+ *   int32.  MPG_ERR_INVALID_ARG: NULL objects, unknown enums.  src == dst is allowed (every point then sits on a triangle corner: one
+ *   weight 1.0 on its own cell).
+ * Cached like every Store and paired with one mpg_handle_release.  The key carries a kind bit of its own, so it collides with neither a
+ *   Mesh -> Grid nor a Grid -> Mesh key, and for bilinear the line type; parked entries go when EITHER mesh is destroyed.
+ *   mpg_mesh_set_source_window on the SOURCE mesh applies to these handles as it does to Mesh -> Grid handles (their sources are that
+ *   mesh's cells); a window on the destination mesh does not touch them.  There is no _begin variant.
+ * mpg_handle_store_ms is filled; mpg_handle_store_stats: [2] points in all, [3] microseconds this Store spent building the source
+ *   mesh's triangle tree (0 when the mesh had it already).
+ * Everything that takes a fixed handle takes this one unchanged: mpg_regrid_dev / _typed[_pitched]_dev / _bundle_typed_dev,
+ *   mpg_regrid_masked_dev, mpg_regrid_transpose_dev, mpg_regrid_to_mesh_dev, the weight getters, mpg_handle_unique_sources, _localize and
+ *   _rebase.  mpg_regrid_rows_dev below reads and writes MPAS file order. */
+int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out);
 /* The same two Stores STARTED and not waited for.  interp.F90:207-437 stores its weight sets one after the other, each in front of
  * the Regrids that use it; they are independent of each other and of every Regrid that does not use them.  A _begin call queues
  * the Store on the library's worker thread (own stream, one Store at a time) and returns; the matching mpg_regrid_store[_grid]
@@ -324,6 +355,22 @@ int mpg_handle_get_dst_frac(mpg_handle rh, double *frac_host);   /* [n_dst]; MPG
  * hipGraph from the first call. */
 int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
                                void *dst_dev, int dst_type, int dst_layout, double scale, double offset, void *hip_stream);
+/* Regrid from rows to rows: [cell][lev] in and [cell][lev] out -- MPAS file order on both sides, what a Mesh -> Mesh job reads from one
+ * MPAS file and writes to another, in one pass (mpg_regrid_typed_dev writes only [lev][point], mpg_regrid_to_mesh_dev reads only
+ * [lev][plane]).  The hot path of a Mesh -> Mesh handle (mpg_regrid_store_mesh); it is not tied to how the handle was stored: any fixed
+ * handle with 1, 3 or 4 slots and no pole caps is accepted.
+ * src_dev: nfields slabs of [n_src][nlev], n_src the handle's current index space (the window count after mpg_mesh_set_source_window,
+ * the local extent after mpg_handle_localize / rebase).  dst_dev: nfields slabs of [n_dst][nlev], fully overwritten; an unmapped point
+ * gets (dst type)(0.0 * scale + offset).
+ * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type)( regrid(src) * scale + offset ) rounded once
+ * at the store.  Refusals.  MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; CSR handles (conservative, from-weights); handles with pole caps.
+ * MPG_ERR_INVALID_ARG: nlev < 1, nfields < 1, NULL.
+ * Contract by identity, no tolerance: element [p][k] has the bits of element [k][p] of what mpg_regrid_typed_dev(rh, src, src_type,
+ * MPG_LAYOUT_LEV_FAST, nlev, nfields, dst, dst_type, scale, offset, stream) writes on the same handle -- slot order, accumulate
+ * expression, unmapped rule and epilogue are the same code.  The same bits across calls and across nfields batching.  No atomics.
+ * Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a hipGraph from the first call. */
+int mpg_regrid_rows_dev(mpg_handle rh, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
+                        double offset, void *hip_stream);
 /* diagnostics: sources with at least one entry, and the longest transposed row (builds the transposed index if needed) */
 int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */

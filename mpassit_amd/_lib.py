@@ -25,6 +25,7 @@ SYMBOLS = [
     "mpg_wind_destagger_pitched_dev", "mpg_dev_to_file_planes", "mpg_regrid_transpose_dev", "mpg_handle_transpose_stats",
     "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev", "mpg_regrid_store_to_mesh", "mpg_regrid_to_mesh_dev",
     "mpg_regrid_store_conserve_to_mesh", "mpg_handle_get_dst_frac", "mpg_regrid_csr_to_mesh_dev",
+    "mpg_regrid_store_mesh", "mpg_regrid_rows_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -113,6 +114,27 @@ def regrid_csr_to_mesh_dev(*args):
     if "capply" not in _to_mesh_fns:
         _to_mesh_fns["capply"] = _CSR_TO_MESH_PROTO(("mpg_regrid_csr_to_mesh_dev", load()))
     return _to_mesh_fns["capply"](*args)
+
+
+# The Mesh -> Mesh calls, bound the same way.
+#   mpg_regrid_store_mesh(src mesh, src_meshloc, dst mesh, dst_meshloc, regridmethod, out)
+#   mpg_regrid_rows_dev(rh, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, hip_stream)
+_STORE_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p))
+_ROWS_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p)
+
+
+def regrid_store_mesh(*args):
+    """The typed binding of mpg_regrid_store_mesh; returns the call's status code."""
+    if "mstore" not in _to_mesh_fns:
+        _to_mesh_fns["mstore"] = _STORE_MESH_PROTO(("mpg_regrid_store_mesh", load()))
+    return _to_mesh_fns["mstore"](*args)
+
+
+def regrid_rows_dev(*args):
+    """The typed binding of mpg_regrid_rows_dev; returns the call's status code."""
+    if "rows" not in _to_mesh_fns:
+        _to_mesh_fns["rows"] = _ROWS_PROTO(("mpg_regrid_rows_dev", load()))
+    return _to_mesh_fns["rows"](*args)
 
 
 _lib = None

@@ -55,6 +55,25 @@ __device__ __forceinline__ bool tri_weights_normal(dv3 P, dv3 A, dv3 B, dv3 C, d
   return w[0] >= -tol && w[1] >= -tol && w[2] >= -tol;
 }
 
+// 63-bit Morton key of a point of [-1, 1]^3 (21 bits per axis): the order of the site BVH (k_store_nearest.hip) and of the triangle BVH
+// (k_store_mesh.hip)
+__device__ __forceinline__ unsigned long long spread21(unsigned long long v) {
+  v &= 0x1fffffull;
+  v = (v | v << 32) & 0x1f00000000ffffull;
+  v = (v | v << 16) & 0x1f0000ff0000ffull;
+  v = (v | v << 8) & 0x100f00f00f00f00full;
+  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
+  v = (v | v << 2) & 0x1249249249249249ull;
+  return v;
+}
+__device__ __forceinline__ unsigned long long morton63(double x, double y, double z) {
+  const double sc = 2097151.0 * 0.5;  // (2^21 - 1) / 2
+  unsigned long long qx = (unsigned long long)fmin(fmax((x + 1.0) * sc, 0.0), 2097151.0);
+  unsigned long long qy = (unsigned long long)fmin(fmax((y + 1.0) * sc, 0.0), 2097151.0);
+  unsigned long long qz = (unsigned long long)fmin(fmax((z + 1.0) * sc, 0.0), 2097151.0);
+  return spread21(qx) | (spread21(qy) << 1) | (spread21(qz) << 2);
+}
+
 // A6: squared chord distance, evaluated as ((dx^2 + dy^2) + dz^2) WITHOUT fma so that host (oracle) and
 // device agree bit for bit and box lower bounds stay monotone.
 __device__ __forceinline__ double dist2_nofma(double px, double py, double pz, double cx, double cy, double cz) {

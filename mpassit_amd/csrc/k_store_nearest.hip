@@ -20,26 +20,13 @@
 #include "geom.h"
 #include "mpg_internal.h"
 
-__device__ __forceinline__ unsigned long long spread21(unsigned long long v) {
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
 __global__ __launch_bounds__(256) void k_morton(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
                                                 const double *__restrict__ z, unsigned long long *__restrict__ key,
                                                 int32_t *__restrict__ id, int64_t first) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   x += first; y += first; z += first;   // sites = cells first .. first + n - 1 (the mesh's geometry window)
-  const double sc = 2097151.0 * 0.5;  // (2^21 - 1) / 2
-  unsigned long long qx = (unsigned long long)fmin(fmax((x[i] + 1.0) * sc, 0.0), 2097151.0);
-  unsigned long long qy = (unsigned long long)fmin(fmax((y[i] + 1.0) * sc, 0.0), 2097151.0);
-  unsigned long long qz = (unsigned long long)fmin(fmax((z[i] + 1.0) * sc, 0.0), 2097151.0);
-  key[i] = spread21(qx) | (spread21(qy) << 1) | (spread21(qz) << 2);
+  key[i] = morton63(x[i], y[i], z[i]);
   id[i] = (int32_t)(first + i);
 }
 __global__ __launch_bounds__(256) void k_gather_sites(int64_t n, const int32_t *__restrict__ id, const double *__restrict__ x,
@@ -327,14 +314,7 @@ __global__ __launch_bounds__(256) void k_nn_max_d2(int64_t P, const double *__re
   if (threadIdx.x == 0) atomicMax(out, (unsigned long long)__double_as_longlong(fmax(fmax(sw[0], sw[1]), fmax(sw[2], sw[3]))));
 }
 
-static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, mpg_handle_s *h, hipStream_t s, int masked = 0) {
-  int rc;
-  const int64_t P = (int64_t)npx * npy;
-  SiteBvh &b = m->bvh;
-  if (b.nnodes[0] >= (1 << 27)) {
-    mpg_set_error("mesh too large for the nearest-neighbour BVH");
-    return MPG_ERR_OVERFLOW;
-  }
+static SiteBvhView site_view(const SiteBvh &b) {
   SiteBvhView v;
   v.n = b.n;
   v.sx = b.sorted.x.p; v.sy = b.sorted.y.p; v.sz = b.sorted.z.p;
@@ -343,6 +323,18 @@ static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, 
   for (int i = 0; i < MPG_BVH_MAXLEV; ++i) v.nnodes[i] = b.nnodes[i];
   for (int i = 0; i <= MPG_BVH_MAXLEV; ++i) v.off[i] = b.off[i];
   v.box = b.box.p;
+  return v;
+}
+
+static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, mpg_handle_s *h, hipStream_t s, int masked = 0) {
+  int rc;
+  const int64_t P = (int64_t)npx * npy;
+  SiteBvh &b = m->bvh;
+  if (b.nnodes[0] >= (1 << 27)) {
+    mpg_set_error("mesh too large for the nearest-neighbour BVH");
+    return MPG_ERR_OVERFLOW;
+  }
+  const SiteBvhView v = site_view(b);
   if (mpg_nearest_variant() == 0) {   // "nn_variant" knob 0: the one-thread-per-point search (kept as the cross-check of the tests)
     k_nearest_query<<<(unsigned)((P + 255) / 256), 256, 0, s>>>(P, pts.x.p, pts.y.p, pts.z.p, v, h->idx.p, masked);
     MPG_HIP(hipGetLastError());
@@ -363,6 +355,28 @@ static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, 
     mpg_set_error("RegridStore(nearest): traversal stack of the wave-cooperative search overflowed");
     return MPG_ERR_OVERFLOW;
   }
+  return MPG_SUCCESS;
+}
+
+// The same exact search for a destination that is a plain list of n points (the cells or vertices of another mesh: k_store_mesh.hip):
+// one thread per point -- a list has no 8 x 8 patches of neighbours for the wave-cooperative form.  idx[n] = the nearest cell of `m`.
+int mpg_k_nearest_points(mpg_mesh_s *m, const PointSet &pts, int64_t n, int32_t *idx, hipStream_t s) {
+  int rc;
+  if ((rc = mpg_k_build_bvh(m, s, true))) return rc;
+  if (m->bvh.nnodes[0] >= (1 << 27)) {
+    mpg_set_error("mesh too large for the nearest-neighbour BVH");
+    return MPG_ERR_OVERFLOW;
+  }
+  if (n == 0) return MPG_SUCCESS;
+  k_nearest_query<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, pts.x.p, pts.y.p, pts.z.p, site_view(m->bvh), idx, 0);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
+// upper level of a Morton-ordered box tree: parent b = the hull of children [8 b, 8 b + 8) (the triangle BVH of k_store_mesh.hip shares it)
+int mpg_k_bvh_up(int64_t nchild, int64_t nparent, const double *child, double *parent, hipStream_t s) {
+  k_bvh_up<<<(unsigned)((nparent + 255) / 256), 256, 0, s>>>(nchild, nparent, child, parent);
+  MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }
 

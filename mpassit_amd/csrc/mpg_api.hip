@@ -133,7 +133,8 @@ void mpg_pool_release() {
 // files); a call that needs a module before the helper got to it simply loads it itself (the runtime serialises that).
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
-  X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh)
+  X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
+  X(k_store_mesh) X(k_apply_rows)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -408,6 +409,7 @@ int mpg_mesh_destroy(mpg_mesh m) {
   m->tri.free();
   m->fan.free();
   m->bvh.free();
+  m->tbvh.free();
   delete m;
   return MPG_SUCCESS;
 }
@@ -586,6 +588,7 @@ struct StoreCtx {
   int stagger;
   int method;
   int meshloc;
+  mpg_mesh_s *dst_mesh = nullptr;   // Mesh -> Mesh Store: the destination mesh (g is nullptr, `stagger` its location)
 };
 
 // ---- the Store worker -------------------------------------------------------------------------------------------------
@@ -979,6 +982,60 @@ int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type,
   return store_common(key, out, store_conserve_to_mesh_build, ctx);
 }
 
+// ---- Mesh -> Mesh Store (k_store_mesh.hip) -------------------------------------------------------------------------------------
+// Cache key: (src mesh, src_meshloc, dst mesh, dst_meshloc, method | line type | kind bit).  The source mesh and its location come first,
+// as in a Mesh -> Grid key, and on purpose: the sources of these handles ARE that mesh's cells, so everything that looks for "the
+// handles whose source is this mesh" -- mpg_mesh_set_source_window, the window offset of mpg_handle_source_range / _unique_sources,
+// mpg_handle_is_windowed -- finds them and treats them as it treats Mesh -> Grid handles; a window on the DESTINATION mesh does not
+// (the destination sits in the third place).  cache_purge looks at both places: parked entries go when either mesh is destroyed.
+// The kind bit keeps the key apart from a Mesh -> Grid key even if a grid and a mesh should ever share an address, and from the
+// Grid -> Mesh bit.
+#define MPG_KEY_MESH_MESH (1 << 21)
+static int store_mesh_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
+  StoreCtx *x = (StoreCtx *)c;
+  h->method = x->method;
+  int rc = mpg_k_store_mesh(x->m, x->dst_mesh, x->stagger, x->method, h, s);
+  if (!rc && x->m->win_count[MPG_MESHLOC_ELEMENT] >= 0)   // the source mesh's cells are windowed: index relative to the window from the start
+    rc = mpg_k_rebase(h, x->m->win_first[MPG_MESHLOC_ELEMENT], x->m->win_count[MPG_MESHLOC_ELEMENT], s, true);
+  return rc;
+}
+
+int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_mesh: NULL argument");
+  MPG_ARG(src_meshloc == MPG_MESHLOC_ELEMENT || src_meshloc == MPG_MESHLOC_NODE, "mpg_regrid_store_mesh: unknown source mesh location");
+  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE, "mpg_regrid_store_mesh: unknown destination mesh location");
+  MPG_ARG(regridmethod >= 0 && regridmethod <= 2, "mpg_regrid_store_mesh: unknown regrid method");
+  if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
+    mpg_set_error("mpg_regrid_store_mesh: conservative Mesh -> Mesh regridding is not supported (bilinear and nearest are): the clip of "
+                  "Voronoi cell against Voronoi cell is not built.  Two hops through a grid (mpg_regrid_store with MPG_REGRIDMETHOD_CONSERVE, "
+                  "then mpg_regrid_store_conserve_to_mesh) are the conservative route today.");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src_meshloc == MPG_MESHLOC_NODE) {
+    mpg_set_error("mpg_regrid_store_mesh: node-located sources are not supported (the fan triangulation onto a mesh is not built); "
+                  "sources are the cell centres, MPG_MESHLOC_ELEMENT -- the destination may be either location");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->geo_grid || dst->geo_grid) {
+    mpg_set_error("mpg_regrid_store_mesh: the %s mesh was cut to a grid (mpg_mesh_create_window): its resident cells are a window; "
+                  "create the whole mesh with mpg_mesh_create",
+                  src->geo_grid ? "source" : "destination");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
+  if (src->nCells > 0x7fffffffLL || src->nVertices > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_mesh: %lld source cells / %lld source triangles / %lld destination points exceed int32 ids",
+                  (long long)src->nCells, (long long)src->nVertices, (long long)n_dst);
+    return MPG_ERR_OVERFLOW;
+  }
+  StoreCtx ctx{src, nullptr, dst_meshloc, regridmethod, src_meshloc, dst};
+  // the line type in force is part of what a bilinear handle IS (as for the Mesh -> Grid Store)
+  HandleKey key(src, src_meshloc, dst, dst_meshloc,
+                regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 16 * mpg_bilinear_linetype() : 0) + MPG_KEY_MESH_MESH);
+  return store_common(key, out, store_mesh_mesh_build, ctx);
+}
+
 int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
   MPG_CHECK_INIT();
   MPG_ARG(h && frac_host, "mpg_handle_get_dst_frac: NULL argument");
@@ -1116,6 +1173,34 @@ int mpg_regrid_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int6
   int rc = dst_stride("mpg_regrid_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_apply_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
+}
+
+// ---- Regrid from [cell][lev] rows to [cell][lev] rows (k_apply_rows.hip) --------------------------------------------------------------
+int mpg_regrid_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
+                        double offset, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_rows: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_rows: nlev and nfields must be >= 1");
+  MPG_ARG(nlev <= (1 << 24), "mpg_regrid_rows: nlev beyond 2^24");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_rows: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_rows: big-endian values (MPG_TYPE_BE) are not supported; mpg_regrid_typed_dev reads and writes them");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->kind != MPG_KIND_FIXED) {
+    mpg_set_error("mpg_regrid_rows: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
+                  "mpg_regrid_typed_dev with MPG_LAYOUT_LEV_FAST serves CSR handles from [cell][lev] rows.");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_rows: handles with pole-cap terms (periodic Grid -> Grid) are not supported; mpg_regrid_typed_dev serves them");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4) {
+    mpg_set_error("mpg_regrid_rows: a fixed handle of %d slots is not supported (1, 3 and 4 are)", h->nnz_per_row);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  return mpg_k_apply_rows(h, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
 }
 
 // ---- Regrid of a CSR handle onto a mesh in either memory order (k_apply_csr_to_mesh.hip) -------------------------------------------

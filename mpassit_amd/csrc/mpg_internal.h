@@ -198,6 +198,29 @@ struct SiteBvhView {
   const double *box;
 };
 
+// Morton-sorted BVH over a mesh's dual triangles (k_store_mesh.hip: the point-in-triangle search of the Mesh -> Mesh bilinear Store).
+// Same shape as the site BVH: leaf = MPG_BVH_LEAF consecutive sorted triangles, fan-out MPG_BVH_FAN; a leaf's box is the union of its
+// valid triangles' padded corner hulls (a triangle without three cells contributes nothing: an all-invalid leaf has an empty box).
+struct TriBvh {
+  int64_t n = 0;              // triangles sorted (= nVertices, the invalid ones included)
+  DevBuf<int32_t> sorted_id;  // triangle (= vertex) id of each sorted slot
+  int nlev = 0;
+  int64_t nnodes[MPG_BVH_MAXLEV];
+  int64_t off[MPG_BVH_MAXLEV + 1];
+  DevBuf<double> box;         // [nodes][6]
+  bool built = false;
+  float build_ms = 0.f;       // GPU time of the build (profiles/r13_mesh_to_mesh.md)
+  void free() { sorted_id.free(); box.free(); built = false; }
+};
+struct TriBvhView {
+  int64_t n;
+  const int32_t *sid;
+  int nlev;
+  int64_t nnodes[MPG_BVH_MAXLEV];
+  int64_t off[MPG_BVH_MAXLEV + 1];
+  const double *box;
+};
+
 struct mpg_handle_s;
 struct mpg_grid_s;
 typedef std::tuple<void *, int, void *, int, int> HandleKey;
@@ -212,6 +235,7 @@ struct mpg_mesh_s {
   DevBuf<int32_t> fan;          // [3][nCells*(maxEdges-2)] fan triangles of the Voronoi polygons (vertex ids), lazily
   int fan_origin = 0;           // the "node_fan_origin" value `fan` was built for
   SiteBvh bvh;
+  TriBvh tbvh;                  // BVH over `tri`, lazily (Mesh -> Mesh bilinear Store)
   // source window per mesh location (ELEMENT, NODE): Regrid sources hold ids [win_first, win_first + win_count) only and
   // every handle of this mesh indexes relative to win_first (mpg_mesh_set_source_window); whole mesh by default
   int64_t win_first[2] = {0, 0}, win_count[2] = {-1, -1};
@@ -456,6 +480,16 @@ int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mp
 // k_apply_csr_to_mesh.hip: Regrid of a CSR handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_csr_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                             double scale, double offset, hipStream_t s);
+// k_store_nearest.hip: the exact nearest-cell search of mesh `m` (its site BVH, built on demand) for a plain list of n points; and one
+// upper level of a Morton-ordered box tree
+int mpg_k_nearest_points(mpg_mesh_s *m, const PointSet &pts, int64_t n, int32_t *idx, hipStream_t s);
+int mpg_k_bvh_up(int64_t nchild, int64_t nparent, const double *child, double *parent, hipStream_t s);
+// k_store_mesh.hip: Mesh -> Mesh Store (bilinear: 3 slots, the dual triangles of `src`; nearest: 1) of the cells of `src` onto the cells /
+// vertices of `dst`
+int mpg_k_store_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int dst_meshloc, int method, mpg_handle_s *h, hipStream_t s);
+// k_apply_rows.hip: Regrid of a fixed-nnz handle from [n_src][nlev] rows onto [n_dst][nlev] rows (MPAS file order on both sides)
+int mpg_k_apply_rows(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale, double offset,
+                     hipStream_t s);
 int mpg_k_bswap(void *buf, int64_t n, int elem_size, hipStream_t s);
 int mpg_k_post_cast(const double *src, int64_t n, double scale, double offset, float *dst, int dst_be, hipStream_t s);
 int mpg_k_post_layer_mean(const double *src, int nlevp1, int64_t P, float *dst, int dst_be, hipStream_t s);

@@ -284,6 +284,23 @@ module mpg
       real(c_double), value :: scale, offset
       integer(c_int) :: rc
     end function mpg_regrid_csr_to_mesh_dev
+    ! Mesh -> Mesh: ESMF_FieldRegridStore(srcField on a Mesh's elements, dstField on another Mesh's location); bilinear and nearest
+    function mpg_regrid_store_mesh(src, src_meshloc, dst, dst_meshloc, regridmethod, rh) bind(C, name="mpg_regrid_store_mesh") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: src_meshloc, dst_meshloc, regridmethod
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_mesh
+    ! ... and the Regrid from [cell][lev] rows to [cell][lev] rows (MPAS file order on both sides) of any fixed handle
+    function mpg_regrid_rows_dev(rh, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, hip_stream) &
+        bind(C, name="mpg_regrid_rows_dev") result(rc)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, nfields, dst_type
+      real(c_double), value :: scale, offset
+      integer(c_int) :: rc
+    end function mpg_regrid_rows_dev
     function mpg_handle_transpose_stats(rh, n_referenced, max_per_source) bind(C, name="mpg_handle_transpose_stats") result(rc)
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: rh
