@@ -214,7 +214,8 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
  * MPG_REGRIDMETHOD_NEAREST_STOD: the source cell centre at the smallest chord distance, the lowest cell id on ties; every destination
  *   point is mapped.  The exact search of the Mesh -> Grid Store over the source mesh's site tree; the grid's index bins are not used.
  * Refusals, each with a message that names the way out.  MPG_ERR_UNSUPPORTED: MPG_REGRIDMETHOD_CONSERVE (Voronoi cell against Voronoi
- *   cell is not built); src_meshloc = MPG_MESHLOC_NODE; either mesh made by mpg_mesh_create_window.  MPG_ERR_OVERFLOW: counts beyond
+ *   cell is not built here: the conservative Mesh -> Mesh Store is a call of its own, with its normalisation argument:
+ *   mpg_regrid_store_conserve_mesh); src_meshloc = MPG_MESHLOC_NODE; either mesh made by mpg_mesh_create_window.  MPG_ERR_OVERFLOW: counts beyond
  *   int32.  MPG_ERR_INVALID_ARG: NULL objects, unknown enums.  src == dst is allowed (every point then sits on a triangle corner: one
  *   weight 1.0 on its own cell).
  * Cached like every Store and paired with one mpg_handle_release.  The key carries a kind bit of its own, so it collides with neither a
@@ -339,7 +340,7 @@ int mpg_regrid_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int
  *   own memory order. */
 enum { MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1 };
 int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type, mpg_handle *out);
-int mpg_handle_get_dst_frac(mpg_handle rh, double *frac_host);   /* [n_dst]; MPG_ERR_INVALID_ARG on a handle that has none */
+int mpg_handle_get_dst_frac(mpg_handle rh, double *frac_host);   /* [n_dst]; MPG_ERR_INVALID_ARG on a handle that has none (mpg_regrid_store_conserve_mesh stores one too) */
 /* CSR Regrid in mesh order: the arguments of mpg_regrid_to_mesh_dev with the same meaning -- grid planes [nfields][nlev][plane], plane =
  * n_src, src_level_stride elements apart (0 = dense; below n_src -> MPG_ERR_INVALID_ARG; the pad is never read), out a slab of
  * nlev * n_dst per field in MPG_LAYOUT_CELL_FAST [lev][cell] or MPG_LAYOUT_LEV_FAST [cell][lev], MPG_TYPE_F64 / MPG_TYPE_F32 on either
@@ -363,7 +364,8 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type,
  * the local extent after mpg_handle_localize / rebase).  dst_dev: nfields slabs of [n_dst][nlev], fully overwritten; an unmapped point
  * gets (dst type)(0.0 * scale + offset).
  * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type)( regrid(src) * scale + offset ) rounded once
- * at the store.  Refusals.  MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; CSR handles (conservative, from-weights); handles with pole caps.
+ * at the store.  Refusals.  MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; CSR handles (conservative, from-weights: mpg_regrid_csr_rows_dev serves
+ * them); handles with pole caps.
  * MPG_ERR_INVALID_ARG: nlev < 1, nfields < 1, NULL.
  * Contract by identity, no tolerance: element [p][k] has the bits of element [k][p] of what mpg_regrid_typed_dev(rh, src, src_type,
  * MPG_LAYOUT_LEV_FAST, nlev, nfields, dst, dst_type, scale, offset, stream) writes on the same handle -- slot order, accumulate
@@ -371,6 +373,50 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type,
  * Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a hipGraph from the first call. */
 int mpg_regrid_rows_dev(mpg_handle rh, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
                         double offset, void *hip_stream);
+/* Conservative Mesh -> Mesh: ESMF_FieldRegridStore(regridmethod=CONSERVE, normType=) with the elements of one Mesh as the source and
+ * the elements of another as the destination -- precipitation, snow, soil water, mass increments and tracers of a global run feeding a
+ * limited-area mesh, of a 15-km state moved onto a 3-km mesh, of a restart after re-meshing -- in ONE conservative step instead of two
+ * hops through a grid (which smear twice and conserve only on the intermediate grid's footprint).
+ * Polygons: the Voronoi cells of both meshes from verticesOnCell, great-circle sides.  I(d, s) is the area of source cell s inside
+ *   destination cell d: the source cell is the subject polygon, made counter-clockwise by the sign of its own fan area (its listed
+ *   order reversed when that is negative); it is clipped by the destination cell's sides in listed order, that cell made
+ *   counter-clockwise the same way; clip-plane normals in difference form a x (b - a); the in-place clip of the other conservative
+ *   Stores with its 1e-15 * |n| inside rule; a side with |b - a|^2 < 1e-24 bounds nothing; the area is the triangle fan from slot 0,
+ *   clamped at 0; area(d) is the cell polygon's own fan area; no floating-point contraction.
+ * Weights, rows keyed by destination cell, columns = source cell ids, ascending.  MPG_NORM_DSTAREA: w = I / area(d).  MPG_NORM_FRACAREA:
+ *   w = I / sum_s I.  An entry is dropped when I <= 1e-14 * area(d); an uncovered cell has an empty row: Regrid gives 0.0.  The dst
+ *   fraction frac(d) = sum_s I / area(d), summed in ascending s, stays with the handle (mpg_handle_get_dst_frac).
+ * The handle is an ordinary CSR one (nnz_per_row 0, method conservative): mpg_handle_info reports n_src = the source mesh's nCells,
+ *   n_dst = nx_dst = the destination's nCells, ny_dst = 1.  Two Stores of the same pair give the same bytes: rows come from a count, a
+ *   scan and an ordered insert, no atomic decides a stored byte.
+ * Candidates: a box tree over the source mesh's cell polygons (built at the first such Store of a source mesh and kept on it) walked
+ *   by every destination cell with its own box; the boxes hold the whole spherical polygons, so no pair with I > 0
+ *   is removed.  The pair list has exact size: there is no fixed per-cell list and no spill path.
+ * Refusals.  MPG_ERR_UNSUPPORTED: either mesh made by mpg_mesh_create_window; maxEdges > 12 on either mesh.  MPG_ERR_OVERFLOW: counts,
+ *   pairs or entries beyond int32; a clipped polygon that outgrew its vertex slots (a non-convex cell).  MPG_ERR_INVALID_ARG: NULL
+ *   arguments, unknown norm_type.  src == dst is allowed (the diagonal, up to slivers below the 1e-14 rule).
+ * Cached like every Store under (src, ELEMENT, dst, ELEMENT, CONSERVE + 256 * norm_type + the Mesh -> Mesh kind bit): the two
+ *   normalisations are two handles; mpg_mesh_set_source_window on the SOURCE mesh rebases these handles like every other Mesh -> Mesh
+ *   handle, a window on the destination mesh passes them by; parked entries go when EITHER mesh is destroyed.  There is no _begin
+ *   variant.  mpg_handle_store_ms is filled; mpg_handle_store_stats: [1] pairs clipped, [2] destination cells that left the common
+ *   path (always 0: there is one path), [3] microseconds this Store spent building the source mesh's cell tree (0 when the mesh had it
+ *   already), [6] vertex slots of the clip (the two meshes' largest vertex counts added, at most 24).
+ * Everything that takes a CSR handle takes this one: mpg_regrid_typed[_pitched]_dev, mpg_regrid_masked_dev, mpg_regrid_transpose_dev,
+ *   mpg_regrid_csr_to_mesh_dev, mpg_handle_get_csr; mpg_regrid_csr_rows_dev reads and writes MPAS file order.
+ *
+ * mpg_regrid_csr_rows_dev: the CSR Regrid of rows onto rows -- the arguments and meaning of mpg_regrid_rows_dev: src_dev nfields slabs of
+ *   [n_src][nlev], dst_dev nfields slabs of [n_dst][nlev], fully overwritten, MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64
+ *   arithmetic.  Accepts ANY CSR handle without pole caps: this Store's, both other conservative Stores', mpg_handle_from_weights'.
+ *   Refusals.  MPG_ERR_UNSUPPORTED: a fixed handle (mpg_regrid_rows_dev serves those); MPG_TYPE_BE; handles with pole caps.
+ *   MPG_ERR_INVALID_ARG: nlev < 1, nfields < 1, NULL.
+ *   Contract by identity, no tolerance: acc = fma(val[q], src[col[q] * nlev + k], acc) from 0.0 in stored order, then
+ *   (dst type) fma(acc, scale, offset); element [p][k] has the bits of element [k][p] of what mpg_regrid_typed_dev(rh, src, src_type,
+ *   MPG_LAYOUT_LEV_FAST, ...) writes on the same handle; an empty row gives (dst type)(0.0 * scale + offset).  The same bits across
+ *   calls and across nfields batching.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing:
+ *   it can be captured in a hipGraph from the first call. */
+int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mpg_handle *out);
+int mpg_regrid_csr_rows_dev(mpg_handle rh, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
+                            double offset, void *hip_stream);
 /* diagnostics: sources with at least one entry, and the longest transposed row (builds the transposed index if needed) */
 int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *max_per_source);
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */

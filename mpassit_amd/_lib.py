@@ -26,6 +26,7 @@ SYMBOLS = [
     "mpg_handle_transpose_build_ms", "mpg_regrid_masked_dev", "mpg_regrid_store_to_mesh", "mpg_regrid_to_mesh_dev",
     "mpg_regrid_store_conserve_to_mesh", "mpg_handle_get_dst_frac", "mpg_regrid_csr_to_mesh_dev",
     "mpg_regrid_store_mesh", "mpg_regrid_rows_dev",
+    "mpg_regrid_store_conserve_mesh", "mpg_regrid_csr_rows_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -135,6 +136,27 @@ def regrid_rows_dev(*args):
     if "rows" not in _to_mesh_fns:
         _to_mesh_fns["rows"] = _ROWS_PROTO(("mpg_regrid_rows_dev", load()))
     return _to_mesh_fns["rows"](*args)
+
+
+# The conservative Mesh -> Mesh calls, bound the same way.
+#   mpg_regrid_store_conserve_mesh(src mesh, dst mesh, norm_type, out)
+#   mpg_regrid_csr_rows_dev(rh, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, hip_stream)
+_STORE_CONSERVE_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p))
+_CSR_ROWS_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p)
+
+
+def regrid_store_conserve_mesh(*args):
+    """The typed binding of mpg_regrid_store_conserve_mesh; returns the call's status code."""
+    if "cmstore" not in _to_mesh_fns:
+        _to_mesh_fns["cmstore"] = _STORE_CONSERVE_MESH_PROTO(("mpg_regrid_store_conserve_mesh", load()))
+    return _to_mesh_fns["cmstore"](*args)
+
+
+def regrid_csr_rows_dev(*args):
+    """The typed binding of mpg_regrid_csr_rows_dev; returns the call's status code."""
+    if "crows" not in _to_mesh_fns:
+        _to_mesh_fns["crows"] = _CSR_ROWS_PROTO(("mpg_regrid_csr_rows_dev", load()))
+    return _to_mesh_fns["crows"](*args)
 
 
 _lib = None

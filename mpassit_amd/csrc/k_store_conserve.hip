@@ -28,8 +28,8 @@
 
 #include "geom.h"
 #include "mpg_internal.h"
+#include "conserve_clip.h"   // CONS_MAXV, CLIP_NT, LdsPoly, clip_halfspace_lds, cell_fan_area
 
-#define CONS_MAXV 12   // max source polygon vertices handled (MPAS maxEdges is 6..10)
 #define CONS_BUF (CONS_MAXV + 4)   // a convex polygon gains at most one vertex per clip plane
 #define CONS_STACK 64
 #define CONS_QUEUE 2048  // breadth-first node queue of the cooperative passes
@@ -411,6 +411,23 @@ __global__ __launch_bounds__(256) void k_max_valence(int64_t nCells, int maxEdge
   if (threadIdx.x == 0) atomicMax(out, smax);
 }
 
+// m->max_valence, counted on first use (one round trip); the Mesh -> Mesh Store asks for both meshes
+int mpg_k_mesh_max_valence(mpg_mesh_s *m, hipStream_t s) {
+  if (m->max_valence >= 0) return MPG_SUCCESS;
+  int rc;
+  TmpBuf<int32_t> mv;
+  if ((rc = mv.alloc(1, s))) return rc;
+  MPG_HIP(hipMemsetAsync(mv.p, 0, sizeof(int32_t), s));
+  const int64_t nC = m->cwn;
+  int32_t hv = 0;
+  if (nC > 0) k_max_valence<<<(unsigned)std::min<int64_t>((nC + 255) / 256, 2048), 256, 0, s>>>(nC, m->maxEdges, m->voc.p, mv.p);
+  MPG_HIP(hipGetLastError());
+  MPG_HIP(hipMemcpyAsync(&hv, mv.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipStreamSynchronize(s));
+  m->max_valence = hv;
+  return MPG_SUCCESS;
+}
+
 __global__ __launch_bounds__(256) void k_csr_sort_rows(int64_t P, const int32_t *__restrict__ rowptr, int32_t *__restrict__ col,
                                                        double *__restrict__ val) {
   int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -458,57 +475,6 @@ __global__ __launch_bounds__(256) void k_conserve_fill_pairs(int64_t nCells, con
   }
 }
 
-#define CLIP_NT 64
-struct LdsPoly {   // vertex i of polygon buffer `buf` of this lane
-  double *base;    // lds + lane
-  int cb;
-  __device__ __forceinline__ dv3 get(int buf, int i) const {
-    const double *p = base + (size_t)((buf * cb + i) * 3) * CLIP_NT;
-    return dv3{p[0], p[CLIP_NT], p[2 * CLIP_NT]};
-  }
-  __device__ __forceinline__ void set(int buf, int i, dv3 v) const {
-    double *p = base + (size_t)((buf * cb + i) * 3) * CLIP_NT;
-    p[0] = v.x;
-    p[CLIP_NT] = v.y;
-    p[2 * CLIP_NT] = v.z;
-  }
-};
-// Sutherland-Hodgman step IN PLACE, the polygon in LDS.  The output of edge i goes to slots <= i + 1 and those have been
-// read by then: vertex i+1 is in registers as X2, and a CONVEX polygon meets the plane at most twice with at least one
-// vertex outside between the two crossings, so the write index never passes i + 1 (the first vertex, needed again for the
-// closing edge, is kept in registers).  One buffer instead of two halves the LDS of the clip kernel: 8 instead of 4
-// wavefronts per CU.  The arithmetic and its order are those of the two-buffer form: the same bits.  A non-convex cell can
-// break the bound or outgrow `cap` = maxEdges + 4 slots; either is reported through *trunc (the Store then fails with
-// MPG_ERR_OVERFLOW), never a silently wrong polygon.
-__device__ __forceinline__ int clip_halfspace_lds(int n, const LdsPoly &L, dv3 nrm, int cap, int *trunc) {
-  int m = 0;
-  double eps = 1e-15 * sqrt(dot3(nrm, nrm));
-  const dv3 first = L.get(0, 0);
-  dv3 X1 = first;
-  const double dfirst = dot3(nrm, first);
-  double d1 = dfirst;
-  for (int i = 0; i < n; ++i) {
-    const dv3 X2 = (i + 1 == n) ? first : L.get(0, i + 1);
-    const double d2 = (i + 1 == n) ? dfirst : dot3(nrm, X2);   // (the same product as the next edge's d1: computed once)
-    bool in1 = d1 >= -eps, in2 = d2 >= -eps;
-    if (in1) {
-      if (m < cap && m <= i + 1) L.set(0, m++, X1);
-      else *trunc = 1;
-    }
-    if (in1 != in2) {
-      dv3 X = X1 * d2 - X2 * d1;
-      double sgn = (d2 - d1) > 0.0 ? 1.0 : -1.0;
-      double nn = sqrt(dot3(X, X));
-      if (nn > 0.0) {
-        if (m < cap && m <= i + 1) L.set(0, m++, X * (sgn / nn));
-        else *trunc = 1;
-      }
-    }
-    X1 = X2;
-    d1 = d2;
-  }
-  return m;
-}
 // RAW = false: Mesh -> Grid, pair_val = I / area(grid cell) above the sliver threshold (else 0) and the grid cell's counter bumped.
 // RAW = true: Grid -> Mesh, pair_val = I itself -- the same polygon, the same area, the other direction normalises by the mesh cell.
 template <bool RAW>
@@ -797,23 +763,6 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
 // The pair list is grouped by mesh cell already, so a row is made by ONE thread from its own run of pairs: count the entries above the
 // sliver threshold, scan, then insert them in ascending grid index -- no atomics, and the stored bytes do not depend on the order in
 // which the cooperative passes happened to list a cell's pairs.
-// area(c): the fan of the cell's vertices in listed order, as the candidate pass forms it, its sign dropped
-__device__ __forceinline__ double cell_fan_area(int64_t c, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
-                                                const double *__restrict__ vy, const double *__restrict__ vz) {
-  dv3 first = dv3{0, 0, 0}, prev = first;
-  int n = 0;
-  double area = 0.0;
-  for (int j = 0; j < maxEdges && n < CONS_MAXV; ++j) {
-    const int32_t v = voc[c * maxEdges + j];
-    if (v <= 0) continue;
-    const dv3 x = dv3{vx[v - 1], vy[v - 1], vz[v - 1]};
-    if (n == 0) first = x;
-    else if (n >= 2) area += sph_tri_area(first, prev, x);
-    prev = x;
-    ++n;
-  }
-  return n < 3 ? 0.0 : fabs(area);
-}
 __global__ __launch_bounds__(256) void k_conserve_tm_count(int64_t nCells, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
                                                            const double *__restrict__ vy, const double *__restrict__ vz,
                                                            const int32_t *__restrict__ poff, const double *__restrict__ pair_val,
@@ -865,6 +814,43 @@ __global__ __launch_bounds__(256) void k_conserve_tm_rows(int64_t nCells, const 
   for (int q = b; q < e; ++q) val[q] = val[q] / d;
 }
 
+// The rows of a handle keyed by the cells of mesh `m` from a pair list grouped by cell (pairs of cell c at [poff[c], poff[c + 1]): column
+// pair_col, intersection area pair_val): count, scan, ordered insert, h->dst_frac.  Shared by the Grid -> Mesh Store above and the Mesh -> Mesh
+// Store (k_store_conserve_mesh.hip).  h->rowptr and h->dst_frac are allocated by the caller; `extra_dev` (nextra int32 counters) travels to
+// `extra_host` in the same round trip as the entry count.
+int mpg_k_conserve_rows(mpg_mesh_s *m, const int32_t *poff, const int32_t *pair_col, const double *pair_val, const int32_t *truncated, int cb,
+                        int norm_type, const char *who, mpg_handle_s *h, hipStream_t s, const int32_t *extra_dev, int32_t *extra_host, int nextra) {
+  int rc;
+  const int64_t nC = m->nCells;
+  TmpBuf<double> carea;
+  TmpBuf<int32_t> cnt;
+  if ((rc = carea.alloc((size_t)nC, s)) || (rc = cnt.alloc((size_t)nC + 1, s))) return rc;
+  const double *vx = m->vx_g(), *vy = m->vy_g(), *vz = m->vz_g();
+  k_conserve_tm_count<<<(unsigned)((nC + 256) / 256), 256, 0, s>>>(nC, m->maxEdges, m->voc.p, vx, vy, vz, poff, pair_val, carea.p, cnt.p);
+  MPG_HIP(hipGetLastError());
+  if ((rc = mpg_scan_excl_i32(cnt.p, h->rowptr.p, nC + 1, s))) return rc;
+  int32_t nnz = 0, was_truncated = 0;
+  if (nextra > 0) MPG_HIP(hipMemcpyAsync(extra_host, extra_dev, sizeof(int32_t) * (size_t)nextra, hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipMemcpyAsync(&nnz, h->rowptr.p + nC, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipMemcpyAsync(&was_truncated, truncated, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipStreamSynchronize(s));
+  if (was_truncated) {
+    mpg_set_error("%s: a clipped polygon outgrew its %d vertex slots (a non-convex mesh cell?)", who, cb);
+    return MPG_ERR_OVERFLOW;
+  }
+  if (nnz < 0) {   // (at most one entry per pair, and the pairs were counted in 64 bits)
+    mpg_set_error("%s: the weight matrix exceeds 2^31 entries", who);
+    return MPG_ERR_OVERFLOW;
+  }
+  h->nnz = nnz;
+  if ((rc = h->col.alloc((size_t)nnz + 1)) || (rc = h->val.alloc((size_t)nnz + 1))) return rc;
+  k_conserve_tm_rows<<<(unsigned)((nC + 255) / 256), 256, 0, s>>>(nC, poff, pair_col, pair_val, carea.p, h->rowptr.p, norm_type, h->col.p, h->val.p,
+                                                                  h->dst_frac.p);
+  MPG_HIP(hipGetLastError());
+  MPG_HIP(hipStreamSynchronize(s));
+  return MPG_SUCCESS;
+}
+
 int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s) {
   int rc;
   PointSet &cor = g->pts[MPG_STAGGERLOC_CORNER];
@@ -895,35 +881,12 @@ int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mp
   }
   ConsPairs X;
   if ((rc = conserve_pairs(m, g, h, s, true, X))) return rc;
-  TmpBuf<double> carea;
-  TmpBuf<int32_t> cnt;
-  if ((rc = carea.alloc((size_t)nC, s)) || (rc = cnt.alloc((size_t)nC + 1, s))) return rc;
-  const double *vx = m->vx_g(), *vy = m->vy_g(), *vz = m->vz_g();
-  k_conserve_tm_count<<<(unsigned)((nC + 256) / 256), 256, 0, s>>>(nC, m->maxEdges, m->voc.p, vx, vy, vz, X.poff.p, X.pair_val.p, carea.p, cnt.p);
-  MPG_HIP(hipGetLastError());
-  if ((rc = mpg_scan_excl_i32(cnt.p, h->rowptr.p, nC + 1, s))) return rc;
-  int32_t nnz = 0, was_truncated = 0, hs[5] = {0, 0, 0, 0, 0};
-  MPG_HIP(hipMemcpyAsync(hs, X.n_ovf.p, sizeof(hs), hipMemcpyDeviceToHost, s));
-  MPG_HIP(hipMemcpyAsync(&nnz, h->rowptr.p + nC, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MPG_HIP(hipMemcpyAsync(&was_truncated, X.truncated.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MPG_HIP(hipStreamSynchronize(s));
-  if (was_truncated) {
-    mpg_set_error("mpg_regrid_store_conserve_to_mesh: a clipped polygon outgrew its %d vertex slots (a non-convex mesh cell?)", X.cb);
-    return MPG_ERR_OVERFLOW;
-  }
-  if (nnz < 0) {   // (at most one entry per pair, and the pairs were counted in 64 bits)
-    mpg_set_error("mpg_regrid_store_conserve_to_mesh: the weight matrix exceeds 2^31 entries");
-    return MPG_ERR_OVERFLOW;
-  }
-  h->nnz = nnz;
+  int32_t hs[5] = {0, 0, 0, 0, 0};
+  if ((rc = mpg_k_conserve_rows(m, X.poff.p, X.pair_p.p, X.pair_val.p, X.truncated.p, X.cb, norm_type, "mpg_regrid_store_conserve_to_mesh", h, s, X.n_ovf.p, hs, 5)))
+    return rc;
   // mpg_handle_store_stats: as the Mesh -> Grid Store's
   h->store_stats[1] = X.npairs; h->store_stats[2] = X.novf; h->store_stats[3] = X.nbig; h->store_stats[4] = hs[3];
   h->store_stats[5] = hs[4]; h->store_stats[6] = X.cb;
-  if ((rc = h->col.alloc((size_t)nnz + 1)) || (rc = h->val.alloc((size_t)nnz + 1))) return rc;
-  k_conserve_tm_rows<<<(unsigned)((nC + 255) / 256), 256, 0, s>>>(nC, X.poff.p, X.pair_p.p, X.pair_val.p, carea.p, h->rowptr.p, norm_type, h->col.p,
-                                                                  h->val.p, h->dst_frac.p);
-  MPG_HIP(hipGetLastError());
-  MPG_HIP(hipStreamSynchronize(s));
   return MPG_SUCCESS;
 }
 

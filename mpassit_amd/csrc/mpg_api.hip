@@ -134,7 +134,7 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -410,6 +410,7 @@ int mpg_mesh_destroy(mpg_mesh m) {
   m->fan.free();
   m->bvh.free();
   m->tbvh.free();
+  m->cbvh.free();
   delete m;
   return MPG_SUCCESS;
 }
@@ -1009,7 +1010,8 @@ int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_m
   if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
     mpg_set_error("mpg_regrid_store_mesh: conservative Mesh -> Mesh regridding is not supported (bilinear and nearest are): the clip of "
                   "Voronoi cell against Voronoi cell is not built.  Two hops through a grid (mpg_regrid_store with MPG_REGRIDMETHOD_CONSERVE, "
-                  "then mpg_regrid_store_conserve_to_mesh) are the conservative route today.");
+                  "then mpg_regrid_store_conserve_to_mesh) are the conservative route today.  mpg_regrid_store_conserve_mesh is the "
+                  "conservative Mesh -> Mesh Store, with its normalisation argument.");
     return MPG_ERR_UNSUPPORTED;
   }
   if (src_meshloc == MPG_MESHLOC_NODE) {
@@ -1036,10 +1038,49 @@ int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_m
   return store_common(key, out, store_mesh_mesh_build, ctx);
 }
 
+// ---- conservative Mesh -> Mesh Store (k_store_conserve_mesh.hip) -------------------------------------------------------------------
+// Cache key: the Mesh -> Mesh key of the element locations with the method MPG_REGRIDMETHOD_CONSERVE -- which mpg_regrid_store_mesh
+// refuses, so no key of that call has it -- plus 256 * norm_type.  The source mesh sits in the first place: mpg_mesh_set_source_window on
+// it rebases these handles like every other Mesh -> Mesh handle, a window on the destination mesh passes them by.
+static int store_conserve_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
+  StoreCtx *x = (StoreCtx *)c;
+  h->method = MPG_REGRIDMETHOD_CONSERVE;
+  int rc = mpg_k_store_conserve_mesh(x->m, x->dst_mesh, x->method, h, s);   // (ctx.method carries the normalisation)
+  if (!rc && x->m->win_count[MPG_MESHLOC_ELEMENT] >= 0)   // the source mesh's cells are windowed: index relative to the window from the start
+    rc = mpg_k_rebase(h, x->m->win_first[MPG_MESHLOC_ELEMENT], x->m->win_count[MPG_MESHLOC_ELEMENT], s, true);
+  return rc;
+}
+
+int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_conserve_mesh: NULL argument");
+  MPG_ARG(norm_type == MPG_NORM_DSTAREA || norm_type == MPG_NORM_FRACAREA,
+          "mpg_regrid_store_conserve_mesh: norm_type must be MPG_NORM_DSTAREA or MPG_NORM_FRACAREA");
+  if (src->geo_grid || dst->geo_grid) {
+    mpg_set_error("mpg_regrid_store_conserve_mesh: the %s mesh was cut to a grid (mpg_mesh_create_window): its resident cells are a window; "
+                  "create the whole mesh with mpg_mesh_create",
+                  src->geo_grid ? "source" : "destination");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->maxEdges > 12 || dst->maxEdges > 12) {
+    mpg_set_error("mpg_regrid_store_conserve_mesh: maxEdges %d > 12", src->maxEdges > dst->maxEdges ? src->maxEdges : dst->maxEdges);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->nCells > 0x7fffffffLL || dst->nCells > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_conserve_mesh: %lld source cells / %lld destination cells exceed int32 ids", (long long)src->nCells,
+                  (long long)dst->nCells);
+    return MPG_ERR_OVERFLOW;
+  }
+  StoreCtx ctx{src, nullptr, MPG_MESHLOC_ELEMENT, norm_type, MPG_MESHLOC_ELEMENT, dst};
+  HandleKey key(src, MPG_MESHLOC_ELEMENT, dst, MPG_MESHLOC_ELEMENT, MPG_REGRIDMETHOD_CONSERVE + 256 * norm_type + MPG_KEY_MESH_MESH);
+  return store_common(key, out, store_conserve_mesh_build, ctx);
+}
+
 int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
   MPG_CHECK_INIT();
   MPG_ARG(h && frac_host, "mpg_handle_get_dst_frac: NULL argument");
-  MPG_ARG(h->dst_frac.p, "mpg_handle_get_dst_frac: the handle has no destination fraction (mpg_regrid_store_conserve_to_mesh stores one)");
+  MPG_ARG(h->dst_frac.p, "mpg_handle_get_dst_frac: the handle has no destination fraction (mpg_regrid_store_conserve_to_mesh stores one, "
+                       "and so does mpg_regrid_store_conserve_mesh)");
   MPG_HIP(hipStreamSynchronize(g_stream));
   if (h->n_dst > 0) MPG_HIP(hipMemcpy(frac_host, h->dst_frac.p, sizeof(double) * (size_t)h->n_dst, hipMemcpyDeviceToHost));
   return MPG_SUCCESS;
@@ -1189,7 +1230,8 @@ int mpg_regrid_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nle
   }
   if (h->kind != MPG_KIND_FIXED) {
     mpg_set_error("mpg_regrid_rows: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
-                  "mpg_regrid_typed_dev with MPG_LAYOUT_LEV_FAST serves CSR handles from [cell][lev] rows.");
+                  "mpg_regrid_typed_dev with MPG_LAYOUT_LEV_FAST serves CSR handles from [cell][lev] rows; mpg_regrid_csr_rows_dev serves them "
+                  "from rows to rows.");
     return MPG_ERR_UNSUPPORTED;
   }
   if (h->n_pole > 0) {
@@ -1201,6 +1243,29 @@ int mpg_regrid_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nle
     return MPG_ERR_UNSUPPORTED;
   }
   return mpg_k_apply_rows(h, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
+}
+
+// ---- Regrid of a CSR handle from [cell][lev] rows to [cell][lev] rows (k_apply_csr_rows.hip) ---------------------------------------
+int mpg_regrid_csr_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
+                            double offset, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_csr_rows: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_csr_rows: nlev and nfields must be >= 1");
+  MPG_ARG(nlev <= (1 << 24), "mpg_regrid_csr_rows: nlev beyond 2^24");
+  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_csr_rows: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_csr_rows: big-endian values (MPG_TYPE_BE) are not supported; mpg_regrid_typed_dev reads and writes them");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->kind != MPG_KIND_CSR) {
+    mpg_set_error("mpg_regrid_csr_rows: fixed 1-, 3- and 4-slot handles are served by mpg_regrid_rows_dev; this call takes CSR handles");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_csr_rows: handles with pole-cap terms are not supported; mpg_regrid_typed_dev serves them");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  return mpg_k_apply_csr_rows(h, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
 }
 
 // ---- Regrid of a CSR handle onto a mesh in either memory order (k_apply_csr_to_mesh.hip) -------------------------------------------

@@ -221,6 +221,31 @@ struct TriBvhView {
   const double *box;
 };
 
+// Morton-sorted box tree over a mesh's CELL POLYGONS (k_store_conserve_mesh.hip: the candidate search of the conservative Mesh -> Mesh
+// Store).  The shape of the other two trees; cellbox holds every sorted cell's own padded hull, a leaf's box is the union of its cells'.
+// A cell with fewer than three vertices has an empty box (lo > hi): it is never a candidate.
+struct CellBvh {
+  int64_t n = 0;              // cells sorted (= nCells)
+  DevBuf<int32_t> sorted_id;  // cell id of each sorted slot
+  DevBuf<double> cellbox;     // [n][6] in sorted order
+  int nlev = 0;
+  int64_t nnodes[MPG_BVH_MAXLEV];
+  int64_t off[MPG_BVH_MAXLEV + 1];
+  DevBuf<double> box;         // [nodes][6]
+  bool built = false;
+  float build_ms = 0.f;       // GPU time of the build (profiles/r14_mesh_conserve.md)
+  void free() { sorted_id.free(); cellbox.free(); box.free(); built = false; }
+};
+struct CellBvhView {
+  int64_t n;
+  const int32_t *sid;
+  const double *cellbox;
+  int nlev;
+  int64_t nnodes[MPG_BVH_MAXLEV];
+  int64_t off[MPG_BVH_MAXLEV + 1];
+  const double *box;
+};
+
 struct mpg_handle_s;
 struct mpg_grid_s;
 typedef std::tuple<void *, int, void *, int, int> HandleKey;
@@ -236,6 +261,7 @@ struct mpg_mesh_s {
   int fan_origin = 0;           // the "node_fan_origin" value `fan` was built for
   SiteBvh bvh;
   TriBvh tbvh;                  // BVH over `tri`, lazily (Mesh -> Mesh bilinear Store)
+  CellBvh cbvh;                 // box tree over the cell polygons, lazily (Mesh -> Mesh conservative Store)
   // source window per mesh location (ELEMENT, NODE): Regrid sources hold ids [win_first, win_first + win_count) only and
   // every handle of this mesh indexes relative to win_first (mpg_mesh_set_source_window); whole mesh by default
   int64_t win_first[2] = {0, 0}, win_count[2] = {-1, -1};
@@ -297,7 +323,7 @@ struct mpg_handle_s {
   DevBuf<int32_t> col;
   DevBuf<double> val;
   int64_t nnz = 0;
-  DevBuf<double> dst_frac;   // [n_dst] covered fraction of every destination cell (conservative Grid -> Mesh Store only; absent otherwise)
+  DevBuf<double> dst_frac;   // [n_dst] covered fraction of every destination cell (conservative Grid -> Mesh and Mesh -> Mesh Stores; absent otherwise)
   int refcount = 1;
   bool cached = false;
   uint64_t parked_at = 0;   // release order of a handle waiting in the cache with refcount 0 (mpg_api.hip)
@@ -477,6 +503,17 @@ int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t 
                         double scale, double offset, hipStream_t s);
 // k_store_conserve.hip: conservative Grid -> Mesh Store (CSR rows keyed by mesh cell, h->dst_frac); norm_type MPG_NORM_*
 int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s);
+// ... its row builder, shared with the Mesh -> Mesh Store: rows keyed by the cells of `m` from a pair list grouped by cell (h->rowptr and
+// h->dst_frac allocated by the caller); and the mesh's largest vertex count (m->max_valence), counted on first use
+int mpg_k_conserve_rows(mpg_mesh_s *m, const int32_t *poff, const int32_t *pair_col, const double *pair_val, const int32_t *truncated, int cb,
+                        int norm_type, const char *who, mpg_handle_s *h, hipStream_t s, const int32_t *extra_dev = nullptr,
+                        int32_t *extra_host = nullptr, int nextra = 0);
+int mpg_k_mesh_max_valence(mpg_mesh_s *m, hipStream_t s);
+// k_store_conserve_mesh.hip: conservative Mesh -> Mesh Store (CSR rows keyed by the cells of `dst`, columns the cells of `src`, h->dst_frac)
+int mpg_k_store_conserve_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int norm_type, mpg_handle_s *h, hipStream_t s);
+// k_apply_csr_rows.hip: Regrid of a CSR handle from [n_src][nlev] rows onto [n_dst][nlev] rows (MPAS file order on both sides)
+int mpg_k_apply_csr_rows(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
+                         double offset, hipStream_t s);
 // k_apply_csr_to_mesh.hip: Regrid of a CSR handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_csr_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                             double scale, double offset, hipStream_t s);

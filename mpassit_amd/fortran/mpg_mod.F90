@@ -301,6 +301,22 @@ module mpg
       real(c_double), value :: scale, offset
       integer(c_int) :: rc
     end function mpg_regrid_rows_dev
+    ! conservative Mesh -> Mesh Store (norm_type as above; mpg_handle_get_dst_frac reads its dst fraction) and the CSR Regrid from rows to rows
+    function mpg_regrid_store_conserve_mesh(src, dst, norm_type, rh) bind(C, name="mpg_regrid_store_conserve_mesh") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: norm_type
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_conserve_mesh
+    function mpg_regrid_csr_rows_dev(rh, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, hip_stream) &
+        bind(C, name="mpg_regrid_csr_rows_dev") result(rc)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: rh, src_dev, dst_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, nfields, dst_type
+      real(c_double), value :: scale, offset
+      integer(c_int) :: rc
+    end function mpg_regrid_csr_rows_dev
     function mpg_handle_transpose_stats(rh, n_referenced, max_per_source) bind(C, name="mpg_handle_transpose_stats") result(rc)
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: rh

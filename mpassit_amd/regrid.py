@@ -20,7 +20,7 @@ from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_N
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
            "regrid_store_to_mesh", "regrid_to_mesh_autograd", "regrid_store_conserve_to_mesh", "regrid_csr_to_mesh_autograd", "NORM_DSTAREA",
-           "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd",
+           "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd", "regrid_store_conserve_mesh", "regrid_csr_rows_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST"]
 
@@ -530,32 +530,42 @@ class RouteHandle:
         contiguous float32 / float64 CUDA tensor.  Returns (nfields, n_dst, nlev) of out_dtype (default: src's) whose element [p][k] has
         the bits of element [k][p] of regrid_typed(layout=LAYOUT_LEV_FAST).  dst = cast(regrid(src) * scale + offset), float64
         arithmetic; an unmapped point gets cast(0.0 * scale + offset)."""
+        return self._rows(L.regrid_rows_dev, "regrid_rows", src, nlev, nfields, out_dtype, scale, offset, out)
+
+    def regrid_csr_rows(self, src, nlev=1, nfields=1, out_dtype=None, scale=1.0, offset=0.0, out=None):
+        """mpg_regrid_csr_rows_dev: regrid_rows for CSR handles (regrid_store_conserve_mesh's, but any CSR handle without pole caps:
+        both other conservative Stores', from_weights') -- [n_src][nlev] rows in, [n_dst][nlev] rows out, MPAS file order on both sides.
+        Same arguments and result shape as regrid_rows; element [p][k] has the bits of element [k][p] of
+        regrid_typed(layout=LAYOUT_LEV_FAST), an empty row gives cast(0.0 * scale + offset)."""
+        return self._rows(L.regrid_csr_rows_dev, "regrid_csr_rows", src, nlev, nfields, out_dtype, scale, offset, out)
+
+    def _rows(self, fn, who, src, nlev, nfields, out_dtype, scale, offset, out):
         import torch
         if not (_is_torch(src) and src.is_cuda and src.dtype in (torch.float32, torch.float64)):
-            raise ValueError("regrid_rows needs a float32/float64 CUDA tensor")
+            raise ValueError(who + " needs a float32/float64 CUDA tensor")
         if int(nlev) < 1 or int(nfields) < 1:
-            raise ValueError("regrid_rows: nlev and nfields must be >= 1")
+            raise ValueError(who + ": nlev and nfields must be >= 1")
         if not src.is_contiguous():
-            raise ValueError("regrid_rows: the source must be contiguous, nfields slabs of (n_src, nlev)")
+            raise ValueError(who + ": the source must be contiguous, nfields slabs of (n_src, nlev)")
         if src.numel() != nfields * nlev * self.n_src:
             raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
         out_dtype = out_dtype or src.dtype
         if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
             out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
         if out_dtype not in (torch.float32, torch.float64):
-            raise ValueError("regrid_rows: out_dtype must be float32 or float64")
+            raise ValueError(who + ": out_dtype must be float32 or float64")
         if out is None:
             out = torch.empty((nfields, self.n_dst, nlev), dtype=out_dtype, device=src.device)
         elif not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64) and
                   out.numel() == nfields * nlev * self.n_dst):
-            raise ValueError("regrid_rows: out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_dst))
+            raise ValueError("%s: out must be a contiguous float32/float64 CUDA tensor of %d elements" % (who, nfields * nlev * self.n_dst))
         _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
-        check(L.regrid_rows_dev(self._h, src.data_ptr(), int(src.dtype == torch.float32), int(nlev), int(nfields), out.data_ptr(),
-                                int(out.dtype == torch.float32), float(scale), float(offset), torch.cuda.current_stream().cuda_stream))
+        check(fn(self._h, src.data_ptr(), int(src.dtype == torch.float32), int(nlev), int(nfields), out.data_ptr(),
+                 int(out.dtype == torch.float32), float(scale), float(offset), torch.cuda.current_stream().cuda_stream))
         return out
 
     def dst_frac(self):
-        """mpg_handle_get_dst_frac: the covered fraction of every destination cell, [n_dst] float64 (conservative Grid -> Mesh handles)."""
+        """mpg_handle_get_dst_frac: the covered fraction of every destination cell, [n_dst] float64 (conservative Grid -> Mesh and Mesh -> Mesh handles)."""
         frac = np.empty(self.n_dst, np.float64)
         check(L.handle_get_dst_frac(self._h, _ptr(frac)))
         return frac
@@ -827,12 +837,46 @@ def regrid_rows_autograd(rh, src, nlev=1, nfields=1):
     return RegridRowsFunction.apply(src, rh, nlev, nfields)
 
 
+if _torch is not None:
+    class RegridCsrRowsFunction(_torch.autograd.Function):
+        """regrid_csr_rows with a gradient: RegridRowsFunction for CSR handles.  Use regrid_csr_rows_autograd()."""
+
+        @staticmethod
+        def forward(ctx, src, rh, nlev, nfields):
+            ctx.rh, ctx.nlev, ctx.nfields = rh, nlev, nfields
+            ctx.src_shape, ctx.src_dtype = src.shape, src.dtype
+            return rh.regrid_csr_rows(src.contiguous(), nlev=nlev, nfields=nfields, out_dtype=src.dtype)
+
+        backward = RegridRowsFunction.backward
+
+
+def regrid_csr_rows_autograd(rh, src, nlev=1, nfields=1):
+    """rh.regrid_csr_rows(src) (scale 1, offset 0) as a differentiable torch op.  The gradient with respect to src is
+    rh.regrid_transpose(..., layout=LAYOUT_LEV_FAST) of the same handle applied to the incoming gradient, in src's shape and dtype."""
+    return RegridCsrRowsFunction.apply(src, rh, nlev, nfields)
+
+
+def regrid_store_conserve_mesh(src_mesh, dst_mesh, norm=NORM_DSTAREA):
+    """ESMF_FieldRegridStore(mesh field -> mesh field, regridmethod=CONSERVE, normType=norm): the source mesh's Voronoi cells onto the
+    destination mesh's, first-order conservative.  NORM_DSTAREA: w = I / area(cell); NORM_FRACAREA: w = I / covered area.  A CSR handle
+    (n_src = the source nCells, n_dst = the destination nCells): regrid_typed, regrid_masked, regrid_transpose, csr() and dst_frac()
+    work on it, regrid_csr_rows reads and writes MPAS file order.  Meshes made with window_grid= are refused by the library."""
+    if not (isinstance(src_mesh, Mesh) and isinstance(dst_mesh, Mesh)):
+        raise TypeError("regrid_store_conserve_mesh: src_mesh and dst_mesh must be Mesh objects")
+    if norm not in (NORM_DSTAREA, NORM_FRACAREA):
+        raise ValueError("regrid_store_conserve_mesh: norm must be NORM_DSTAREA or NORM_FRACAREA, not %r" % (norm,))
+    h = C.c_void_p()
+    check(L.regrid_store_conserve_mesh(src_mesh._h, dst_mesh._h, int(norm), C.byref(h)))
+    return RouteHandle(h)
+
+
 def regrid_store_mesh(src_mesh, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR, src_meshloc=MESHLOC_ELEMENT, dst_meshloc=MESHLOC_ELEMENT):
     """ESMF_FieldRegridStore(mesh field -> mesh field): the source mesh's cell centres onto the destination mesh's cells
     (MESHLOC_ELEMENT) or vertices (MESHLOC_NODE), bilinear (the source mesh's dual triangles, the lowest passing triangle id) or
     nearest.  The handle is an ordinary fixed one (n_src = the source nCells, n_dst = the destination count): regrid_typed,
     regrid_masked, regrid_transpose, regrid_to_mesh and the getters work on it; regrid_rows reads and writes MPAS file order.
-    Conservative, node-located sources and meshes made with window_grid= are refused by the library (MpgError, rc 4)."""
+    Conservative (regrid_store_conserve_mesh is that Store), node-located sources and meshes made with window_grid= are refused by the
+    library (MpgError, rc 4)."""
     if not (isinstance(src_mesh, Mesh) and isinstance(dst_mesh, Mesh)):
         raise TypeError("regrid_store_mesh: src_mesh and dst_mesh must be Mesh objects")
     if regridmethod not in (REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE, REGRIDMETHOD_NEAREST_STOD):
