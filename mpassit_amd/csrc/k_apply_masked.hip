@@ -18,8 +18,7 @@
 //                 LDS, lanes = levels over a wave-uniform row base, results transposed through an LDS tile [64][65] doubles per
 //                 chunk of 64 levels (bounded whatever nlev is), stores with lanes = points
 //   k_masked_csr  CSR (conservative, mpg_handle_from_weights), both layouts: one thread per point, two levels per pass over the row
-#include "geom.h"
-#include "mpg_internal.h"
+#include "apply_mesh.h"
 
 struct MaskPar {            // by value in the kernels' argument block
   const uint8_t *mask;      // [n_src] non-zero = never use, or nullptr
@@ -271,11 +270,10 @@ int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layou
   const int64_t P = h->n_dst;
   if (P == 0 || nlev == 0 || nfields == 0) return MPG_SUCCESS;
   if (ld == 0) ld = P;
-  const int sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
   if (h->n_src == 0) {
     const int nblk = (int)((P + 255) / 256);
     const unsigned nwg = (unsigned)nblk * (unsigned)(nlev * nfields);
-    if (df32) k_masked_fill<float><<<nwg, 256, 0, s>>>((float *)dst, P, nblk, ld, o->fill_value);
+    if (dst_type & MPG_TYPE_F32) k_masked_fill<float><<<nwg, 256, 0, s>>>((float *)dst, P, nblk, ld, o->fill_value);
     else k_masked_fill<double><<<nwg, 256, 0, s>>>((double *)dst, P, nblk, ld, o->fill_value);
     MPG_HIP(hipGetLastError());
     return MPG_SUCCESS;
@@ -290,10 +288,9 @@ int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layou
   m.use_nan = (o->flags & MPG_MISSING_NAN) != 0;
   m.use_val = (o->flags & MPG_MISSING_VALUE) != 0;
   const int lev_fast = layout == MPG_LAYOUT_LEV_FAST && nlev > 1;   // (a single level is the same memory in both layouts)
-  if (sf32 && df32) return launch_masked<float, float>(h, src, lev_fast, nlev, nfields, dst, ld, m, s);
-  if (sf32) return launch_masked<float, double>(h, src, lev_fast, nlev, nfields, dst, ld, m, s);
-  if (df32) return launch_masked<double, float>(h, src, lev_fast, nlev, nfields, dst, ld, m, s);
-  return launch_masked<double, double>(h, src, lev_fast, nlev, nfields, dst, ld, m, s);
+  return mpg_dispatch_types(src_type, dst_type, [&](auto ts, auto td) {   // (apply_mesh.h)
+    return launch_masked<decltype(ts), decltype(td)>(h, src, lev_fast, nlev, nfields, dst, ld, m, s);
+  });
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

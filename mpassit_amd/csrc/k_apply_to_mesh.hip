@@ -2,50 +2,35 @@
 // mesh field: [lev][cell] or MPAS file order [cell][lev] (mpg_regrid_to_mesh_dev).  The source is a stack of grid planes, possibly
 // pitched.  Serves every fixed-nnz handle: 4 weights (Grid -> Mesh bilinear, Grid -> Grid), 3 (Mesh -> Grid bilinear), 1 (nearest).
 //
-// One workgroup owns 64 consecutive destination points and all levels.  The points' indices and weights are staged through LDS once
-// and then held in registers.  Lanes run along points, so neighbouring mesh cells gather neighbouring grid points (A / B and D / C of
-// a quad are adjacent pairs in two adjacent grid rows); wave w takes levels w, w + 4, ...  Arithmetic and epilogue are those of the
-// typed Regrid (geom.h wsum_fixed, then fma(x, scale, offset) rounded once to the destination type): the same bits.
+// The points' indices and weights are staged through LDS once (apply_mesh.h am_stage_fixed) and then held in registers.  Lanes run along
+// points, so neighbouring mesh cells gather neighbouring grid points (A / B and D / C of a quad are adjacent pairs in two adjacent grid
+// rows); wave w takes levels w, w + 4, ...  Arithmetic and epilogue are those of the typed Regrid (geom.h wsum_fixed, then
+// fma(x, scale, offset) rounded once to the destination type): the same bits.
 //   [lev][cell]  every level's 64 results go straight out, one run per level
-//   [cell][lev]  results are staged in LDS as [cell][lev] (row stride odd: the column writes of a wave hit distinct banks) and leave as
-//                ONE contiguous run of cells * nlev elements per workgroup, whole lines non-temporal (geom.h stream_store_lane).  When
-//                64 * nlev results outgrow the LDS tile the levels go in chunks of a multiple of 32 (a 128-byte line of a float32
-//                row, two of a float64 row) and each chunk leaves as 64 pieces of a row.
+//   [cell][lev]  results are staged in the LDS tile and leave through am_drain_tile, in level chunks when the tile outgrows its cap
+//                (apply_mesh.h am_tile_plan)
 // No atomics, no allocation, no synchronisation with the host: the call is capturable in a hipGraph from the first call.
-#include <algorithm>
-
-#include "geom.h"
-#include "mpg_internal.h"
-
-#define TM_CELLS 64
-#define TM_TILE_BYTES (64 * 1024)
+#include "apply_mesh.h"
 
 template <typename TS, typename TD, int NNZ, bool LEVF>
 __global__ __launch_bounds__(256) void k_apply_to_mesh(const int32_t *__restrict__ idx, const double *__restrict__ w, const TS *__restrict__ src,
                                                        TD *__restrict__ dst, int64_t P, int64_t ld, int nlev, unsigned ntile, int kc, int S,
                                                        double scale, double offset) {
   extern __shared__ double sw[];                       // sw[NNZ][64] | sidx[NNZ][64] | tile[64][S] in the destination type
-  int32_t *sidx = (int32_t *)(sw + NNZ * TM_CELLS);
-  TD *tile = (TD *)(sidx + NNZ * TM_CELLS);
+  int32_t *sidx = (int32_t *)(sw + NNZ * AM_CELLS);
+  TD *tile = (TD *)(sidx + NNZ * AM_CELLS);
   const unsigned lin = xcd_remap(blockIdx.x, gridDim.x);
   const unsigned tl = lin % ntile;
   const int f = (int)(lin / ntile);
-  const int64_t p0 = (int64_t)tl * TM_CELLS;
+  const int64_t p0 = (int64_t)tl * AM_CELLS;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t < NNZ * TM_CELLS) {
-    const int pt = t & 63, q = t >> 6;
-    const bool in = p0 + pt < P;
-    const int64_t p = in ? p0 + pt : 0;
-    sidx[q * TM_CELLS + pt] = in ? idx[q * P + p] : -1;
-    if (NNZ > 1) sw[q * TM_CELLS + pt] = w[q * P + p];
-  }
-  __syncthreads();
+  am_stage_fixed<NNZ>(idx, w, P, p0, t, sidx, sw);
   int32_t c[NNZ];
   double ww[NNZ];
 #pragma unroll
   for (int q = 0; q < NNZ; ++q) {
-    c[q] = sidx[q * TM_CELLS + lane];
-    ww[q] = NNZ > 1 ? sw[q * TM_CELLS + lane] : 1.0;
+    c[q] = sidx[q * AM_CELLS + lane];
+    ww[q] = NNZ > 1 ? sw[q * AM_CELLS + lane] : 1.0;
   }
   const bool mapped = c[0] >= 0;
 #pragma unroll
@@ -53,7 +38,7 @@ __global__ __launch_bounds__(256) void k_apply_to_mesh(const int32_t *__restrict
   const bool in = p0 + lane < P;
   const TS *sf = src + (int64_t)f * nlev * ld;
   TD *df = dst + (int64_t)f * nlev * P;
-  const int ncell = (int)min((int64_t)TM_CELLS, P - p0);
+  const int ncell = (int)min((int64_t)AM_CELLS, P - p0);
   for (int k0 = 0; k0 < nlev; k0 += kc) {
     const int kn = min(kc, nlev - k0);
     const TS *sk = sf + (int64_t)(k0 + wave) * ld;
@@ -82,25 +67,7 @@ __global__ __launch_bounds__(256) void k_apply_to_mesh(const int32_t *__restrict
       put(k, v0);
     }
     if (LEVF) {
-      __syncthreads();
-      // the chunk's results in destination order: element e = cell (e / kn), level k0 + (e % kn); with kn == nlev one contiguous run
-      const int total = ncell * kn;
-      const int dc = 256 / kn, dk = 256 % kn;
-      int cc = t / kn, kk = t % kn;
-      TD *out = df + p0 * nlev + k0;
-      const bool run = kn == nlev;   // workgroup-uniform
-      for (int e = t; e < total; e += 256) {
-        TD *a = out + (int64_t)cc * nlev + kk;
-        const TD r = tile[cc * S + kk];
-        if (run) stream_store_lane(r, a, (unsigned)lane * (unsigned)sizeof(TD));
-        else *a = r;
-        cc += dc;
-        kk += dk;
-        if (kk >= kn) {
-          kk -= kn;
-          ++cc;
-        }
-      }
+      am_drain_tile(tile, S, df, p0, k0, ncell, kn, nlev, t, lane);
       if (k0 + kc < nlev) __syncthreads();   // the next chunk overwrites the tile
     }
   }
@@ -110,24 +77,14 @@ template <typename TS, typename TD, int NNZ>
 static int launch_layout(mpg_handle_s *h, const void *src, int64_t ld, int nlev, int nfields, void *dst, bool levf, double scale, double offset,
                          hipStream_t s) {
   const int64_t P = h->n_dst;
-  const uint64_t ntile = (uint64_t)((P + TM_CELLS - 1) / TM_CELLS);
-  if (ntile * (uint64_t)nfields > 0x7fffffffull) {
-    mpg_set_error("mpg_regrid_to_mesh: %lld points x %d fields exceed one launch", (long long)P, nfields);
-    return MPG_ERR_OVERFLOW;
-  }
-  const size_t head = (size_t)NNZ * TM_CELLS * (sizeof(double) + sizeof(int32_t));
-  int kc = nlev, S = 0;
-  size_t lds = head;
-  if (levf) {
-    // all levels in one tile when they fit, else chunks of a multiple of 32 levels; row stride odd
-    if ((size_t)TM_CELLS * (size_t)(nlev | 1) * sizeof(TD) > TM_TILE_BYTES) kc = (int)(TM_TILE_BYTES / (TM_CELLS * sizeof(TD)) - 1) / 32 * 32;
-    S = kc | 1;
-    lds += (size_t)TM_CELLS * (size_t)S * sizeof(TD);
-  }
+  uint64_t ntile;
+  int rc = am_grid("mpg_regrid_to_mesh", P, nfields, &ntile);
+  if (rc) return rc;
+  const TilePlan tp = am_tile_plan(nlev, sizeof(TD), levf, (size_t)NNZ * AM_CELLS * (sizeof(double) + sizeof(int32_t)));
   auto fn = levf ? k_apply_to_mesh<TS, TD, NNZ, true> : k_apply_to_mesh<TS, TD, NNZ, false>;
-  if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  fn<<<(unsigned)(ntile * (uint64_t)nfields), 256, lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, P, ld, nlev, (unsigned)ntile, kc, S, scale,
-                                                             offset);
+  if ((rc = am_allow_lds((const void *)fn, tp.lds))) return rc;
+  fn<<<(unsigned)(ntile * (uint64_t)nfields), 256, tp.lds, s>>>(h->idx.p, h->w.p, (const TS *)src, (TD *)dst, P, ld, nlev, (unsigned)ntile, tp.kc, tp.S,
+                                                                scale, offset);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }
@@ -144,19 +101,12 @@ static int launch_nnz(mpg_handle_s *h, const void *src, int64_t ld, int nlev, in
 int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                         double scale, double offset, hipStream_t s) {
   if (h->n_dst == 0 || nlev == 0 || nfields == 0) return MPG_SUCCESS;
-  const int sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
-  if (h->n_src == 0) {   // nothing mapped: the destination is the epilogue of 0.0 (as mpg_regrid_typed_dev)
-    if (offset != 0.0) {
-      mpg_set_error("mpg_regrid_to_mesh: handle without sources and a non-zero offset is not supported");
-      return MPG_ERR_UNSUPPORTED;
-    }
-    return mpg_zero_planes(dst, df32 ? 4 : 8, h->n_dst, (int64_t)nlev * nfields, h->n_dst, s);
-  }
+  // nothing mapped: nlev * nfields planes of n_dst points, whichever the layout
+  if (h->n_src == 0) return am_no_sources("mpg_regrid_to_mesh", dst, dst_type, h->n_dst, (int64_t)nlev * nfields, h->n_dst, offset, s);
   const bool levf = layout == MPG_LAYOUT_LEV_FAST && nlev > 1;   // (a single level is the same memory in both layouts)
-  if (sf32 && df32) return launch_nnz<float, float>(h, src, ld, nlev, nfields, dst, levf, scale, offset, s);
-  if (sf32) return launch_nnz<float, double>(h, src, ld, nlev, nfields, dst, levf, scale, offset, s);
-  if (df32) return launch_nnz<double, float>(h, src, ld, nlev, nfields, dst, levf, scale, offset, s);
-  return launch_nnz<double, double>(h, src, ld, nlev, nfields, dst, levf, scale, offset, s);
+  return mpg_dispatch_types(src_type, dst_type, [&](auto ts, auto td) {
+    return launch_nnz<decltype(ts), decltype(td)>(h, src, ld, nlev, nfields, dst, levf, scale, offset, s);
+  });
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

@@ -27,7 +27,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "mpg_internal.h"
+#include "apply_mesh.h"
 
 #define TR_SHORT 16   // longest segment served by one lane (registers); longer ones go to k_tr_long
 #define TR_LF_CELLS 64
@@ -413,11 +413,9 @@ int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, 
   if (rc) return rc;
   if (ld == 0) ld = h->n_dst;
   const bool levf = layout == MPG_LAYOUT_LEV_FAST && nlev > 1;   // (a single level is the same memory in both layouts)
-  const bool sf32 = src_type & MPG_TYPE_F32, df32 = dst_type & MPG_TYPE_F32;
-  if (sf32 && df32) return launch_tr<float, float>(h, src, ld, nlev, nfields, dst, levf, s);
-  if (sf32) return launch_tr<float, double>(h, src, ld, nlev, nfields, dst, levf, s);
-  if (df32) return launch_tr<double, float>(h, src, ld, nlev, nfields, dst, levf, s);
-  return launch_tr<double, double>(h, src, ld, nlev, nfields, dst, levf, s);
+  return mpg_dispatch_types(src_type, dst_type, [&](auto ts, auto td) {   // (apply_mesh.h)
+    return launch_tr<decltype(ts), decltype(td)>(h, src, ld, nlev, nfields, dst, levf, s);
+  });
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

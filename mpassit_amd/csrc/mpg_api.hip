@@ -1189,107 +1189,88 @@ int mpg_regrid_transpose_dev(mpg_handle h, const void *src_dev, int src_type, in
   return mpg_k_transpose(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
 }
 
-// ---- Regrid onto a mesh in either memory order of a mesh field (k_apply_to_mesh.hip) ------------------------------------------
+// ---- the four Regrid calls for results in mesh memory order: one set of argument checks -----------------------------------------------
+struct MeshOrderCall {
+  const char *name;         // as the messages give it
+  int kind;                 // the handle kind the call takes
+  const char *be_way;       // what follows "big-endian values (MPG_TYPE_BE) are not supported": the call that reads and writes them
+  const char *other_kind;   // a handle of the other kind: the call that serves it
+  const char *pole;         // a handle with pole caps
+};
+// ld: where the checked source level stride goes (src_level_stride as given; the checks of a destination stride).  NULL for the two
+// rows calls, which have neither a stride nor a layout argument and bound nlev instead (a row's elements are counted in int).
+static int check_mesh_order(const MeshOrderCall &c, mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
+                            const void *dst_dev, int dst_type, int dst_layout, int64_t *ld) {
+  auto fail = [&](int rc, const char *what) {
+    mpg_set_error("%s: %s", c.name, what);
+    return rc;
+  };
+  MPG_CHECK_INIT();
+  if (!(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0))) return fail(MPG_ERR_INVALID_ARG, "NULL argument");
+  if (!(nlev >= 1 && nfields >= 1)) return fail(MPG_ERR_INVALID_ARG, "nlev and nfields must be >= 1");
+  if (ld && dst_layout != MPG_LAYOUT_CELL_FAST && dst_layout != MPG_LAYOUT_LEV_FAST) return fail(MPG_ERR_INVALID_ARG, "bad dst_layout");
+  if (!ld && nlev > (1 << 24)) return fail(MPG_ERR_INVALID_ARG, "nlev beyond 2^24");
+  if (!(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3))
+    return fail(MPG_ERR_INVALID_ARG, "src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("%s: big-endian values (MPG_TYPE_BE) are not supported%s", c.name, c.be_way);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->kind != c.kind) return fail(MPG_ERR_UNSUPPORTED, c.other_kind);
+  if (h->n_pole > 0) return fail(MPG_ERR_UNSUPPORTED, c.pole);
+  if (c.kind == MPG_KIND_FIXED && h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4) {   // (no Store makes such a handle)
+    mpg_set_error("%s: a fixed handle of %d slots is not supported (1, 3 and 4 are)", c.name, h->nnz_per_row);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (!ld) return MPG_SUCCESS;
+  return dst_stride((std::string(c.name) + ": source").c_str(), h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, ld);
+}
+
+// Regrid onto a mesh in either memory order of a mesh field (k_apply_to_mesh.hip)
 int mpg_regrid_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields, void *dst_dev,
                            int dst_type, int dst_layout, double scale, double offset, void *hip_stream) {
-  MPG_CHECK_INIT();
-  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_to_mesh: NULL argument");
-  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_to_mesh: nlev and nfields must be >= 1");
-  MPG_ARG(dst_layout == MPG_LAYOUT_CELL_FAST || dst_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_to_mesh: bad dst_layout");
-  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_to_mesh: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
-  if ((src_type | dst_type) & MPG_TYPE_BE) {
-    mpg_set_error("mpg_regrid_to_mesh: big-endian values (MPG_TYPE_BE) are not supported");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->kind != MPG_KIND_FIXED || (h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4)) {
-    mpg_set_error("mpg_regrid_to_mesh: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
-                  "mpg_regrid_csr_to_mesh_dev serves CSR handles.");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->n_pole > 0) {
-    mpg_set_error("mpg_regrid_to_mesh: handles with pole-cap terms (periodic Grid -> Grid) are not supported");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  int64_t ld;   // the source's level stride, checked as a destination stride is
-  int rc = dst_stride("mpg_regrid_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+  static const MeshOrderCall call = {"mpg_regrid_to_mesh", MPG_KIND_FIXED, "",
+                                     "CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
+                                     "mpg_regrid_csr_to_mesh_dev serves CSR handles.",
+                                     "handles with pole-cap terms (periodic Grid -> Grid) are not supported"};
+  int64_t ld;
+  int rc = check_mesh_order(call, h, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, &ld);
   if (rc) return rc;
   return mpg_k_apply_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }
 
-// ---- Regrid from [cell][lev] rows to [cell][lev] rows (k_apply_rows.hip) --------------------------------------------------------------
+// Regrid from [cell][lev] rows to [cell][lev] rows (k_apply_rows.hip)
 int mpg_regrid_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
                         double offset, void *hip_stream) {
-  MPG_CHECK_INIT();
-  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_rows: NULL argument");
-  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_rows: nlev and nfields must be >= 1");
-  MPG_ARG(nlev <= (1 << 24), "mpg_regrid_rows: nlev beyond 2^24");
-  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_rows: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
-  if ((src_type | dst_type) & MPG_TYPE_BE) {
-    mpg_set_error("mpg_regrid_rows: big-endian values (MPG_TYPE_BE) are not supported; mpg_regrid_typed_dev reads and writes them");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->kind != MPG_KIND_FIXED) {
-    mpg_set_error("mpg_regrid_rows: CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
-                  "mpg_regrid_typed_dev with MPG_LAYOUT_LEV_FAST serves CSR handles from [cell][lev] rows; mpg_regrid_csr_rows_dev serves them "
-                  "from rows to rows.");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->n_pole > 0) {
-    mpg_set_error("mpg_regrid_rows: handles with pole-cap terms (periodic Grid -> Grid) are not supported; mpg_regrid_typed_dev serves them");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->nnz_per_row != 1 && h->nnz_per_row != 3 && h->nnz_per_row != 4) {
-    mpg_set_error("mpg_regrid_rows: a fixed handle of %d slots is not supported (1, 3 and 4 are)", h->nnz_per_row);
-    return MPG_ERR_UNSUPPORTED;
-  }
+  static const MeshOrderCall call = {"mpg_regrid_rows", MPG_KIND_FIXED, "; mpg_regrid_typed_dev reads and writes them",
+                                     "CSR handles (conservative, from-weights) are not supported: fixed 1-, 3- and 4-slot handles are. "
+                                     "mpg_regrid_typed_dev with MPG_LAYOUT_LEV_FAST serves CSR handles from [cell][lev] rows; "
+                                     "mpg_regrid_csr_rows_dev serves them from rows to rows.",
+                                     "handles with pole-cap terms (periodic Grid -> Grid) are not supported; mpg_regrid_typed_dev serves them"};
+  int rc = check_mesh_order(call, h, src_dev, src_type, 0, nlev, nfields, dst_dev, dst_type, 0, nullptr);
+  if (rc) return rc;
   return mpg_k_apply_rows(h, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
 }
 
-// ---- Regrid of a CSR handle from [cell][lev] rows to [cell][lev] rows (k_apply_csr_rows.hip) ---------------------------------------
+// Regrid of a CSR handle from [cell][lev] rows to [cell][lev] rows (k_apply_csr_rows.hip)
 int mpg_regrid_csr_rows_dev(mpg_handle h, const void *src_dev, int src_type, int nlev, int nfields, void *dst_dev, int dst_type, double scale,
                             double offset, void *hip_stream) {
-  MPG_CHECK_INIT();
-  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_csr_rows: NULL argument");
-  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_csr_rows: nlev and nfields must be >= 1");
-  MPG_ARG(nlev <= (1 << 24), "mpg_regrid_csr_rows: nlev beyond 2^24");
-  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_csr_rows: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
-  if ((src_type | dst_type) & MPG_TYPE_BE) {
-    mpg_set_error("mpg_regrid_csr_rows: big-endian values (MPG_TYPE_BE) are not supported; mpg_regrid_typed_dev reads and writes them");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->kind != MPG_KIND_CSR) {
-    mpg_set_error("mpg_regrid_csr_rows: fixed 1-, 3- and 4-slot handles are served by mpg_regrid_rows_dev; this call takes CSR handles");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->n_pole > 0) {
-    mpg_set_error("mpg_regrid_csr_rows: handles with pole-cap terms are not supported; mpg_regrid_typed_dev serves them");
-    return MPG_ERR_UNSUPPORTED;
-  }
+  static const MeshOrderCall call = {"mpg_regrid_csr_rows", MPG_KIND_CSR, "; mpg_regrid_typed_dev reads and writes them",
+                                     "fixed 1-, 3- and 4-slot handles are served by mpg_regrid_rows_dev; this call takes CSR handles",
+                                     "handles with pole-cap terms are not supported; mpg_regrid_typed_dev serves them"};
+  int rc = check_mesh_order(call, h, src_dev, src_type, 0, nlev, nfields, dst_dev, dst_type, 0, nullptr);
+  if (rc) return rc;
   return mpg_k_apply_csr_rows(h, src_dev, src_type, nlev, nfields, dst_dev, dst_type, scale, offset, (hipStream_t)hip_stream);
 }
 
-// ---- Regrid of a CSR handle onto a mesh in either memory order (k_apply_csr_to_mesh.hip) -------------------------------------------
+// Regrid of a CSR handle onto a mesh in either memory order (k_apply_csr_to_mesh.hip)
 int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields, void *dst_dev,
                                int dst_type, int dst_layout, double scale, double offset, void *hip_stream) {
-  MPG_CHECK_INIT();
-  MPG_ARG(h && (dst_dev || h->n_dst == 0) && (src_dev || h->n_src == 0), "mpg_regrid_csr_to_mesh: NULL argument");
-  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_csr_to_mesh: nlev and nfields must be >= 1");
-  MPG_ARG(dst_layout == MPG_LAYOUT_CELL_FAST || dst_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_csr_to_mesh: bad dst_layout");
-  MPG_ARG(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3, "mpg_regrid_csr_to_mesh: src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
-  if ((src_type | dst_type) & MPG_TYPE_BE) {
-    mpg_set_error("mpg_regrid_csr_to_mesh: big-endian values (MPG_TYPE_BE) are not supported");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->kind != MPG_KIND_CSR) {
-    mpg_set_error("mpg_regrid_csr_to_mesh: fixed 1-, 3- and 4-slot handles are served by mpg_regrid_to_mesh_dev; this call takes CSR handles");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  if (h->n_pole > 0) {
-    mpg_set_error("mpg_regrid_csr_to_mesh: handles with pole-cap terms are not supported");
-    return MPG_ERR_UNSUPPORTED;
-  }
-  int64_t ld;   // the source's level stride, checked as a destination stride is
-  int rc = dst_stride("mpg_regrid_csr_to_mesh: source", h->n_src, (int64_t)nlev * nfields, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+  static const MeshOrderCall call = {"mpg_regrid_csr_to_mesh", MPG_KIND_CSR, "",
+                                     "fixed 1-, 3- and 4-slot handles are served by mpg_regrid_to_mesh_dev; this call takes CSR handles",
+                                     "handles with pole-cap terms are not supported"};
+  int64_t ld;
+  int rc = check_mesh_order(call, h, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, &ld);
   if (rc) return rc;
   return mpg_k_apply_csr_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }

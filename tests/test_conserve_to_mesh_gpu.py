@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 NORMS = [CR.NORM_DSTAREA, CR.NORM_FRACAREA]
 APPLY_BAR = 2.4e-16          # the project's float64 apply bar, of max |src| x the row's sum |w|
-LDS_CHUNK = 1024             # entries of a 64-row run the apply kernel keeps in LDS (k_apply_csr_to_mesh.hip CM_CHUNK)
+LDS_CHUNK = 1024             # entries of a 64-row run the apply kernel keeps in LDS (apply_mesh.h AM_CHUNK)
 
 
 class Pair:

@@ -15,7 +15,7 @@ from _oracle_compare import Banded, assert_all_finite, assert_close
 pytestmark = pytest.mark.gpu
 
 NLEVS = [1, 3, 55, 64, 70]
-LDS_CHUNK = 1024                                   # entries of a 64-row run resident in LDS (k_apply_csr_rows.hip CR_CHUNK)
+LDS_CHUNK = 1024                                   # entries of a 64-row run resident in LDS (apply_mesh.h AM_CHUNK)
 SYN_LENGTHS = [1, 1023, 0, 1024, 2, 1025, 3000]    # row lengths of the synthetic handle, repeated: 1 + 1023 ends a row ON a chunk boundary
 SYN_ROWS, SYN_NSRC = 200, 4001
 

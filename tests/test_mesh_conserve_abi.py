@@ -179,4 +179,7 @@ def test_kernel_sources_are_built_and_anchored():
     assert '#include "conserve_clip.h"' in old
     rows = open(os.path.join(csrc, "k_apply_csr_rows.hip")).read()
     assert "atomic" not in rows.split("#include")[-1], "the CSR rows Regrid uses no atomics"
+    assert '#include "apply_mesh.h"' in rows and "apply_mesh.h" in build.HEADERS
+    helpers = open(os.path.join(csrc, "apply_mesh.h")).read()
+    assert "atomic" not in helpers.split("#include")[-1], "nor do the helpers it shares with the other mesh-order kernels"
     assert "xcd_remap" in rows and "stream_store_lane" in rows and "int64_t" in rows

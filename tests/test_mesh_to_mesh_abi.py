@@ -151,6 +151,9 @@ def test_kernel_sources_are_built_and_anchored():
     assert "#pragma clang fp contract(off)" in store, "geometry translation units are compiled without floating-point contraction"
     rows = open(os.path.join(ROOT, "mpassit_amd", "csrc", "k_apply_rows.hip")).read()
     assert "atomic" not in rows.split("#include")[-1], "the rows Regrid uses no atomics"
+    assert '#include "apply_mesh.h"' in rows and "apply_mesh.h" in build.HEADERS
+    shared = open(os.path.join(ROOT, "mpassit_amd", "csrc", "apply_mesh.h")).read()
+    assert "atomic" not in shared.split("#include")[-1], "nor do the helpers it shares with the other mesh-order kernels"
     assert "xcd_remap" in rows and "wsum_fixed" in rows and "stream_store_lane" in rows
 
 
