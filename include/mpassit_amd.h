@@ -184,7 +184,8 @@ int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc,
  * MPG_REGRIDMETHOD_NEAREST_STOD: the stagger point at the smallest chord distance, the lowest source index on ties; every mesh point
  *   is mapped.  A pyramid descent, seeded from the inverse projection where there is one.
  * Refusals.  MPG_ERR_UNSUPPORTED: MPG_REGRIDMETHOD_CONSERVE; bilinear on a grid created with MPG_GRID_PERIODIC_I (pole caps and the i-wrap
- *   towards a mesh are not built; nearest on such a grid is accepted); a mesh of mpg_mesh_create_window (its resident cells are a window:
+ *   towards a mesh are not built into THIS call: mpg_regrid_store_periodic_to_mesh below is the bilinear Store of such a grid, with its
+ *   pole method argument; nearest on such a grid is accepted); a mesh of mpg_mesh_create_window (its resident cells are a window:
  *   the result would be a partial mesh).  MPG_ERR_OVERFLOW: snx * sny or the mesh count beyond int32.  MPG_ERR_INVALID_ARG: NULL
  *   objects, unknown enums.
  * Cached like every Store -- the key carries the direction, so (mesh, loc, grid, stagger, method) of the two directions never collide --
@@ -196,6 +197,49 @@ int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc,
  *   _localize and _rebase work.  mpg_regrid_to_mesh_dev below adds the mesh's own memory order.  The conservative method has a
  *   Store of its own, with its normalisation argument: mpg_regrid_store_conserve_to_mesh. */
 int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out);
+/* Periodic Grid -> Mesh: ESMF_FieldRegridStore(srcField on the CENTER stagger of a Grid of ESMF_GridCreate1PeriDim with MONOPOLE caps,
+ * dstField on a Mesh location, regridmethod=BILINEAR, polemethod=) -- a global lat-lon analysis (GFS, ERA5, an SST product) taken onto MPAS
+ * cells by the default method.  The grid must have been created with MPG_GRID_PERIODIC_I.
+ * Source points: the grid's nx x ny CENTER points, source index = j * nx + i.  Destinations: the mesh's cell centres (MPG_MESHLOC_ELEMENT)
+ *   or vertices (MPG_MESHLOC_NODE).
+ * Quads: b in [0, ny - 2], a in [0, nx - 1]; A = (b, a), B = (b, (a + 1) mod nx), C = (b + 1, (a + 1) mod nx), D = (b + 1, a);
+ *   quad id = b * nx + a.  A point belongs to the lowest quad id for which the bilinear map of mpg_regrid_store_to_mesh has a solution
+ *   with xi, eta in [-tol, 1 + tol], tol = 10^-grid_inside_tol_exp; weights (1-xi)(1-eta), xi (1-eta), xi eta, (1-xi) eta on A, B, C, D.
+ *   It is that call's per-quad code: for a quad with a < nx - 1 the four weights are the bits mpg_regrid_store_to_mesh produces for the
+ *   same coordinates handed over as a non-periodic grid; the seam quads a = nx - 1 are what that call cannot reach.
+ * Pole caps are tried only when no quad passed, under MPG_POLEMETHOD_ALLAVG (ESMF_POLEMETHOD_ALLAVG, ESMF's default).  Cap ids run
+ *   0 .. nx - 1 for the south (row 0), then nx .. 2 nx - 1 for the north (row ny - 1); the lowest passing id wins.  The triangles are those of
+ *   the Grid -> Grid Store: north (A, B, N) with A = (ny - 1, a), B = (ny - 1, (a + 1) mod nx), south (B, A, S) on row 0, planar barycentric
+ *   weights seen from the sphere's centre, tolerance 1e-10 whatever grid_inside_tol_exp says.  The pole node's value is the mean of its
+ *   CENTER row, so a cap row has nx entries: every column of the row gets wr = t_pole / nx, columns A and B get t_A + wr and t_B + wr.
+ *   MPG_GRID_NO_SOUTH_POLE / MPG_GRID_NO_NORTH_POLE (a row block) drop that end's cap.  MPG_POLEMETHOD_NONE (ESMF_POLEMETHOD_NONE): no caps.
+ *   A point with no quad and no cap gets an empty row: Regrid gives 0.0 (mpg_regrid_masked_dev: fill_value).
+ *   ESMF's NPNTAVG and TEETH pole methods are not built.  Other source staggers are not built either: the EDGE / CORNER columns of a
+ *   periodic grid duplicate column 0, and their end rows sit on or beyond the poles.
+ * The handle is an ordinary CSR one (nnz_per_row 0, method bilinear) with no pole terms (mpg_handle_pole_count gives 0) and
+ *   no dst fraction: mpg_handle_info reports n_src = nx * ny, n_dst = nx_dst = the mesh count, ny_dst = 1.  A quad row has
+ *   exactly 4 entries, zeros included, a cap row exactly nx -- ESMF's factor list for the row, row_len entries of w_pole / row_len;
+ *   columns ascend within a row.
+ *   No atomic decides a stored byte: two Stores on fresh objects give identical rowptr / col / val.
+ *   Candidate search, two routes with identical results: on a lat-lon grid that closes the circle, with its projection attached
+ *   (mpg_grid_create_proj, mpg_grid_attach_proj) and cells whose parallels leave their row by at most 0.04 index units, the quads around
+ *   the point's own (i, j), a taken mod nx; where the inverse gives no index (poleward of 85 degrees), and on every other grid, a walk of a
+ *   box pyramid over the nx x (ny - 1) quads, the seam column included.  mpg_tune("store_boxes", 0) selects the walk everywhere;
+ *   mpg_handle_store_path reports 1 (index space) or 0.  Cap candidates are found the same way on both routes: the points no quad took
+ *   are compacted into a list and only those are tested against the nx triangles of each live end.
+ * Refusals, each with a message that names the way out.  MPG_ERR_INVALID_ARG: NULL arguments; an unknown dst_meshloc or pole_method;
+ *   nx < 3 or ny < 2.  MPG_ERR_UNSUPPORTED: a grid without MPG_GRID_PERIODIC_I (mpg_regrid_store_to_mesh is its Store); a mesh of
+ *   mpg_mesh_create_window.  MPG_ERR_OVERFLOW: nx * ny or the mesh count beyond int32; nnz >= 2^31.
+ * Cached like every Store and paired with one mpg_handle_release: the key carries the direction bit, a kind bit of its own and
+ *   pole_method, so it collides with no Grid -> Mesh, conservative or Mesh -> Grid key and the two pole methods are two handles; parked
+ *   entries go when the mesh or the grid is destroyed.  mpg_mesh_set_source_window passes these handles by.  There is no _begin variant.
+ * mpg_handle_store_ms is filled; mpg_handle_store_stats: [1] points that had an index and still took the walk, [2] points in all,
+ *   [3] points mapped by a cap, [4] points mapped by a seam quad (a = nx - 1).
+ * Everything that takes a CSR handle takes this one, with no kernel of its own: mpg_regrid_csr_to_mesh_dev in both mesh orders,
+ *   mpg_regrid_csr_rows_dev, mpg_regrid_typed[_pitched]_dev, mpg_regrid_masked_dev, mpg_regrid_transpose_dev, mpg_handle_get_csr.
+ *   mpg_regrid_to_mesh_dev and mpg_regrid_rows_dev refuse it as they refuse every CSR handle. */
+enum { MPG_POLEMETHOD_NONE = 0, MPG_POLEMETHOD_ALLAVG = 1 };
+int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshloc, int pole_method, mpg_handle *out);
 /* Mesh -> Mesh: ESMF_FieldRegridStore(srcField on a Mesh's elements, dstField on another Mesh's location) -- a global run feeding the
  * boundary and initial fields of a limited-area mesh, a 15-km state moved onto a 3-km or variable-resolution mesh, a restart remapped
  * after re-meshing -- in ONE interpolation instead of two hops through an intermediate grid.

@@ -27,6 +27,7 @@ SYMBOLS = [
     "mpg_regrid_store_conserve_to_mesh", "mpg_handle_get_dst_frac", "mpg_regrid_csr_to_mesh_dev",
     "mpg_regrid_store_mesh", "mpg_regrid_rows_dev",
     "mpg_regrid_store_conserve_mesh", "mpg_regrid_csr_rows_dev",
+    "mpg_regrid_store_periodic_to_mesh",
 ]
 
 MPG_SUCCESS = 0
@@ -40,6 +41,8 @@ GRID_PERIODIC_I, GRID_NO_SOUTH_POLE, GRID_NO_NORTH_POLE = 1, 2, 4
 MISSING_NAN, MISSING_VALUE = 1, 2
 MPG_NORM_DSTAREA, MPG_NORM_FRACAREA = 0, 1
 NORM_DSTAREA, NORM_FRACAREA = MPG_NORM_DSTAREA, MPG_NORM_FRACAREA
+MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG = 0, 1
+POLEMETHOD_NONE, POLEMETHOD_ALLAVG = MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG
 
 
 class MaskOpts(C.Structure):
@@ -157,6 +160,18 @@ def regrid_csr_rows_dev(*args):
     if "crows" not in _to_mesh_fns:
         _to_mesh_fns["crows"] = _CSR_ROWS_PROTO(("mpg_regrid_csr_rows_dev", load()))
     return _to_mesh_fns["crows"](*args)
+
+
+# The bilinear Grid -> Mesh Store of a periodic grid, bound the same way.
+#   mpg_regrid_store_periodic_to_mesh(src grid, dst mesh, dst_meshloc, pole_method, out)
+_STORE_PERIODIC_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p))
+
+
+def regrid_store_periodic_to_mesh(*args):
+    """The typed binding of mpg_regrid_store_periodic_to_mesh; returns the call's status code."""
+    if "pstore" not in _to_mesh_fns:
+        _to_mesh_fns["pstore"] = _STORE_PERIODIC_TO_MESH_PROTO(("mpg_regrid_store_periodic_to_mesh", load()))
+    return _to_mesh_fns["pstore"](*args)
 
 
 _lib = None

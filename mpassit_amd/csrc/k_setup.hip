@@ -257,9 +257,39 @@ __global__ __launch_bounds__(256) void k_pyr_up(int cnx, int cny, int pnx, int p
   o[3] = hi[0]; o[4] = hi[1]; o[5] = hi[2];
 }
 
-static int build_pyr(const PointSet &pts, int npx, int npy, int halo, Pyramid &pyr, hipStream_t s) {
-  // node grid of level 0 counts blocks of points (halo=0) or of cells (halo=1: npx-1 x npy-1 cells)
-  int ux = npx - halo, uy = npy - halo;
+// Leaves of the wrap-aware quad pyramid of a grid periodic in i (k_store_periodic_to_mesh.hip): node (bx, by) covers the quads
+// [i0, i0 + B0) x [j0, j0 + B0) of the npx x (npy - 1) quads whose corners are points (j, i) and (j, (i + 1) mod npx) of rows j, j + 1 --
+// the seam column a = npx - 1 included, so a leaf at the end of a row reaches round to column 0.
+__global__ __launch_bounds__(256) void k_pyr_leaf_wrap(int npx, int npy, int nbx, int nby, const double *__restrict__ x,
+                                                       const double *__restrict__ y, const double *__restrict__ z,
+                                                       double *__restrict__ box) {
+  int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (b >= (int64_t)nbx * nby) return;
+  int bx = (int)(b % nbx), by = (int)(b / nbx);
+  int i0 = bx * MPG_PYR_B0, j0 = by * MPG_PYR_B0;
+  int i1 = min(i0 + MPG_PYR_B0, npx) + 1, j1 = min(j0 + MPG_PYR_B0 + 1, npy);   // i1 <= npx + 1: column npx is column 0
+  double lo[3] = {2, 2, 2}, hi[3] = {-2, -2, -2};
+  for (int j = j0; j < j1; ++j)
+    for (int i = i0; i < i1; ++i) {
+      int64_t p = (int64_t)j * npx + (i == npx ? 0 : i);
+      double v[3] = {x[p], y[p], z[p]};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = fmin(lo[k], v[k]);
+        hi[k] = fmax(hi[k], v[k]);
+      }
+    }
+  // as for the cell boxes above: the quads bulge beyond the hull of their corners by <= diameter^2 / 2
+  double d2 = (hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]);
+  double pad = 0.5 * d2 + 1e-9;
+  double *o = box + 6 * b;
+  o[0] = lo[0] - pad; o[1] = lo[1] - pad; o[2] = lo[2] - pad;
+  o[3] = hi[0] + pad; o[4] = hi[1] + pad; o[5] = hi[2] + pad;
+}
+
+static int build_pyr(const PointSet &pts, int npx, int npy, int halo, Pyramid &pyr, hipStream_t s, bool wrap = false) {
+  // node grid of level 0 counts blocks of points (halo=0) or of cells (halo=1: npx-1 x npy-1 cells; wrap: npx x npy-1 quads)
+  int ux = wrap ? npx : npx - halo, uy = npy - halo;
   if (ux < 1 || uy < 1) {
     mpg_set_error("pyramid: empty grid");
     return MPG_ERR_INVALID_ARG;
@@ -286,7 +316,8 @@ static int build_pyr(const PointSet &pts, int npx, int npy, int halo, Pyramid &p
   int rc;
   if ((rc = pyr.box.alloc(6 * (size_t)total))) return rc;
   int64_t n0 = (int64_t)pyr.nx[0] * pyr.ny[0];
-  k_pyr_leaf<<<(unsigned)((n0 + 255) / 256), 256, 0, s>>>(npx, npy, pyr.nx[0], pyr.ny[0], halo, pts.x.p, pts.y.p, pts.z.p, pyr.box.p);
+  if (wrap) k_pyr_leaf_wrap<<<(unsigned)((n0 + 255) / 256), 256, 0, s>>>(npx, npy, pyr.nx[0], pyr.ny[0], pts.x.p, pts.y.p, pts.z.p, pyr.box.p);
+  else k_pyr_leaf<<<(unsigned)((n0 + 255) / 256), 256, 0, s>>>(npx, npy, pyr.nx[0], pyr.ny[0], halo, pts.x.p, pts.y.p, pts.z.p, pyr.box.p);
   for (int l = 1; l < nlev; ++l) {
     int64_t nl = (int64_t)pyr.nx[l] * pyr.ny[l];
     k_pyr_up<<<(unsigned)((nl + 255) / 256), 256, 0, s>>>(pyr.nx[l - 1], pyr.ny[l - 1], pyr.nx[l], pyr.ny[l],
@@ -301,6 +332,9 @@ int mpg_k_build_pyramid(const PointSet &pts, int nx, int ny, Pyramid &pyr, hipSt
 }
 int mpg_k_build_cell_pyramid(const PointSet &corner, int nx, int ny, Pyramid &pyr, hipStream_t s) {
   return build_pyr(corner, nx + 1, ny + 1, 1, pyr, s);
+}
+int mpg_k_build_wrap_pyramid(const PointSet &pts, int nx, int ny, Pyramid &pyr, hipStream_t s) {
+  return build_pyr(pts, nx, ny, 1, pyr, s, true);
 }
 PyramidView mpg_pyr_view(const Pyramid &p) {
   PyramidView v;

@@ -30,20 +30,8 @@
 __device__ __forceinline__ bool tm_try_quad(dv3 P, int a, int b, int snx, const double *__restrict__ sx, const double *__restrict__ sy,
                                             const double *__restrict__ sz, double tol, int32_t *id, double *ww) {
   const int64_t iA = (int64_t)b * snx + a, iB = iA + 1, iC = iB + snx, iD = iA + snx;
-  const dv3 A = ld3(sx, sy, sz, iA), B = ld3(sx, sy, sz, iB), C = ld3(sx, sy, sz, iC), D = ld3(sx, sy, sz, iD);
-  const double lox = fmin(fmin(A.x, B.x), fmin(C.x, D.x)), hix = fmax(fmax(A.x, B.x), fmax(C.x, D.x));
-  const double loy = fmin(fmin(A.y, B.y), fmin(C.y, D.y)), hiy = fmax(fmax(A.y, B.y), fmax(C.y, D.y));
-  const double loz = fmin(fmin(A.z, B.z), fmin(C.z, D.z)), hiz = fmax(fmax(A.z, B.z), fmax(C.z, D.z));
-  // the patch lies in the hull of its corners; its image on the sphere bulges out of it by <= d^2 / 2, and a point within tol of the
-  // parametric range by <= 2 tol d more (d: the box's diagonal)
-  const double d2 = (hix - lox) * (hix - lox) + (hiy - loy) * (hiy - loy) + (hiz - loz) * (hiz - loz);
-  const double pad = 0.5 * d2 + 2.0 * tol * sqrt(d2) + 1e-9;
-  if (P.x < lox - pad || P.x > hix + pad || P.y < loy - pad || P.y > hiy + pad || P.z < loz - pad || P.z > hiz + pad) return false;
-  double xi, eta;
-  if (!quad_solve(P, A, B, C, D, &xi, &eta)) return false;
-  if (xi < -tol || xi > 1.0 + tol || eta < -tol || eta > 1.0 + tol) return false;
+  if (!quad_try(P, ld3(sx, sy, sz, iA), ld3(sx, sy, sz, iB), ld3(sx, sy, sz, iC), ld3(sx, sy, sz, iD), tol, ww)) return false;   // (quad_solve.h)
   id[0] = (int32_t)iA; id[1] = (int32_t)iB; id[2] = (int32_t)iC; id[3] = (int32_t)iD;
-  ww[0] = (1 - xi) * (1 - eta); ww[1] = xi * (1 - eta); ww[2] = xi * eta; ww[3] = (1 - xi) * eta;
   return true;
 }
 

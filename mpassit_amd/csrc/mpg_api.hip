@@ -134,7 +134,7 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -472,6 +472,7 @@ int mpg_grid_destroy(mpg_grid g) {
   }
   g->cellpyr.free();
   for (int st = 0; st < 4; ++st) g->quadpyr[st].free();
+  g->wrappyr.free();
   for (int st = 0; st < 4; ++st) {
     g->lon[st].free();
     g->lat[st].free();
@@ -929,7 +930,7 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
   }
   if (regridmethod == MPG_REGRIDMETHOD_BILINEAR && (src->periodic & MPG_GRID_PERIODIC_I)) {
     mpg_set_error("mpg_regrid_store_to_mesh: bilinear from a periodic grid (MPG_GRID_PERIODIC_I: the i-wrap and the pole caps) is not supported; "
-                  "nearest is");
+                  "nearest is, and mpg_regrid_store_periodic_to_mesh is the bilinear Store of such a grid, with its pole method argument");
     return MPG_ERR_UNSUPPORTED;
   }
   if (dst->geo_grid) {
@@ -952,6 +953,56 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
   HandleKey key(src, 200 + src_staggerloc, dst, dst_meshloc,
                 regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 256 * mpg_grid_inside_tol_exp() : 0) + MPG_KEY_TO_MESH);
   return store_common(key, out, store_to_mesh_build, ctx);
+}
+
+// ---- bilinear Grid -> Mesh Store of a periodic grid (k_store_periodic_to_mesh.hip) --------------------------------------------------
+// Cache key: the Grid -> Mesh key of the CENTER stagger with the bilinear method, the inside tolerance and the direction bit, plus a kind
+// bit of its own -- mpg_regrid_store_to_mesh refuses bilinear on a periodic grid, and the bit keeps the key apart whatever that call
+// accepts one day -- and 65536 * pole_method: the two pole methods are two handles.  The grid sits in the first place, so
+// mpg_mesh_set_source_window passes these handles by; cache_purge looks at both places.
+#define MPG_KEY_PERIODIC (1 << 22)
+static int store_periodic_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
+  StoreCtx *x = (StoreCtx *)c;
+  h->method = MPG_REGRIDMETHOD_BILINEAR;
+  return mpg_k_store_periodic_to_mesh(x->g, x->m, x->meshloc, x->method, h, s);   // (ctx.method carries the pole method)
+}
+
+int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshloc, int pole_method, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_periodic_to_mesh: NULL argument");
+  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE,
+          "mpg_regrid_store_periodic_to_mesh: unknown mesh location (MPG_MESHLOC_ELEMENT or MPG_MESHLOC_NODE)");
+  MPG_ARG(pole_method == MPG_POLEMETHOD_NONE || pole_method == MPG_POLEMETHOD_ALLAVG,
+          "mpg_regrid_store_periodic_to_mesh: pole_method must be MPG_POLEMETHOD_NONE or MPG_POLEMETHOD_ALLAVG (NPNTAVG and TEETH are not built)");
+  if (!(src->periodic & MPG_GRID_PERIODIC_I)) {
+    mpg_set_error("mpg_regrid_store_periodic_to_mesh: the grid was not created with MPG_GRID_PERIODIC_I; mpg_regrid_store_to_mesh is the "
+                  "Store of a regional grid");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->geo_grid) {
+    mpg_set_error("mpg_regrid_store_periodic_to_mesh: the mesh was cut to a grid (mpg_mesh_create_window): its resident cells are a window and "
+                  "the result would be a partial mesh; create the whole mesh with mpg_mesh_create");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->nx < 3 || src->ny < 2) {
+    mpg_set_error("mpg_regrid_store_periodic_to_mesh: a periodic bilinear Store needs nx >= 3 and ny >= 2 CENTER points, not %d x %d", src->nx,
+                  src->ny);
+    return MPG_ERR_INVALID_ARG;
+  }
+  const int64_t n_src = (int64_t)src->nx * src->ny;
+  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
+  if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_periodic_to_mesh: %lld source points / %lld mesh points exceed int32 ids", (long long)n_src, (long long)n_dst);
+    return MPG_ERR_OVERFLOW;
+  }
+  if (src->pts[MPG_STAGGERLOC_CENTER].n != n_src) {
+    mpg_set_error("mpg_regrid_store_periodic_to_mesh: the grid holds no CENTER coordinates");
+    return MPG_ERR_INVALID_ARG;
+  }
+  StoreCtx ctx{dst, src, MPG_STAGGERLOC_CENTER, pole_method, dst_meshloc};
+  HandleKey key(src, 200 + MPG_STAGGERLOC_CENTER, dst, dst_meshloc,
+                MPG_REGRIDMETHOD_BILINEAR + 256 * mpg_grid_inside_tol_exp() + 65536 * pole_method + MPG_KEY_TO_MESH + MPG_KEY_PERIODIC);
+  return store_common(key, out, store_periodic_to_mesh_build, ctx);
 }
 
 // ---- conservative Grid -> Mesh Store (k_store_conserve.hip) ---------------------------------------------------------------------

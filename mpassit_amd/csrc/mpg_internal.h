@@ -296,6 +296,7 @@ struct mpg_grid_s {
   Pyramid pyr[4];   // point pyramids (per stagger), built lazily
   Pyramid cellpyr;  // pyramid over CENTER cells bounded by CORNER points (conservative)
   Pyramid quadpyr[4];   // pyramids over the quads of four neighbouring points of one stagger (Grid -> Mesh bilinear Store), built lazily
+  Pyramid wrappyr;      // pyramid over the nx x (ny - 1) CENTER quads of a grid periodic in i, the seam column included (periodic Grid -> Mesh Store), lazily
   // grids created from a projection (mpg_grid_create_proj) also keep what the output file needs
   bool from_proj = false;
   int proj_code = 0;
@@ -427,6 +428,8 @@ int mpg_k_mesh_coords_dev(int64_t n, const double *lon_rad_dev, const double *la
                           hipStream_t s);
 int mpg_k_build_pyramid(const PointSet &pts, int nx, int ny, Pyramid &pyr, hipStream_t s);
 int mpg_k_build_cell_pyramid(const PointSet &corner, int nx, int ny, Pyramid &pyr, hipStream_t s);
+// ... over the nx x (ny - 1) quads of nx x ny points periodic in i: quad (b, a) has corners (b, a), (b, (a + 1) mod nx) and the same of row b + 1
+int mpg_k_build_wrap_pyramid(const PointSet &pts, int nx, int ny, Pyramid &pyr, hipStream_t s);
 PyramidView mpg_pyr_view(const Pyramid &p);
 int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int meshloc, mpg_handle_s *h, hipStream_t s);
 int mpg_k_store_nearest(mpg_mesh_s *m, mpg_grid_s *g, int stagger, mpg_handle_s *h, hipStream_t s);
@@ -498,6 +501,9 @@ int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layou
                        const mpg_mask_opts *opts, hipStream_t s);
 // k_store_to_mesh.hip: Grid -> Mesh Store (bilinear: 4 slots, nearest: 1) of the grid's `stagger` points onto the mesh's cells / vertices
 int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s);
+// k_store_periodic_to_mesh.hip: bilinear Store of a grid periodic in i (CENTER points, the i-wrap and the pole caps) onto the mesh's cells /
+// vertices: a CSR handle, quad rows of 4 entries, cap rows of nx; pole_method MPG_POLEMETHOD_*
+int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s);
 // k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                         double scale, double offset, hipStream_t s);

@@ -32,3 +32,21 @@ __device__ inline bool quad_solve(dv3 P, dv3 A, dv3 B, dv3 C, dv3 D, double *xi,
   *eta = t;
   return lam > 0.0;
 }
+
+// One quad of the Grid -> Mesh Stores (k_store_to_mesh.hip, k_store_periodic_to_mesh.hip: the same text, hence the same weights): is P
+// inside the quad of corners A, B, C, D?  -> its four weights in corner order.  The quad is solved only when its box holds the point.
+__device__ __forceinline__ bool quad_try(dv3 P, dv3 A, dv3 B, dv3 C, dv3 D, double tol, double *ww) {
+  const double lox = fmin(fmin(A.x, B.x), fmin(C.x, D.x)), hix = fmax(fmax(A.x, B.x), fmax(C.x, D.x));
+  const double loy = fmin(fmin(A.y, B.y), fmin(C.y, D.y)), hiy = fmax(fmax(A.y, B.y), fmax(C.y, D.y));
+  const double loz = fmin(fmin(A.z, B.z), fmin(C.z, D.z)), hiz = fmax(fmax(A.z, B.z), fmax(C.z, D.z));
+  // the patch lies in the hull of its corners; its image on the sphere bulges out of it by <= d^2 / 2, and a point within tol of the
+  // parametric range by <= 2 tol d more (d: the box's diagonal)
+  const double d2 = (hix - lox) * (hix - lox) + (hiy - loy) * (hiy - loy) + (hiz - loz) * (hiz - loz);
+  const double pad = 0.5 * d2 + 2.0 * tol * sqrt(d2) + 1e-9;
+  if (P.x < lox - pad || P.x > hix + pad || P.y < loy - pad || P.y > hiy + pad || P.z < loz - pad || P.z > hiz + pad) return false;
+  double xi, eta;
+  if (!quad_solve(P, A, B, C, D, &xi, &eta)) return false;
+  if (xi < -tol || xi > 1.0 + tol || eta < -tol || eta > 1.0 + tol) return false;
+  ww[0] = (1 - xi) * (1 - eta); ww[1] = xi * (1 - eta); ww[2] = xi * eta; ww[3] = (1 - xi) * eta;
+  return true;
+}

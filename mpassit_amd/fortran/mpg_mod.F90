@@ -261,6 +261,16 @@ module mpg
       real(c_double), value :: scale, offset
       integer(c_int) :: rc
     end function mpg_regrid_to_mesh_dev
+    ! bilinear Grid -> Mesh Store of a grid periodic in i: the i-wrap and the pole caps (pole_method: MPG_POLEMETHOD_NONE = 0,
+    ! MPG_POLEMETHOD_ALLAVG = 1); a CSR handle, regridded by mpg_regrid_csr_to_mesh_dev below
+    function mpg_regrid_store_periodic_to_mesh(src, dst, dst_meshloc, pole_method, rh) &
+        bind(C, name="mpg_regrid_store_periodic_to_mesh") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: dst_meshloc, pole_method
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_periodic_to_mesh
     ! conservative Grid -> Mesh Store (norm_type: MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1), its dst fraction and the CSR Regrid in mesh order
     function mpg_regrid_store_conserve_to_mesh(src, dst, norm_type, rh) bind(C, name="mpg_regrid_store_conserve_to_mesh") result(rc)
       import :: c_int, c_ptr

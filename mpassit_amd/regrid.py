@@ -16,13 +16,14 @@ import numpy as np
 from . import _lib as L
 from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
-                   NORM_DSTAREA, NORM_FRACAREA, check)
+                   NORM_DSTAREA, NORM_FRACAREA, POLEMETHOD_NONE, POLEMETHOD_ALLAVG, check)
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
            "regrid_store_to_mesh", "regrid_to_mesh_autograd", "regrid_store_conserve_to_mesh", "regrid_csr_to_mesh_autograd", "NORM_DSTAREA",
            "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd", "regrid_store_conserve_mesh", "regrid_csr_rows_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
-           "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST"]
+           "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
+           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG"]
 
 
 def _f64(a):
@@ -905,6 +906,21 @@ def regrid_store_to_mesh(src_grid, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR,
     regrid_masked, regrid_transpose and the getters work on it, regrid_to_mesh writes the mesh's own memory orders."""
     h = C.c_void_p()
     check(L.regrid_store_to_mesh(src_grid._h, int(staggerloc), dst_mesh._h, int(meshloc), int(regridmethod), C.byref(h)))
+    return RouteHandle(h)
+
+
+def regrid_store_periodic_to_mesh(src_grid, dst_mesh, meshloc=MESHLOC_ELEMENT, pole_method=POLEMETHOD_ALLAVG):
+    """ESMF_FieldRegridStore(grid field -> mesh field, regridmethod=BILINEAR, polemethod=pole_method) from a grid that is periodic in i
+    (Grid(..., periodic=True), a global Grid.from_target / from_proj): the CENTER points onto the mesh's cells (MESHLOC_ELEMENT) or vertices
+    (MESHLOC_NODE), the seam column between i = nx - 1 and i = 0 and -- under POLEMETHOD_ALLAVG -- the pole caps included; POLEMETHOD_NONE
+    leaves the points poleward of the first and last row unmapped.  A CSR handle without pole terms (n_dst = the mesh count; quad rows of 4
+    entries, cap rows of nx): regrid_csr_to_mesh writes the mesh's own memory orders, regrid_csr_rows, regrid_typed, regrid_masked,
+    regrid_transpose, csr() and to_esmf_weights() work on it.  A non-periodic grid is refused (MpgError, rc 4): regrid_store_to_mesh is
+    its Store."""
+    if not (isinstance(src_grid, Grid) and isinstance(dst_mesh, Mesh)):
+        raise TypeError("regrid_store_periodic_to_mesh: src_grid must be a Grid and dst_mesh a Mesh")
+    h = C.c_void_p()
+    check(L.regrid_store_periodic_to_mesh(src_grid._h, dst_mesh._h, int(meshloc), int(pole_method), C.byref(h)))
     return RouteHandle(h)
 
 
