@@ -105,7 +105,11 @@ int mpg_mesh_window_info(mpg_mesh mesh, int64_t *cell_first, int64_t *cell_count
  *   in the regional case; the extra EDGE1 / CORNER column (index nx) duplicates column 0 one period later
  *   (ESMF's periodic staggers hold only the first nx columns).  Only Grid -> Grid RegridStore reads the flag.
  * OR in MPG_GRID_NO_SOUTH_POLE / MPG_GRID_NO_NORTH_POLE for a row block of a periodic grid that does not
- *   touch that pole (multi-GPU row sharding).
+ *   touch that pole (multi-GPU row sharding).  The two flags name an END of the row range, not a hemisphere: NO_SOUTH_POLE means
+ *   "rows precede row 0", NO_NORTH_POLE "rows follow row ny - 1" -- on rows numbered south to north, which is how a row block is cut
+ *   and the only numbering the Grid -> Grid RegridStore serves (it places its caps by row number and refuses a periodic grid whose
+ *   rows are numbered north to south with MPG_ERR_UNSUPPORTED: reverse the rows).  mpg_regrid_store_periodic_to_mesh takes either
+ *   numbering and finds each end's pole from the end row itself.
  * A coordinate that is NaN / Inf (or |lat| > 180) is refused with MPG_ERR_INVALID_ARG and the point's index; latitudes a little beyond
  * the pole (the corner row of a global lat-lon grid) are angles and pass. */
 enum { MPG_GRID_PERIODIC_I = 1, MPG_GRID_NO_SOUTH_POLE = 2, MPG_GRID_NO_NORTH_POLE = 4 };
@@ -207,12 +211,19 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
  *   with xi, eta in [-tol, 1 + tol], tol = 10^-grid_inside_tol_exp; weights (1-xi)(1-eta), xi (1-eta), xi eta, (1-xi) eta on A, B, C, D.
  *   It is that call's per-quad code: for a quad with a < nx - 1 the four weights are the bits mpg_regrid_store_to_mesh produces for the
  *   same coordinates handed over as a non-periodic grid; the seam quads a = nx - 1 are what that call cannot reach.
- * Pole caps are tried only when no quad passed, under MPG_POLEMETHOD_ALLAVG (ESMF_POLEMETHOD_ALLAVG, ESMF's default).  Cap ids run
- *   0 .. nx - 1 for the south (row 0), then nx .. 2 nx - 1 for the north (row ny - 1); the lowest passing id wins.  The triangles are those of
- *   the Grid -> Grid Store: north (A, B, N) with A = (ny - 1, a), B = (ny - 1, (a + 1) mod nx), south (B, A, S) on row 0, planar barycentric
- *   weights seen from the sphere's centre, tolerance 1e-10 whatever grid_inside_tol_exp says.  The pole node's value is the mean of its
- *   CENTER row, so a cap row has nx entries: every column of the row gets wr = t_pole / nx, columns A and B get t_A + wr and t_B + wr.
- *   MPG_GRID_NO_SOUTH_POLE / MPG_GRID_NO_NORTH_POLE (a row block) drop that end's cap.  MPG_POLEMETHOD_NONE (ESMF_POLEMETHOD_NONE): no caps.
+ * Pole caps are tried only when no quad passed, under MPG_POLEMETHOD_ALLAVG (ESMF_POLEMETHOD_ALLAVG, ESMF's default).  Each end row
+ *   is closed by a fan of nx triangles onto a pole node, and the node sits where the end row's own points say, not where the row number
+ *   says: the pole of an end is (0, 0, sign of the mean z of that end's CENTER row).  Rows numbered south to north (this project's
+ *   lat-lon grids) have the south pole at row 0; rows numbered north to south (GRIB, ERA5, the IFS and JRA-55 Gaussian grids) have the
+ *   north pole there, and both give the interpolation of the same physical grid.  With A = (row, a), B = (row, (a + 1) mod nx) the
+ *   triangle is (A, B, N) at the north pole and (B, A, S) at the south pole -- counter-clockwise seen from outside, the triangles of the
+ *   Grid -> Grid Store -- with planar barycentric weights seen from the sphere's centre, tolerance 1e-10 whatever grid_inside_tol_exp
+ *   says.  Cap ids run 0 .. nx - 1 for the row-0 end, then nx .. 2 nx - 1 for the row-(ny - 1) end; the lowest passing id wins.  The pole
+ *   node's value is the mean of its CENTER row, so a cap row has nx entries: every column of the row gets wr = t_pole / nx, columns A
+ *   and B get t_A + wr and t_B + wr.  An end row that sits on its pole leaves no point to a cap.
+ *   MPG_GRID_NO_SOUTH_POLE drops the cap of the row-0 end and MPG_GRID_NO_NORTH_POLE that of the row-(ny - 1) end, whichever pole that
+ *   end closes on: they describe a row block.  Two live ends whose rows lie in the same hemisphere are refused (at most one of them
+ *   closes on a pole).  MPG_POLEMETHOD_NONE (ESMF_POLEMETHOD_NONE): no caps.
  *   A point with no quad and no cap gets an empty row: Regrid gives 0.0 (mpg_regrid_masked_dev: fill_value).
  *   ESMF's NPNTAVG and TEETH pole methods are not built.  Other source staggers are not built either: the EDGE / CORNER columns of a
  *   periodic grid duplicate column 0, and their end rows sit on or beyond the poles.
@@ -228,7 +239,8 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
  *   mpg_handle_store_path reports 1 (index space) or 0.  Cap candidates are found the same way on both routes: the points no quad took
  *   are compacted into a list and only those are tested against the nx triangles of each live end.
  * Refusals, each with a message that names the way out.  MPG_ERR_INVALID_ARG: NULL arguments; an unknown dst_meshloc or pole_method;
- *   nx < 3 or ny < 2.  MPG_ERR_UNSUPPORTED: a grid without MPG_GRID_PERIODIC_I (mpg_regrid_store_to_mesh is its Store); a mesh of
+ *   nx < 3 or ny < 2; under ALLAVG, rows 0 and ny - 1 in one hemisphere with neither MPG_GRID_NO_SOUTH_POLE nor MPG_GRID_NO_NORTH_POLE
+ *   set.  MPG_ERR_UNSUPPORTED: a grid without MPG_GRID_PERIODIC_I (mpg_regrid_store_to_mesh is its Store); a mesh of
  *   mpg_mesh_create_window.  MPG_ERR_OVERFLOW: nx * ny or the mesh count beyond int32; nnz >= 2^31.
  * Cached like every Store and paired with one mpg_handle_release: the key carries the direction bit, a kind bit of its own and
  *   pole_method, so it collides with no Grid -> Mesh, conservative or Mesh -> Grid key and the two pole methods are two handles; parked

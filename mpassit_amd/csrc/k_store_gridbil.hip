@@ -97,6 +97,19 @@ int mpg_k_store_grid_bilinear(mpg_grid_s *g, int dst_stagger, mpg_handle_s *h, h
     mpg_set_error("grid RegridStore: stagger %d has no coordinates", dst_stagger);
     return MPG_ERR_INVALID_ARG;
   }
+  if (g->periodic & MPG_GRID_PERIODIC_I) {
+    // The caps of k_grid_bilinear go by row number: (B, A, S) below row 0, (A, B, N) above row ny - 1.  On rows numbered north to south
+    // the stagger points beyond an end row lie on the far side of both triangles and stay unmapped, and the pole terms (k_pole_fix,
+    // k_tr_pole) would carry the wrong pole: such a grid is refused rather than served in part.
+    if ((rc = mpg_k_grid_end_poles(g, s))) return rc;
+    const bool first = !(g->periodic & MPG_GRID_NO_SOUTH_POLE), last = !(g->periodic & MPG_GRID_NO_NORTH_POLE);
+    if ((first && g->end_pole[0] > 0) || (last && g->end_pole[1] < 0)) {
+      mpg_set_error("grid RegridStore: the periodic grid's CENTER rows are numbered north to south (row 0 closes on the north pole or row %d "
+                    "on the south pole); its pole caps go by row number: reverse the rows so that row 0 is the southernmost",
+                    g->ny - 1);
+      return MPG_ERR_UNSUPPORTED;
+    }
+  }
   h->kind = MPG_KIND_FIXED;
   h->nnz_per_row = 4;
   h->n_src = cen.n;

@@ -6,9 +6,14 @@
 //   quads  b in [0, ny - 2], a in [0, nx - 1]: A = (b, a), B = (b, (a + 1) mod nx), C = (b + 1, (a + 1) mod nx), D = (b + 1, a), quad id
 //          b * nx + a.  A point belongs to the LOWEST quad id for which quad_try (quad_solve.h: the per-quad code of k_store_to_mesh.hip)
 //          passes; the weights of a quad with a < nx - 1 are therefore the bits mpg_regrid_store_to_mesh produces for the same coordinates.
-//   caps   only for points no quad took, under MPG_POLEMETHOD_ALLAVG: the triangles of k_grid_bilinear (k_store_gridbil.hip) -- north
-//          tri_weights(P, A, B, (0, 0, 1)) with A = (ny - 1, a), B = (ny - 1, (a + 1) mod nx), south tri_weights(P, B, A, (0, 0, -1)) on row
-//          0, MPG_TOL whatever the inside-tolerance knob says.  Cap ids 0 .. nx - 1 south, nx .. 2 nx - 1 north, the lowest passing id wins.
+//   caps   only for points no quad took, under MPG_POLEMETHOD_ALLAVG: one fan of nx triangles per end row, A = (row, a), B = (row, (a + 1)
+//          mod nx) and the pole that row closes on -- (0, 0, sign of the row's mean z), so the pole node sits where the end row's own
+//          points say, not where the row number says (ESMF's MONOPOLE cap): rows numbered south to north have the south pole at row 0,
+//          rows numbered north to south (GRIB, the Gaussian grids) the north pole.  Counter-clockwise seen from outside: tri_weights(P, A,
+//          B, (0, 0, 1)) at the north pole, tri_weights(P, B, A, (0, 0, -1)) at the south pole (the triangles of k_grid_bilinear,
+//          k_store_gridbil.hip), MPG_TOL whatever the inside-tolerance knob says.  Cap ids 0 .. nx - 1 on row 0, nx .. 2 nx - 1 on row
+//          ny - 1, the lowest passing id wins.  The two signs are found once per grid on the host (mpg_k_grid_end_poles); two live ends on the
+//          same pole are refused.
 //          The pole's value is the mean of its CENTER row: the row has nx entries, each wr = t_pole / nx, columns A and B t_A + wr, t_B + wr.
 // The handle is an ordinary CSR one with no pole terms: quad rows of exactly 4 entries (zeros included) sorted by column, cap rows of
 // exactly nx in column order, empty rows for points nothing mapped.
@@ -22,6 +27,8 @@
 // No floating-point contraction in this translation unit (see k_store_conserve.hip).
 #pragma clang fp contract(off)
 #include <math.h>
+
+#include <vector>
 
 #include "geom.h"
 #include "mpg_internal.h"
@@ -144,28 +151,31 @@ __global__ __launch_bounds__(256) void k_ptm_list(int64_t n, const int32_t *__re
   if (p < n && qid[p] < 0) list[moff[p]] = (int32_t)p;
 }
 
-// One wavefront per listed point, lanes over the cap ids (south 0 .. nx - 1, north nx .. 2 nx - 1) in steps of 64: every lane keeps the
-// first -- its lowest -- passing id, the wavefront takes the minimum.  A point in a cap: qid = -2 - cap id, wq[0 .. 2] = t_A, t_B, t_pole.
+// One wavefront per listed point, lanes over the cap ids (row 0: 0 .. nx - 1, row ny - 1: nx .. 2 nx - 1) in steps of 64: every lane keeps
+// the first -- its lowest -- passing id, the wavefront takes the minimum.  A point in a cap: qid = -2 - cap id, wq[0 .. 2] = t_A, t_B, t_pole.
+// pole0 / pole1: the z (+1 or -1) of the pole row 0 / row ny - 1 closes on.
 __global__ __launch_bounds__(256) void k_ptm_caps(int nlist, const int32_t *__restrict__ list, int64_t n, const double *__restrict__ px,
                                                   const double *__restrict__ py, const double *__restrict__ pz, int nx, int ny, int flags,
-                                                  const double *__restrict__ sx, const double *__restrict__ sy, const double *__restrict__ sz,
-                                                  int32_t *__restrict__ qid, double *__restrict__ wq) {
+                                                  double pole0, double pole1, const double *__restrict__ sx, const double *__restrict__ sy,
+                                                  const double *__restrict__ sz, int32_t *__restrict__ qid, double *__restrict__ wq) {
   const int lane = threadIdx.x & (MPG_WAVE - 1);
   const int k = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / MPG_WAVE);
   if (k >= nlist) return;   // (the whole wavefront)
   const int64_t p = list[k];
   const dv3 P = dv3{px[p], py[p], pz[p]};
-  const bool south = !(flags & MPG_GRID_NO_SOUTH_POLE), north = !(flags & MPG_GRID_NO_NORTH_POLE);
+  const bool first = !(flags & MPG_GRID_NO_SOUTH_POLE), last = !(flags & MPG_GRID_NO_NORTH_POLE);   // the row-0 end, the row-(ny - 1) end
   int mine = PTM_CAP_NONE;
   double tA = 0.0, tB = 0.0, tP = 0.0;
-  for (int id = (south ? 0 : nx) + lane; id < (north ? 2 * nx : nx); id += MPG_WAVE) {
-    const bool is_north = id >= nx;
-    const int a = is_north ? id - nx : id, a1 = a + 1 == nx ? 0 : a + 1;
-    const int64_t row0 = is_north ? (int64_t)(ny - 1) * nx : 0;
+  for (int id = (first ? 0 : nx) + lane; id < (last ? 2 * nx : nx); id += MPG_WAVE) {
+    const bool is_last = id >= nx;
+    const int a = is_last ? id - nx : id, a1 = a + 1 == nx ? 0 : a + 1;
+    const int64_t row0 = is_last ? (int64_t)(ny - 1) * nx : 0;
+    const double pole = is_last ? pole1 : pole0;
+    const bool is_north = pole > 0.0;
     const dv3 A = ld3(sx, sy, sz, row0 + a), B = ld3(sx, sy, sz, row0 + a1);
     double t[3];
-    // counter-clockwise seen from outside: (A, B, N) in the north, (B, A, S) in the south
-    const bool in = is_north ? tri_weights(P, A, B, dv3{0.0, 0.0, 1.0}, MPG_TOL, t) : tri_weights(P, B, A, dv3{0.0, 0.0, -1.0}, MPG_TOL, t);
+    // counter-clockwise seen from outside: (A, B, N) at the north pole, (B, A, S) at the south pole
+    const bool in = is_north ? tri_weights(P, A, B, dv3{0.0, 0.0, pole}, MPG_TOL, t) : tri_weights(P, B, A, dv3{0.0, 0.0, pole}, MPG_TOL, t);
     if (in) {
       mine = id;
       tA = is_north ? t[0] : t[1];
@@ -263,6 +273,24 @@ static bool ptm_index_route(const mpg_grid_s *g) {
   return bulge <= 0.04;
 }
 
+// The pole each end row closes on, once per grid: the sign of the mean z of CENTER row 0 and of row ny - 1, summed on the host in column
+// order (one number per end decides every triangle of its fan; no lane, no atomic takes part).
+int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s) {
+  if (g->end_pole[0] && g->end_pole[1]) return MPG_SUCCESS;
+  const int nx = g->nx;
+  const double *z = g->pts[MPG_STAGGERLOC_CENTER].z.p;
+  std::vector<double> row(2 * (size_t)nx);
+  MPG_HIP(hipMemcpyAsync(row.data(), z, sizeof(double) * nx, hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipMemcpyAsync(row.data() + nx, z + (int64_t)(g->ny - 1) * nx, sizeof(double) * nx, hipMemcpyDeviceToHost, s));
+  MPG_HIP(hipStreamSynchronize(s));
+  for (int e = 0; e < 2; ++e) {
+    double sum = 0.0;
+    for (int i = 0; i < nx; ++i) sum += row[(size_t)e * nx + i];
+    g->end_pole[e] = sum < 0.0 ? -1 : 1;
+  }
+  return MPG_SUCCESS;
+}
+
 int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s) {
   int rc;
   const PointSet &src = g->pts[MPG_STAGGERLOC_CENTER];
@@ -281,6 +309,17 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
     MPG_HIP(hipMemsetAsync(h->rowptr.p, 0, sizeof(int32_t), s));
     MPG_HIP(hipStreamSynchronize(s));
     return MPG_SUCCESS;
+  }
+  const int no_pole = g->periodic & (MPG_GRID_NO_SOUTH_POLE | MPG_GRID_NO_NORTH_POLE);
+  const bool caps = pole_method == MPG_POLEMETHOD_ALLAVG && no_pole != (MPG_GRID_NO_SOUTH_POLE | MPG_GRID_NO_NORTH_POLE);
+  if (caps) {
+    if ((rc = mpg_k_grid_end_poles(g, s))) return rc;
+    if (!no_pole && g->end_pole[0] == g->end_pole[1]) {
+      mpg_set_error("mpg_regrid_store_periodic_to_mesh: CENTER rows 0 and %d both lie in the %s hemisphere, so at most one of them closes on a "
+                    "pole; a row block passes MPG_GRID_NO_SOUTH_POLE (row 0) / MPG_GRID_NO_NORTH_POLE (row ny - 1) for the end that does not",
+                    g->ny - 1, g->end_pole[0] > 0 ? "northern" : "southern");
+      return MPG_ERR_INVALID_ARG;
+    }
   }
   Pyramid &pyr = g->wrappyr;
   if (!pyr.built && (rc = mpg_k_build_wrap_pyramid(src, nx, ny, pyr, s))) return rc;
@@ -309,8 +348,6 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
   MPG_HIP(hipGetLastError());
   // the points no quad took, as a list of exact size: count, scan, fill (len serves as the flags and then as the offsets)
   int32_t nlist = 0;
-  const bool caps = pole_method == MPG_POLEMETHOD_ALLAVG &&
-                    (g->periodic & (MPG_GRID_NO_SOUTH_POLE | MPG_GRID_NO_NORTH_POLE)) != (MPG_GRID_NO_SOUTH_POLE | MPG_GRID_NO_NORTH_POLE);
   if (caps) {
     k_ptm_miss<<<nb1, 256, 0, s>>>(n, qid.p, len.p);
     MPG_HIP(hipGetLastError());
@@ -321,7 +358,7 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
       if ((rc = list.alloc((size_t)nlist, s))) return rc;
       k_ptm_list<<<nb, 256, 0, s>>>(n, qid.p, len.p, list.p);
       k_ptm_caps<<<(unsigned)(((int64_t)nlist * MPG_WAVE + 255) / 256), 256, 0, s>>>(nlist, list.p, n, dst.x.p, dst.y.p, dst.z.p, nx, ny, g->periodic,
-                                                                                    src.x.p, src.y.p, src.z.p, qid.p, wq.p);
+                                                                                    (double)g->end_pole[0], (double)g->end_pole[1], src.x.p, src.y.p, src.z.p, qid.p, wq.p);
       MPG_HIP(hipGetLastError());
     }
   }

@@ -297,6 +297,8 @@ struct mpg_grid_s {
   Pyramid cellpyr;  // pyramid over CENTER cells bounded by CORNER points (conservative)
   Pyramid quadpyr[4];   // pyramids over the quads of four neighbouring points of one stagger (Grid -> Mesh bilinear Store), built lazily
   Pyramid wrappyr;      // pyramid over the nx x (ny - 1) CENTER quads of a grid periodic in i, the seam column included (periodic Grid -> Mesh Store), lazily
+  int end_pole[2] = {0, 0};   // the pole each end row of a periodic grid closes on: the sign of the mean z of CENTER row 0 / row ny - 1 (+1 north, -1 south);
+                              // 0 = not looked at yet (periodic Grid -> Mesh Store, lazily)
   // grids created from a projection (mpg_grid_create_proj) also keep what the output file needs
   bool from_proj = false;
   int proj_code = 0;
@@ -504,6 +506,8 @@ int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, 
 // k_store_periodic_to_mesh.hip: bilinear Store of a grid periodic in i (CENTER points, the i-wrap and the pole caps) onto the mesh's cells /
 // vertices: a CSR handle, quad rows of 4 entries, cap rows of nx; pole_method MPG_POLEMETHOD_*
 int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s);
+// ... and the pole each end row of a periodic grid closes on, into g->end_pole (once per grid; a host read of the two CENTER rows)
+int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s);
 // k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                         double scale, double offset, hipStream_t s);

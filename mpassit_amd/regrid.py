@@ -913,7 +913,9 @@ def regrid_store_periodic_to_mesh(src_grid, dst_mesh, meshloc=MESHLOC_ELEMENT, p
     """ESMF_FieldRegridStore(grid field -> mesh field, regridmethod=BILINEAR, polemethod=pole_method) from a grid that is periodic in i
     (Grid(..., periodic=True), a global Grid.from_target / from_proj): the CENTER points onto the mesh's cells (MESHLOC_ELEMENT) or vertices
     (MESHLOC_NODE), the seam column between i = nx - 1 and i = 0 and -- under POLEMETHOD_ALLAVG -- the pole caps included; POLEMETHOD_NONE
-    leaves the points poleward of the first and last row unmapped.  A CSR handle without pole terms (n_dst = the mesh count; quad rows of 4
+    leaves the points poleward of the first and last row unmapped.  Each end row closes on the pole of its own hemisphere (the sign of the
+    row's mean z), so the rows may be numbered south to north or north to south (GRIB, ERA5, the Gaussian grids); GRID_NO_SOUTH_POLE /
+    GRID_NO_NORTH_POLE name the row-0 / row-(ny-1) end of a row block, and two live ends in one hemisphere are refused (rc 2).  A CSR handle without pole terms (n_dst = the mesh count; quad rows of 4
     entries, cap rows of nx): regrid_csr_to_mesh writes the mesh's own memory orders, regrid_csr_rows, regrid_typed, regrid_masked,
     regrid_transpose, csr() and to_esmf_weights() work on it.  A non-periodic grid is refused (MpgError, rc 4): regrid_store_to_mesh is
     its Store."""

@@ -4,12 +4,14 @@ Not a copy of the kernel: no pyramid, no index boxes, no candidate list, no sort
   quads  _to_mesh_ref.to_mesh_bilinear on the CENTER points padded with column 0 as column nx: its quad (b, a) of the padded grid IS
          quad (b, a) of the periodic one (id b * nx + a, lowest id first), and its columns map back by a + 1 -> (a + 1) mod nx.
   caps   the oracle's bilinear_weights (planar barycentric weights seen from the sphere's centre, the lowest passing triangle id) on the
-         points of the two end rows plus the two pole points; triangle ids 0 .. nx - 1 south (B, A, S), nx .. 2 nx - 1 north (A, B, N).
+         points of the two end rows plus one pole point per end, (0, 0, sign of that end row's mean z): (A, B, N) at the north pole,
+         (B, A, S) at the south pole; triangle ids 0 .. nx - 1 on row 0, nx .. 2 nx - 1 on row ny - 1, whichever way the rows are numbered.
          Only points no quad took are asked.
   rows   quad rows: 4 entries, zeros included; cap rows: nx entries, wr = t_pole / nx everywhere, t_A + wr and t_B + wr on A and B;
          columns ascending.
 `mutate` builds deliberately wrong variants for the reference's own tests: "seam_swap_bc" (B and C exchanged in the seam quads),
-"cap_no_division" (wr = t_pole), "caps_first" (a cap is tried before the quads).
+"cap_no_division" (wr = t_pole), "caps_first" (a cap is tried before the quads), "caps_by_row_index" (row 0 always takes the pole (0, 0, -1)
+and row ny - 1 (0, 0, 1): Arctic points of a grid numbered north to south then get rows of the Antarctic end row).
 """
 import numpy as np
 
@@ -20,28 +22,33 @@ POLE_NONE, POLE_ALLAVG = 0, 1
 KIND_NONE, KIND_QUAD, KIND_CAP = 0, 1, 2
 
 
-def _caps(oracle, cen, pts, flags):
-    """-> (cap id [n], -1 = none; t_A, t_B, t_pole [n]; smallest barycentric coordinate [n])"""
+def _caps(oracle, cen, pts, flags, by_row_index=False):
+    """-> (cap id [n], -1 = none; t_A, t_B, t_pole [n]; smallest barycentric coordinate [n]).
+    The pole of an end is (0, 0, sign of that end row's mean z); by_row_index: the rule before that one, (0, 0, -1) for row 0 and
+    (0, 0, 1) for row ny - 1 whatever the rows' latitudes."""
     ny, nx, _ = cen.shape
-    cells = np.concatenate([cen[0], cen[ny - 1], [[0.0, 0.0, -1.0]], [[0.0, 0.0, 1.0]]])
+    pole = [-1.0, 1.0] if by_row_index else [-1.0 if cen[j, :, 2].mean() < 0.0 else 1.0 for j in (0, ny - 1)]
+    if not by_row_index and not flags & (NO_SOUTH | NO_NORTH) and pole[0] == pole[1]:
+        raise ValueError("both end rows lie in one hemisphere: at most one closes on a pole (MPG_GRID_NO_SOUTH_POLE / MPG_GRID_NO_NORTH_POLE)")
+    cells = np.concatenate([cen[0], cen[ny - 1], [[0.0, 0.0, pole[0]]], [[0.0, 0.0, pole[1]]]])
     a = np.arange(nx)
     a1 = (a + 1) % nx
-    south = np.stack([a1, a, np.full(nx, 2 * nx)], axis=1)            # (B, A, S)
-    north = np.stack([nx + a, nx + a1, np.full(nx, 2 * nx + 1)], axis=1)   # (A, B, N)
+    # counter-clockwise seen from outside: (A, B, N) at the north pole, (B, A, S) at the south pole
+    ends = [np.stack([e * nx + a, e * nx + a1, np.full(nx, 2 * nx + e)], axis=1) if pole[e] > 0 else
+            np.stack([e * nx + a1, e * nx + a, np.full(nx, 2 * nx + e)], axis=1) for e in (0, 1)]
     if flags & NO_SOUTH:
-        south[:] = -1
+        ends[0][:] = -1
     if flags & NO_NORTH:
-        north[:] = -1
-    idx, w = oracle.bilinear_weights(cells, np.concatenate([south, north]).astype(np.int32), pts)
+        ends[1][:] = -1
+    idx, w = oracle.bilinear_weights(cells, np.concatenate(ends).astype(np.int32), pts)
     n = pts.shape[0]
     cap, tA, tB, tP = np.full(n, -1, np.int64), np.zeros(n), np.zeros(n), np.zeros(n)
     hit = idx[:, 0] >= 0
-    is_north = hit & (idx[:, 2] == 2 * nx + 1)
-    is_south = hit & ~is_north
-    cap[is_south] = idx[is_south, 1]
-    tA[is_south], tB[is_south] = w[is_south, 1], w[is_south, 0]
-    cap[is_north] = idx[is_north, 0]            # nx + a already
-    tA[is_north], tB[is_north] = w[is_north, 0], w[is_north, 1]
+    for e in (0, 1):
+        at = hit & (idx[:, 2] == 2 * nx + e)
+        ia, ib = (0, 1) if pole[e] > 0 else (1, 0)
+        cap[at] = idx[at, ia]            # e * nx + a already
+        tA[at], tB[at] = w[at, ia], w[at, ib]
     tP[hit] = w[hit, 2]
     return cap, tA, tB, tP, np.where(hit, w.min(axis=1), np.nan)
 
@@ -69,7 +76,7 @@ def periodic_to_mesh(oracle, cen_xyz, pts, pole_method=POLE_ALLAVG, flags=0, tol
     if pole_method == POLE_ALLAVG:
         ask = np.arange(n) if mutate == "caps_first" else np.nonzero(~inq)[0]
         if ask.size:
-            c, ta, tb, tp, bary = _caps(oracle, cen, pts[ask], flags)
+            c, ta, tb, tp, bary = _caps(oracle, cen, pts[ask], flags, by_row_index=mutate == "caps_by_row_index")
             hit = c >= 0
             cap[ask[hit]] = c[hit]
             tA, tB, tP = np.zeros(n), np.zeros(n), np.zeros(n)

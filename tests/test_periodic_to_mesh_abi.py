@@ -36,7 +36,9 @@ def test_header_states_the_rule():
     doc = _doc(STORE, "Periodic Grid -> Mesh: ESMF_FieldRegridStore")
     for phrase in ("MPG_GRID_PERIODIC_I", "j * nx + i", "(a + 1) mod nx", "quad id = b * nx + a", "lowest quad id", "grid_inside_tol_exp",
                    "the bits mpg_regrid_store_to_mesh produces", "only when no quad passed", "MPG_POLEMETHOD_ALLAVG", "MPG_POLEMETHOD_NONE",
-                   "0 .. nx - 1 for the south", "nx .. 2 nx - 1 for the north", "the lowest passing id wins", "wr = t_pole / nx", "t_A + wr",
+                   "0 .. nx - 1 for the row-0 end", "nx .. 2 nx - 1 for the row-(ny - 1) end", "the lowest passing id wins",
+                   "sign of the mean z of that end's CENTER row", "(A, B, N) at the north pole", "(B, A, S) at the south pole", "numbered north to south",
+                   "in the same hemisphere are refused", "wr = t_pole / nx", "t_A + wr",
                    "MPG_GRID_NO_SOUTH_POLE", "MPG_GRID_NO_NORTH_POLE", "an empty row", "NPNTAVG", "TEETH", "EDGE / CORNER columns",
                    "nnz_per_row 0", "mpg_handle_pole_count gives 0", "no dst fraction", "exactly 4 entries, zeros included", "exactly nx",
                    "columns ascend within a row", "No atomic decides a stored byte", "store_boxes", "mpg_handle_store_path",

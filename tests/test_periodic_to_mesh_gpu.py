@@ -389,6 +389,17 @@ def test_refusals(case, gpu_lib, conus_grid_30km):
     plain = R.Grid(g.lon, g.lat)
     refused(store(plain._h, mesh._h, 0, 1, C.byref(h)), L.MPG_ERR_UNSUPPORTED, "MPG_GRID_PERIODIC_I", "mpg_regrid_store_to_mesh")
     plain.destroy()
+    # both end rows in one hemisphere: at most one of them closes on a pole, and the flags say which end does not
+    north_rows = g.lat[:, 0] > 0.0
+    half = R.Grid(g.lon[north_rows], g.lat[north_rows], periodic=L.GRID_PERIODIC_I)
+    refused(store(half._h, mesh._h, 0, 1, C.byref(h)), L.MPG_ERR_INVALID_ARG, "northern hemisphere", "MPG_GRID_NO_SOUTH_POLE", "MPG_GRID_NO_NORTH_POLE")
+    assert store(half._h, mesh._h, 0, R.POLEMETHOD_NONE, C.byref(h)) == L.MPG_SUCCESS, "without caps no pole is asked for"
+    R.RouteHandle(h).release()
+    half.destroy()
+    block = R.Grid(g.lon[north_rows], g.lat[north_rows], periodic=L.GRID_PERIODIC_I | L.GRID_NO_SOUTH_POLE)
+    assert store(block._h, mesh._h, 0, 1, C.byref(h)) == L.MPG_SUCCESS, lib.mpg_last_error().decode()
+    R.RouteHandle(h).release()
+    block.destroy()
     wgrid = R.Grid.from_target(conus_grid_30km, rows=(10, 60))
     wmesh = R.Mesh.from_mpas(case["m"], window_grid=wgrid)
     refused(store(grid._h, wmesh._h, 0, 1, C.byref(h)), L.MPG_ERR_UNSUPPORTED, "mpg_mesh_create_window", "mpg_mesh_create")
