@@ -36,7 +36,6 @@
 #include "mpg_internal.h"
 
 #define WIN_K 2.0        // assumed bound on the ratio of two cells' distances from a vertex they share
-#define WIN_STACK 64
 #define WIN_MAXPYR 4
 
 struct WinPyrs {
@@ -60,8 +59,10 @@ __global__ void k_grid_spacing(int nx, int ny, const double *__restrict__ x, con
 }
 
 // squared distance from (X, Y, Z) to the nearest leaf box of one pyramid if that is <= best2 (found = true), else best2
+// (its own branch and bound, not walk_nearest of tree_walk.h: the leaf's value is the bound already computed for the node, and with the
+// helper recomputing it the two kernels that call this took 7 more VGPRs; the stack has the helper's proven size)
 __device__ double pyr_dist2(const PyramidView &pyr, double X, double Y, double Z, double best2, bool &found) {
-  int stack[WIN_STACK];
+  int stack[WalkCap<PyrTree>::NEAREST];
   int sp = 0;
   const int top = pyr.nlev - 1;
   if (boxdist2_nofma(X, Y, Z, pyr.box + 6 * pyr.off[top]) > best2) return best2;
@@ -97,7 +98,7 @@ __device__ double pyr_dist2(const PyramidView &pyr, double X, double Y, double Z
       cd[k] = dc;
       cc[k] = child;
     }
-    for (int k = 0; k < nc && sp < WIN_STACK; ++k) stack[sp++] = ((lev - 1) << 26) | cc[k];
+    for (int k = 0; k < nc; ++k) stack[sp++] = ((lev - 1) << 26) | cc[k];
   }
   return best2;
 }
@@ -242,6 +243,8 @@ int mpg_k_mesh_window(mpg_mesh_s *m, mpg_grid_s *g, const double *latVertex, con
       pyrs.v[pyrs.n++] = mpg_pyr_view(g->pyr[st]);
     }
   }
+  for (int q = 0; q < pyrs.n; ++q)
+    if ((rc = mpg_walk_check<PyrTree>((int64_t)pyrs.v[q].nx[0] * pyrs.v[q].ny[0], "mpg_mesh_create_window"))) return rc;
   const int64_t nC = m->nCells, nV = m->nVertices;
   const unsigned nbC = (unsigned)((nC + 255) / 256);
   TmpBuf<unsigned long long> stats;

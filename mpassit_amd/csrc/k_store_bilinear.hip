@@ -20,7 +20,7 @@
 
 #include "mpg_internal.h"
 
-#define RASTER_STACK 64
+#define RASTER_STACK 64   // of k_tri_raster_big, which reports a full stack; k_tri_raster walks with tree_walk.h
 #define RASTER_BIG_LEAVES 16   // 4 x 4-point leaves a lane rasterises by itself before it hands its triangle over
 
 template <bool NORMAL>
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_tri_raster(int64_t nTri, const int32_t 
                                                     const double *__restrict__ cz, PyramidView pyr, int npx, int npy,
                                                     const double *__restrict__ px, const double *__restrict__ py,
                                                     const double *__restrict__ pz, int32_t *__restrict__ owner,
-                                                    int32_t *__restrict__ overflow, int32_t *__restrict__ big, int32_t *__restrict__ nbig,
+                                                    int32_t *__restrict__ big, int32_t *__restrict__ nbig,
                                                     int big_cap, const float *__restrict__ sij, float di, float dj, float pad_coef, float pad_latlon, float e_max) {
   int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= nTri) return;
@@ -93,75 +93,39 @@ __global__ __launch_bounds__(256) void k_tri_raster(int64_t nTri, const int32_t 
   double lo[3] = {fmin(A.x, fmin(B.x, C.x)) - pad, fmin(A.y, fmin(B.y, C.y)) - pad, fmin(A.z, fmin(B.z, C.z)) - pad};
   double hi[3] = {fmax(A.x, fmax(B.x, C.x)) + pad, fmax(A.y, fmax(B.y, C.y)) + pad, fmax(A.z, fmax(B.z, C.z)) + pad};
 
-  // Depth-first walk.  A node's four children are box-tested BEFORE they are pushed -- their 4 x 6 bounds are fetched in one
-  // round trip and only the ones the triangle's box meets go on the stack -- so the walk makes one iteration per node
-  // that meets the triangle (one or two per level for a triangle smaller than a leaf), not four per level, each of which
-  // was a dependent pop + box load (round 2; 82 % of this kernel's wave cycles were parked on those, profiles/r03_store_pmc.md).
-  auto meets = [&](int lev, int node) -> bool {
-    const double *bx = pyr.box + 6 * (pyr.off[lev] + node);
-    return !(bx[0] > hi[0] || bx[3] < lo[0] || bx[1] > hi[1] || bx[4] < lo[1] || bx[2] > hi[2] || bx[5] < lo[2]);
-  };
-  // The node to visit next lives in a register (`cur`); only the SIBLINGS that also meet the triangle go on the stack, which
-  // is a run-time-indexed private array, i.e. scratch memory: a triangle smaller than a leaf descends all ten levels without
-  // touching it.
-  int stack[RASTER_STACK];
-  int sp = 0;
-  int top = pyr.nlev - 1;
+  // walk_filter (tree_walk.h): one iteration per node that meets the triangle's box (one or two per level for a triangle smaller than a
+  // leaf), the node to visit next in a register, so that such a triangle descends all ten levels without touching the scratch stack
+  // (round 2; 82 % of this kernel's wave cycles were parked on dependent pops and box loads, profiles/r03_store_pmc.md).
+  const PyrTree tree{pyr};
   int nleaf = 0;
-  int cur = meets(top, 0) ? (top << 26) : -1;  // node 0 of the top level; node index < 2^26 per level
-  for (;;) {
-    if (cur < 0) {
-      if (sp == 0) break;
-      cur = stack[--sp];
-    }
-    const int e = cur;
-    cur = -1;
-    int lev = e >> 26;
-    int node = e & ((1 << 26) - 1);
-    int nxl = pyr.nx[lev];
-    int bi = node % nxl, bj = node / nxl;
-    if (lev == 0) {
-      // A triangle that spreads over many leaves (the cells around the pole of a lat-lon grid cover thousands of points each;
-      // every triangle of a mesh much coarser than the grid) is handed to k_tri_raster_big, one wavefront per triangle:
-      // here it would keep one lane busy for milliseconds.  What this lane has already marked stays valid (atomicMin).
-      if (++nleaf > RASTER_BIG_LEAVES && big_cap > 0) {
-        int slot = atomicAdd(nbig, 1);
-        if (slot < big_cap) {
-          big[slot] = (int32_t)t;
-          return;
+  walk_filter(
+      tree, walk_enc<PyrTree>(tree.top(), 0), true,
+      [&](const double *bx) { return !(bx[0] > hi[0] || bx[3] < lo[0] || bx[1] > hi[1] || bx[4] < lo[1] || bx[2] > hi[2] || bx[5] < lo[2]); },
+      [&](int node) {
+        // A triangle that spreads over many leaves (the cells around the pole of a lat-lon grid cover thousands of points each;
+        // every triangle of a mesh much coarser than the grid) is handed to k_tri_raster_big, one wavefront per triangle:
+        // here it would keep one lane busy for milliseconds.  What this lane has already marked stays valid (atomicMin).
+        if (++nleaf > RASTER_BIG_LEAVES && big_cap > 0) {
+          int slot = atomicAdd(nbig, 1);
+          if (slot < big_cap) {
+            big[slot] = (int32_t)t;
+            return true;
+          }
+          big_cap = 0;   // queue full: finish here
         }
-        big_cap = 0;   // queue full: finish here
-      }
-      int i0 = bi * MPG_PYR_B0, j0 = bj * MPG_PYR_B0;
-      int i1 = min(i0 + MPG_PYR_B0, npx), j1 = min(j0 + MPG_PYR_B0, npy);
-      for (int j = j0; j < j1; ++j)
-        for (int i = i0; i < i1; ++i) {
-          int64_t p = (int64_t)j * npx + i;
-          dv3 P = dv3{px[p], py[p], pz[p]};
-          if (P.x < lo[0] || P.x > hi[0] || P.y < lo[1] || P.y > hi[1] || P.z < lo[2] || P.z > hi[2]) continue;
-          double w[3];
-          if (NORMAL ? tri_weights_normal(P, A, B, C, MPG_TOL, w) : tri_weights(P, A, B, C, MPG_TOL, w)) atomicMin(&owner[p], (int32_t)t);
-        }
-    } else {
-      int cnx = pyr.nx[lev - 1], cny = pyr.ny[lev - 1];
-      bool go[4];
-#pragma unroll
-      for (int ch = 0; ch < 4; ++ch) {
-        int ci = 2 * bi + (ch & 1), cj = 2 * bj + (ch >> 1);
-        go[ch] = ci < cnx && cj < cny && meets(lev - 1, cj * cnx + ci);
-      }
-#pragma unroll
-      for (int ch = 0; ch < 4; ++ch)
-        if (go[ch]) {
-          const int child = ((lev - 1) << 26) | ((2 * bj + (ch >> 1)) * cnx + 2 * bi + (ch & 1));
-          // only nodes that meet the triangle are kept: a full stack cannot happen for a triangle smaller than the grid,
-          // and if it ever did it is reported (MPG_ERR_OVERFLOW), never a silently unmapped point
-          if (cur < 0) cur = child;
-          else if (sp < RASTER_STACK) stack[sp++] = child;
-          else atomicOr(overflow, 1);
-        }
-    }
-  }
+        int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
+        int i0 = bi * MPG_PYR_B0, j0 = bj * MPG_PYR_B0;
+        int i1 = min(i0 + MPG_PYR_B0, npx), j1 = min(j0 + MPG_PYR_B0, npy);
+        for (int j = j0; j < j1; ++j)
+          for (int i = i0; i < i1; ++i) {
+            int64_t p = (int64_t)j * npx + i;
+            dv3 P = dv3{px[p], py[p], pz[p]};
+            if (P.x < lo[0] || P.x > hi[0] || P.y < lo[1] || P.y > hi[1] || P.z < lo[2] || P.z > hi[2]) continue;
+            double w[3];
+            if (NORMAL ? tri_weights_normal(P, A, B, C, MPG_TOL, w) : tri_weights(P, A, B, C, MPG_TOL, w)) atomicMin(&owner[p], (int32_t)t);
+          }
+        return false;
+      });
 }
 
 // One wavefront per handed-over triangle: the same walk with a per-wave stack in LDS; four lanes test a node's children,
@@ -333,10 +297,7 @@ int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int mes
     return MPG_ERR_INVALID_ARG;
   }
   if (!g->pyr[stagger].built && (rc = mpg_k_build_pyramid(pts, npx, npy, g->pyr[stagger], s))) return rc;
-  if ((int64_t)g->pyr[stagger].nx[0] * g->pyr[stagger].ny[0] >= (1 << 26)) {
-    mpg_set_error("target grid too large for the raster pyramid");
-    return MPG_ERR_OVERFLOW;
-  }
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)g->pyr[stagger].nx[0] * g->pyr[stagger].ny[0], "RegridStore(bilinear)"))) return rc;
   h->kind = MPG_KIND_FIXED;
   h->nnz_per_row = 3;
   h->n_src = meshloc == MPG_MESHLOC_NODE ? m->nVertices : m->nCells;
@@ -350,7 +311,7 @@ int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int mes
   if ((rc = owner.alloc((size_t)P, s))) return rc;
   int fb = (int)((P + 255) / 256);
   if (fb > 8192) fb = 8192;
-  // one scratch allocation: [0] overflow flag, [1] length of the queue of handed-over triangles, [2 ...] the queue (nobody
+  // one scratch allocation: [0] overflow flag of k_tri_raster_big, [1] length of the queue of handed-over triangles, [2 ...] the queue (nobody
   // reads the length on the host)
   const int big_cap = (int)std::min<int64_t>(nT, 1 << 18);   // 0 for an empty window: nothing is handed over
   TmpBuf<int32_t> ovf;
@@ -376,7 +337,7 @@ int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int mes
   }
   if (nT > 0) {
     raster<<<(unsigned)((nT + 255) / 256), 256, 0, s>>>(nT, trip, nT, sx, sy, sz, mpg_pyr_view(g->pyr[stagger]), npx, npy, pts.x.p, pts.y.p, pts.z.p,
-                                                       owner.p, ovf.p, ovf.p + 2, ovf.p + 1, big_cap, sijp, di, dj, (float)mpg_grid_box_pad_coef(g), (float)mpg_grid_box_pad_latlon(g),
+                                                       owner.p, ovf.p + 2, ovf.p + 1, big_cap, sijp, di, dj, (float)mpg_grid_box_pad_coef(g), (float)mpg_grid_box_pad_latlon(g),
                                                        (float)mpg_grid_box_emax(g));
     raster_big<<<1024, 256, 0, s>>>(ovf.p + 2, ovf.p + 1, big_cap, trip, nT, sx, sy, sz, mpg_pyr_view(g->pyr[stagger]), npx, npy, pts.x.p, pts.y.p,
                                    pts.z.p, owner.p, ovf.p);
@@ -391,8 +352,7 @@ int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int mes
   h->store_stats[1] = std::min<int64_t>(h2[1], big_cap);   // triangles a wavefront rasterised (k_tri_raster_big)
   h->store_stats[2] = nT;
   if (h_ovf) {
-    mpg_set_error("RegridStore(bilinear): traversal stack of the triangle rasteriser overflowed (pyramid deeper than %d levels)",
-                  (RASTER_STACK - 1) / 3);
+    mpg_set_error("RegridStore(bilinear): traversal stack of the wave-cooperative triangle rasteriser overflowed");
     return MPG_ERR_OVERFLOW;
   }
   return MPG_SUCCESS;

@@ -31,7 +31,9 @@
 #include "conserve_clip.h"   // CONS_MAXV, CLIP_NT, LdsPoly, clip_halfspace_lds, cell_fan_area
 
 #define CONS_BUF (CONS_MAXV + 4)   // a convex polygon gains at most one vertex per clip plane
-#define CONS_STACK 64
+#define CONS_STACK 64   // this kernel keeps its own walk (its registers did not stay the same on tree_walk.h: profiles/r17_store_walks.md);
+                        // the bound of tree_walk.h holds for it too: 45 entries at most, so the guard below is never taken
+static_assert(CONS_STACK >= WalkCap<PyrTree>::FILTER, "the stack holds the walk's proven bound (tree_walk.h): its guard is never taken");
 #define CONS_QUEUE 2048  // breadth-first node queue of the cooperative passes
 
 // The pyramid walk of one source cell.  MODE 3 ("candidates", one thread per source cell): every destination cell that
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(MODE == 3 ? 128 : CONS_COOP_NT) void k_conserve_ras
   }
   if (MODE == 7) return;   // (only polygons with a usable box are queued)
   int stack[CONS_STACK];
-  // Seeds of the depth-first walk.  MODE 0: the root.  Cooperative modes: the workgroup first expands the pyramid
+  // Seeds of the depth-first walk.  MODE 3: the root.  Cooperative modes: the workgroup first expands the pyramid
   // breadth-first in LDS (one node per thread and level) down to 8 x 8-cell nodes, then every thread walks its share.
   __shared__ int q_nodes[2][CONS_QUEUE];
   __shared__ int q_n[2], q_over, s_found;
@@ -706,6 +708,7 @@ int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStrea
     return MPG_ERR_UNSUPPORTED;
   }
   if (!g->cellpyr.built && (rc = mpg_k_build_cell_pyramid(cor, nx, ny, g->cellpyr, s))) return rc;
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)g->cellpyr.nx[0] * g->cellpyr.ny[0], "conservative RegridStore"))) return rc;
   h->kind = MPG_KIND_CSR;
   h->nnz_per_row = 0;
   h->n_src = m->nCells;
@@ -864,6 +867,7 @@ int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mp
     return MPG_ERR_UNSUPPORTED;
   }
   if (!g->cellpyr.built && (rc = mpg_k_build_cell_pyramid(cor, nx, ny, g->cellpyr, s))) return rc;
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)g->cellpyr.nx[0] * g->cellpyr.ny[0], "mpg_regrid_store_conserve_to_mesh"))) return rc;
   const int64_t nC = m->nCells;   // (window meshes are refused by the entry point: every cell is resident)
   h->kind = MPG_KIND_CSR;
   h->nnz_per_row = 0;

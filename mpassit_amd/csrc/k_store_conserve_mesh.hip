@@ -32,18 +32,10 @@
 #include "mpg_internal.h"
 #include "conserve_clip.h"
 
-#define CM_STACK 96   // 7 siblings pushed per level, <= MPG_BVH_MAXLEV levels
-
-__global__ __launch_bounds__(256) void k_cell_morton(int64_t nC, const double *__restrict__ cx, const double *__restrict__ cy,
-                                                     const double *__restrict__ cz, unsigned long long *__restrict__ key,
-                                                     int32_t *__restrict__ id) {
-  const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (c >= nC) return;
-  id[c] = (int32_t)c;
-  key[c] = morton63(cx[c], cy[c], cz[c]);
-}
+#define CM_STACK 96   // 7 siblings pushed per level, <= MPG_BVH_MAXLEV levels (tree_walk.h: 77 entries at most)
 
 // the padded coordinate hull of cell c (see the head of this file); false: fewer than three vertices
+static_assert(CM_STACK >= WalkCap<BvhTree>::FILTER, "the stack holds the walk's proven bound (tree_walk.h): its guard is never taken");
 __device__ __forceinline__ bool cell_box(int64_t c, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
                                          const double *__restrict__ vy, const double *__restrict__ vz, double *lo, double *hi) {
   lo[0] = lo[1] = lo[2] = 2.0;
@@ -109,89 +101,28 @@ __global__ __launch_bounds__(256) void k_cbvh_cellbox(int64_t n, const int32_t *
   o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = hi[0]; o[4] = hi[1]; o[5] = hi[2];
 }
 
-__global__ __launch_bounds__(256) void k_cbvh_leaf(int64_t n, int64_t nleaf, const double *__restrict__ cellbox, double *__restrict__ box) {
-  const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (b >= nleaf) return;
-  double lo[3] = {2, 2, 2}, hi[3] = {-2, -2, -2};
-  const int64_t e = min(n, (b + 1) * MPG_BVH_LEAF);
-  for (int64_t i = b * MPG_BVH_LEAF; i < e; ++i) {
-    const double *c = cellbox + 6 * i;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = fmin(lo[k], c[k]);
-      hi[k] = fmax(hi[k], c[3 + k]);
-    }
-  }
-  double *o = box + 6 * b;
-  o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = hi[0]; o[4] = hi[1]; o[5] = hi[2];
-}
-
 static int build_cell_bvh(mpg_mesh_s *m, hipStream_t s) {
   CellBvh &b = m->cbvh;
   if (b.built) return MPG_SUCCESS;
   int rc;
   const int64_t n = m->nCells;
-  b.n = n;
-  int nlev = 0;
-  int64_t total = 0, cnt = std::max<int64_t>((n + MPG_BVH_LEAF - 1) / MPG_BVH_LEAF, 1);
-  if (cnt >= (1 << 27)) {
-    mpg_set_error("mpg_regrid_store_conserve_mesh: the source mesh has too many cells for the walk");
-    return MPG_ERR_OVERFLOW;
-  }
-  while (true) {
-    if (nlev >= MPG_BVH_MAXLEV) {
-      mpg_set_error("mpg_regrid_store_conserve_mesh: cell tree: too many levels");
-      return MPG_ERR_OVERFLOW;
-    }
-    b.nnodes[nlev] = cnt;
-    b.off[nlev] = total;
-    total += cnt;
-    ++nlev;
-    if (cnt == 1) break;
-    cnt = (cnt + MPG_BVH_FAN - 1) / MPG_BVH_FAN;
-  }
-  b.off[nlev] = total;
-  b.nlev = nlev;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  MPG_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    mpg_set_error("mpg_regrid_store_conserve_mesh: hipEventCreate failed");
-    return MPG_ERR_HIP;
-  }
-  auto build = [&]() -> int {
-    TmpBuf<unsigned long long> key_in, key_out;
-    TmpBuf<int32_t> id_in;
-    if ((rc = key_in.alloc(n, s)) || (rc = key_out.alloc(n, s)) || (rc = id_in.alloc(n, s)) || (rc = b.sorted_id.alloc(n)) ||
-        (rc = b.cellbox.alloc(6 * (size_t)n)) || (rc = b.box.alloc(6 * (size_t)total)))
-      return rc;
-    MPG_HIP(hipEventRecord(e0, s));
-    k_cell_morton<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, m->cell.x.p, m->cell.y.p, m->cell.z.p, key_in.p, id_in.p);
-    if ((rc = mpg_sort_pairs_u64_i32(key_in.p, key_out.p, id_in.p, b.sorted_id.p, n, s))) return rc;   // (k_sort.hip)
-    k_cbvh_cellbox<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, b.sorted_id.p, m->maxEdges, m->voc.p, m->vert.x.p, m->vert.y.p, m->vert.z.p,
-                                                               b.cellbox.p);
-    k_cbvh_leaf<<<(unsigned)((b.nnodes[0] + 255) / 256), 256, 0, s>>>(n, b.nnodes[0], b.cellbox.p, b.box.p);
-    MPG_HIP(hipGetLastError());
-    for (int l = 1; l < nlev; ++l)
-      if ((rc = mpg_k_bvh_up(b.nnodes[l - 1], b.nnodes[l], b.box.p + 6 * b.off[l - 1], b.box.p + 6 * b.off[l], s))) return rc;
-    MPG_HIP(hipEventRecord(e1, s));
-    MPG_HIP(hipEventSynchronize(e1));
-    MPG_HIP(hipEventElapsedTime(&b.build_ms, e0, e1));
-    return MPG_SUCCESS;
-  };
-  rc = build();
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc) {
-    b.free();
-    return rc;
-  }
-  b.built = true;
-  return MPG_SUCCESS;
+  if ((rc = b.cellbox.alloc(6 * (size_t)n))) return rc;
+  rc = mpg_bvh_build(
+      b, n, "mpg_regrid_store_conserve_mesh",
+      [&](unsigned long long *key, int32_t *id) { return mpg_k_morton(n, m->cell.x.p, m->cell.y.p, m->cell.z.p, key, id, 0, s); },
+      [&]() {
+        k_cbvh_cellbox<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, b.sorted_id.p, m->maxEdges, m->voc.p, m->vert.x.p, m->vert.y.p, m->vert.z.p,
+                                                                   b.cellbox.p);
+        static_assert(MPG_BVH_LEAF == MPG_BVH_FAN, "a leaf's box is the hull of its cells' boxes as an upper node's is of its children's");
+        return mpg_k_bvh_up(n, b.nnodes[0], b.cellbox.p, b.box.p, s);
+      },
+      s, true);
+  if (rc) b.free();
+  return rc;
 }
 
-// One thread per destination cell: depth-first over the nodes whose box meets the cell's (k_mesh_bilinear's shape: the node to visit next
-// in a register, only siblings on the stack); every source cell of every leaf reached whose own box meets it is a candidate.
+// One thread per destination cell: depth-first over the nodes whose box meets the cell's (its own loop, as k_mesh_bilinear's: the node to visit
+// next in a register, only siblings on the stack); every source cell of every leaf reached whose own box meets it is a candidate.
 // FILL = false counts them (cnt[d]; the scan's extra element cnt[nD] = 0), FILL = true writes them at poff[d] .. in the same order.
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_cm_candidates(int64_t nD, int maxEdges, const int32_t *__restrict__ voc, const double *__restrict__ vx,
@@ -366,13 +297,8 @@ int mpg_k_store_conserve_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int norm_type, m
   if ((rc = build_cell_bvh(src, s))) return rc;
   const CellBvh &b = src->cbvh;
   CellBvhView v;
-  v.n = b.n;
-  v.sid = b.sorted_id.p;
+  mpg_bvh_view(b, v);
   v.cellbox = b.cellbox.p;
-  v.nlev = b.nlev;
-  for (int i = 0; i < MPG_BVH_MAXLEV; ++i) v.nnodes[i] = i < b.nlev ? b.nnodes[i] : 0;
-  for (int i = 0; i <= MPG_BVH_MAXLEV; ++i) v.off[i] = i <= b.nlev ? b.off[i] : 0;
-  v.box = b.box.p;
   const double *sx = src->vert.x.p, *sy = src->vert.y.p, *sz = src->vert.z.p, *dx = dst->vert.x.p, *dy = dst->vert.y.p, *dz = dst->vert.z.p;
   // (1) orientation of both meshes' cells
   TmpBuf<uint8_t> orient_s, orient_d;

@@ -29,9 +29,10 @@
 #include "geom.h"
 #include "mpg_internal.h"
 
-#define MM_STACK 96   // 7 siblings pushed per level, <= MPG_BVH_MAXLEV levels
+#define MM_STACK 96   // 7 siblings pushed per level, <= MPG_BVH_MAXLEV levels (tree_walk.h: 77 entries at most)
 
 // key of triangle t = Morton code of its corners' centroid; a triangle without three cells sorts behind every real one
+static_assert(MM_STACK >= WalkCap<BvhTree>::FILTER, "the stack holds the walk's proven bound (tree_walk.h): its guard is never taken");
 __global__ __launch_bounds__(256) void k_tri_morton(int64_t nV, const int32_t *__restrict__ tri, const double *__restrict__ cx,
                                                     const double *__restrict__ cy, const double *__restrict__ cz,
                                                     unsigned long long *__restrict__ key, int32_t *__restrict__ id) {
@@ -78,73 +79,30 @@ __global__ __launch_bounds__(256) void k_tbvh_leaf(int64_t n, int64_t nleaf, con
 static int build_tri_bvh(mpg_mesh_s *m, hipStream_t s) {
   TriBvh &b = m->tbvh;
   if (b.built) return MPG_SUCCESS;
-  int rc;
   const int64_t n = m->nVertices;
-  b.n = n;
-  int nlev = 0;
-  int64_t total = 0, cnt = (n + MPG_BVH_LEAF - 1) / MPG_BVH_LEAF;
-  if (cnt >= (1 << 27)) {
-    mpg_set_error("mpg_regrid_store_mesh: the source mesh has too many triangles for the walk");
-    return MPG_ERR_OVERFLOW;
-  }
-  while (true) {
-    if (nlev >= MPG_BVH_MAXLEV) {
-      mpg_set_error("mpg_regrid_store_mesh: triangle BVH: too many levels");
-      return MPG_ERR_OVERFLOW;
-    }
-    b.nnodes[nlev] = cnt;
-    b.off[nlev] = total;
-    total += cnt;
-    ++nlev;
-    if (cnt == 1) break;
-    cnt = (cnt + MPG_BVH_FAN - 1) / MPG_BVH_FAN;
-  }
-  b.off[nlev] = total;
-  b.nlev = nlev;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  MPG_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    mpg_set_error("mpg_regrid_store_mesh: hipEventCreate failed");
-    return MPG_ERR_HIP;
-  }
-  auto build = [&]() -> int {
-    TmpBuf<unsigned long long> key_in, key_out;
-    TmpBuf<int32_t> id_in;
-    if ((rc = key_in.alloc(n, s)) || (rc = key_out.alloc(n, s)) || (rc = id_in.alloc(n, s)) || (rc = b.sorted_id.alloc(n)) ||
-        (rc = b.box.alloc(6 * (size_t)total)))
-      return rc;
-    MPG_HIP(hipEventRecord(e0, s));
-    k_tri_morton<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, m->tri.p, m->cell.x.p, m->cell.y.p, m->cell.z.p, key_in.p, id_in.p);
-    if ((rc = mpg_sort_pairs_u64_i32(key_in.p, key_out.p, id_in.p, b.sorted_id.p, n, s))) return rc;   // (k_sort.hip)
-    k_tbvh_leaf<<<(unsigned)((b.nnodes[0] + 255) / 256), 256, 0, s>>>(n, b.nnodes[0], b.sorted_id.p, m->tri.p, n, m->cell.x.p, m->cell.y.p,
-                                                                      m->cell.z.p, MPG_TOL, b.box.p);
-    MPG_HIP(hipGetLastError());
-    for (int l = 1; l < nlev; ++l)
-      if ((rc = mpg_k_bvh_up(b.nnodes[l - 1], b.nnodes[l], b.box.p + 6 * b.off[l - 1], b.box.p + 6 * b.off[l], s))) return rc;
-    MPG_HIP(hipEventRecord(e1, s));
-    MPG_HIP(hipEventSynchronize(e1));
-    MPG_HIP(hipEventElapsedTime(&b.build_ms, e0, e1));
-    return MPG_SUCCESS;
-  };
-  rc = build();
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc) {
-    b.free();
-    return rc;
-  }
-  b.built = true;
-  return MPG_SUCCESS;
+  const double *cx = m->cell.x.p, *cy = m->cell.y.p, *cz = m->cell.z.p;
+  const int rc = mpg_bvh_build(
+      b, n, "mpg_regrid_store_mesh",
+      [&](unsigned long long *key, int32_t *id) {
+        k_tri_morton<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, m->tri.p, cx, cy, cz, key, id);
+        return MPG_SUCCESS;
+      },
+      [&]() {
+        k_tbvh_leaf<<<(unsigned)((b.nnodes[0] + 255) / 256), 256, 0, s>>>(n, b.nnodes[0], b.sorted_id.p, m->tri.p, n, cx, cy, cz, MPG_TOL, b.box.p);
+        return MPG_SUCCESS;
+      },
+      s);
+  if (rc) b.free();
+  return rc;
 }
 
-// One thread per destination point: depth-first over the nodes whose box holds the point (k_to_mesh_bilinear's shape: the node to visit
-// next in a register, only siblings on the stack), every valid triangle of every leaf reached is tested, the lowest passing id is kept.
+// One thread per destination point: depth-first over the nodes whose box holds the point (its own loop, not walk_filter of tree_walk.h: on the helper the
+// Store was slower, profiles/r17_store_walks.md; the node to visit next in a register, only siblings on the stack), every valid triangle of every leaf reached is tested, the lowest passing id is kept.
 template <bool NORMAL>
 __global__ __launch_bounds__(256) void k_mesh_bilinear(int64_t n, const double *__restrict__ px, const double *__restrict__ py,
                                                        const double *__restrict__ pz, const int32_t *__restrict__ tri, int64_t nV,
                                                        const double *__restrict__ cx, const double *__restrict__ cy,
-                                                       const double *__restrict__ cz, TriBvhView b, double tol, int32_t *__restrict__ idx,
+                                                       const double *__restrict__ cz, BvhView b, double tol, int32_t *__restrict__ idx,
                                                        double *__restrict__ w, int32_t *__restrict__ overflow) {
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= n) return;
@@ -228,14 +186,8 @@ int mpg_k_store_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int dst_meshloc, int meth
   const bool had = src->tbvh.built;
   if ((rc = build_tri_bvh(src, s))) return rc;
   if (!had) h->store_stats[3] = (int64_t)(src->tbvh.build_ms * 1e3f);
-  const TriBvh &b = src->tbvh;
-  TriBvhView v;
-  v.n = b.n;
-  v.sid = b.sorted_id.p;
-  v.nlev = b.nlev;
-  for (int i = 0; i < MPG_BVH_MAXLEV; ++i) v.nnodes[i] = i < b.nlev ? b.nnodes[i] : 0;
-  for (int i = 0; i <= MPG_BVH_MAXLEV; ++i) v.off[i] = i <= b.nlev ? b.off[i] : 0;
-  v.box = b.box.p;
+  BvhView v;
+  mpg_bvh_view(src->tbvh, v);
   TmpBuf<int32_t> ovf;
   if ((rc = ovf.alloc(1, s))) return rc;
   MPG_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));

@@ -72,36 +72,37 @@ __global__ __launch_bounds__(256) void k_bvh_up(int64_t nchild, int64_t nparent,
   o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = hi[0]; o[4] = hi[1]; o[5] = hi[2];
 }
 
-// whole = false: only the cells of the mesh's geometry window are sites (a mesh cut to one rank's grid,
-// mpg_mesh_create_window); every cell centre is on the device in either case, so a search that turns out to need the
-// cells outside the window (mpg_k_store_nearest checks) rebuilds with whole = true
-int mpg_k_build_bvh(mpg_mesh_s *m, hipStream_t s, bool whole) {
-  SiteBvh &b = m->bvh;
-  if (b.built && (m->bvh_whole || !whole)) return MPG_SUCCESS;
-  if (b.built) b.free();
+// upper level of a Morton-ordered box tree: parent b = the hull of children [8 b, 8 b + 8)
+int mpg_k_bvh_up(int64_t nchild, int64_t nparent, const double *child, double *parent, hipStream_t s) {
+  k_bvh_up<<<(unsigned)((nparent + 255) / 256), 256, 0, s>>>(nchild, nparent, child, parent);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+int mpg_k_morton(int64_t n, const double *x, const double *y, const double *z, unsigned long long *key, int32_t *id, int64_t first, hipStream_t s) {
+  k_morton<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, x, y, z, key, id, first);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
+void mpg_bvh_view(const Bvh &b, BvhView &v) {
+  v.n = b.n;
+  v.sid = b.sorted_id.p;
+  v.nlev = b.nlev;
+  for (int i = 0; i < MPG_BVH_MAXLEV; ++i) v.nnodes[i] = i < b.nlev ? b.nnodes[i] : 0;
+  for (int i = 0; i <= MPG_BVH_MAXLEV; ++i) v.off[i] = i <= b.nlev ? b.off[i] : 0;
+  v.box = b.box.p;
+}
+
+// level sizes of a tree over n items
+static int bvh_plan(Bvh &b, int64_t n, const char *who, bool empty_leaf) {
   int rc;
-  const int64_t first = whole ? 0 : m->cw0;
-  int64_t n = whole ? m->nCells : m->cwn;
-  if (n == 0) {   // an empty window: the whole mesh it is
-    whole = true;
-    n = m->nCells;
-  }
-  m->bvh_whole = whole;
   b.n = n;
-  TmpBuf<unsigned long long> key_in, key_out;
-  TmpBuf<int32_t> id_in;
-  if ((rc = key_in.alloc(n, s)) || (rc = key_out.alloc(n, s)) || (rc = id_in.alloc(n, s)) || (rc = b.sorted_id.alloc(n))) return rc;
-  if ((rc = b.sorted.alloc(n))) return rc;
-  unsigned nb = (unsigned)((n + 255) / 256);
-  k_morton<<<nb, 256, 0, s>>>(n, m->cell.x.p, m->cell.y.p, m->cell.z.p, key_in.p, id_in.p, first);
-  if ((rc = mpg_sort_pairs_u64_i32(key_in.p, key_out.p, id_in.p, b.sorted_id.p, n, s))) return rc;   // (k_sort.hip: rocPRIM's radix sort)
-  k_gather_sites<<<nb, 256, 0, s>>>(n, b.sorted_id.p, m->cell.x.p, m->cell.y.p, m->cell.z.p, b.sorted.x.p, b.sorted.y.p, b.sorted.z.p);
-  // level sizes
   int nlev = 0;
-  int64_t total = 0, cnt = (n + MPG_BVH_LEAF - 1) / MPG_BVH_LEAF;
+  int64_t total = 0, cnt = std::max<int64_t>((n + MPG_BVH_LEAF - 1) / MPG_BVH_LEAF, empty_leaf ? 1 : 0);
+  if ((rc = mpg_walk_check<BvhTree>(cnt, who))) return rc;
   while (true) {
     if (nlev >= MPG_BVH_MAXLEV) {
-      mpg_set_error("bvh: too many levels");
+      mpg_set_error("%s: BVH: too many levels", who);
       return MPG_ERR_OVERFLOW;
     }
     b.nnodes[nlev] = cnt;
@@ -113,23 +114,78 @@ int mpg_k_build_bvh(mpg_mesh_s *m, hipStream_t s, bool whole) {
   }
   b.off[nlev] = total;
   b.nlev = nlev;
-  if ((rc = b.box.alloc(6 * (size_t)total))) return rc;
-  k_bvh_leaf<<<(unsigned)((b.nnodes[0] + 255) / 256), 256, 0, s>>>(n, b.nnodes[0], b.sorted.x.p, b.sorted.y.p, b.sorted.z.p, b.box.p);
-  for (int l = 1; l < nlev; ++l)
-    k_bvh_up<<<(unsigned)((b.nnodes[l] + 255) / 256), 256, 0, s>>>(b.nnodes[l - 1], b.nnodes[l], b.box.p + 6 * b.off[l - 1],
-                                                                  b.box.p + 6 * b.off[l]);
-  MPG_HIP(hipGetLastError());
-  MPG_HIP(hipStreamSynchronize(s));
-  key_in.free(); key_out.free(); id_in.free();
-  b.built = true;
   return MPG_SUCCESS;
+}
+
+int mpg_bvh_build(Bvh &b, int64_t n, const char *who, const std::function<int(unsigned long long *, int32_t *)> &keys,
+                  const std::function<int()> &leaves, hipStream_t s, bool empty_leaf) {
+  int rc;
+  if ((rc = bvh_plan(b, n, who, empty_leaf))) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  MPG_HIP(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    mpg_set_error("%s: hipEventCreate failed", who);
+    return MPG_ERR_HIP;
+  }
+  auto build = [&]() -> int {
+    TmpBuf<unsigned long long> key_in, key_out;
+    TmpBuf<int32_t> id_in;
+    if ((rc = key_in.alloc(n, s)) || (rc = key_out.alloc(n, s)) || (rc = id_in.alloc(n, s)) || (rc = b.sorted_id.alloc(n)) ||
+        (rc = b.box.alloc(6 * (size_t)b.off[b.nlev])))
+      return rc;
+    MPG_HIP(hipEventRecord(e0, s));
+    if ((rc = keys(key_in.p, id_in.p))) return rc;
+    if ((rc = mpg_sort_pairs_u64_i32(key_in.p, key_out.p, id_in.p, b.sorted_id.p, n, s))) return rc;   // (k_sort.hip: rocPRIM's radix sort)
+    if ((rc = leaves())) return rc;
+    MPG_HIP(hipGetLastError());
+    for (int l = 1; l < b.nlev; ++l)
+      if ((rc = mpg_k_bvh_up(b.nnodes[l - 1], b.nnodes[l], b.box.p + 6 * b.off[l - 1], b.box.p + 6 * b.off[l], s))) return rc;
+    MPG_HIP(hipEventRecord(e1, s));
+    MPG_HIP(hipEventSynchronize(e1));
+    MPG_HIP(hipEventElapsedTime(&b.build_ms, e0, e1));
+    return MPG_SUCCESS;
+  };
+  rc = build();
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  b.built = rc == MPG_SUCCESS;
+  return rc;
+}
+
+// whole = false: only the cells of the mesh's geometry window are sites (a mesh cut to one rank's grid,
+// mpg_mesh_create_window); every cell centre is on the device in either case, so a search that turns out to need the
+// cells outside the window (mpg_k_store_nearest checks) rebuilds with whole = true
+int mpg_k_build_bvh(mpg_mesh_s *m, hipStream_t s, bool whole) {
+  SiteBvh &b = m->bvh;
+  if (b.built && (m->bvh_whole || !whole)) return MPG_SUCCESS;
+  if (b.built) b.free();
+  int rc;
+  int64_t first = whole ? 0 : m->cw0, n = whole ? m->nCells : m->cwn;
+  if (n == 0) {   // an empty window: the whole mesh it is
+    whole = true;
+    first = 0;
+    n = m->nCells;
+  }
+  m->bvh_whole = whole;
+  if ((rc = b.sorted.alloc(n))) return rc;
+  const double *cx = m->cell.x.p, *cy = m->cell.y.p, *cz = m->cell.z.p;
+  rc = mpg_bvh_build(
+      b, n, "nearest-neighbour search", [&](unsigned long long *key, int32_t *id) { return mpg_k_morton(n, cx, cy, cz, key, id, first, s); },
+      [&]() {
+        k_gather_sites<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, b.sorted_id.p, cx, cy, cz, b.sorted.x.p, b.sorted.y.p, b.sorted.z.p);
+        k_bvh_leaf<<<(unsigned)((b.nnodes[0] + 255) / 256), 256, 0, s>>>(n, b.nnodes[0], b.sorted.x.p, b.sorted.y.p, b.sorted.z.p, b.box.p);
+        return MPG_SUCCESS;
+      },
+      s);
+  if (rc) b.free();
+  return rc;
 }
 
 static int g_nn_variant = 1;   // "nn_variant": 1 = wave-cooperative search (default), 0 = one thread per point
 int mpg_nearest_variant() { return g_nn_variant; }
 void mpg_set_nearest_variant(int v) { g_nn_variant = v; }
 
-#define NN_STACK 96
 // masked != 0: only the points whose out[] entry is negative are searched (the ones the index-space search could not settle)
 __global__ __launch_bounds__(256) void k_nearest_query(int64_t P, const double *__restrict__ px, const double *__restrict__ py,
                                                        const double *__restrict__ pz, SiteBvhView b, int32_t *__restrict__ out, int masked) {
@@ -139,46 +195,19 @@ __global__ __launch_bounds__(256) void k_nearest_query(int64_t P, const double *
   double X = px[p], Y = py[p], Z = pz[p];
   double best = INFINITY;
   int32_t best_id = 0x7fffffff;
-  int stack[NN_STACK];
-  int sp = 0;
-  stack[sp++] = (b.nlev - 1) << 27;  // node < 2^27 per level
-  while (sp > 0) {
-    int e = stack[--sp];
-    int lev = e >> 27;
-    int64_t node = e & ((1 << 27) - 1);
-    double dbox = boxdist2_nofma(X, Y, Z, b.box + 6 * (b.off[lev] + node));
-    if (dbox > best) continue;  // equal bounds are explored: a tie with a lower id may hide inside
-    if (lev == 0) {
-      int64_t e1 = min(b.n, (node + 1) * MPG_BVH_LEAF);
-      for (int64_t i = node * MPG_BVH_LEAF; i < e1; ++i) {
-        double d = dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]);
-        int32_t id = b.sid[i];
-        if (d < best || (d == best && id < best_id)) {
-          best = d;
-          best_id = id;
+  walk_nearest(
+      BvhTree{b}, [&](const double *bx) { return boxdist2_nofma(X, Y, Z, bx); }, best, [&](int64_t node) {
+        int64_t e1 = min(b.n, (node + 1) * MPG_BVH_LEAF);
+        for (int64_t i = node * MPG_BVH_LEAF; i < e1; ++i) {
+          double d = dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]);
+          int32_t id = b.sid[i];
+          if (d < best || (d == best && id < best_id)) {
+            best = d;
+            best_id = id;
+          }
         }
-      }
-    } else {
-      // children sorted by decreasing bound so that the nearest is popped first
-      int64_t c0 = node * MPG_BVH_FAN, c1 = min(b.nnodes[lev - 1], c0 + MPG_BVH_FAN);
-      double cd[MPG_BVH_FAN];
-      int ci[MPG_BVH_FAN];
-      int nc = 0;
-      for (int64_t c = c0; c < c1; ++c) {
-        double d = boxdist2_nofma(X, Y, Z, b.box + 6 * (b.off[lev - 1] + c));
-        if (d > best) continue;
-        int k = nc++;
-        while (k > 0 && cd[k - 1] < d) {
-          cd[k] = cd[k - 1];
-          ci[k] = ci[k - 1];
-          --k;
-        }
-        cd[k] = d;
-        ci[k] = (int)(c - c0);
-      }
-      for (int k = 0; k < nc && sp < NN_STACK; ++k) stack[sp++] = ((lev - 1) << 27) | (int)(c0 + ci[k]);
-    }
-  }
+        return false;
+      });
   out[p] = best_id;
 }
 
@@ -316,25 +345,15 @@ __global__ __launch_bounds__(256) void k_nn_max_d2(int64_t P, const double *__re
 
 static SiteBvhView site_view(const SiteBvh &b) {
   SiteBvhView v;
-  v.n = b.n;
+  mpg_bvh_view(b, v);
   v.sx = b.sorted.x.p; v.sy = b.sorted.y.p; v.sz = b.sorted.z.p;
-  v.sid = b.sorted_id.p;
-  v.nlev = b.nlev;
-  for (int i = 0; i < MPG_BVH_MAXLEV; ++i) v.nnodes[i] = b.nnodes[i];
-  for (int i = 0; i <= MPG_BVH_MAXLEV; ++i) v.off[i] = b.off[i];
-  v.box = b.box.p;
   return v;
 }
 
 static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, mpg_handle_s *h, hipStream_t s, int masked = 0) {
   int rc;
   const int64_t P = (int64_t)npx * npy;
-  SiteBvh &b = m->bvh;
-  if (b.nnodes[0] >= (1 << 27)) {
-    mpg_set_error("mesh too large for the nearest-neighbour BVH");
-    return MPG_ERR_OVERFLOW;
-  }
-  const SiteBvhView v = site_view(b);
+  const SiteBvhView v = site_view(m->bvh);
   if (mpg_nearest_variant() == 0) {   // "nn_variant" knob 0: the one-thread-per-point search (kept as the cross-check of the tests)
     k_nearest_query<<<(unsigned)((P + 255) / 256), 256, 0, s>>>(P, pts.x.p, pts.y.p, pts.z.p, v, h->idx.p, masked);
     MPG_HIP(hipGetLastError());
@@ -363,19 +382,8 @@ static int nearest_search(mpg_mesh_s *m, int npx, int npy, const PointSet &pts, 
 int mpg_k_nearest_points(mpg_mesh_s *m, const PointSet &pts, int64_t n, int32_t *idx, hipStream_t s) {
   int rc;
   if ((rc = mpg_k_build_bvh(m, s, true))) return rc;
-  if (m->bvh.nnodes[0] >= (1 << 27)) {
-    mpg_set_error("mesh too large for the nearest-neighbour BVH");
-    return MPG_ERR_OVERFLOW;
-  }
   if (n == 0) return MPG_SUCCESS;
   k_nearest_query<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, pts.x.p, pts.y.p, pts.z.p, site_view(m->bvh), idx, 0);
-  MPG_HIP(hipGetLastError());
-  return MPG_SUCCESS;
-}
-
-// upper level of a Morton-ordered box tree: parent b = the hull of children [8 b, 8 b + 8) (the triangle BVH of k_store_mesh.hip shares it)
-int mpg_k_bvh_up(int64_t nchild, int64_t nparent, const double *child, double *parent, hipStream_t s) {
-  k_bvh_up<<<(unsigned)((nparent + 255) / 256), 256, 0, s>>>(nchild, nparent, child, parent);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }

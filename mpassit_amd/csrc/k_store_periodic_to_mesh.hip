@@ -34,7 +34,6 @@
 #include "mpg_internal.h"
 #include "quad_solve.h"
 
-#define PTM_STACK 64
 #define PTM_CAP_NONE 0x7fffffff
 
 // quad (a, b) of the periodic CENTER stagger, column a + 1 wrapped
@@ -87,53 +86,31 @@ __global__ __launch_bounds__(256) void k_ptm_quads(int64_t n, const double *__re
     }
   }
   if (!placed) {
-    // the walk of k_to_mesh_bilinear (k_store_to_mesh.hip) over the wrap-aware pyramid: the node to visit next in a register, only
-    // siblings on the stack; the margin covers a point within tol outside a quad the node's pad was not built for
+    // walk_filter (tree_walk.h) over the wrap-aware pyramid; the margin covers a point within tol outside a quad the node's pad was not
+    // built for
     const double mg = 2.0 * tol;
-    auto holds = [&](int lev, int node) -> bool {
-      const double *bx = pyr.box + 6 * (pyr.off[lev] + node);
-      return !(P.x < bx[0] - mg || P.x > bx[3] + mg || P.y < bx[1] - mg || P.y > bx[4] + mg || P.z < bx[2] - mg || P.z > bx[5] + mg);
-    };
-    int stack[PTM_STACK];
-    int sp = 0;
-    const int top = pyr.nlev - 1;
-    int cur = holds(top, 0) ? (top << 26) : -1;
-    for (;;) {
-      if (cur < 0) {
-        if (sp == 0) break;
-        cur = stack[--sp];
-      }
-      const int e = cur;
-      cur = -1;
-      const int lev = e >> 26, node = e & ((1 << 26) - 1);
-      const int bi = node % pyr.nx[lev], bj = node / pyr.nx[lev];
-      if (lev == 0) {
-        const int a1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, nx), b1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, qny);
-        for (int b = bj * MPG_PYR_B0; b < b1; ++b)
-          for (int a = bi * MPG_PYR_B0; a < a1; ++a) {
-            const int q = b * nx + a;
-            if (q >= best) continue;
-            double tw[4];
-            if (ptm_try_quad(P, a, b, nx, sx, sy, sz, tol, tw)) {
-              best = q;
+    const PyrTree tree{pyr};
+    walk_filter(
+        tree, walk_enc<PyrTree>(tree.top(), 0), true,
+        [&](const double *bx) {
+          return !(P.x < bx[0] - mg || P.x > bx[3] + mg || P.y < bx[1] - mg || P.y > bx[4] + mg || P.z < bx[2] - mg || P.z > bx[5] + mg);
+        },
+        [&](int node) {
+          const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
+          const int a1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, nx), b1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, qny);
+          for (int b = bj * MPG_PYR_B0; b < b1; ++b)
+            for (int a = bi * MPG_PYR_B0; a < a1; ++a) {
+              const int q = b * nx + a;
+              if (q >= best) continue;
+              double tw[4];
+              if (ptm_try_quad(P, a, b, nx, sx, sy, sz, tol, tw)) {
+                best = q;
 #pragma unroll
-              for (int c = 0; c < 4; ++c) ww[c] = tw[c];
+                for (int c = 0; c < 4; ++c) ww[c] = tw[c];
+              }
             }
-          }
-        continue;
-      }
-      const int cnx = pyr.nx[lev - 1], cny = pyr.ny[lev - 1];
-      for (int dj2 = 0; dj2 < 2; ++dj2)
-        for (int di2 = 0; di2 < 2; ++di2) {
-          const int ci = 2 * bi + di2, cj = 2 * bj + dj2;
-          if (ci >= cnx || cj >= cny) continue;
-          const int child = cj * cnx + ci;
-          if (!holds(lev - 1, child)) continue;
-          const int enc = ((lev - 1) << 26) | child;
-          if (cur < 0) cur = enc;
-          else if (sp < PTM_STACK) stack[sp++] = enc;
-        }
-    }
+          return false;
+        });
   }
   qid[p] = best == 0x7fffffff ? -1 : best;
 #pragma unroll
@@ -323,10 +300,7 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
   }
   Pyramid &pyr = g->wrappyr;
   if (!pyr.built && (rc = mpg_k_build_wrap_pyramid(src, nx, ny, pyr, s))) return rc;
-  if ((int64_t)pyr.nx[0] * pyr.ny[0] >= (1 << 26)) {
-    mpg_set_error("mpg_regrid_store_periodic_to_mesh: the grid has too many pyramid leaves for the walk");
-    return MPG_ERR_OVERFLOW;
-  }
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], "mpg_regrid_store_periodic_to_mesh"))) return rc;
   TmpBuf<float> ij;
   const bool use_ij = ptm_index_route(g);
   if (use_ij) {

@@ -24,7 +24,8 @@
 #include "mpg_internal.h"
 #include "quad_solve.h"
 
-#define TM_STACK 64
+#define TM_STACK 64   // of k_to_mesh_bilinear's own walk; its guard is never taken:
+static_assert(TM_STACK >= WalkCap<PyrTree>::FILTER, "the stack holds the walk's proven bound (tree_walk.h)");
 
 // quad (a, b) of the stagger: inside -> its four source ids and weights
 __device__ __forceinline__ bool tm_try_quad(dv3 P, int a, int b, int snx, const double *__restrict__ sx, const double *__restrict__ sy,
@@ -66,8 +67,9 @@ __global__ __launch_bounds__(256) void k_to_mesh_bilinear(int64_t n, const doubl
     }
   }
   if (!placed) {
-    // depth-first walk over the nodes whose box holds the point (k_store_bilinear.hip's shape: the node to visit next in a register,
-    // only siblings on the stack); the margin covers a point within tol outside a quad the node's pad was not built for
+    // depth-first walk over the nodes whose box holds the point: its own loop, child by child, not walk_filter of tree_walk.h (on the
+    // helper this Store was 2-4 % slower, profiles/r17_store_walks.md); the node to visit next in a register, only siblings on the
+    // stack; the margin covers a point within tol outside a quad the node's pad was not built for
     const double mg = 2.0 * tol;
     auto holds = [&](int lev, int node) -> bool {
       const double *bx = pyr.box + 6 * (pyr.off[lev] + node);
@@ -147,50 +149,21 @@ __global__ __launch_bounds__(256) void k_to_mesh_nearest(int64_t n, const double
       best_d = dist2_nofma(X, Y, Z, sx[best], sy[best], sz[best]);
     }
   }
-  int stack[TM_STACK];
-  int sp = 0;
-  stack[sp++] = (pyr.nlev - 1) << 26;
-  while (sp > 0) {
-    const int e = stack[--sp];
-    const int lev = e >> 26, node = e & ((1 << 26) - 1);
-    if (boxdist2_nofma(X, Y, Z, pyr.box + 6 * (pyr.off[lev] + node)) > best_d) continue;   // (equal: a lower index may wait there)
-    const int bi = node % pyr.nx[lev], bj = node / pyr.nx[lev];
-    if (lev == 0) {
-      const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
-      for (int j = bj * MPG_PYR_B0; j < j1; ++j)
-        for (int i = bi * MPG_PYR_B0; i < i1; ++i) {
-          const int c = j * snx + i;
-          const double d = dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]);
-          if (d < best_d || (d == best_d && c < best)) {
-            best_d = d;
-            best = c;
+  walk_nearest(
+      PyrTree{pyr}, [&](const double *bx) { return boxdist2_nofma(X, Y, Z, bx); }, best_d, [&](int node) {
+        const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
+        const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
+        for (int j = bj * MPG_PYR_B0; j < j1; ++j)
+          for (int i = bi * MPG_PYR_B0; i < i1; ++i) {
+            const int c = j * snx + i;
+            const double d = dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]);
+            if (d < best_d || (d == best_d && c < best)) {
+              best_d = d;
+              best = c;
+            }
           }
-        }
-      continue;
-    }
-    // children that can still hold the answer, the nearest box on top of the stack
-    const int cnx = pyr.nx[lev - 1], cny = pyr.ny[lev - 1];
-    int ch[4];
-    double cd[4];
-    int nc = 0;
-    for (int dj2 = 0; dj2 < 2; ++dj2)
-      for (int di2 = 0; di2 < 2; ++di2) {
-        const int ci = 2 * bi + di2, cj = 2 * bj + dj2;
-        if (ci >= cnx || cj >= cny) continue;
-        const int child = cj * cnx + ci;
-        const double lb = boxdist2_nofma(X, Y, Z, pyr.box + 6 * (pyr.off[lev - 1] + child));
-        if (lb > best_d) continue;
-        int k = nc++;
-        while (k > 0 && cd[k - 1] < lb) {   // descending: the last pushed is the nearest
-          cd[k] = cd[k - 1];
-          ch[k] = ch[k - 1];
-          --k;
-        }
-        cd[k] = lb;
-        ch[k] = ((lev - 1) << 26) | child;
-      }
-    for (int k = 0; k < nc && sp < TM_STACK; ++k) stack[sp++] = ch[k];
-  }
+        return false;
+      });
   idx[p] = best;
 }
 
@@ -221,10 +194,7 @@ int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, 
     rc = nearest ? mpg_k_build_pyramid(src, snx, sny, pyr, s) : mpg_k_build_cell_pyramid(src, snx - 1, sny - 1, pyr, s);
     if (rc) return rc;
   }
-  if ((int64_t)pyr.nx[0] * pyr.ny[0] >= (1 << 26)) {
-    mpg_set_error("mpg_regrid_store_to_mesh: the grid has too many pyramid leaves for the walk");
-    return MPG_ERR_OVERFLOW;
-  }
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], "mpg_regrid_store_to_mesh"))) return rc;
   // index space: bilinear quads only where the Stores' boxes are valid; the nearest seed is good wherever the inverse answers
   TmpBuf<float> ij;
   const bool use_ij = mpg_grid_has_inverse(g, stagger) && mpg_store_boxes();

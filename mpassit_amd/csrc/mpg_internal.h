@@ -2,12 +2,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
 #include <vector>
 
 #include "../../include/mpassit_amd.h"
+#include "tree_walk.h"
 
 // Tiles of the Regrid kernels are txu x tyu target points whose x origin is shifted per grid row so that every segment of a
 // row a workgroup stores starts at a multiple of A elements of the flattened [ny][nx] plane (A = 32: 128 bytes for
@@ -155,9 +157,7 @@ struct PointSet {
 };
 
 // AABB pyramid over a structured (nx x ny) point set: level 0 = blocks of B0 x B0 points, each upper
-// level merges 2x2 nodes.  box[level] is [nodes][6] = lo.xyz, hi.xyz.
-#define MPG_PYR_B0 4
-#define MPG_PYR_MAXLEV 16
+// level merges 2x2 nodes.  box[level] is [nodes][6] = lo.xyz, hi.xyz.  (MPG_PYR_*, PyramidView: tree_walk.h)
 struct Pyramid {
   int nlev = 0;
   int nx[MPG_PYR_MAXLEV], ny[MPG_PYR_MAXLEV];
@@ -166,84 +166,41 @@ struct Pyramid {
   bool built = false;
   void free() { box.free(); built = false; nlev = 0; }
 };
-struct PyramidView {  // passed by value to kernels
-  int nlev;
-  int nx[MPG_PYR_MAXLEV], ny[MPG_PYR_MAXLEV];
-  int64_t off[MPG_PYR_MAXLEV + 1];
-  const double *box;
-};
 
-// Morton-sorted site BVH (leaf = 8 consecutive sorted sites, fan-out 8)
-#define MPG_BVH_LEAF 8
-#define MPG_BVH_FAN 8
-#define MPG_BVH_MAXLEV 12
-struct SiteBvh {
+// Morton-sorted BVH over n items of a mesh (leaf = MPG_BVH_LEAF consecutive sorted items, fan-out MPG_BVH_FAN; MPG_BVH_*, BvhView:
+// tree_walk.h).  The three trees of a mesh are this plus what their leaves need:
+//   SiteBvh  the cell centres (k_store_nearest.hip: the nearest searches), with the centres themselves in sorted order;
+//   TriBvh   the dual triangles (k_store_mesh.hip: the point-in-triangle search of the Mesh -> Mesh bilinear Store); n = nVertices, the
+//            invalid ones included; a leaf's box is the union of its valid triangles' padded corner hulls (a triangle without three cells
+//            contributes nothing: an all-invalid leaf has an empty box);
+//   CellBvh  the cell polygons (k_store_conserve_mesh.hip: the candidate search of the conservative Mesh -> Mesh Store); cellbox holds
+//            every sorted cell's own padded hull, a leaf's box is the union of its cells'.  A cell with fewer than three vertices has an
+//            empty box (lo > hi): it is never a candidate.
+struct Bvh {
   int64_t n = 0;
-  PointSet sorted;          // sites in Morton order
-  DevBuf<int32_t> sorted_id;  // original cell id of each sorted site
+  DevBuf<int32_t> sorted_id;  // original id of each sorted item
   int nlev = 0;
   int64_t nnodes[MPG_BVH_MAXLEV];
   int64_t off[MPG_BVH_MAXLEV + 1];
   DevBuf<double> box;  // [nodes][6]
   bool built = false;
-  void free() { sorted.free(); sorted_id.free(); box.free(); built = false; }
-};
-struct SiteBvhView {
-  int64_t n;
-  const double *sx, *sy, *sz;
-  const int32_t *sid;
-  int nlev;
-  int64_t nnodes[MPG_BVH_MAXLEV];
-  int64_t off[MPG_BVH_MAXLEV + 1];
-  const double *box;
-};
-
-// Morton-sorted BVH over a mesh's dual triangles (k_store_mesh.hip: the point-in-triangle search of the Mesh -> Mesh bilinear Store).
-// Same shape as the site BVH: leaf = MPG_BVH_LEAF consecutive sorted triangles, fan-out MPG_BVH_FAN; a leaf's box is the union of its
-// valid triangles' padded corner hulls (a triangle without three cells contributes nothing: an all-invalid leaf has an empty box).
-struct TriBvh {
-  int64_t n = 0;              // triangles sorted (= nVertices, the invalid ones included)
-  DevBuf<int32_t> sorted_id;  // triangle (= vertex) id of each sorted slot
-  int nlev = 0;
-  int64_t nnodes[MPG_BVH_MAXLEV];
-  int64_t off[MPG_BVH_MAXLEV + 1];
-  DevBuf<double> box;         // [nodes][6]
-  bool built = false;
-  float build_ms = 0.f;       // GPU time of the build (profiles/r13_mesh_to_mesh.md)
+  float build_ms = 0.f;  // GPU time of the build (profiles/r13_mesh_to_mesh.md, r14_mesh_conserve.md)
   void free() { sorted_id.free(); box.free(); built = false; }
 };
-struct TriBvhView {
-  int64_t n;
-  const int32_t *sid;
-  int nlev;
-  int64_t nnodes[MPG_BVH_MAXLEV];
-  int64_t off[MPG_BVH_MAXLEV + 1];
-  const double *box;
+typedef Bvh TriBvh;
+struct SiteBvh : Bvh {
+  PointSet sorted;  // sites in Morton order
+  void free() { sorted.free(); Bvh::free(); }
 };
-
-// Morton-sorted box tree over a mesh's CELL POLYGONS (k_store_conserve_mesh.hip: the candidate search of the conservative Mesh -> Mesh
-// Store).  The shape of the other two trees; cellbox holds every sorted cell's own padded hull, a leaf's box is the union of its cells'.
-// A cell with fewer than three vertices has an empty box (lo > hi): it is never a candidate.
-struct CellBvh {
-  int64_t n = 0;              // cells sorted (= nCells)
-  DevBuf<int32_t> sorted_id;  // cell id of each sorted slot
-  DevBuf<double> cellbox;     // [n][6] in sorted order
-  int nlev = 0;
-  int64_t nnodes[MPG_BVH_MAXLEV];
-  int64_t off[MPG_BVH_MAXLEV + 1];
-  DevBuf<double> box;         // [nodes][6]
-  bool built = false;
-  float build_ms = 0.f;       // GPU time of the build (profiles/r14_mesh_conserve.md)
-  void free() { sorted_id.free(); cellbox.free(); box.free(); built = false; }
+struct SiteBvhView : BvhView {
+  const double *sx, *sy, *sz;
 };
-struct CellBvhView {
-  int64_t n;
-  const int32_t *sid;
+struct CellBvh : Bvh {
+  DevBuf<double> cellbox;  // [n][6] in sorted order
+  void free() { cellbox.free(); Bvh::free(); }
+};
+struct CellBvhView : BvhView {
   const double *cellbox;
-  int nlev;
-  int64_t nnodes[MPG_BVH_MAXLEV];
-  int64_t off[MPG_BVH_MAXLEV + 1];
-  const double *box;
 };
 
 struct mpg_handle_s;
@@ -433,6 +390,13 @@ int mpg_k_build_cell_pyramid(const PointSet &corner, int nx, int ny, Pyramid &py
 // ... over the nx x (ny - 1) quads of nx x ny points periodic in i: quad (b, a) has corners (b, a), (b, (a + 1) mod nx) and the same of row b + 1
 int mpg_k_build_wrap_pyramid(const PointSet &pts, int nx, int ny, Pyramid &pyr, hipStream_t s);
 PyramidView mpg_pyr_view(const Pyramid &p);
+// the one check that a tree's leaf level fits the walks' stack entries (tree_walk.h); `who` names the Store that asks
+template <class Tree>
+static inline int mpg_walk_check(int64_t leaves, const char *who) {
+  if (walk_fits<Tree>(leaves)) return MPG_SUCCESS;
+  mpg_set_error("%s: %lld tree leaves are too many for the walk (2^%d at most)", who, (long long)leaves, Tree::SHIFT);
+  return MPG_ERR_OVERFLOW;
+}
 int mpg_k_store_bilinear_mesh(mpg_mesh_s *m, mpg_grid_s *g, int stagger, int meshloc, mpg_handle_s *h, hipStream_t s);
 int mpg_k_store_nearest(mpg_mesh_s *m, mpg_grid_s *g, int stagger, mpg_handle_s *h, hipStream_t s);
 int mpg_k_store_conserve(mpg_mesh_s *m, mpg_grid_s *g, mpg_handle_s *h, hipStream_t s);
@@ -531,6 +495,14 @@ int mpg_k_apply_csr_to_mesh(mpg_handle_s *h, const void *src, int src_type, int6
 // upper level of a Morton-ordered box tree
 int mpg_k_nearest_points(mpg_mesh_s *m, const PointSet &pts, int64_t n, int32_t *idx, hipStream_t s);
 int mpg_k_bvh_up(int64_t nchild, int64_t nparent, const double *child, double *parent, hipStream_t s);
+// ... and what the three BVHs of a mesh share.  mpg_k_morton: key[i] = Morton code of point first + i, id[i] = first + i.  mpg_bvh_build:
+// the level plan for n items (`who` names the caller in its two overflow messages; with empty_leaf a tree over nothing keeps one empty leaf,
+// as the cell tree always did; the others end in "too many levels"), then on stream s
+// keys(key, id) -> radix sort into b.sorted_id -> leaves() fills b.box's level 0 -> the upper levels; b.build_ms = the GPU time of it.
+int mpg_k_morton(int64_t n, const double *x, const double *y, const double *z, unsigned long long *key, int32_t *id, int64_t first, hipStream_t s);
+int mpg_bvh_build(Bvh &b, int64_t n, const char *who, const std::function<int(unsigned long long *, int32_t *)> &keys,
+                  const std::function<int()> &leaves, hipStream_t s, bool empty_leaf = false);   // (empty_leaf: the cell tree's, n = 0)
+void mpg_bvh_view(const Bvh &b, BvhView &v);
 // k_store_mesh.hip: Mesh -> Mesh Store (bilinear: 3 slots, the dual triangles of `src`; nearest: 1) of the cells of `src` onto the cells /
 // vertices of `dst`
 int mpg_k_store_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int dst_meshloc, int method, mpg_handle_s *h, hipStream_t s);
