@@ -584,6 +584,43 @@ int mpg_wind_destagger_pitched_dev(mpg_handle rh_edge1, mpg_handle rh_edge2, con
 int mpg_wind_destagger(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *cosa_host, const double *sina_host,
                        const double *umass_host, const double *vmass_host, int nlev, void *u_host, void *v_host, int dst_type,
                        double *umass_rot_host, double *vmass_rot_host);
+/* The wind chain turned round: U on one stagger and V on another -- grid-relative on a Lambert grid -- onto the points of a mesh as
+ * earth-relative winds (uReconstructZonal / uReconstructMeridional), in ONE pass: the two Regrids, the rotation and the cast, without
+ * float64 intermediates.  The inverse of interp.F90:737-748, which is algebraically u_g = u_e ca + v_e sa, v_g = v_e ca - u_e sa.
+ *   rh_u, rh_v           fixed handles onto the SAME n_dst points, both with nnz_per_row 4 or both 1: typically
+ *                        mpg_regrid_store_to_mesh(grid, EDGE1 / EDGE2, mesh, loc, BILINEAR).  rh_u == rh_v is allowed (winds on mass
+ *                        points, any CENTER handle); the kernel then stages one set of indices.
+ *   u_dev, v_dev         [nlev][rh_u.n_src], [nlev][rh_v.n_src] of src_type, planes u_level_stride / v_level_stride elements apart
+ *                        (0 = dense; below n_src -> MPG_ERR_INVALID_ARG): the pitched U / V of mpg_wind_destagger_pitched_dev are
+ *                        accepted as they are, their pad is never read
+ *   cosa_dev, sina_dev   [n_dst] float64 at the DESTINATION points (mpg_mesh_rotang_dev), or both NULL: no rotation; exactly one NULL
+ *                        -> MPG_ERR_INVALID_ARG
+ *   ue_dev, ve_dev       nlev * n_dst each of dst_type, in dst_layout: MPG_LAYOUT_CELL_FAST [lev][cell] or MPG_LAYOUT_LEV_FAST
+ *                        [cell][lev] (MPAS file order).  Both fully overwritten; neither may alias the other, a source or the
+ *                        angles (MPG_ERR_INVALID_ARG)
+ * Values, a contract by identity: float64 arithmetic without contraction (as mpg_rotate_winds_dev), per (point, level)
+ *   a  = wsum_fixed<NNZ>(w_u, U[idx_u])       exactly mpg_regrid_to_mesh_dev(rh_u, dst F64, scale 1, offset 0)
+ *   b  = wsum_fixed<NNZ>(w_v, V[idx_v])
+ *   ue = a * ca - b * sa ;  ve = a * sa + b * ca     four products and two sums, each rounded; no rotation: ue = a, ve = b
+ *   store (TD)ue, (TD)ve                              one rounding to the destination type
+ * A point that is unmapped in either handle gets (TD)(+0.0) in BOTH results.  The same bits for both layouts ([c][k] of one is [k][c]
+ * of the other), for dense and pitched sources, and from call to call.  No atomics.  Stream as mpg_regrid_dev.  The call allocates
+ * nothing and synchronises nothing: it can be captured in a hipGraph from the first call.
+ * Refusals, each with a message that names the way out.  MPG_ERR_UNSUPPORTED: CSR handles (conservative, periodic, from-weights: winds
+ * from a periodic global grid are out of scope), handles with pole caps, 3-slot handles or a pair of mixed nnz_per_row, MPG_TYPE_BE on
+ * either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays, rh_u.n_dst != rh_v.n_dst, nlev < 1, unknown enums.  MPG_ERR_OVERFLOW: more
+ * 64-point blocks than one launch holds. */
+int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev,
+                         const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev,
+                         void *ve_dev, int dst_type, int dst_layout, void *hip_stream);
+/* cos / sin of the rotation angle at the cells (MPG_MESHLOC_ELEMENT, [nCells]) or vertices (MPG_MESHLOC_NODE, [nVertices]) of a mesh,
+ * float64 device arrays for mpg_wind_to_mesh_dev: alpha = -hemi * cone * wrap180(lon - stand_lon) * pi / 180 with hemi, cone and
+ * stand_lon of the grid's own projection and lon = atan2(y, x) in degrees of the mesh's stored unit vectors; cosa = cos(alpha), sina =
+ * sin(alpha).  The sign is get_rotang's (model_grid.F90:2450-2507), whose centred differences the closed form meets to 2.3e-6 in sina on
+ * the interior rows of a 30-km grid.  PROJ_LC only, as mpg_grid_get_rotang: any other projection -> MPG_ERR_UNSUPPORTED ("the forward
+ * chain does not rotate there: pass NULL angles"), as are a grid without a projection (mpg_grid_create without mpg_grid_attach_proj) and
+ * a mesh of mpg_mesh_create_window.  Asynchronous on hip_stream (as mpg_regrid_dev); allocates nothing. */
+int mpg_mesh_rotang_dev(mpg_grid grid, mpg_mesh mesh, int meshloc, double *cosa_dev, double *sina_dev, void *hip_stream);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

@@ -28,6 +28,7 @@ SYMBOLS = [
     "mpg_regrid_store_mesh", "mpg_regrid_rows_dev",
     "mpg_regrid_store_conserve_mesh", "mpg_regrid_csr_rows_dev",
     "mpg_regrid_store_periodic_to_mesh",
+    "mpg_wind_to_mesh_dev", "mpg_mesh_rotang_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -172,6 +173,29 @@ def regrid_store_periodic_to_mesh(*args):
     if "pstore" not in _to_mesh_fns:
         _to_mesh_fns["pstore"] = _STORE_PERIODIC_TO_MESH_PROTO(("mpg_regrid_store_periodic_to_mesh", load()))
     return _to_mesh_fns["pstore"](*args)
+
+
+# The wind chain turned round and the rotation angles it needs, bound the same way.
+#   mpg_wind_to_mesh_dev(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev,
+#                        dst_type, dst_layout, hip_stream)
+#   mpg_mesh_rotang_dev(grid, mesh, meshloc, cosa_dev, sina_dev, hip_stream)
+_WIND_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+_MESH_ROTANG_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def wind_to_mesh_dev(*args):
+    """The typed binding of mpg_wind_to_mesh_dev; returns the call's status code."""
+    if "wind" not in _to_mesh_fns:
+        _to_mesh_fns["wind"] = _WIND_TO_MESH_PROTO(("mpg_wind_to_mesh_dev", load()))
+    return _to_mesh_fns["wind"](*args)
+
+
+def mesh_rotang_dev(*args):
+    """The typed binding of mpg_mesh_rotang_dev; returns the call's status code."""
+    if "rotang" not in _to_mesh_fns:
+        _to_mesh_fns["rotang"] = _MESH_ROTANG_PROTO(("mpg_mesh_rotang_dev", load()))
+    return _to_mesh_fns["rotang"](*args)
 
 
 _lib = None

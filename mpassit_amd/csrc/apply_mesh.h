@@ -121,6 +121,18 @@ static inline TilePlan am_tile_plan(int nlev, size_t esz, bool levf, size_t head
   }
   return p;
 }
+// ... and TWO such tiles of one shape behind `head` (k_wind_to_mesh.hip: a wind's two components): both together stay within
+// AM_TILE_BYTES, so each has half the cap -- all levels up to 63 (float64) / 127 (float32), else chunks of 32 / 96 levels.  lds counts both.
+static inline TilePlan am_tile_plan_pair(int nlev, size_t esz, bool levf, size_t head) {
+  TilePlan p{nlev, 0, head};
+  if (levf) {
+    const size_t cap = AM_TILE_BYTES / 2;
+    if ((size_t)AM_CELLS * (size_t)(nlev | 1) * esz > cap) p.kc = (int)(cap / (AM_CELLS * esz) - 1) / 32 * 32;
+    p.S = p.kc | 1;
+    p.lds += 2 * (size_t)AM_CELLS * (size_t)p.S * esz;
+  }
+  return p;
+}
 static inline int am_allow_lds(const void *fn, size_t lds) {
   if (lds > 48 * 1024) MPG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return MPG_SUCCESS;

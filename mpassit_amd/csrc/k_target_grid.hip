@@ -330,6 +330,30 @@ __global__ __launch_bounds__(256) void k_rotang(int nx, int ny, const double *__
   cosa[q] = cos(alpha);
 }
 
+// The same angle in closed form at points that lie on no grid row (mpg_mesh_rotang_dev): a Lambert grid's +j axis points along the
+// meridian turned by cone * (lon - stdlon), so alpha = -hemi * cone * wrap180(lon - stdlon) in get_rotang's sign convention (the two
+// agree to 2.3e-6 in sina on the interior rows of a 30-km grid; the difference is the truncation of get_rotang's centred difference).
+// lon = atan2(y, x) of the point's unit vector.
+__global__ __launch_bounds__(256) void k_mesh_rotang(ProjDev p, int64_t n, const double *__restrict__ x, const double *__restrict__ y,
+                                                     double *__restrict__ cosa, double *__restrict__ sina) {
+#pragma clang fp contract(off)
+  int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  double d = atan2(y[q], x[q]) * TG_DEG_PER_RAD - p.stdlon;
+  if (d > 180.0) d -= 360.0;
+  else if (d < -180.0) d += 360.0;
+  const double alpha = -p.hemi * p.cone * d * TG_RAD_PER_DEG;
+  sina[q] = sin(alpha);
+  cosa[q] = cos(alpha);
+}
+
+int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s) {
+  if (n == 0) return MPG_SUCCESS;
+  k_mesh_rotang<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->proj, n, x, y, cosa, sina);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
 static double wrap180(double x) {
   for (int it = 0; fabs(x) > 180.0 && it < 10; ++it) {
     if (x < -180.0) x += 360.0;

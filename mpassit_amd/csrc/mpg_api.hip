@@ -134,7 +134,7 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_to_mesh)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -567,6 +567,31 @@ int mpg_grid_get_rotang(mpg_grid g, double *cosa_host, double *sina_host) {
   if (cosa_host) MPG_HIP(hipMemcpy(cosa_host, c, bytes, hipMemcpyDeviceToHost));
   if (sina_host) MPG_HIP(hipMemcpy(sina_host, s, bytes, hipMemcpyDeviceToHost));
   return MPG_SUCCESS;
+}
+
+// cos / sin of the rotation angle at the points of a mesh, for mpg_wind_to_mesh_dev (k_target_grid.hip k_mesh_rotang)
+int mpg_mesh_rotang_dev(mpg_grid g, mpg_mesh mesh, int meshloc, double *cosa_dev, double *sina_dev, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(g && mesh, "mpg_mesh_rotang: NULL grid or mesh");
+  MPG_ARG(meshloc == MPG_MESHLOC_ELEMENT || meshloc == MPG_MESHLOC_NODE, "mpg_mesh_rotang: unknown mesh location (MPG_MESHLOC_ELEMENT or MPG_MESHLOC_NODE)");
+  if (!g->has_inverse) {
+    mpg_set_error("mpg_mesh_rotang: the grid carries no projection (mpg_grid_create_proj or mpg_grid_attach_proj give it one); "
+                  "without one the forward chain does not rotate there: pass NULL angles");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (g->proj.code != MPG_PROJ_LC) {
+    mpg_set_error("mpg_mesh_rotang: cos/sin(alpha) exist for PROJ_LC grids only (model_grid.F90:1113); "
+                  "the forward chain does not rotate there: pass NULL angles");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (mesh->geo_grid) {
+    mpg_set_error("mpg_mesh_rotang: the mesh was cut to a grid (mpg_mesh_create_window): its resident points are a window; "
+                  "create the whole mesh (mpg_mesh_create) for results on the mesh");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  const PointSet &pts = meshloc == MPG_MESHLOC_ELEMENT ? mesh->cell : mesh->vert;
+  MPG_ARG(pts.n == 0 || (cosa_dev && sina_dev), "mpg_mesh_rotang: NULL output");
+  return mpg_k_mesh_rotang(g, pts.n, pts.x.p, pts.y.p, cosa_dev, sina_dev, (hipStream_t)hip_stream);
 }
 
 // ---- RegridStore ----------------------------------------------------------------------------------
@@ -1324,6 +1349,80 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, 
   int rc = check_mesh_order(call, h, src_dev, src_type, src_level_stride, nlev, nfields, dst_dev, dst_type, dst_layout, &ld);
   if (rc) return rc;
   return mpg_k_apply_csr_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
+}
+
+// ---- the wind chain turned round: U / V staggers onto mesh points as earth-relative winds, one pass (k_wind_to_mesh.hip) ---------------
+int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev, const void *v_dev,
+                         int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev, void *ve_dev, int dst_type,
+                         int dst_layout, void *hip_stream) {
+  auto fail = [](int rc, const char *what) {
+    mpg_set_error("mpg_wind_to_mesh: %s", what);
+    return rc;
+  };
+  MPG_CHECK_INIT();
+  if (!(rh_u && rh_v)) return fail(MPG_ERR_INVALID_ARG, "NULL handle");
+  if (!((u_dev || rh_u->n_src == 0) && (v_dev || rh_v->n_src == 0) && ((ue_dev && ve_dev) || rh_u->n_dst == 0))) return fail(MPG_ERR_INVALID_ARG, "NULL array");
+  if ((cosa_dev == nullptr) != (sina_dev == nullptr)) return fail(MPG_ERR_INVALID_ARG, "cosa and sina come together (both NULL: no rotation)");
+  if (nlev < 1) return fail(MPG_ERR_INVALID_ARG, "nlev must be >= 1");
+  if (dst_layout != MPG_LAYOUT_CELL_FAST && dst_layout != MPG_LAYOUT_LEV_FAST) return fail(MPG_ERR_INVALID_ARG, "bad dst_layout");
+  if (!(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3))
+    return fail(MPG_ERR_INVALID_ARG, "src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((src_type | dst_type) & MPG_TYPE_BE)
+    return fail(MPG_ERR_UNSUPPORTED, "big-endian values (MPG_TYPE_BE) are not supported; mpg_bswap_dev swaps an array in place before or after the call");
+  for (mpg_handle h : {rh_u, rh_v}) {
+    if (h->kind != MPG_KIND_FIXED)
+      return fail(MPG_ERR_UNSUPPORTED, "CSR handles (conservative, periodic, from-weights) are not supported: pairs of fixed 4-slot or 1-slot handles are. "
+                                       "mpg_regrid_csr_to_mesh_dev into float64 on each handle, then the rotation, is the route for those.");
+    if (h->n_pole > 0)
+      return fail(MPG_ERR_UNSUPPORTED, "handles with pole-cap terms (periodic Grid -> Grid) are not supported; mpg_regrid_typed_dev on each handle, then "
+                                       "the rotation, serves them");
+  }
+  if (rh_u->nnz_per_row != rh_v->nnz_per_row || (rh_u->nnz_per_row != 4 && rh_u->nnz_per_row != 1)) {
+    mpg_set_error("mpg_wind_to_mesh: handles of %d and %d slots are not supported (both 4 -- bilinear -- or both 1 -- nearest); "
+                  "mpg_regrid_to_mesh_dev into float64 on each handle, then the rotation, serves any fixed pair",
+                  rh_u->nnz_per_row, rh_v->nnz_per_row);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh_u->n_dst != rh_v->n_dst) {
+    mpg_set_error("mpg_wind_to_mesh: the handles map onto %lld and %lld points: both must be Stores onto the same points of one mesh",
+                  (long long)rh_u->n_dst, (long long)rh_v->n_dst);
+    return MPG_ERR_INVALID_ARG;
+  }
+  const int es = (src_type & MPG_TYPE_F32) ? 4 : 8, ed = (dst_type & MPG_TYPE_F32) ? 4 : 8;
+  // a source's level stride: 0 = dense, else at least its plane, and nlev planes of it addressable
+  auto src_stride = [&](const char *arg, int64_t plane, int64_t ld, int64_t *out) {
+    if (ld == 0) ld = plane;
+    if (ld < plane) {
+      mpg_set_error("mpg_wind_to_mesh: %s %lld is below the source plane of %lld points (0 = dense)", arg, (long long)ld, (long long)plane);
+      return MPG_ERR_INVALID_ARG;
+    }
+    if (ld > 0 && (int64_t)nlev > (INT64_MAX / es) / ld) {
+      mpg_set_error("mpg_wind_to_mesh: %d planes of %s %lld cannot be addressed", nlev, arg, (long long)ld);
+      return MPG_ERR_INVALID_ARG;
+    }
+    *out = ld;
+    return MPG_SUCCESS;
+  };
+  int64_t ldu, ldv;
+  int rc;
+  if ((rc = src_stride("u_level_stride", rh_u->n_src, u_level_stride, &ldu))) return rc;
+  if ((rc = src_stride("v_level_stride", rh_v->n_src, v_level_stride, &ldv))) return rc;
+  if (rh_u->n_dst > 0 && (int64_t)nlev > (INT64_MAX / ed) / rh_u->n_dst) return fail(MPG_ERR_INVALID_ARG, "nlev planes of n_dst results cannot be addressed");
+  // neither result may alias the other, a source or the angles (a workgroup's stores would race another's loads)
+  const uintptr_t nb = (uintptr_t)nlev * (uintptr_t)rh_u->n_dst * (uintptr_t)ed, na = (uintptr_t)rh_u->n_dst * sizeof(double);
+  auto overlap = [](const void *p, uintptr_t np, const void *q, uintptr_t nq) {
+    return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
+  };
+  const uintptr_t nu = (uintptr_t)nlev * (uintptr_t)ldu * (uintptr_t)es, nv = (uintptr_t)nlev * (uintptr_t)ldv * (uintptr_t)es;
+  if (overlap(ue_dev, nb, ve_dev, nb)) return fail(MPG_ERR_INVALID_ARG, "ue_dev and ve_dev alias each other: give each result its own array");
+  for (void *r : {ue_dev, ve_dev}) {
+    if (overlap(r, nb, u_dev, nu) || overlap(r, nb, v_dev, nv))
+      return fail(MPG_ERR_INVALID_ARG, "a result may not alias a source (u_dev, v_dev): give each result its own array");
+    if (overlap(r, nb, cosa_dev, na) || overlap(r, nb, sina_dev, na))
+      return fail(MPG_ERR_INVALID_ARG, "a result may not alias the angles (cosa_dev, sina_dev): give each result its own array");
+  }
+  return mpg_k_wind_to_mesh(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
+                            (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

@@ -401,6 +401,23 @@ module mpg
       integer(c_int), value :: nlev, dst_type
       integer(c_int) :: rc
     end function mpg_wind_destagger
+    !> the wind chain turned round: U / V on two staggers onto mesh points as earth-relative winds in one pass, the inverse of
+    !! interp.F90:737-748 (cosa_dev / sina_dev at the MESH points, both c_null_ptr: no rotation; include/mpassit_amd.h)
+    function mpg_wind_to_mesh_dev(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, ue_dev, &
+                                  ve_dev, dst_type, dst_layout, hip_stream) bind(C, name="mpg_wind_to_mesh_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, ue_dev, ve_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride, v_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_to_mesh_dev
+    !> ... and cos / sin of the rotation angle at the mesh's cells (meshloc 0) or vertices (1): Lambert grids only
+    function mpg_mesh_rotang_dev(grid, mesh, meshloc, cosa_dev, sina_dev, hip_stream) bind(C, name="mpg_mesh_rotang_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: grid, mesh, cosa_dev, sina_dev, hip_stream
+      integer(c_int), value :: meshloc
+      integer(c_int) :: rc
+    end function mpg_mesh_rotang_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

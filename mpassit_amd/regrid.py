@@ -23,7 +23,7 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd", "regrid_store_conserve_mesh", "regrid_csr_rows_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
-           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG"]
+           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd"]
 
 
 def _f64(a):
@@ -1044,3 +1044,132 @@ def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, d
                                                   C.c_int(int(out_dtype == torch.float32) | (2 if dst_be else 0)), p(ur), p(vr), C.c_int64(ld),
                                                   _stream_ptr()))
     return u, v, ur, vr
+
+
+def _wind_source(t, rh, nlev, who):
+    """The level stride (elements, 0 = dense) of one wind component for wind_to_mesh, after the checks RouteHandle._to_mesh makes of its source."""
+    import torch
+    if not (_is_torch(t) and t.is_cuda and t.dtype in (torch.float32, torch.float64)):
+        raise ValueError(who + " needs float32/float64 CUDA tensors")
+    if t.is_contiguous():
+        if t.numel() != nlev * rh.n_src:
+            raise ValueError("%s: a source has %d elements, its handle expects %d" % (who, t.numel(), nlev * rh.n_src))
+        return 0
+    if t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[0] != 1):
+        raise ValueError(who + ": a strided source must be (nlev, ny, nx) or (1, nlev, ny, nx) with plane-pitched levels")
+    ny, nx = int(t.shape[-2]), int(t.shape[-1])
+    if ny * nx != rh.n_src:
+        raise ValueError("%s: source planes have %d points, the handle expects %d" % (who, ny * nx, rh.n_src))
+    return _level_stride(t, (1, nlev) if t.dim() == 4 else (nlev,), ny, nx, who)
+
+
+def wind_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, outs=None):
+    """mpg_wind_to_mesh_dev: the wind chain turned round, in one pass -- U through rh_u and V through rh_v onto the SAME mesh points (the
+    typical pair: regrid_store_to_mesh(grid, mesh, staggerloc=STAGGERLOC_EDGE1 / STAGGERLOC_EDGE2); rh_u is rh_v is allowed), then the
+    rotation from grid-relative to earth-relative winds with cosa / sina at the mesh points (mesh_rotang; both None: no rotation) and the
+    cast: ue = a ca - b sa, ve = a sa + b ca with a, b the float64 results of rh_u.regrid_to_mesh(u) and rh_v.regrid_to_mesh(v), the
+    inverse of rotate_winds_cgrid.  u, v: float32 / float64 CUDA tensors of one dtype, [nlev][n_src of their handle], contiguous or
+    plane-pitched views (nlev, ny, nx) as empty_pitched and wind_destagger(outs=) make.  Returns (ue, ve) of out_dtype (default: u's):
+    (nlev, n_dst) for LAYOUT_CELL_FAST, (n_dst, nlev) for LAYOUT_LEV_FAST -- MPAS file order; a point either handle leaves unmapped is
+    +0.0 in both.  outs=(ue, ve): contiguous CUDA tensors of nlev * n_dst elements to write into.  Bit-identical to the separate calls."""
+    import torch
+    who = "wind_to_mesh"
+    ldu, ldv = _wind_source(u, rh_u, nlev, who), _wind_source(v, rh_v, nlev, who)
+    if u.dtype != v.dtype:
+        raise ValueError(who + ": u and v must have one dtype")
+    if (cosa is None) != (sina is None):
+        raise ValueError(who + ": cosa and sina come together (both None: no rotation)")
+    for t in (cosa, sina):
+        if t is not None and not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == rh_u.n_dst):
+            raise ValueError(who + ": cosa / sina must be contiguous float64 CUDA tensors of n_dst = %d elements" % rh_u.n_dst)
+    given = [t for t in (outs or ()) if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
+    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+    shape = (nlev, rh_u.n_dst) if layout == LAYOUT_CELL_FAST else (rh_u.n_dst, nlev)
+    ue, ve = outs if outs is not None else (None, None)
+    if ue is None:
+        ue = torch.empty(shape, dtype=out_dtype, device=u.device)
+    if ve is None:
+        ve = torch.empty(shape, dtype=out_dtype, device=u.device)
+    for t in (ue, ve):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh_u.n_dst):
+            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh_u.n_dst))
+    if ACCOUNT is not None:     # L (U_u + U_v) e_s + 2 P L e_d + P (2 NNZ 12 + 16): both sources read once, both results written once, the
+        for rh in (rh_u, rh_v):  # indices and weights of both handles and the angles once
+            if getattr(rh, "_acc_U", None) is None:
+                rh._acc_U = int(rh.unique_sources().size)
+        ACCOUNT.append(("wind_to_mesh nnz%d L%d" % (rh_u.nnz_per_row, nlev),
+                        nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + 2 * rh_u.n_dst * nlev * ue.element_size()
+                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + (16 if cosa is not None else 0))))
+
+    def p(t):
+        return t.data_ptr() if t is not None else None
+    check(L.wind_to_mesh_dev(rh_u._h, rh_v._h, p(cosa), p(sina), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv, int(nlev),
+                             ue.data_ptr(), ve.data_ptr(), int(out_dtype == torch.float32), int(layout), torch.cuda.current_stream().cuda_stream))
+    return ue, ve
+
+
+def mesh_rotang(grid, mesh, meshloc=MESHLOC_ELEMENT):
+    """mpg_mesh_rotang_dev: (cosa, sina) of a Lambert grid's rotation angle at the mesh's cells (MESHLOC_ELEMENT) or vertices
+    (MESHLOC_NODE), float64 CUDA tensors for wind_to_mesh; target_grid.rotang_at is the numpy mirror.  MpgError (rc 4) for a grid that
+    is not Lambert or carries no projection -- the forward chain does not rotate there: pass None angles -- and for a windowed mesh."""
+    import torch
+    if meshloc not in (MESHLOC_ELEMENT, MESHLOC_NODE):
+        raise ValueError("mesh_rotang: meshloc must be MESHLOC_ELEMENT or MESHLOC_NODE")
+    n = mesh.nCells if meshloc == MESHLOC_ELEMENT else mesh.nVertices
+    cosa = torch.empty(n, dtype=torch.float64, device="cuda")
+    sina = torch.empty(n, dtype=torch.float64, device="cuda")
+    check(L.mesh_rotang_dev(grid._h, mesh._h, int(meshloc), cosa.data_ptr(), sina.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return cosa, sina
+
+
+def _unmapped_mask(rh):
+    """The points a fixed handle leaves unmapped (idx[0] < 0) as a bool CUDA tensor [n_dst], downloaded once per handle object."""
+    if getattr(rh, "_unmapped_dev", None) is None:
+        rh._unmapped_dev = _torch.as_tensor(rh.weights()[0][:, 0] < 0, device="cuda")
+    return rh._unmapped_dev
+
+
+if _torch is not None:
+    class WindToMeshFunction(_torch.autograd.Function):
+        """wind_to_mesh with a gradient: forward is wind_to_mesh in u's dtype; backward takes (g_ue, g_ve) back to [lev][cell], zeroes
+        them where either handle leaves the point unmapped (the forward stores a constant +0.0 in both results there), turns them by the
+        transposed rotation in torch and applies each handle's regrid_transpose.  Use wind_to_mesh_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, v, rh_u, rh_v, cosa, sina, nlev, layout):
+            ctx.rh_u, ctx.rh_v, ctx.cosa, ctx.sina, ctx.nlev, ctx.layout = rh_u, rh_v, cosa, sina, nlev, layout
+            ctx.shapes, ctx.dtypes = (u.shape, v.shape), (u.dtype, v.dtype)
+            return wind_to_mesh(rh_u, rh_v, cosa, sina, u.contiguous(), v.contiguous(), nlev, layout=layout, out_dtype=u.dtype)
+
+        @staticmethod
+        def backward(ctx, g_ue, g_ve):
+            n, nlev = ctx.rh_u.n_dst, ctx.nlev
+            if ctx.layout == LAYOUT_LEV_FAST:     # regrid_transpose reads [nlev][n_dst] planes
+                g_ue, g_ve = g_ue.reshape(n, nlev).t(), g_ve.reshape(n, nlev).t()
+            g_ue, g_ve = g_ue.reshape(nlev, n), g_ve.reshape(nlev, n)
+            # a point unmapped in EITHER handle is a constant of the forward: without this a point mapped in one handle only would send
+            # its gradient through that handle's transpose, a term the forward does not have
+            un = _unmapped_mask(ctx.rh_u)
+            if ctx.rh_v is not ctx.rh_u:
+                un = un | _unmapped_mask(ctx.rh_v)
+            g_ue, g_ve = g_ue.masked_fill(un, 0.0), g_ve.masked_fill(un, 0.0)
+            if ctx.cosa is not None:
+                ca, sa = ctx.cosa.to(g_ue.dtype), ctx.sina.to(g_ue.dtype)
+                g_a, g_b = g_ue * ca + g_ve * sa, g_ve * ca - g_ue * sa
+            else:
+                g_a, g_b = g_ue, g_ve
+            # two separate gradients even when rh_u is rh_v: one of u, one of v
+            gu = ctx.rh_u.regrid_transpose(g_a.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[0])
+            gv = ctx.rh_v.regrid_transpose(g_b.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[1])
+            return gu.reshape(ctx.shapes[0]), gv.reshape(ctx.shapes[1]), None, None, None, None, None, None
+
+
+def wind_to_mesh_autograd(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST):
+    """wind_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout) in u's dtype as a differentiable torch op.  The gradients with respect
+    to u and v: the incoming (g_ue, g_ve), taken back to [lev][cell] and set to zero where either handle leaves the point unmapped (the
+    forward's +0.0 there depends on neither u nor v), give g_a = g_ue ca + g_ve sa and g_b = -g_ue sa + g_ve ca, and
+    rh_u.regrid_transpose(g_a), rh_v.regrid_transpose(g_b) are returned in u's and v's shapes and dtypes: the exact adjoint of the
+    forward.  The first backward on a handle downloads its indices once for the mask."""
+    return WindToMeshFunction.apply(u, v, rh_u, rh_v, cosa, sina, nlev, layout)
