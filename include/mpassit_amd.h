@@ -40,7 +40,7 @@ enum {
 /* ESMF_REGRIDMETHOD_* (interp.F90:119,204,370,420) */
 enum { MPG_REGRIDMETHOD_BILINEAR = 0, MPG_REGRIDMETHOD_CONSERVE = 1, MPG_REGRIDMETHOD_NEAREST_STOD = 2 };
 /* ESMF_MESHLOC_* (input_data.F90:927,1116-1123) */
-enum { MPG_MESHLOC_ELEMENT = 0, MPG_MESHLOC_NODE = 1 };
+enum { MPG_MESHLOC_ELEMENT = 0, MPG_MESHLOC_NODE = 1, MPG_MESHLOC_EDGE = 2 };   /* EDGE: a destination only, after mpg_mesh_set_edges */
 /* ESMF_STAGGERLOC_* (interp.F90:480,489,509; model_grid.F90:706-728) */
 enum { MPG_STAGGERLOC_CENTER = 0, MPG_STAGGERLOC_EDGE1 = 1, MPG_STAGGERLOC_EDGE2 = 2, MPG_STAGGERLOC_CORNER = 3 };
 /* memory order of a source field with an ungridded (level) dimension */
@@ -93,6 +93,19 @@ int mpg_mesh_destroy(mpg_mesh mesh); /* ESMF_MeshDestroy model_grid.F90:2154 */
 int mpg_mesh_create_window(int64_t nCells, int64_t nVertices, int maxEdges, const double *latCell, const double *lonCell,
                            const double *latVertex, const double *lonVertex, const int32_t *verticesOnCell, mpg_grid grid, mpg_mesh *out);
 int mpg_mesh_window_info(mpg_mesh mesh, int64_t *cell_first, int64_t *cell_count, int64_t *vertex_first, int64_t *vertex_count, double *margin);
+/* The mesh's EDGES (MPG_MESHLOC_EDGE): the points that carry MPAS's prognostic wind `u`, the component normal to each cell edge.  Host
+ * arrays as the MPAS file holds them, in radians: latEdge, lonEdge [nEdges] and angleEdge [nEdges], the angle of the edge's normal
+ * from local east.  The coordinates go through the SAME conversion as the cell centres in mpg_mesh_create (degrees, the (-180, 180]
+ * wrap, unit vectors): an edge given a cell centre's latitude and longitude gets that centre's unit vector bit for bit.  angleEdge is
+ * kept on the device as given; it may be NULL, and mpg_mesh_edge_rotang_dev is then refused.  Edges are a DESTINATION location only:
+ * mpg_regrid_store_to_mesh(..., MPG_MESHLOC_EDGE, ...) is their Store; every call that takes a source location, the other Stores onto
+ * a mesh and mpg_mesh_rotang_dev go on refusing location 2.  The edge arrays are freed with the mesh.
+ * Refusals.  MPG_ERR_INVALID_ARG, with the offending index in mpg_last_error: a NaN / Inf coordinate or angle, |lat| > pi/2; nEdges < 1;
+ * NULL mesh or coordinates; a second call on the same mesh ("edges are already set": handles onto the edges, cached ones included,
+ * stay valid that way).  MPG_ERR_OVERFLOW: nEdges beyond int32.  MPG_ERR_UNSUPPORTED: a mesh of mpg_mesh_create_window. */
+int mpg_mesh_set_edges(mpg_mesh mesh, int64_t nEdges, const double *latEdge, const double *lonEdge, const double *angleEdge);
+/* the number of edges mpg_mesh_set_edges gave the mesh; 0 for a mesh without edges */
+int mpg_mesh_edge_count(mpg_mesh mesh, int64_t *nEdges);
 
 /* ---- ESMF_GridCreateNoPeriDim / 1PeriDim + GridAddCoord x4 (model_grid.F90:684-728,736-1038) ------
  * nx, ny = mass (CENTER) point counts (i_target, j_target).  Coordinates in DEGREES, C order with i
@@ -173,7 +186,9 @@ int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc,
  * Regrid below is the adjoint of a Mesh -> Grid handle and does not regrid back; this Store builds the interpolation itself.)
  * Source points: the grid's points of src_staggerloc, snx x sny of them (CENTER nx x ny, EDGE1 (nx+1) x ny, EDGE2 nx x (ny+1), CORNER
  *   (nx+1) x (ny+1)), source index = j * snx + i; any stagger whose coordinates the grid holds (a stagger without coordinates ->
- *   MPG_ERR_INVALID_ARG).  Destinations: the mesh's cell centres (MPG_MESHLOC_ELEMENT) or vertices (MPG_MESHLOC_NODE).  The handle is
+ *   MPG_ERR_INVALID_ARG).  Destinations: the mesh's cell centres (MPG_MESHLOC_ELEMENT), vertices (MPG_MESHLOC_NODE) or -- on a mesh
+ *   that mpg_mesh_set_edges gave edges -- its edge points (MPG_MESHLOC_EDGE; same search, same weights, nothing but the point set
+ *   differs; a mesh without edges -> MPG_ERR_INVALID_ARG).  The handle is
  *   an ordinary fixed one (MPG_KIND_FIXED), nnz_per_row 4 (bilinear) or 1 (nearest); mpg_handle_info reports n_src = snx * sny,
  *   n_dst = nx_dst = the mesh count, ny_dst = 1.
  * MPG_REGRIDMETHOD_BILINEAR: source cells are the quads of four neighbouring stagger points A = (b, a), B = (b, a+1), C = (b+1, a+1),
@@ -621,6 +636,46 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
  * chain does not rotate there: pass NULL angles"), as are a grid without a projection (mpg_grid_create without mpg_grid_attach_proj) and
  * a mesh of mpg_mesh_create_window.  Asynchronous on hip_stream (as mpg_regrid_dev); allocates nothing. */
 int mpg_mesh_rotang_dev(mpg_grid grid, mpg_mesh mesh, int meshloc, double *cosa_dev, double *sina_dev, void *hip_stream);
+/* The same angles for the mesh's EDGES, composed with the projection onto the edge normal: per edge phi = angleEdge - alpha (one
+ * float64 subtraction), cn = cos(phi), sn = sin(phi), float64 device arrays [nEdges] for mpg_wind_to_edges_dev.  alpha is exactly
+ * mpg_mesh_rotang_dev's, -hemi * cone * wrap180(lon - stand_lon) * pi / 180 with lon = atan2(y, x) of the edge's stored unit vector;
+ * the rotation to earth-relative winds (alpha) and the projection onto the normal (theta = angleEdge) are ONE rotation by theta - alpha.
+ * grid == NULL gives alpha = 0: winds that are already earth-relative (a lat-lon or Mercator source).  A grid whose projection is not
+ * PROJ_LC, or that carries none -> MPG_ERR_UNSUPPORTED ("the forward chain does not rotate there: pass a NULL grid").  A mesh without
+ * edges or without angleEdge -> MPG_ERR_INVALID_ARG (mpg_mesh_set_edges).  Asynchronous on hip_stream; allocates nothing. */
+int mpg_mesh_edge_rotang_dev(mpg_grid grid, mpg_mesh mesh, double *cn_dev, double *sn_dev, void *hip_stream);
+/* Winds onto mesh EDGES: U on one stagger and V on another -- grid-relative on a Lambert grid -- onto the edge points of a mesh as the
+ * edge-normal wind `u` MPAS carries (and, when asked, the tangential component), in ONE pass: the two Regrids, one rotation and the
+ * cast, without float64 intermediates.
+ *   rh_u, rh_v           fixed handles onto the SAME n_dst points, both with nnz_per_row 4 or both 1: typically
+ *                        mpg_regrid_store_to_mesh(grid, EDGE1 / EDGE2, mesh, MPG_MESHLOC_EDGE, BILINEAR).  rh_u == rh_v is allowed; the
+ *                        kernel then stages one set of indices.  The call does not look at the mesh: any such pair is served.
+ *   cn_dev, sn_dev       [n_dst] float64, cos / sin of phi = angleEdge - alpha (mpg_mesh_edge_rotang_dev).  REQUIRED: there is no
+ *                        un-rotated form; a host that wants one passes cos / sin of angleEdge
+ *   u_dev, v_dev         [nlev][rh_u.n_src], [nlev][rh_v.n_src] of src_type, planes u_level_stride / v_level_stride elements apart
+ *                        (0 = dense; below n_src -> MPG_ERR_INVALID_ARG): the pitched U / V of mpg_wind_destagger_pitched_dev are
+ *                        accepted as they are, their pad is never read
+ *   un_dev, ut_dev       nlev * n_dst each of dst_type, in dst_layout: MPG_LAYOUT_CELL_FAST [lev][edge] or MPG_LAYOUT_LEV_FAST
+ *                        [edge][lev], the file order of u(nEdges, nVertLevels).  ut_dev may be NULL: only the normal component is
+ *                        computed and stored.  Fully overwritten; neither may alias the other, a source or the angles
+ *                        (MPG_ERR_INVALID_ARG)
+ * Values, a contract by identity: float64 arithmetic without contraction, per (point, level)
+ *   a  = fma(wsum_fixed<NNZ>(w_u, U[idx_u]), 1.0, 0.0)    exactly mpg_regrid_to_mesh_dev(rh_u, dst F64, scale 1, offset 0)
+ *   b  = fma(wsum_fixed<NNZ>(w_v, V[idx_v]), 1.0, 0.0)
+ *   un = a * cn + b * sn        two products and one sum, each rounded
+ *   ut = b * cn - a * sn        only when ut_dev != NULL (the tangential component, 90 degrees counter-clockwise of the normal)
+ *   store (TD)un [, (TD)ut]     one rounding to the destination type
+ * (un = ue cos(theta) + ve sin(theta) with the earth-relative ue = a ca - b sa, ve = a sa + b ca of mpg_wind_to_mesh_dev, composed.)
+ * A point that is unmapped in either handle gets (TD)(+0.0) in every result.  The same bits for both layouts, for dense and pitched
+ * sources, and from call to call.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it
+ * can be captured in a hipGraph from the first call.
+ * Refusals, those of mpg_wind_to_mesh_dev under the name mpg_wind_to_edges.  MPG_ERR_UNSUPPORTED: CSR handles (conservative, periodic,
+ * from-weights: winds from a periodic global grid are out of scope), handles with pole caps, 3-slot handles or a pair of mixed
+ * nnz_per_row, MPG_TYPE_BE on either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays (cn_dev / sn_dev included), rh_u.n_dst !=
+ * rh_v.n_dst, nlev < 1, unknown enums, aliased arrays.  MPG_ERR_OVERFLOW: more 64-point blocks than one launch holds. */
+int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev,
+                          const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev,
+                          void *un_dev, void *ut_dev, int dst_type, int dst_layout, void *hip_stream);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

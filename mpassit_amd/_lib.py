@@ -29,12 +29,13 @@ SYMBOLS = [
     "mpg_regrid_store_conserve_mesh", "mpg_regrid_csr_rows_dev",
     "mpg_regrid_store_periodic_to_mesh",
     "mpg_wind_to_mesh_dev", "mpg_mesh_rotang_dev",
+    "mpg_mesh_set_edges", "mpg_mesh_edge_count", "mpg_mesh_edge_rotang_dev", "mpg_wind_to_edges_dev",
 ]
 
 MPG_SUCCESS = 0
 MPG_ERR_INVALID_ARG, MPG_ERR_UNSUPPORTED, MPG_ERR_OVERFLOW = 2, 4, 5
 REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE, REGRIDMETHOD_NEAREST_STOD = 0, 1, 2
-MESHLOC_ELEMENT, MESHLOC_NODE = 0, 1
+MESHLOC_ELEMENT, MESHLOC_NODE, MESHLOC_EDGE = 0, 1, 2
 STAGGERLOC_CENTER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2, STAGGERLOC_CORNER = 0, 1, 2, 3
 LAYOUT_CELL_FAST, LAYOUT_LEV_FAST = 0, 1
 GRID_PERIODIC_I, GRID_NO_SOUTH_POLE, GRID_NO_NORTH_POLE = 1, 2, 4
@@ -196,6 +197,47 @@ def mesh_rotang_dev(*args):
     if "rotang" not in _to_mesh_fns:
         _to_mesh_fns["rotang"] = _MESH_ROTANG_PROTO(("mpg_mesh_rotang_dev", load()))
     return _to_mesh_fns["rotang"](*args)
+
+
+# The mesh's edges and the winds onto them, bound the same way.
+#   mpg_mesh_set_edges(mesh, nEdges, latEdge, lonEdge, angleEdge)
+#   mpg_mesh_edge_count(mesh, nEdges)
+#   mpg_mesh_edge_rotang_dev(grid, mesh, cn_dev, sn_dev, hip_stream)
+#   mpg_wind_to_edges_dev(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev,
+#                         dst_type, dst_layout, hip_stream)
+_MESH_SET_EDGES_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_MESH_EDGE_COUNT_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64))
+_MESH_EDGE_ROTANG_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_WIND_TO_EDGES_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+
+
+def mesh_set_edges(*args):
+    """The typed binding of mpg_mesh_set_edges; returns the call's status code."""
+    if "set_edges" not in _to_mesh_fns:
+        _to_mesh_fns["set_edges"] = _MESH_SET_EDGES_PROTO(("mpg_mesh_set_edges", load()))
+    return _to_mesh_fns["set_edges"](*args)
+
+
+def mesh_edge_count(*args):
+    """The typed binding of mpg_mesh_edge_count; returns the call's status code."""
+    if "edge_count" not in _to_mesh_fns:
+        _to_mesh_fns["edge_count"] = _MESH_EDGE_COUNT_PROTO(("mpg_mesh_edge_count", load()))
+    return _to_mesh_fns["edge_count"](*args)
+
+
+def mesh_edge_rotang_dev(*args):
+    """The typed binding of mpg_mesh_edge_rotang_dev; returns the call's status code."""
+    if "edge_rotang" not in _to_mesh_fns:
+        _to_mesh_fns["edge_rotang"] = _MESH_EDGE_ROTANG_PROTO(("mpg_mesh_edge_rotang_dev", load()))
+    return _to_mesh_fns["edge_rotang"](*args)
+
+
+def wind_to_edges_dev(*args):
+    """The typed binding of mpg_wind_to_edges_dev; returns the call's status code."""
+    if "wind_edges" not in _to_mesh_fns:
+        _to_mesh_fns["wind_edges"] = _WIND_TO_EDGES_PROTO(("mpg_wind_to_edges_dev", load()))
+    return _to_mesh_fns["wind_edges"](*args)
 
 
 _lib = None

@@ -170,9 +170,10 @@ __global__ __launch_bounds__(256) void k_to_mesh_nearest(int64_t n, const double
 int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s) {
   int rc;
   const PointSet &src = g->pts[stagger];
-  const PointSet &dst = meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
+  // the destination points: cells, vertices or (mpg_mesh_set_edges) edges -- nothing else differs between the three
+  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
   const int snx = g->snx[stagger], sny = g->sny[stagger];
-  const int64_t n = meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
   const bool nearest = method == MPG_REGRIDMETHOD_NEAREST_STOD;
   if (!nearest && (snx < 2 || sny < 2)) {
     mpg_set_error("mpg_regrid_store_to_mesh: a bilinear Store needs at least 2 x 2 points of stagger %d", stagger);

@@ -334,22 +334,45 @@ __global__ __launch_bounds__(256) void k_rotang(int nx, int ny, const double *__
 // meridian turned by cone * (lon - stdlon), so alpha = -hemi * cone * wrap180(lon - stdlon) in get_rotang's sign convention (the two
 // agree to 2.3e-6 in sina on the interior rows of a 30-km grid; the difference is the truncation of get_rotang's centred difference).
 // lon = atan2(y, x) of the point's unit vector.
+__device__ __forceinline__ double mesh_rotang_alpha(const ProjDev &p, double x, double y) {
+#pragma clang fp contract(off)
+  double d = atan2(y, x) * TG_DEG_PER_RAD - p.stdlon;
+  if (d > 180.0) d -= 360.0;
+  else if (d < -180.0) d += 360.0;
+  return -p.hemi * p.cone * d * TG_RAD_PER_DEG;
+}
 __global__ __launch_bounds__(256) void k_mesh_rotang(ProjDev p, int64_t n, const double *__restrict__ x, const double *__restrict__ y,
                                                      double *__restrict__ cosa, double *__restrict__ sina) {
+  int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const double alpha = mesh_rotang_alpha(p, x[q], y[q]);
+  sina[q] = sin(alpha);
+  cosa[q] = cos(alpha);
+}
+// ... and composed with the projection onto an edge's normal (mpg_mesh_edge_rotang_dev): phi = angleEdge - alpha, one subtraction;
+// rot false: alpha = 0 (winds that are earth-relative already)
+__global__ __launch_bounds__(256) void k_mesh_edge_rotang(ProjDev p, bool rot, int64_t n, const double *__restrict__ x, const double *__restrict__ y,
+                                                          const double *__restrict__ angle, double *__restrict__ cn, double *__restrict__ sn) {
 #pragma clang fp contract(off)
   int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (q >= n) return;
-  double d = atan2(y[q], x[q]) * TG_DEG_PER_RAD - p.stdlon;
-  if (d > 180.0) d -= 360.0;
-  else if (d < -180.0) d += 360.0;
-  const double alpha = -p.hemi * p.cone * d * TG_RAD_PER_DEG;
-  sina[q] = sin(alpha);
-  cosa[q] = cos(alpha);
+  const double alpha = rot ? mesh_rotang_alpha(p, x[q], y[q]) : 0.0;
+  const double phi = angle[q] - alpha;
+  sn[q] = sin(phi);
+  cn[q] = cos(phi);
 }
 
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s) {
   if (n == 0) return MPG_SUCCESS;
   k_mesh_rotang<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->proj, n, x, y, cosa, sina);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
+int mpg_k_mesh_edge_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, const double *angle, double *cn, double *sn,
+                           hipStream_t s) {
+  if (n == 0) return MPG_SUCCESS;
+  k_mesh_edge_rotang<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g ? g->proj : ProjDev{}, g != nullptr, n, x, y, angle, cn, sn);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }

@@ -134,7 +134,8 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_to_mesh)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_to_mesh) \
+  X(k_wind_to_edges)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -405,6 +406,8 @@ int mpg_mesh_destroy(mpg_mesh m) {
     }
   m->cell.free();
   m->vert.free();
+  m->edge.free();
+  m->angle_edge.free();
   m->voc.free();
   m->tri.free();
   m->fan.free();
@@ -412,6 +415,57 @@ int mpg_mesh_destroy(mpg_mesh m) {
   m->tbvh.free();
   m->cbvh.free();
   delete m;
+  return MPG_SUCCESS;
+}
+
+// The mesh's edge points (MPG_MESHLOC_EDGE): a third PointSet through the cell centres' conversion, angleEdge kept as given.  Once per
+// mesh, so that handles onto the edges -- cached ones included -- never outlive the points they were stored for.
+int mpg_mesh_set_edges(mpg_mesh m, int64_t nEdges, const double *latEdge, const double *lonEdge, const double *angleEdge) {
+  MPG_CHECK_INIT();
+  MPG_ARG(m, "mpg_mesh_set_edges: NULL mesh");
+  if (m->geo_grid) {
+    mpg_set_error("mpg_mesh_set_edges: the mesh was cut to a grid (mpg_mesh_create_window): its resident points are a window; "
+                  "create the whole mesh (mpg_mesh_create) for results on its edges");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  MPG_ARG(m->edge.n == 0, "mpg_mesh_set_edges: edges are already set on this mesh (handles onto them stay valid; create another mesh for other edges)");
+  MPG_ARG(nEdges >= 1, "mpg_mesh_set_edges: nEdges must be >= 1");
+  if (nEdges >= 0x7fffffff) {
+    mpg_set_error("mpg_mesh_set_edges: %lld edges exceed int32 ids", (long long)nEdges);
+    return MPG_ERR_OVERFLOW;
+  }
+  MPG_ARG(latEdge && lonEdge, "mpg_mesh_set_edges: NULL coordinates (latEdge, lonEdge)");
+  if (angleEdge)
+    for (int64_t i = 0; i < nEdges; ++i)
+      if (!std::isfinite(angleEdge[i])) {
+        mpg_set_error("mpg_mesh_set_edges: angleEdge of edge %lld is %.17g -- not an angle in RADIANS (finite)", (long long)i, angleEdge[i]);
+        return MPG_ERR_INVALID_ARG;
+      }
+  hipStream_t s = g_stream;
+  PointSet pts;
+  DevBuf<double> ang;
+  int rc = mpg_k_mesh_coords(nEdges, lonEdge, latEdge, pts, s);   // synchronises: the host arrays are free on return
+  if (!rc && angleEdge && !(rc = ang.alloc((size_t)nEdges))) {
+    hipError_t he = hipMemcpyAsync(ang.p, angleEdge, sizeof(double) * (size_t)nEdges, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) {
+      mpg_set_error("mpg_mesh_set_edges: uploading angleEdge failed: %s", hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  if (rc) {   // the mesh stays without edges
+    pts.free();
+    ang.free();
+    return rc;
+  }
+  m->edge = pts;
+  m->angle_edge = ang;
+  return MPG_SUCCESS;
+}
+
+int mpg_mesh_edge_count(mpg_mesh m, int64_t *nEdges) {
+  MPG_ARG(m && nEdges, "mpg_mesh_edge_count: NULL argument");
+  *nEdges = m->edge.n;
   return MPG_SUCCESS;
 }
 
@@ -592,6 +646,28 @@ int mpg_mesh_rotang_dev(mpg_grid g, mpg_mesh mesh, int meshloc, double *cosa_dev
   const PointSet &pts = meshloc == MPG_MESHLOC_ELEMENT ? mesh->cell : mesh->vert;
   MPG_ARG(pts.n == 0 || (cosa_dev && sina_dev), "mpg_mesh_rotang: NULL output");
   return mpg_k_mesh_rotang(g, pts.n, pts.x.p, pts.y.p, cosa_dev, sina_dev, (hipStream_t)hip_stream);
+}
+
+// cos / sin of phi = angleEdge - alpha at the edges of a mesh, for mpg_wind_to_edges_dev (k_target_grid.hip k_mesh_edge_rotang); a NULL
+// grid: alpha = 0.  (A windowed mesh has no edges: mpg_mesh_set_edges refuses it.)
+int mpg_mesh_edge_rotang_dev(mpg_grid g, mpg_mesh mesh, double *cn_dev, double *sn_dev, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(mesh, "mpg_mesh_edge_rotang: NULL mesh");
+  MPG_ARG(mesh->edge.n > 0, "mpg_mesh_edge_rotang: the mesh has no edges: mpg_mesh_set_edges gives it some");
+  MPG_ARG(mesh->angle_edge.p, "mpg_mesh_edge_rotang: the mesh's edges carry no angleEdge: mpg_mesh_set_edges takes it with the coordinates");
+  if (g && !g->has_inverse) {
+    mpg_set_error("mpg_mesh_edge_rotang: the grid carries no projection (mpg_grid_create_proj or mpg_grid_attach_proj give it one); "
+                  "without one the forward chain does not rotate there: pass a NULL grid");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (g && g->proj.code != MPG_PROJ_LC) {
+    mpg_set_error("mpg_mesh_edge_rotang: cos/sin(alpha) exist for PROJ_LC grids only (model_grid.F90:1113); "
+                  "the forward chain does not rotate there: pass a NULL grid");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  MPG_ARG(cn_dev && sn_dev, "mpg_mesh_edge_rotang: NULL output");
+  const PointSet &pts = mesh->edge;
+  return mpg_k_mesh_edge_rotang(g, pts.n, pts.x.p, pts.y.p, mesh->angle_edge.p, cn_dev, sn_dev, (hipStream_t)hip_stream);
 }
 
 // ---- RegridStore ----------------------------------------------------------------------------------
@@ -946,7 +1022,10 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
   MPG_CHECK_INIT();
   MPG_ARG(src && dst && out, "mpg_regrid_store_to_mesh: NULL argument");
   MPG_ARG(src_staggerloc >= MPG_STAGGERLOC_CENTER && src_staggerloc <= MPG_STAGGERLOC_CORNER, "mpg_regrid_store_to_mesh: unknown stagger location");
-  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE, "mpg_regrid_store_to_mesh: unknown mesh location");
+  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE || dst_meshloc == MPG_MESHLOC_EDGE,
+          "mpg_regrid_store_to_mesh: unknown mesh location");
+  MPG_ARG(dst_meshloc != MPG_MESHLOC_EDGE || dst->edge.n > 0,
+          "mpg_regrid_store_to_mesh: mesh location MPG_MESHLOC_EDGE on a mesh without edges: mpg_mesh_set_edges gives it some");
   MPG_ARG(regridmethod >= 0 && regridmethod <= 2, "mpg_regrid_store_to_mesh: unknown regrid method");
   if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
     mpg_set_error("mpg_regrid_store_to_mesh: conservative Grid -> Mesh regridding is not supported (bilinear and nearest are). "
@@ -964,7 +1043,7 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
     return MPG_ERR_UNSUPPORTED;
   }
   const int64_t n_src = (int64_t)src->snx[src_staggerloc] * src->sny[src_staggerloc];
-  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
+  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_EDGE ? dst->edge.n : dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
   if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
     mpg_set_error("mpg_regrid_store_to_mesh: %lld source points / %lld mesh points exceed int32 ids", (long long)n_src, (long long)n_dst);
     return MPG_ERR_OVERFLOW;
@@ -1351,18 +1430,25 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, 
   return mpg_k_apply_csr_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }
 
-// ---- the wind chain turned round: U / V staggers onto mesh points as earth-relative winds, one pass (k_wind_to_mesh.hip) ---------------
-int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev, const void *v_dev,
-                         int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev, void *ve_dev, int dst_type,
-                         int dst_layout, void *hip_stream) {
-  auto fail = [](int rc, const char *what) {
-    mpg_set_error("mpg_wind_to_mesh: %s", what);
+// ---- the wind chain turned round: U / V staggers onto mesh points, one pass (k_wind_to_mesh.hip, k_wind_to_edges.hip) --------------------
+// What mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev check alike, under the caller's name: the handles, the enums, the strides (out:
+// ldu / ldv in elements) and the aliases of the results r0 / r1 with each other, the sources and the angles a0 / a1.
+struct WindCall {
+  const char *who, *results, *angles;   // "mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev"
+  bool need_angles, need_r1;            // false: both angles may be NULL together / r1 may be NULL
+};
+static int wind_pair_checks(const WindCall &c, mpg_handle rh_u, mpg_handle rh_v, const double *a0, const double *a1, const void *u_dev,
+                            const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *r0, void *r1,
+                            int dst_type, int dst_layout, int64_t *ldu_out, int64_t *ldv_out) {
+  const char *who = c.who;
+  auto fail = [who](int rc, const char *what) {
+    mpg_set_error("%s: %s", who, what);
     return rc;
   };
   MPG_CHECK_INIT();
   if (!(rh_u && rh_v)) return fail(MPG_ERR_INVALID_ARG, "NULL handle");
-  if (!((u_dev || rh_u->n_src == 0) && (v_dev || rh_v->n_src == 0) && ((ue_dev && ve_dev) || rh_u->n_dst == 0))) return fail(MPG_ERR_INVALID_ARG, "NULL array");
-  if ((cosa_dev == nullptr) != (sina_dev == nullptr)) return fail(MPG_ERR_INVALID_ARG, "cosa and sina come together (both NULL: no rotation)");
+  if (!((u_dev || rh_u->n_src == 0) && (v_dev || rh_v->n_src == 0) && ((r0 && (r1 || !c.need_r1) && (!c.need_angles || (a0 && a1))) || rh_u->n_dst == 0))) return fail(MPG_ERR_INVALID_ARG, "NULL array");
+  if (!c.need_angles && (a0 == nullptr) != (a1 == nullptr)) return fail(MPG_ERR_INVALID_ARG, "cosa and sina come together (both NULL: no rotation)");
   if (nlev < 1) return fail(MPG_ERR_INVALID_ARG, "nlev must be >= 1");
   if (dst_layout != MPG_LAYOUT_CELL_FAST && dst_layout != MPG_LAYOUT_LEV_FAST) return fail(MPG_ERR_INVALID_ARG, "bad dst_layout");
   if (!(src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3))
@@ -1378,13 +1464,13 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
                                        "the rotation, serves them");
   }
   if (rh_u->nnz_per_row != rh_v->nnz_per_row || (rh_u->nnz_per_row != 4 && rh_u->nnz_per_row != 1)) {
-    mpg_set_error("mpg_wind_to_mesh: handles of %d and %d slots are not supported (both 4 -- bilinear -- or both 1 -- nearest); "
+    mpg_set_error("%s: handles of %d and %d slots are not supported (both 4 -- bilinear -- or both 1 -- nearest); "
                   "mpg_regrid_to_mesh_dev into float64 on each handle, then the rotation, serves any fixed pair",
-                  rh_u->nnz_per_row, rh_v->nnz_per_row);
+                  who, rh_u->nnz_per_row, rh_v->nnz_per_row);
     return MPG_ERR_UNSUPPORTED;
   }
   if (rh_u->n_dst != rh_v->n_dst) {
-    mpg_set_error("mpg_wind_to_mesh: the handles map onto %lld and %lld points: both must be Stores onto the same points of one mesh",
+    mpg_set_error("%s: the handles map onto %lld and %lld points: both must be Stores onto the same points of one mesh", who,
                   (long long)rh_u->n_dst, (long long)rh_v->n_dst);
     return MPG_ERR_INVALID_ARG;
   }
@@ -1393,17 +1479,17 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
   auto src_stride = [&](const char *arg, int64_t plane, int64_t ld, int64_t *out) {
     if (ld == 0) ld = plane;
     if (ld < plane) {
-      mpg_set_error("mpg_wind_to_mesh: %s %lld is below the source plane of %lld points (0 = dense)", arg, (long long)ld, (long long)plane);
+      mpg_set_error("%s: %s %lld is below the source plane of %lld points (0 = dense)", who, arg, (long long)ld, (long long)plane);
       return MPG_ERR_INVALID_ARG;
     }
     if (ld > 0 && (int64_t)nlev > (INT64_MAX / es) / ld) {
-      mpg_set_error("mpg_wind_to_mesh: %d planes of %s %lld cannot be addressed", nlev, arg, (long long)ld);
+      mpg_set_error("%s: %d planes of %s %lld cannot be addressed", who, nlev, arg, (long long)ld);
       return MPG_ERR_INVALID_ARG;
     }
     *out = ld;
     return MPG_SUCCESS;
   };
-  int64_t ldu, ldv;
+  int64_t ldu = 0, ldv = 0;
   int rc;
   if ((rc = src_stride("u_level_stride", rh_u->n_src, u_level_stride, &ldu))) return rc;
   if ((rc = src_stride("v_level_stride", rh_v->n_src, v_level_stride, &ldv))) return rc;
@@ -1414,15 +1500,45 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
     return p && q && (uintptr_t)p < (uintptr_t)q + nq && (uintptr_t)q < (uintptr_t)p + np;
   };
   const uintptr_t nu = (uintptr_t)nlev * (uintptr_t)ldu * (uintptr_t)es, nv = (uintptr_t)nlev * (uintptr_t)ldv * (uintptr_t)es;
-  if (overlap(ue_dev, nb, ve_dev, nb)) return fail(MPG_ERR_INVALID_ARG, "ue_dev and ve_dev alias each other: give each result its own array");
-  for (void *r : {ue_dev, ve_dev}) {
+  if (overlap(r0, nb, r1, nb)) {
+    mpg_set_error("%s: %s alias each other: give each result its own array", who, c.results);
+    return MPG_ERR_INVALID_ARG;
+  }
+  for (void *r : {r0, r1}) {
     if (overlap(r, nb, u_dev, nu) || overlap(r, nb, v_dev, nv))
       return fail(MPG_ERR_INVALID_ARG, "a result may not alias a source (u_dev, v_dev): give each result its own array");
-    if (overlap(r, nb, cosa_dev, na) || overlap(r, nb, sina_dev, na))
-      return fail(MPG_ERR_INVALID_ARG, "a result may not alias the angles (cosa_dev, sina_dev): give each result its own array");
+    if (overlap(r, nb, a0, na) || overlap(r, nb, a1, na)) {
+      mpg_set_error("%s: a result may not alias the angles (%s): give each result its own array", who, c.angles);
+      return MPG_ERR_INVALID_ARG;
+    }
   }
+  *ldu_out = ldu;
+  *ldv_out = ldv;
+  return MPG_SUCCESS;
+}
+
+int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev, const void *v_dev,
+                         int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev, void *ve_dev, int dst_type,
+                         int dst_layout, void *hip_stream) {
+  int64_t ldu, ldv;
+  int rc = wind_pair_checks({"mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev", false, true}, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev,
+                            src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev, dst_type, dst_layout, &ldu, &ldv);
+  if (rc) return rc;
   return mpg_k_wind_to_mesh(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
                             (hipStream_t)hip_stream);
+}
+
+// ... and onto mesh EDGES as the edge-normal wind (and the tangential one when ut_dev is given): the same checks, ONE rotation by
+// phi = angleEdge - alpha whose cos / sin are required (k_wind_to_edges.hip)
+int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev, const void *v_dev,
+                          int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *un_dev, void *ut_dev, int dst_type,
+                          int dst_layout, void *hip_stream) {
+  int64_t ldu, ldv;
+  int rc = wind_pair_checks({"mpg_wind_to_edges", "un_dev and ut_dev", "cn_dev, sn_dev", true, false}, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev,
+                            src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev, dst_type, dst_layout, &ldu, &ldv);
+  if (rc) return rc;
+  return mpg_k_wind_to_edges(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
+                             (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

@@ -211,7 +211,9 @@ struct mpg_mesh_s {
   int64_t nCells = 0, nVertices = 0;
   int maxEdges = 0;
   PointSet cell, vert;          // unit vectors of cell centres / vertices
-  DevBuf<int32_t> voc;          // [nCells][maxEdges] 1-based, 0-padded (as given)
+  PointSet edge;                // unit vectors of the edge points (mpg_mesh_set_edges; n == 0: the mesh has no edges).  A destination only
+  DevBuf<double> angle_edge;    // [edge.n] angleEdge in radians as given, or empty (set_edges without angles)
+  DevBuf<int32_t> voc;         // [nCells][maxEdges] 1-based, 0-padded (as given)
   DevBuf<int32_t> tri;          // [3][nVertices] dual triangles (cells), -1 = none; CCW
   int64_t nTriValid = 0;
   DevBuf<int32_t> fan;          // [3][nCells*(maxEdges-2)] fan triangles of the Voronoi polygons (vertex ids), lazily
@@ -220,7 +222,8 @@ struct mpg_mesh_s {
   TriBvh tbvh;                  // BVH over `tri`, lazily (Mesh -> Mesh bilinear Store)
   CellBvh cbvh;                 // box tree over the cell polygons, lazily (Mesh -> Mesh conservative Store)
   // source window per mesh location (ELEMENT, NODE): Regrid sources hold ids [win_first, win_first + win_count) only and
-  // every handle of this mesh indexes relative to win_first (mpg_mesh_set_source_window); whole mesh by default
+  // every handle of this mesh indexes relative to win_first (mpg_mesh_set_source_window); whole mesh by default.  Edges are never a
+  // source location: these two are NOT indexed with MPG_MESHLOC_EDGE
   int64_t win_first[2] = {0, 0}, win_count[2] = {-1, -1};
   // GEOMETRY window (mpg_mesh_create_window; the whole mesh after mpg_mesh_create): `voc` holds the rows of cells
   // [cw0, cw0 + cwn) only, `vert` and `tri` the vertices [vw0, vw0 + vwn) only; `cell` always holds every cell centre
@@ -481,6 +484,13 @@ int mpg_k_wind_to_mesh(mpg_handle_s *hu, mpg_handle_s *hv, const double *cosa, c
                        int64_t ldu, int64_t ldv, int nlev, void *ue, void *ve, int dst_type, int layout, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
+// ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0
+int mpg_k_mesh_edge_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, const double *angle, double *cn, double *sn,
+                           hipStream_t s);
+// k_wind_to_edges.hip: the two Regrids of a wind's components onto one set of points and ONE rotation onto the edge normal (and tangent:
+// ut != nullptr), one pass (include/mpassit_amd.h mpg_wind_to_edges_dev; arguments checked by the API entry point)
+int mpg_k_wind_to_edges(mpg_handle_s *hu, mpg_handle_s *hv, const double *cn, const double *sn, const void *u, const void *v, int src_type,
+                        int64_t ldu, int64_t ldv, int nlev, void *un, void *ut, int dst_type, int layout, hipStream_t s);
 // k_store_conserve.hip: conservative Grid -> Mesh Store (CSR rows keyed by mesh cell, h->dst_frac); norm_type MPG_NORM_*
 int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s);
 // ... its row builder, shared with the Mesh -> Mesh Store: rows keyed by the cells of `m` from a pair list grouped by cell (h->rowptr and

@@ -17,7 +17,7 @@ module mpg
 
   integer(c_int), parameter :: MPG_SUCCESS = 0, MPG_ERR_UNSUPPORTED = 4
   integer(c_int), parameter :: MPG_REGRIDMETHOD_BILINEAR = 0, MPG_REGRIDMETHOD_CONSERVE = 1, MPG_REGRIDMETHOD_NEAREST_STOD = 2
-  integer(c_int), parameter :: MPG_MESHLOC_ELEMENT = 0, MPG_MESHLOC_NODE = 1
+  integer(c_int), parameter :: MPG_MESHLOC_ELEMENT = 0, MPG_MESHLOC_NODE = 1, MPG_MESHLOC_EDGE = 2
   integer(c_int), parameter :: MPG_STAGGERLOC_CENTER = 0, MPG_STAGGERLOC_EDGE1 = 1, MPG_STAGGERLOC_EDGE2 = 2, &
                                MPG_STAGGERLOC_CORNER = 3
   integer(c_int), parameter :: MPG_LAYOUT_CELL_FAST = 0, MPG_LAYOUT_LEV_FAST = 1
@@ -418,6 +418,36 @@ module mpg
       integer(c_int), value :: meshloc
       integer(c_int) :: rc
     end function mpg_mesh_rotang_dev
+    !> the mesh's edges (MPG_MESHLOC_EDGE, a destination of mpg_regrid_store_to_mesh): latEdge / lonEdge / angleEdge as the MPAS file
+    !! holds them, radians; angleEdge may be c_null_ptr.  Once per mesh (include/mpassit_amd.h)
+    function mpg_mesh_set_edges(mesh, nEdges, latEdge, lonEdge, angleEdge) bind(C, name="mpg_mesh_set_edges") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: mesh, latEdge, lonEdge, angleEdge
+      integer(c_int64_t), value :: nEdges
+      integer(c_int) :: rc
+    end function mpg_mesh_set_edges
+    function mpg_mesh_edge_count(mesh, nEdges) bind(C, name="mpg_mesh_edge_count") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: mesh
+      integer(c_int64_t), intent(out) :: nEdges
+      integer(c_int) :: rc
+    end function mpg_mesh_edge_count
+    !> cos / sin of phi = angleEdge - alpha at the mesh's edges (grid = c_null_ptr: alpha = 0, earth-relative winds)
+    function mpg_mesh_edge_rotang_dev(grid, mesh, cn_dev, sn_dev, hip_stream) bind(C, name="mpg_mesh_edge_rotang_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: grid, mesh, cn_dev, sn_dev, hip_stream
+      integer(c_int) :: rc
+    end function mpg_mesh_edge_rotang_dev
+    !> winds onto mesh edges in one pass: un = a cn + b sn, the edge-normal wind u(nEdges, nVertLevels) with MPG_LAYOUT_LEV_FAST, and
+    !! ut = b cn - a sn unless ut_dev is c_null_ptr (include/mpassit_amd.h)
+    function mpg_wind_to_edges_dev(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, un_dev, &
+                                   ut_dev, dst_type, dst_layout, hip_stream) bind(C, name="mpg_wind_to_edges_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, un_dev, ut_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride, v_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_to_edges_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
+from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, MESHLOC_EDGE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
                    NORM_DSTAREA, NORM_FRACAREA, POLEMETHOD_NONE, POLEMETHOD_ALLAVG, check)
 
@@ -23,7 +23,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd", "regrid_store_conserve_mesh", "regrid_csr_rows_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
-           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd"]
+           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
+           "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd"]
 
 
 def _f64(a):
@@ -107,6 +108,7 @@ class Mesh:
         if voc.ndim != 2 or voc.shape[0] != latCell.size:
             raise ValueError("verticesOnCell must be [nCells][maxEdges]")
         self.nCells, self.nVertices, self.maxEdges = int(latCell.size), int(latVertex.size), int(voc.shape[1])
+        self.nEdges = 0
         self._h = C.c_void_p()
         args = (C.c_int64(self.nCells), C.c_int64(self.nVertices), C.c_int(self.maxEdges), _ptr(latCell), _ptr(lonCell), _ptr(latVertex),
                 _ptr(lonVertex), _ptr(voc))
@@ -117,7 +119,25 @@ class Mesh:
 
     @classmethod
     def from_mpas(cls, m, window_grid=None):
-        return cls(m.latCell, m.lonCell, m.latVertex, m.lonVertex, m.verticesOnCell, window_grid=window_grid)
+        mesh = cls(m.latCell, m.lonCell, m.latVertex, m.lonVertex, m.verticesOnCell, window_grid=window_grid)
+        if getattr(m, "latEdge", None) is not None and window_grid is None:     # (a windowed mesh takes no edges)
+            mesh.set_edges(m.latEdge, m.lonEdge, getattr(m, "angleEdge", None))
+        return mesh
+
+    def set_edges(self, latEdge, lonEdge, angleEdge=None):
+        """mpg_mesh_set_edges: the mesh's edge points (radians, as the MPAS file holds latEdge / lonEdge / angleEdge), the destination
+        MESHLOC_EDGE of regrid_store_to_mesh.  Once per mesh; without angleEdge, mesh_edge_rotang is refused."""
+        latEdge, lonEdge = _f64(latEdge), _f64(lonEdge)
+        if latEdge.ndim != 1 or latEdge.shape != lonEdge.shape:
+            raise ValueError("set_edges: latEdge and lonEdge must be 1-D arrays of one size")
+        if angleEdge is not None:
+            angleEdge = _f64(angleEdge)
+            if angleEdge.shape != latEdge.shape:
+                raise ValueError("set_edges: angleEdge must have latEdge's size")
+        check(L.mesh_set_edges(self._h, int(latEdge.size), _ptr(latEdge), _ptr(lonEdge), _ptr(angleEdge)))
+        n = C.c_int64()
+        check(L.mesh_edge_count(self._h, C.byref(n)))
+        self.nEdges = int(n.value)
 
     def window_info(self):
         """(cell_first, cell_count, vertex_first, vertex_count, margin): the resident part of the geometry (the whole mesh
@@ -902,7 +922,8 @@ def regrid_store_conserve_to_mesh(src_grid, dst_mesh, norm=NORM_DSTAREA):
 
 def regrid_store_to_mesh(src_grid, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER, meshloc=MESHLOC_ELEMENT):
     """ESMF_FieldRegridStore(grid field -> mesh field): the grid's `staggerloc` points onto the mesh's cells (MESHLOC_ELEMENT) or
-    vertices (MESHLOC_NODE), bilinear or nearest.  The handle is an ordinary fixed one (n_dst = the mesh count): regrid_typed,
+    vertices (MESHLOC_NODE), bilinear or nearest -- or, on a mesh with edges (Mesh.set_edges), onto its edge points (MESHLOC_EDGE).  The
+    handle is an ordinary fixed one (n_dst = the mesh count): regrid_typed,
     regrid_masked, regrid_transpose and the getters work on it, regrid_to_mesh writes the mesh's own memory orders."""
     h = C.c_void_p()
     check(L.regrid_store_to_mesh(src_grid._h, int(staggerloc), dst_mesh._h, int(meshloc), int(regridmethod), C.byref(h)))
@@ -1173,3 +1194,113 @@ def wind_to_mesh_autograd(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL
     rh_u.regrid_transpose(g_a), rh_v.regrid_transpose(g_b) are returned in u's and v's shapes and dtypes: the exact adjoint of the
     forward.  The first backward on a handle downloads its indices once for the mask."""
     return WindToMeshFunction.apply(u, v, rh_u, rh_v, cosa, sina, nlev, layout)
+
+
+def mesh_edge_rotang(grid, mesh):
+    """mpg_mesh_edge_rotang_dev: (cn, sn) = cos / sin of phi = angleEdge - alpha at the mesh's edges, float64 CUDA tensors [nEdges] for
+    wind_to_edges -- the rotation from a Lambert grid's grid-relative winds to earth-relative ones (alpha, as mesh_rotang) and the
+    projection onto the edge normal (angleEdge) composed into one rotation; target_grid.edge_rotang_at is the numpy mirror.  grid=None:
+    alpha = 0, winds that are earth-relative already (a lat-lon or Mercator source).  MpgError (rc 4) for a grid that is not Lambert or
+    carries no projection -- pass None there -- and (rc 2) for a mesh without edges or without angleEdge (Mesh.set_edges)."""
+    import torch
+    n = int(mesh.nEdges)          # (0: the library refuses a mesh without edges before it looks at the outputs)
+    cn = torch.empty(n, dtype=torch.float64, device="cuda")
+    sn = torch.empty(n, dtype=torch.float64, device="cuda")
+    check(L.mesh_edge_rotang_dev(grid._h if grid is not None else None, mesh._h, cn.data_ptr(), sn.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream))
+    return cn, sn
+
+
+def wind_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, tangential=False, outs=None):
+    """mpg_wind_to_edges_dev: winds onto mesh EDGES in one pass -- U through rh_u and V through rh_v onto the SAME points (the typical
+    pair: regrid_store_to_mesh(grid, mesh, staggerloc=STAGGERLOC_EDGE1 / STAGGERLOC_EDGE2, meshloc=MESHLOC_EDGE); rh_u is rh_v is
+    allowed), then ONE rotation by phi = angleEdge - alpha with cn / sn = cos / sin(phi) at the points (mesh_edge_rotang; required) and
+    the cast: un = a cn + b sn, the edge-normal wind `u` MPAS carries, and with tangential=True ut = b cn - a sn, with a, b the float64
+    results of rh_u.regrid_to_mesh(u) and rh_v.regrid_to_mesh(v).  u, v: float32 / float64 CUDA tensors of one dtype,
+    [nlev][n_src of their handle], contiguous or plane-pitched views (nlev, ny, nx).  Returns un, or (un, ut), of out_dtype (default:
+    u's): (nlev, n_dst) for LAYOUT_CELL_FAST, (n_dst, nlev) for LAYOUT_LEV_FAST -- the file order of u(nEdges, nVertLevels); a point
+    either handle leaves unmapped is +0.0.  outs: the tensor (tangential: the pair) to write into, contiguous, nlev * n_dst elements.
+    Bit-identical to the separate calls."""
+    import torch
+    who = "wind_to_edges"
+    ldu, ldv = _wind_source(u, rh_u, nlev, who), _wind_source(v, rh_v, nlev, who)
+    if u.dtype != v.dtype:
+        raise ValueError(who + ": u and v must have one dtype")
+    for t in (cn, sn):
+        if not (t is not None and _is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == rh_u.n_dst):
+            raise ValueError(who + ": cn / sn must be contiguous float64 CUDA tensors of n_dst = %d elements" % rh_u.n_dst)
+    nout = 2 if tangential else 1
+    if outs is None:
+        outs = (None,) * nout
+    elif _is_torch(outs):
+        outs = (outs,)
+    outs = tuple(outs)
+    if len(outs) != nout:
+        raise ValueError(who + ": outs must hold %d tensor(s)" % nout)
+    given = [t for t in outs if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
+    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+    shape = (nlev, rh_u.n_dst) if layout == LAYOUT_CELL_FAST else (rh_u.n_dst, nlev)
+    res = [t if t is not None else torch.empty(shape, dtype=out_dtype, device=u.device) for t in outs]
+    for t in res:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh_u.n_dst):
+            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh_u.n_dst))
+    if ACCOUNT is not None:     # L (U_u + U_v) e_s + n_out P L e_d + P (2 NNZ 12 + 16): both sources read once, every result written once,
+        for rh in (rh_u, rh_v):  # the indices and weights of both handles and the angles once
+            if getattr(rh, "_acc_U", None) is None:
+                rh._acc_U = int(rh.unique_sources().size)
+        ACCOUNT.append(("wind_to_edges nnz%d L%d x%d" % (rh_u.nnz_per_row, nlev, nout),
+                        nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + nout * rh_u.n_dst * nlev * res[0].element_size()
+                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + 16)))
+    check(L.wind_to_edges_dev(rh_u._h, rh_v._h, cn.data_ptr(), sn.data_ptr(), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv,
+                              int(nlev), res[0].data_ptr(), res[1].data_ptr() if tangential else None, int(out_dtype == torch.float32), int(layout),
+                              torch.cuda.current_stream().cuda_stream))
+    return (res[0], res[1]) if tangential else res[0]
+
+
+if _torch is not None:
+    class WindToEdgesFunction(_torch.autograd.Function):
+        """wind_to_edges with a gradient: forward is wind_to_edges in u's dtype; backward takes g_un (and g_ut) back to [lev][edge],
+        zeroes them where either handle leaves the point unmapped (the forward stores a constant +0.0 there), turns them by the
+        transposed rotation in torch and applies each handle's regrid_transpose.  Use wind_to_edges_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential):
+            ctx.rh_u, ctx.rh_v, ctx.cn, ctx.sn, ctx.nlev, ctx.layout, ctx.tangential = rh_u, rh_v, cn, sn, nlev, layout, tangential
+            ctx.shapes, ctx.dtypes = (u.shape, v.shape), (u.dtype, v.dtype)
+            return wind_to_edges(rh_u, rh_v, cn, sn, u.contiguous(), v.contiguous(), nlev, layout=layout, out_dtype=u.dtype, tangential=tangential)
+
+        @staticmethod
+        def backward(ctx, g_un, g_ut=None):
+            n, nlev = ctx.rh_u.n_dst, ctx.nlev
+
+            def planes(g):            # regrid_transpose reads [nlev][n_dst] planes
+                if ctx.layout == LAYOUT_LEV_FAST:
+                    g = g.reshape(n, nlev).t()
+                return g.reshape(nlev, n)
+            # a point unmapped in EITHER handle is a constant of the forward: without this a point mapped in one handle only would send
+            # its gradient through that handle's transpose, a term the forward does not have
+            un = _unmapped_mask(ctx.rh_u)
+            if ctx.rh_v is not ctx.rh_u:
+                un = un | _unmapped_mask(ctx.rh_v)
+            g_un = planes(g_un).masked_fill(un, 0.0)
+            cn, sn = ctx.cn.to(g_un.dtype), ctx.sn.to(g_un.dtype)
+            if ctx.tangential:
+                g_ut = planes(g_ut).masked_fill(un, 0.0)
+                g_a, g_b = g_un * cn - g_ut * sn, g_un * sn + g_ut * cn
+            else:
+                g_a, g_b = g_un * cn, g_un * sn
+            # two separate gradients even when rh_u is rh_v: one of u, one of v
+            gu = ctx.rh_u.regrid_transpose(g_a.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[0])
+            gv = ctx.rh_v.regrid_transpose(g_b.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[1])
+            return gu.reshape(ctx.shapes[0]), gv.reshape(ctx.shapes[1]), None, None, None, None, None, None, None
+
+
+def wind_to_edges_autograd(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, tangential=False):
+    """wind_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout, tangential=tangential) in u's dtype as a differentiable torch op.  The
+    gradients with respect to u and v: the incoming g_un (and g_ut), taken back to [lev][edge] and set to zero where either handle
+    leaves the point unmapped, give g_a = g_un cn - g_ut sn and g_b = g_un sn + g_ut cn, and rh_u.regrid_transpose(g_a),
+    rh_v.regrid_transpose(g_b) are returned in u's and v's shapes and dtypes: the exact adjoint of the forward.  The first backward on a
+    handle downloads its indices once for the mask."""
+    return WindToEdgesFunction.apply(u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential)

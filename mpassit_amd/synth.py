@@ -22,6 +22,15 @@ class MpasMesh:
     latVertex: np.ndarray
     lonVertex: np.ndarray
     verticesOnCell: np.ndarray  # [nCells][maxEdges] int32, 1-based, 0 = pad
+    # the edges (mesh_edges derives them; None: the mesh carries none)
+    latEdge: np.ndarray = None
+    lonEdge: np.ndarray = None
+    angleEdge: np.ndarray = None    # [nEdges] radians: the angle of the edge's normal (from cellsOnEdge[:, 0] towards [:, 1]) from local east
+    cellsOnEdge: np.ndarray = None  # [nEdges][2] int32, 1-based, 0 = none (a rim edge)
+
+    @property
+    def nEdges(self):
+        return 0 if self.latEdge is None else self.latEdge.size
 
     @property
     def nCells(self):
@@ -312,6 +321,45 @@ def regional_mesh_for_lambert(proj, nx, ny, n_cells, margin=0.05, seed=SEED):
     x0 = 1.0 - margin * (nx - 1) - 0.25 * spacing
     y0 = 1.0 - margin * (ny - 1) - ((r_cells - 1) * spacing * (3.0 ** 0.5 / 2.0) - h) / 2.0
     return regional_hex_mesh(proj, x0, y0, q_cells, r_cells, spacing, seed=seed)
+
+
+def mesh_edges(m):
+    """The mesh with its edges derived from verticesOnCell, as an MPAS file holds them (latEdge, lonEdge, angleEdge, cellsOnEdge): one
+    edge per unordered pair of consecutive vertices of a cell, in ascending (min vertex, max vertex) order; cellsOnEdge = the one or two
+    cells that list the pair, lower id first, 0 for none; the edge point = the normalised midpoint of the two vertices; the normal = the
+    tangent-plane projection at that point of (centre 2 - centre 1), on a rim edge of (edge point - centre 1); angleEdge =
+    atan2(n . north, n . east).  A new MpasMesh; the arrays of `m` are shared, not copied."""
+    import dataclasses
+    voc = np.asarray(m.verticesOnCell, np.int64)
+    nc, me = voc.shape
+    nv = int(m.nVertices)
+    k = (voc > 0).sum(axis=1)[:, None]
+    j = np.arange(me)[None, :]
+    valid = j < k
+    nxt = np.where(j + 1 < k, np.roll(voc, -1, axis=1), voc[:, :1])     # the cell's next vertex, the first one after the last
+    a, b = voc[valid] - 1, nxt[valid] - 1
+    cell = np.broadcast_to(np.arange(nc, dtype=np.int64)[:, None], voc.shape)[valid]
+    keep = a != b
+    a, b, cell = a[keep], b[keep], cell[keep]
+    key = np.minimum(a, b) * nv + np.maximum(a, b)
+    order = np.lexsort((cell, key))
+    key, cell = key[order], cell[order]
+    uk, first, cnt = np.unique(key, return_index=True, return_counts=True)
+    if cnt.max() > 2:
+        raise ValueError("mesh_edges: a pair of vertices is listed by %d cells" % cnt.max())
+    c1 = cell[first]
+    c2 = np.where(cnt == 2, cell[np.minimum(first + 1, cell.size - 1)], -1)
+    vert, cen = latlon_rad_to_xyz(m.latVertex, m.lonVertex), latlon_rad_to_xyz(m.latCell, m.lonCell)
+    p = vert[uk // nv] + vert[uk % nv]
+    p /= np.linalg.norm(p, axis=1, keepdims=True)
+    d = np.where((c2 >= 0)[:, None], cen[np.maximum(c2, 0)] - cen[c1], p - cen[c1])
+    n = d - np.einsum("ij,ij->i", d, p)[:, None] * p
+    lat, lon = _xyz_to_latlon_rad(p)
+    east = np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)], axis=1)
+    north = np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)], axis=1)
+    angle = np.arctan2(np.einsum("ij,ij->i", n, north), np.einsum("ij,ij->i", n, east))
+    coe = np.stack([c1 + 1, c2 + 1], axis=1).astype(np.int32)
+    return dataclasses.replace(m, latEdge=lat, lonEdge=lon, angleEdge=angle, cellsOnEdge=coe)
 
 
 def renumber_cells(m, perm):

@@ -273,6 +273,23 @@ def rotang_at(proj, lon_deg):
     return np.cos(alpha), np.sin(alpha)
 
 
+def edge_rotang_at(proj, lon_deg, angle_edge):
+    """(cn, sn) = cos / sin of phi = angle_edge - alpha at mesh edges: alpha as rotang_at at the edges' longitudes (degrees), angle_edge
+    the MPAS angleEdge (radians) -- the rotation to earth-relative winds and the projection onto the edge normal as ONE rotation.  The
+    host mirror of mpg_mesh_edge_rotang_dev.  proj=None: alpha = 0 (winds that are earth-relative already); else PROJ_LC only."""
+    theta = np.asarray(angle_edge, dtype=np.float64)
+    if proj is None:
+        phi = theta - 0.0
+    else:
+        if proj.code != PROJ_LC:
+            raise ValueError("edge_rotang_at: cos/sin(alpha) exist for PROJ_LC only; the forward chain does not rotate elsewhere: pass proj=None")
+        d = np.asarray(lon_deg, dtype=np.float64) - proj.stdlon
+        for _ in range(2):
+            d = np.where(d > 180.0, d - 360.0, np.where(d < -180.0, d + 360.0, d))
+        phi = theta - (-proj.hemi * proj.cone * d * RAD_PER_DEG)
+    return np.cos(phi), np.sin(phi)
+
+
 @dataclass
 class TargetGrid:
     """Host copy of what `define_target_grid_params` leaves in the ESMF Grid (all [nj][ni], degrees)."""
