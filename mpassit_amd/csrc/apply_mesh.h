@@ -1,8 +1,9 @@
-// What the four mesh-order Regrid kernels share (k_apply_to_mesh / k_apply_csr_to_mesh / k_apply_rows / k_apply_csr_rows.hip): the
-// staging of a block's indices and weights or of its CSR run through LDS, the (point, level) cursor along a block's [cell][lev] run,
-// the drain of the [cell][lev] result tile, and on the host the tile plan, the launch grid, the path of a handle without sources and
-// the (src_type, dst_type) dispatch.  One workgroup of 256 threads owns AM_CELLS consecutive destination points and all levels in every
-// one of the four; the LDS arrays are declared by the kernels (dynamic or static) and handed in as pointers; the main loops stay there.
+// What the four mesh-order Regrid kernels (k_apply_to_mesh / k_apply_csr_to_mesh / k_apply_rows / k_apply_csr_rows.hip) and the wind
+// kernel on two fixed handles (k_wind_pair.hip) share: the staging of a block's indices and weights or of its CSR run through LDS, the
+// (point, level) cursor along a block's [cell][lev] run, the drain of the [cell][lev] result tile, and on the host the tile plan, the
+// launch grid, the path of a handle without sources and the (src_type, dst_type) dispatch.  One workgroup of 256 threads owns AM_CELLS
+// consecutive destination points and all levels in every one of the five; the LDS arrays are declared by the kernels (dynamic or static)
+// and handed in as pointers; the main loops stay there.
 #pragma once
 #include <algorithm>
 
@@ -105,31 +106,22 @@ __device__ __forceinline__ void am_drain_tile(const TD *tile, int S, TD *df, int
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-// The [cell][lev] tile of a 64-point block behind `head` bytes of dynamic LDS: all levels in one tile when they fit AM_TILE_BYTES, else
-// chunks of kc levels, a multiple of 32 (a 128-byte line of a float32 row, two of a float64 row); row stride S odd, so that the column
-// writes of a wave hit distinct banks.  No tile for [lev][cell] results (levf false).
+// The ntiles (1 or 2) [cell][lev] tiles of one shape of a 64-point block behind `head` bytes of dynamic LDS; together they stay within
+// AM_TILE_BYTES: all levels in one tile when they fit the cap -- AM_TILE_BYTES for one tile, half of it for each of two (k_wind_pair.hip:
+// a wind's two components; all levels up to 63 float64 / 127 float32, else chunks of 32 / 96) -- else chunks of kc levels, a multiple of
+// 32 (a 128-byte line of a float32 row, two of a float64 row); row stride S odd, so that the column writes of a wave hit distinct banks.
+// lds counts every tile.  No tile for [lev][cell] results (levf false).
 struct TilePlan {
   int kc, S;
   size_t lds;
 };
-static inline TilePlan am_tile_plan(int nlev, size_t esz, bool levf, size_t head) {
+static inline TilePlan am_tile_plan(int nlev, size_t esz, bool levf, size_t head, int ntiles) {
   TilePlan p{nlev, 0, head};
   if (levf) {
-    if ((size_t)AM_CELLS * (size_t)(nlev | 1) * esz > AM_TILE_BYTES) p.kc = (int)(AM_TILE_BYTES / (AM_CELLS * esz) - 1) / 32 * 32;
-    p.S = p.kc | 1;
-    p.lds += (size_t)AM_CELLS * (size_t)p.S * esz;
-  }
-  return p;
-}
-// ... and TWO such tiles of one shape behind `head` (k_wind_to_mesh.hip: a wind's two components): both together stay within
-// AM_TILE_BYTES, so each has half the cap -- all levels up to 63 (float64) / 127 (float32), else chunks of 32 / 96 levels.  lds counts both.
-static inline TilePlan am_tile_plan_pair(int nlev, size_t esz, bool levf, size_t head) {
-  TilePlan p{nlev, 0, head};
-  if (levf) {
-    const size_t cap = AM_TILE_BYTES / 2;
+    const size_t cap = AM_TILE_BYTES / ntiles;
     if ((size_t)AM_CELLS * (size_t)(nlev | 1) * esz > cap) p.kc = (int)(cap / (AM_CELLS * esz) - 1) / 32 * 32;
     p.S = p.kc | 1;
-    p.lds += 2 * (size_t)AM_CELLS * (size_t)p.S * esz;
+    p.lds += ntiles * (size_t)AM_CELLS * (size_t)p.S * esz;
   }
   return p;
 }

@@ -81,7 +81,7 @@ static int launch_layout(mpg_handle_s *h, const void *src, int64_t ld, int nlev,
   uint64_t ntile;
   int rc = am_grid("mpg_regrid_csr_to_mesh", P, nfields, &ntile);
   if (rc) return rc;
-  const TilePlan tp = am_tile_plan(nlev, sizeof(TD), levf, (size_t)AM_CHUNK * (sizeof(double) + sizeof(int32_t)) + CM_RP * sizeof(int32_t));
+  const TilePlan tp = am_tile_plan(nlev, sizeof(TD), levf, (size_t)AM_CHUNK * (sizeof(double) + sizeof(int32_t)) + CM_RP * sizeof(int32_t), 1);
   auto fn = levf ? k_apply_csr_to_mesh<TS, TD, true> : k_apply_csr_to_mesh<TS, TD, false>;
   if ((rc = am_allow_lds((const void *)fn, tp.lds))) return rc;
   fn<<<(unsigned)(ntile * (uint64_t)nfields), 256, tp.lds, s>>>(h->rowptr.p, h->col.p, h->val.p, (const TS *)src, (TD *)dst, P, ld, nlev, (unsigned)ntile,

@@ -134,8 +134,7 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_to_mesh) \
-  X(k_wind_to_edges)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1430,7 +1429,7 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, 
   return mpg_k_apply_csr_to_mesh(h, src_dev, src_type, ld, nlev, nfields, dst_dev, dst_type, dst_layout, scale, offset, (hipStream_t)hip_stream);
 }
 
-// ---- the wind chain turned round: U / V staggers onto mesh points, one pass (k_wind_to_mesh.hip, k_wind_to_edges.hip) --------------------
+// ---- the wind chain turned round: U / V staggers onto mesh points, one pass (k_wind_pair.hip) -----------------------------------------
 // What mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev check alike, under the caller's name: the handles, the enums, the strides (out:
 // ldu / ldv in elements) and the aliases of the results r0 / r1 with each other, the sources and the angles a0 / a1.
 struct WindCall {
@@ -1524,12 +1523,12 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
   int rc = wind_pair_checks({"mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev", false, true}, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev,
                             src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev, dst_type, dst_layout, &ldu, &ldv);
   if (rc) return rc;
-  return mpg_k_wind_to_mesh(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
-                            (hipStream_t)hip_stream);
+  return mpg_k_wind_pair(false, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
+                         (hipStream_t)hip_stream);
 }
 
 // ... and onto mesh EDGES as the edge-normal wind (and the tangential one when ut_dev is given): the same checks, ONE rotation by
-// phi = angleEdge - alpha whose cos / sin are required (k_wind_to_edges.hip)
+// phi = angleEdge - alpha whose cos / sin are required (k_wind_pair.hip: the Edges policies)
 int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev, const void *v_dev,
                           int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *un_dev, void *ut_dev, int dst_type,
                           int dst_layout, void *hip_stream) {
@@ -1537,8 +1536,8 @@ int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev
   int rc = wind_pair_checks({"mpg_wind_to_edges", "un_dev and ut_dev", "cn_dev, sn_dev", true, false}, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev,
                             src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev, dst_type, dst_layout, &ldu, &ldv);
   if (rc) return rc;
-  return mpg_k_wind_to_edges(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
-                             (hipStream_t)hip_stream);
+  return mpg_k_wind_pair(true, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
+                         (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

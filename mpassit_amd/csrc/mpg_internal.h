@@ -478,19 +478,16 @@ int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s);
 // k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
 int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                         double scale, double offset, hipStream_t s);
-// k_wind_to_mesh.hip: the two Regrids of a wind's components onto one set of points and the rotation to earth-relative winds, one pass
-// (include/mpassit_amd.h mpg_wind_to_mesh_dev; arguments checked by the API entry point); ldu / ldv: the sources' level strides in elements
-int mpg_k_wind_to_mesh(mpg_handle_s *hu, mpg_handle_s *hv, const double *cosa, const double *sina, const void *u, const void *v, int src_type,
-                       int64_t ldu, int64_t ldv, int nlev, void *ue, void *ve, int dst_type, int layout, hipStream_t s);
+// k_wind_pair.hip: the two Regrids of a wind's components onto one set of points and one rotation, one pass (arguments checked by the
+// API entry point); ldu / ldv: the sources' level strides in elements.  edges false: mpg_wind_to_mesh_dev, (c, s) = (cosa, sina) or both
+// nullptr, (r0, r1) = (ue, ve); edges true: mpg_wind_to_edges_dev, (c, s) = (cn, sn), (r0, r1) = (un, ut), ut may be nullptr
+int mpg_k_wind_pair(bool edges, mpg_handle_s *hu, mpg_handle_s *hv, const double *c, const double *s_, const void *u, const void *v, int src_type,
+                    int64_t ldu, int64_t ldv, int nlev, void *r0, void *r1, int dst_type, int layout, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0
 int mpg_k_mesh_edge_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, const double *angle, double *cn, double *sn,
                            hipStream_t s);
-// k_wind_to_edges.hip: the two Regrids of a wind's components onto one set of points and ONE rotation onto the edge normal (and tangent:
-// ut != nullptr), one pass (include/mpassit_amd.h mpg_wind_to_edges_dev; arguments checked by the API entry point)
-int mpg_k_wind_to_edges(mpg_handle_s *hu, mpg_handle_s *hv, const double *cn, const double *sn, const void *u, const void *v, int src_type,
-                        int64_t ldu, int64_t ldv, int nlev, void *un, void *ut, int dst_type, int layout, hipStream_t s);
 // k_store_conserve.hip: conservative Grid -> Mesh Store (CSR rows keyed by mesh cell, h->dst_frac); norm_type MPG_NORM_*
 int mpg_k_store_conserve_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int norm_type, mpg_handle_s *h, hipStream_t s);
 // ... its row builder, shared with the Mesh -> Mesh Store: rows keyed by the cells of `m` from a pair list grouped by cell (h->rowptr and

@@ -1084,6 +1084,48 @@ def _wind_source(t, rh, nlev, who):
     return _level_stride(t, (1, nlev) if t.dim() == 4 else (nlev,), ny, nx, who)
 
 
+def _wind_pair(who, call, rh_u, rh_v, angles, names, need_angles, u, v, nlev, layout, out_dtype, outs, nout, label=""):
+    """The body of wind_to_mesh and wind_to_edges: the checks of the sources, the two angle arrays `names` (need_angles False: both may be
+    None) and the nout results (outs: a sequence of nout tensors or None each), the allocation, the ACCOUNT entry and the call.  Returns
+    the tuple of results."""
+    import torch
+    ldu, ldv = _wind_source(u, rh_u, nlev, who), _wind_source(v, rh_v, nlev, who)
+    if u.dtype != v.dtype:
+        raise ValueError(who + ": u and v must have one dtype")
+    if not need_angles and (angles[0] is None) != (angles[1] is None):
+        raise ValueError("%s: %s come together (both None: no rotation)" % (who, names.replace(" / ", " and ")))
+    for t in angles:
+        if (need_angles or t is not None) and not (t is not None and _is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+                                                   and t.numel() == rh_u.n_dst):
+            raise ValueError("%s: %s must be contiguous float64 CUDA tensors of n_dst = %d elements" % (who, names, rh_u.n_dst))
+    outs = tuple(outs) if outs is not None else (None,) * nout
+    if len(outs) != nout:
+        raise ValueError(who + ": outs must hold %d tensor(s)" % nout)
+    given = [t for t in outs if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
+    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+    shape = (nlev, rh_u.n_dst) if layout == LAYOUT_CELL_FAST else (rh_u.n_dst, nlev)
+    res = [t if t is not None else torch.empty(shape, dtype=out_dtype, device=u.device) for t in outs]
+    for t in res:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh_u.n_dst):
+            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh_u.n_dst))
+    if ACCOUNT is not None:     # L (U_u + U_v) e_s + n_out P L e_d + P (2 NNZ 12 + 16): both sources read once, every result written once,
+        for rh in (rh_u, rh_v):  # the indices and weights of both handles and the angles (when given) once
+            if getattr(rh, "_acc_U", None) is None:
+                rh._acc_U = int(rh.unique_sources().size)
+        ACCOUNT.append(("%s nnz%d L%d%s" % (who, rh_u.nnz_per_row, nlev, label),
+                        nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + nout * rh_u.n_dst * nlev * res[0].element_size()
+                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + (16 if angles[0] is not None else 0))))
+
+    def p(t):
+        return t.data_ptr() if t is not None else None
+    check(call(rh_u._h, rh_v._h, p(angles[0]), p(angles[1]), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv, int(nlev),
+               res[0].data_ptr(), p(res[1] if nout == 2 else None), int(out_dtype == torch.float32), int(layout),
+               torch.cuda.current_stream().cuda_stream))
+    return tuple(res)
+
+
 def wind_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, outs=None):
     """mpg_wind_to_mesh_dev: the wind chain turned round, in one pass -- U through rh_u and V through rh_v onto the SAME mesh points (the
     typical pair: regrid_store_to_mesh(grid, mesh, staggerloc=STAGGERLOC_EDGE1 / STAGGERLOC_EDGE2); rh_u is rh_v is allowed), then the
@@ -1093,42 +1135,7 @@ def wind_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST, ou
     plane-pitched views (nlev, ny, nx) as empty_pitched and wind_destagger(outs=) make.  Returns (ue, ve) of out_dtype (default: u's):
     (nlev, n_dst) for LAYOUT_CELL_FAST, (n_dst, nlev) for LAYOUT_LEV_FAST -- MPAS file order; a point either handle leaves unmapped is
     +0.0 in both.  outs=(ue, ve): contiguous CUDA tensors of nlev * n_dst elements to write into.  Bit-identical to the separate calls."""
-    import torch
-    who = "wind_to_mesh"
-    ldu, ldv = _wind_source(u, rh_u, nlev, who), _wind_source(v, rh_v, nlev, who)
-    if u.dtype != v.dtype:
-        raise ValueError(who + ": u and v must have one dtype")
-    if (cosa is None) != (sina is None):
-        raise ValueError(who + ": cosa and sina come together (both None: no rotation)")
-    for t in (cosa, sina):
-        if t is not None and not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == rh_u.n_dst):
-            raise ValueError(who + ": cosa / sina must be contiguous float64 CUDA tensors of n_dst = %d elements" % rh_u.n_dst)
-    given = [t for t in (outs or ()) if t is not None]
-    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
-    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
-        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
-    shape = (nlev, rh_u.n_dst) if layout == LAYOUT_CELL_FAST else (rh_u.n_dst, nlev)
-    ue, ve = outs if outs is not None else (None, None)
-    if ue is None:
-        ue = torch.empty(shape, dtype=out_dtype, device=u.device)
-    if ve is None:
-        ve = torch.empty(shape, dtype=out_dtype, device=u.device)
-    for t in (ue, ve):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh_u.n_dst):
-            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh_u.n_dst))
-    if ACCOUNT is not None:     # L (U_u + U_v) e_s + 2 P L e_d + P (2 NNZ 12 + 16): both sources read once, both results written once, the
-        for rh in (rh_u, rh_v):  # indices and weights of both handles and the angles once
-            if getattr(rh, "_acc_U", None) is None:
-                rh._acc_U = int(rh.unique_sources().size)
-        ACCOUNT.append(("wind_to_mesh nnz%d L%d" % (rh_u.nnz_per_row, nlev),
-                        nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + 2 * rh_u.n_dst * nlev * ue.element_size()
-                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + (16 if cosa is not None else 0))))
-
-    def p(t):
-        return t.data_ptr() if t is not None else None
-    check(L.wind_to_mesh_dev(rh_u._h, rh_v._h, p(cosa), p(sina), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv, int(nlev),
-                             ue.data_ptr(), ve.data_ptr(), int(out_dtype == torch.float32), int(layout), torch.cuda.current_stream().cuda_stream))
-    return ue, ve
+    return _wind_pair("wind_to_mesh", L.wind_to_mesh_dev, rh_u, rh_v, (cosa, sina), "cosa / sina", False, u, v, nlev, layout, out_dtype, outs, 2)
 
 
 def mesh_rotang(grid, mesh, meshloc=MESHLOC_ELEMENT):
@@ -1152,6 +1159,27 @@ def _unmapped_mask(rh):
     return rh._unmapped_dev
 
 
+def _wind_pair_backward(ctx, grads, turn):
+    """The backward both wind ops share: the incoming gradients back to [lev][point] planes, zeroed where either handle leaves the point
+    unmapped, turned by the op's transposed rotation `turn` into (g_a, g_b), and each handle's regrid_transpose in its input's shape."""
+    n, nlev = ctx.rh_u.n_dst, ctx.nlev
+
+    def planes(g):            # regrid_transpose reads [nlev][n_dst] planes
+        if ctx.layout == LAYOUT_LEV_FAST:
+            g = g.reshape(n, nlev).t()
+        return g.reshape(nlev, n)
+    # a point unmapped in EITHER handle is a constant of the forward: without this a point mapped in one handle only would send
+    # its gradient through that handle's transpose, a term the forward does not have
+    un = _unmapped_mask(ctx.rh_u)
+    if ctx.rh_v is not ctx.rh_u:
+        un = un | _unmapped_mask(ctx.rh_v)
+    g_a, g_b = turn(*[planes(g).masked_fill(un, 0.0) for g in grads])
+    # two separate gradients even when rh_u is rh_v: one of u, one of v
+    gu = ctx.rh_u.regrid_transpose(g_a.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[0])
+    gv = ctx.rh_v.regrid_transpose(g_b.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[1])
+    return gu.reshape(ctx.shapes[0]), gv.reshape(ctx.shapes[1])
+
+
 if _torch is not None:
     class WindToMeshFunction(_torch.autograd.Function):
         """wind_to_mesh with a gradient: forward is wind_to_mesh in u's dtype; backward takes (g_ue, g_ve) back to [lev][cell], zeroes
@@ -1166,25 +1194,12 @@ if _torch is not None:
 
         @staticmethod
         def backward(ctx, g_ue, g_ve):
-            n, nlev = ctx.rh_u.n_dst, ctx.nlev
-            if ctx.layout == LAYOUT_LEV_FAST:     # regrid_transpose reads [nlev][n_dst] planes
-                g_ue, g_ve = g_ue.reshape(n, nlev).t(), g_ve.reshape(n, nlev).t()
-            g_ue, g_ve = g_ue.reshape(nlev, n), g_ve.reshape(nlev, n)
-            # a point unmapped in EITHER handle is a constant of the forward: without this a point mapped in one handle only would send
-            # its gradient through that handle's transpose, a term the forward does not have
-            un = _unmapped_mask(ctx.rh_u)
-            if ctx.rh_v is not ctx.rh_u:
-                un = un | _unmapped_mask(ctx.rh_v)
-            g_ue, g_ve = g_ue.masked_fill(un, 0.0), g_ve.masked_fill(un, 0.0)
-            if ctx.cosa is not None:
+            def turn(g_ue, g_ve):
+                if ctx.cosa is None:
+                    return g_ue, g_ve
                 ca, sa = ctx.cosa.to(g_ue.dtype), ctx.sina.to(g_ue.dtype)
-                g_a, g_b = g_ue * ca + g_ve * sa, g_ve * ca - g_ue * sa
-            else:
-                g_a, g_b = g_ue, g_ve
-            # two separate gradients even when rh_u is rh_v: one of u, one of v
-            gu = ctx.rh_u.regrid_transpose(g_a.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[0])
-            gv = ctx.rh_v.regrid_transpose(g_b.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[1])
-            return gu.reshape(ctx.shapes[0]), gv.reshape(ctx.shapes[1]), None, None, None, None, None, None
+                return g_ue * ca + g_ve * sa, g_ve * ca - g_ue * sa
+            return _wind_pair_backward(ctx, (g_ue, g_ve), turn) + (None,) * 6
 
 
 def wind_to_mesh_autograd(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST):
@@ -1221,42 +1236,12 @@ def wind_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, out_d
     u's): (nlev, n_dst) for LAYOUT_CELL_FAST, (n_dst, nlev) for LAYOUT_LEV_FAST -- the file order of u(nEdges, nVertLevels); a point
     either handle leaves unmapped is +0.0.  outs: the tensor (tangential: the pair) to write into, contiguous, nlev * n_dst elements.
     Bit-identical to the separate calls."""
-    import torch
-    who = "wind_to_edges"
-    ldu, ldv = _wind_source(u, rh_u, nlev, who), _wind_source(v, rh_v, nlev, who)
-    if u.dtype != v.dtype:
-        raise ValueError(who + ": u and v must have one dtype")
-    for t in (cn, sn):
-        if not (t is not None and _is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == rh_u.n_dst):
-            raise ValueError(who + ": cn / sn must be contiguous float64 CUDA tensors of n_dst = %d elements" % rh_u.n_dst)
     nout = 2 if tangential else 1
-    if outs is None:
-        outs = (None,) * nout
-    elif _is_torch(outs):
+    if _is_torch(outs):
         outs = (outs,)
-    outs = tuple(outs)
-    if len(outs) != nout:
-        raise ValueError(who + ": outs must hold %d tensor(s)" % nout)
-    given = [t for t in outs if t is not None]
-    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
-    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
-        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
-    shape = (nlev, rh_u.n_dst) if layout == LAYOUT_CELL_FAST else (rh_u.n_dst, nlev)
-    res = [t if t is not None else torch.empty(shape, dtype=out_dtype, device=u.device) for t in outs]
-    for t in res:
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh_u.n_dst):
-            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh_u.n_dst))
-    if ACCOUNT is not None:     # L (U_u + U_v) e_s + n_out P L e_d + P (2 NNZ 12 + 16): both sources read once, every result written once,
-        for rh in (rh_u, rh_v):  # the indices and weights of both handles and the angles once
-            if getattr(rh, "_acc_U", None) is None:
-                rh._acc_U = int(rh.unique_sources().size)
-        ACCOUNT.append(("wind_to_edges nnz%d L%d x%d" % (rh_u.nnz_per_row, nlev, nout),
-                        nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + nout * rh_u.n_dst * nlev * res[0].element_size()
-                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + 16)))
-    check(L.wind_to_edges_dev(rh_u._h, rh_v._h, cn.data_ptr(), sn.data_ptr(), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv,
-                              int(nlev), res[0].data_ptr(), res[1].data_ptr() if tangential else None, int(out_dtype == torch.float32), int(layout),
-                              torch.cuda.current_stream().cuda_stream))
-    return (res[0], res[1]) if tangential else res[0]
+    res = _wind_pair("wind_to_edges", L.wind_to_edges_dev, rh_u, rh_v, (cn, sn), "cn / sn", True, u, v, nlev, layout, out_dtype, outs, nout,
+                     label=" x%d" % nout)
+    return res if tangential else res[0]
 
 
 if _torch is not None:
@@ -1273,28 +1258,12 @@ if _torch is not None:
 
         @staticmethod
         def backward(ctx, g_un, g_ut=None):
-            n, nlev = ctx.rh_u.n_dst, ctx.nlev
-
-            def planes(g):            # regrid_transpose reads [nlev][n_dst] planes
-                if ctx.layout == LAYOUT_LEV_FAST:
-                    g = g.reshape(n, nlev).t()
-                return g.reshape(nlev, n)
-            # a point unmapped in EITHER handle is a constant of the forward: without this a point mapped in one handle only would send
-            # its gradient through that handle's transpose, a term the forward does not have
-            un = _unmapped_mask(ctx.rh_u)
-            if ctx.rh_v is not ctx.rh_u:
-                un = un | _unmapped_mask(ctx.rh_v)
-            g_un = planes(g_un).masked_fill(un, 0.0)
-            cn, sn = ctx.cn.to(g_un.dtype), ctx.sn.to(g_un.dtype)
-            if ctx.tangential:
-                g_ut = planes(g_ut).masked_fill(un, 0.0)
-                g_a, g_b = g_un * cn - g_ut * sn, g_un * sn + g_ut * cn
-            else:
-                g_a, g_b = g_un * cn, g_un * sn
-            # two separate gradients even when rh_u is rh_v: one of u, one of v
-            gu = ctx.rh_u.regrid_transpose(g_a.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[0])
-            gv = ctx.rh_v.regrid_transpose(g_b.contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[1])
-            return gu.reshape(ctx.shapes[0]), gv.reshape(ctx.shapes[1]), None, None, None, None, None, None, None
+            def turn(g_un, g_ut=None):
+                cn, sn = ctx.cn.to(g_un.dtype), ctx.sn.to(g_un.dtype)
+                if g_ut is None:
+                    return g_un * cn, g_un * sn
+                return g_un * cn - g_ut * sn, g_un * sn + g_ut * cn
+            return _wind_pair_backward(ctx, (g_un, g_ut) if ctx.tangential else (g_un,), turn) + (None,) * 7
 
 
 def wind_to_edges_autograd(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, tangential=False):

@@ -71,7 +71,7 @@ def test_lib_lists_binds_and_exports_them():
     for name in ARGS:
         assert name in _lib.SYMBOLS
     assert _lib.MESHLOC_EDGE == 2
-    assert "k_wind_to_edges.hip" in build.SOURCES
+    assert "k_wind_pair.hip" in build.SOURCES
     build.build()
     lib = _lib.load()
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True).stdout

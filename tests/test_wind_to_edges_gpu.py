@@ -14,13 +14,14 @@ import dataclasses
 import numpy as np
 import pytest
 
+from _wind_pair_helpers import _bytes_equal, _pitched, _unmapped, _winds
 from conftest import LAMBERT
 
 pytestmark = pytest.mark.gpu
 
 # [edge][lev] results leave through ONE LDS tile of at most 64 KB with an odd row stride when only un is asked (apply_mesh.h am_tile_plan:
 # all levels in the tile up to 127 float64 / 255 float32 levels, level chunks beyond), through TWO tiles of half the cap each with ut
-# (am_tile_plan_pair: 63 / 127)
+# (am_tile_plan with two tiles: 63 / 127)
 SINGLE_EDGE = {"f64": (127, 128, 129), "f32": (255, 256, 257)}
 PAIR_EDGE = {"f64": (63, 64), "f32": (127, 128)}
 
@@ -54,28 +55,6 @@ def case(gpu_lib):
         d[k].release()
     for k in ("mesh_over", "mesh_in", "ga"):
         d[k].destroy()
-
-
-def _unmapped(torch, rh_u, rh_v):
-    """the points either handle leaves unmapped, as a CUDA mask"""
-    un = (rh_u.weights()[0][:, 0] < 0) | (rh_v.weights()[0][:, 0] < 0)
-    return torch.as_tensor(un, device="cuda")
-
-
-def _bytes_equal(a, b):
-    import torch
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    bits = torch.int64 if a.dtype == torch.float64 else torch.int32       # compared as integers: -0.0 is not +0.0, NaN equals itself
-    return torch.equal(a.contiguous().reshape(-1).view(bits), b.contiguous().reshape(-1).view(bits))
-
-
-def _winds(torch, rh_u, rh_v, nlev, sdt, seed):
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(seed)
-    u = (torch.randn((nlev, rh_u.n_src), dtype=torch.float64, device="cuda", generator=gen) * 12.0).to(sdt)
-    v = (torch.randn((nlev, rh_v.n_src), dtype=torch.float64, device="cuda", generator=gen) * 12.0).to(sdt)
-    return u, v
 
 
 def _chain(torch, rh_u, rh_v, rot, un, u, v, nlev, ddt):
@@ -378,12 +357,6 @@ def test_sign(case):
 
 
 # ---- sources, bands, capture --------------------------------------------------------------------------------------------------------
-def _pitched(torch, nlev, ny, nx, dt, ld):
-    """a NaN-filled buffer and its (nlev, ny, nx) view with level planes ld elements apart"""
-    buf = torch.full((nlev * ld,), float("nan"), dtype=dt, device="cuda")
-    return buf, buf.as_strided((nlev, ny, nx), (ld, nx, 1))
-
-
 @pytest.mark.parametrize("dt", ["f64", "f32"])
 def test_pitched_sources(case, dt):
     """U and V in plane-pitched views whose pad is NaN go into the call as they are: the bytes of the dense call, and no NaN."""

@@ -62,7 +62,7 @@ def test_header_states_the_rule():
 def test_lib_lists_binds_and_exports_them():
     from mpassit_amd import _lib, build
     assert WIND in _lib.SYMBOLS and ROTANG in _lib.SYMBOLS
-    assert "k_wind_to_mesh.hip" in build.SOURCES
+    assert "k_wind_pair.hip" in build.SOURCES
     build.build()
     lib = _lib.load()
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True).stdout

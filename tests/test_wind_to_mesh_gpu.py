@@ -9,12 +9,13 @@ The case is that of tests/test_to_mesh_gpu.py: a 60 x 40 Lambert grid built from
 import numpy as np
 import pytest
 
+from _wind_pair_helpers import _bytes_equal, _pitched, _unmapped, _winds
 from conftest import LAMBERT
 
 pytestmark = pytest.mark.gpu
 
 # [cell][lev] results leave through two LDS tiles that share the 64 KB tile cap: all levels in one pair of tiles up to 63 (float64) /
-# 127 (float32) levels, level chunks from 64 / 128 on (apply_mesh.h am_tile_plan_pair)
+# 127 (float32) levels, level chunks from 64 / 128 on (apply_mesh.h am_tile_plan with two tiles)
 CHUNK_EDGE = {"f64": (63, 64), "f32": (127, 128)}
 
 
@@ -38,28 +39,6 @@ def case(gpu_lib):
         d[k].release()
     for k in ("mesh_over", "mesh_in", "ga"):
         d[k].destroy()
-
-
-def _unmapped(torch, rh_u, rh_v):
-    """the points either handle leaves unmapped, as a CUDA mask"""
-    un = (rh_u.weights()[0][:, 0] < 0) | (rh_v.weights()[0][:, 0] < 0)
-    return torch.as_tensor(un, device="cuda")
-
-
-def _bytes_equal(a, b):
-    import torch
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    bits = torch.int64 if a.dtype == torch.float64 else torch.int32       # compared as integers: -0.0 is not +0.0, NaN equals itself
-    return torch.equal(a.contiguous().reshape(-1).view(bits), b.contiguous().reshape(-1).view(bits))
-
-
-def _winds(torch, rh_u, rh_v, nlev, sdt, seed):
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(seed)
-    u = (torch.randn((nlev, rh_u.n_src), dtype=torch.float64, device="cuda", generator=gen) * 12.0).to(sdt)
-    v = (torch.randn((nlev, rh_v.n_src), dtype=torch.float64, device="cuda", generator=gen) * 12.0).to(sdt)
-    return u, v
 
 
 def _chain(torch, rh_u, rh_v, rot, un, u, v, nlev, ddt):
@@ -136,6 +115,28 @@ def test_no_rotation(case, types):
     bits = torch.int64 if ddt == torch.float64 else torch.int32
     assert (ue[:, un].contiguous().view(bits) == 0).all() and (ve[:, un].contiguous().view(bits) == 0).all(), "+0.0 where either is unmapped"
     assert (a[:, un] != 0).any() or (b[:, un] != 0).any(), "some point is mapped in one handle only"
+
+
+def test_edges_call_with_minus_sina_is_the_cells_call(case):
+    """The policies of the one kernel tied together on the cell handles: wind_to_edges with (ca, -sa) and the tangential component is
+    wind_to_mesh with (ca, sa) BIT FOR BIT -- un = a ca + b (-sa) is ue = a ca - b sa and ut = b ca - a (-sa) is ve = a sa + b ca, exact in
+    IEEE arithmetic (b * (-s) == -(b * s), x + (-y) == x - y, b * c + a * s == a * s + b * c) -- and the normal-only call gives the un of
+    the tangential one.  Both layouts, below and in the level chunks of the pair, float32 and float64 sources."""
+    import torch
+    from mpassit_amd import regrid as R
+    rh_u, rh_v, (ca, sa) = case["u_over"], case["v_over"], case["rot_over"]
+    msa = -sa
+    for sdt in (torch.float32, torch.float64):
+        for nlev in (3, 64):
+            u, v = _winds(torch, rh_u, rh_v, nlev, sdt, 800 + nlev)
+            for layout in (R.LAYOUT_CELL_FAST, R.LAYOUT_LEV_FAST):
+                ue, ve = R.wind_to_mesh(rh_u, rh_v, ca, sa, u, v, nlev, layout=layout, out_dtype=torch.float32)
+                un, ut = R.wind_to_edges(rh_u, rh_v, ca, msa, u, v, nlev, layout=layout, out_dtype=torch.float32, tangential=True)
+                assert _bytes_equal(un, ue), "un of (ca, -sa) is not ue (layout %d, %d levels, %s)" % (layout, nlev, sdt)
+                assert _bytes_equal(ut, ve), "ut of (ca, -sa) is not ve (layout %d, %d levels, %s)" % (layout, nlev, sdt)
+                alone = R.wind_to_edges(rh_u, rh_v, ca, msa, u, v, nlev, layout=layout, out_dtype=torch.float32)
+                assert _bytes_equal(alone, un), "un alone is not the un of the pair (layout %d, %d levels, %s)" % (layout, nlev, sdt)
+            assert float(ue.abs().max()) > 1 and float(ve.abs().max()) > 1 and not _bytes_equal(ue, ve)
 
 
 def test_nearest_pair_and_one_handle_twice(case):
@@ -231,12 +232,6 @@ def test_mesh_rotang(case, gpu_lib):
     refused(L.mesh_rotang_dev(None, case["mesh_in"]._h, 0, out.data_ptr(), out.data_ptr(), None), L.MPG_ERR_INVALID_ARG)
     assert L.mesh_rotang_dev(*args(ga, case["mesh_in"])) == 0
     torch.cuda.synchronize()
-
-
-def _pitched(torch, nlev, ny, nx, dt, ld):
-    """a NaN-filled buffer and its (nlev, ny, nx) view with level planes ld elements apart (RouteHandle.empty_pitched with a given stride)"""
-    buf = torch.full((nlev * ld,), float("nan"), dtype=dt, device="cuda")
-    return buf, buf.as_strided((nlev, ny, nx), (ld, nx, 1))
 
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])
