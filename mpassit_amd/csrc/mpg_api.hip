@@ -7,10 +7,6 @@
 #include <string.h>
 #include <time.h>
 
-#include <condition_variable>
-#include <deque>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -22,16 +18,16 @@ static thread_local char g_err[1024] = "";
 static bool g_init = false;
 static int g_device = -1;
 static hipStream_t g_stream = nullptr;
-static std::map<HandleKey, mpg_handle_s *> g_cache;
-// Released handles stay in the cache ("parked", refcount 0) until their mesh or grid is destroyed, the library is finalized
-// or more than MPG_MAX_PARKED of them wait: the reference stores the SAME element -> CENTER bilinear weights in
+// Released handles stay in the cache ("parked", refcount 0; StoreCache, store_cache.h) until their mesh or grid is destroyed, the
+// library is finalized or more than MPG_MAX_PARKED of them wait: the reference stores the SAME element -> CENTER bilinear weights in
 // interp_diag_data and again in interp_hist_data with a release in between (interp.F90:123,148 and :207), and a second
-// mpg_regrid_store of a released 5-tuple was a second run of the rasteriser (r02j: 2 x k_tri_raster in one job).
+// mpg_regrid_store of a released key was a second run of the rasteriser (r02j: 2 x k_tri_raster in one job).
 #define MPG_MAX_PARKED 8
-static uint64_t g_park_clock = 0;
-// The cache is shared with the Store worker below (it inserts finished handles): every walk, lookup and change holds this lock.
-static std::recursive_mutex g_cache_mu;
-#define CACHE_LOCK() std::lock_guard<std::recursive_mutex> cache_lock_(g_cache_mu)
+static void handle_free(mpg_handle_s *h);
+static StoreCache<mpg_handle_s> &cache() {   // on the heap, never destroyed: the Store worker below holds a reference to it
+  static StoreCache<mpg_handle_s> *c = new StoreCache<mpg_handle_s>(handle_free, MPG_MAX_PARKED);
+  return *c;
+}
 static void store_worker_drain();   // below: every queued / running Store has finished when this returns
 static void store_worker_stop();
 static int store_worker_start(int device);
@@ -46,13 +42,7 @@ bool mpg_is_initialized() { return g_init; }
 hipStream_t mpg_setup_stream() { return g_stream; }
 int mpg_device_index() { return g_device; }
 
-void mpg_cache_detach(mpg_handle_s *h) {
-  CACHE_LOCK();
-  if (h->cached) {
-    g_cache.erase(h->key);
-    h->cached = false;
-  }
-}
+void mpg_cache_detach(mpg_handle_s *h) { cache().detach(h); }
 
 // ---- cache of temporary device blocks (TmpBuf::alloc(count, stream), mpg_internal.h) ------------------------------------
 namespace {
@@ -186,10 +176,8 @@ static void warm_join() {   // mpg_finalize, and atexit (registered after the HI
 
 // Everything the library holds only as a cache goes back to the driver: parked handles, scratch blocks.  Called when an
 // allocation fails, before it is tried once more (DevBuf::alloc, mpg_dev_alloc).
-static void drop_parked(void *obj);
-static bool g_cache_busy = false;   // a caller is walking g_cache (mpg_mesh_set_source_window): its entries must stay
 void mpg_release_caches() {
-  if (!g_cache_busy) drop_parked(nullptr);
+  if (!cache().busy()) cache().drop_parked();
   mpg_pool_release();
 }
 
@@ -248,25 +236,11 @@ int mpg_warmup_wait(void) {
   return MPG_SUCCESS;
 }
 
-static void handle_free(mpg_handle_s *h);
-static void drop_parked(void *obj) {   // obj == nullptr: all of them
-  CACHE_LOCK();
-  for (auto it = g_cache.begin(); it != g_cache.end();) {
-    mpg_handle_s *h = it->second;
-    if (h->refcount == 0 && (!obj || std::get<0>(it->first) == obj || std::get<2>(it->first) == obj)) {
-      it = g_cache.erase(it);
-      handle_free(h);
-    } else {
-      ++it;
-    }
-  }
-}
-
 int mpg_finalize(void) {
   if (!g_init) return MPG_SUCCESS;
   warm_join();
   store_worker_stop();
-  drop_parked(nullptr);
+  cache().drop_parked();
   mpg_fileio_release();
   mpg_hostpipe_release();
   (void)hipStreamSynchronize(g_stream);
@@ -325,6 +299,7 @@ int mpg_mesh_create_window(int64_t nCells, int64_t nVertices, int maxEdges, cons
   m->maxEdges = maxEdges;
   m->geo_grid = grid;
   g_meshes.push_back(m);
+  store_worker_drain();   // mpg_k_mesh_window builds and reads grid->pyr[] / cellpyr: a begun Store on this grid builds them on the worker
   if ((rc = mpg_k_mesh_coords(nCells, lonCell, latCell, m->cell, g_stream)) ||
       (rc = mpg_k_mesh_window(m, grid, latVertex, lonVertex, verticesOnCell, g_stream))) {
     mpg_mesh_destroy(m);
@@ -383,16 +358,7 @@ int mpg_mesh_create(int64_t nCells, int64_t nVertices, int maxEdges, const doubl
 // handles outlive neither their mesh nor their grid in the cache: a recycled address must never hit
 static void cache_purge(void *obj) {
   store_worker_drain();   // a Store in flight reads the mesh and the grid it was started on
-  CACHE_LOCK();
-  drop_parked(obj);
-  for (auto it = g_cache.begin(); it != g_cache.end();) {
-    if (std::get<0>(it->first) == obj || std::get<2>(it->first) == obj) {
-      it->second->cached = false;
-      it = g_cache.erase(it);
-    } else {
-      ++it;
-    }
-  }
+  cache().purge(obj);
 }
 
 int mpg_mesh_destroy(mpg_mesh m) {
@@ -457,6 +423,7 @@ int mpg_mesh_set_edges(mpg_mesh m, int64_t nEdges, const double *latEdge, const 
     ang.free();
     return rc;
   }
+  // (no drain: a Store onto edges is refused until they are set and they are set once, so no begun Store reads m->edge)
   m->edge = pts;
   m->angle_edge = ang;
   return MPG_SUCCESS;
@@ -569,6 +536,7 @@ int mpg_grid_attach_proj(mpg_grid g, const mpg_proj *proj, int row0) {
   MPG_CHECK_INIT();
   MPG_ARG(g && proj, "mpg_grid_attach_proj: NULL argument");
   MPG_ARG(row0 >= 0, "mpg_grid_attach_proj: row0 must be >= 0");
+  store_worker_drain();   // a begun Store on this grid reads g->proj / has_inverse to choose its candidate search
   return mpg_k_attach_proj(g, proj, row0, g_stream);
 }
 
@@ -684,14 +652,20 @@ static void handle_free(mpg_handle_s *h) {
   delete h;
 }
 
-struct StoreCtx {
-  mpg_mesh_s *m;
-  mpg_grid_s *g;
-  int stagger;
-  int method;
-  int meshloc;
-  mpg_mesh_s *dst_mesh = nullptr;   // Mesh -> Mesh Store: the destination mesh (g is nullptr, `stagger` its location)
+struct StoreCtx {   // what a Store's build reads: the key's objects, typed by what its kind says they are
+  mpg_mesh_s *src_mesh = nullptr, *dst_mesh = nullptr;
+  mpg_grid_s *src_grid = nullptr, *dst_grid = nullptr;
+  int src_loc, dst_loc;   // MPG_MESHLOC_* of a mesh, MPG_STAGGERLOC_* of a grid
+  int method, pole_method, norm_type;
+  explicit StoreCtx(const StoreKey &k) : src_loc(k.src_loc), dst_loc(k.dst_loc), method(k.method), pole_method(k.pole_method), norm_type(k.norm_type) {
+    if (k.source_is_mesh()) src_mesh = (mpg_mesh_s *)k.src;
+    else src_grid = (mpg_grid_s *)k.src;
+    if (k.kind == STORE_MESH_TO_GRID || k.kind == STORE_GRID_TO_GRID) dst_grid = (mpg_grid_s *)k.dst;
+    else dst_mesh = (mpg_mesh_s *)k.dst;
+  }
 };
+typedef int (*StoreBuildFn)(mpg_handle_s *, const StoreCtx &, hipStream_t);
+static StoreBuildFn store_build_fn(StoreKind kind);   // below, after the seven builds
 
 // ---- the Store worker -------------------------------------------------------------------------------------------------
 // interp.F90:207-437 stores its weight sets one after the other, each in front of the Regrids that use it; they are
@@ -701,39 +675,27 @@ struct StoreCtx {
 // While the worker builds the conservative and nearest-neighbour weights (3 of the 4.6 ms of configuration 4's Stores,
 // compute-bound kernels) the caller's thread is already issuing the bilinear Regrids (HBM-bound) on ITS stream.  One
 // Store at a time: the lazily built search structures of a mesh / grid (pyramids, BVH, fans) are only ever touched by this
-// thread.  The weights do not depend on which thread builds them.
-struct StoreJob {
-  HandleKey key;
-  int (*build)(mpg_handle_s *, void *, hipStream_t);
-  StoreCtx ctx;
+// thread, or by an entry point that has drained it first (mpg_mesh_create_window; DESIGN.md lists the entries).  The weights do not
+// depend on which thread builds them.  The key, the cache and the queue are store_cache.h.
+struct StoreWork {
   hipEvent_t ready = nullptr;   // recorded on the set-up stream when the job was queued: the mesh / grid uploads and kernels issued there come first
-  bool done = false;
-  int rc = MPG_SUCCESS;
-  char err[1024] = "";
-  ~StoreJob() {
+  ~StoreWork() {
     if (ready) (void)hipEventDestroy(ready);
   }
 };
+typedef StoreQueue<mpg_handle_s, StoreWork> StoreWorker;
+static int store_build_now(StoreWorker::Job &job, void *stream);
 // The worker's state lives on the heap and is never destroyed: a process that ends without mpg_finalize (a Fortran `stop`, an error exit)
 // must not run the destructor of a condition variable the worker is waiting on (that blocks for ever).
-struct StoreWorker {
-  std::mutex mu, start_mu;
-  std::condition_variable cv;
-  std::deque<std::shared_ptr<StoreJob>> queue;
-  std::map<HandleKey, std::shared_ptr<StoreJob>> pending;   // queued or running
-  std::thread *thread = nullptr;
-  hipStream_t stream = nullptr;
-  bool stop = false;
-};
 static StoreWorker &SW() {
-  static StoreWorker *w = new StoreWorker();
+  static StoreWorker *w = new StoreWorker(cache(), store_build_now);
   return *w;
 }
-static const char *mpg_last_error_cstr() { return g_err; }
 
-static int store_build_now(StoreJob &job, hipStream_t s) {
+static int store_build(StoreWorker::Job &job, hipStream_t s) {
   mpg_handle_s *h = new mpg_handle_s();
   h->refcount = 0;   // nobody holds it yet: parked in the cache until a mpg_regrid_store collects it
+  h->method = job.key.method;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
     mpg_set_error("hipEventCreate failed in a RegridStore");
@@ -741,7 +703,7 @@ static int store_build_now(StoreJob &job, hipStream_t s) {
     return MPG_ERR_HIP;
   }
   (void)hipEventRecord(e0, s);
-  int rc = job.build(h, &job.ctx, s);
+  int rc = store_build_fn(job.key.kind)(h, StoreCtx(job.key), s);
   if (!rc) {
     hipError_t e = hipEventRecord(e1, s);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
@@ -757,140 +719,69 @@ static int store_build_now(StoreJob &job, hipStream_t s) {
     handle_free(h);
     return rc;
   }
-  CACHE_LOCK();
-  h->key = job.key;
-  h->cached = true;
-  h->parked_at = ++g_park_clock;
-  g_cache[job.key] = h;
+  job.handle = h;   // the worker parks it in the cache and leaves `pending` in one step (StoreQueue::run)
   return MPG_SUCCESS;
 }
-
-static void store_worker_main(int device) {
-  // a worker that cannot bind its device keeps serving the queue -- with the error: a thread that simply left would make every later
-  // RegridStore wait for ever on a job nobody runs
-  const hipError_t dev_err = hipSetDevice(device);
-  for (;;) {
-    std::shared_ptr<StoreJob> job;
-    {
-      std::unique_lock<std::mutex> lk(SW().mu);
-      SW().cv.wait(lk, [] { return SW().stop || !SW().queue.empty(); });
-      if (SW().queue.empty()) return;   // stop asked and nothing left
-      job = SW().queue.front();
-      SW().queue.pop_front();
-    }
-    g_err[0] = 0;
-    int rc;
-    if (dev_err != hipSuccess) {
-      mpg_set_error("RegridStore: the Store worker could not bind device %d: %s", device, hipGetErrorString(dev_err));
-      rc = MPG_ERR_HIP;
-    } else {
-      if (job->ready) (void)hipStreamWaitEvent(SW().stream, job->ready, 0);
-      rc = store_build_now(*job, SW().stream);
-    }
-    {
-      std::lock_guard<std::mutex> lk(SW().mu);
-      job->rc = rc;
-      if (rc) snprintf(job->err, sizeof(job->err), "%s", mpg_last_error_cstr());
-      job->done = true;
-      SW().pending.erase(job->key);
-    }
-    SW().cv.notify_all();
-  }
+static int store_build_now(StoreWorker::Job &job, void *stream) {   // on the worker's thread; a failed job carries its error text
+  g_err[0] = 0;
+  if (job.work.ready) (void)hipStreamWaitEvent((hipStream_t)stream, job.work.ready, 0);
+  const int rc = store_build(job, (hipStream_t)stream);
+  if (rc) job.err = g_err;
+  return rc;
 }
 
 static int store_worker_start(int device) {   // mpg_init's helper thread starts it; a Store that comes first starts it itself
-  std::lock_guard<std::mutex> lk(SW().start_mu);
-  if (SW().thread) return MPG_SUCCESS;
-  MPG_HIP(hipStreamCreateWithFlags(&SW().stream, hipStreamNonBlocking));
-  SW().stop = false;
-  SW().thread = new std::thread(store_worker_main, device);
+  return SW().start(
+      [](void **stream) -> int {
+        MPG_HIP(hipStreamCreateWithFlags((hipStream_t *)stream, hipStreamNonBlocking));
+        return MPG_SUCCESS;
+      },
+      [device](std::string &err) -> int {
+        const hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) return MPG_SUCCESS;
+        mpg_set_error("RegridStore: the Store worker could not bind device %d: %s", device, hipGetErrorString(e));
+        err = g_err;
+        return MPG_ERR_HIP;
+      });
+}
+static void store_worker_drain() { SW().drain(); }
+static void store_worker_stop() {   // mpg_finalize
+  if (void *stream = SW().stop()) (void)hipStreamDestroy((hipStream_t)stream);
+}
+
+// out == nullptr: start the Store and return (mpg_regrid_store[_grid]_begin); else return the handle, waiting for its Store.  In use
+// elsewhere, or parked by an earlier release / a finished _begin: the same weights, no device work.
+static int store_common(const StoreKey &key, mpg_handle *out) {
+  int rc = store_worker_start(g_device);
+  if (rc) return rc;
+  std::string err;
+  rc = SW().get(key, out, [](StoreWorker::Job &job) {
+    if (hipEventCreateWithFlags(&job.work.ready, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(job.work.ready, g_stream);
+  }, &err);
+  if (rc) {
+    mpg_set_error("%s", err.c_str());
+    return rc;
+  }
+  if (out && !*out) {   // a flood of releases has pushed the finished handle out again, twice
+    mpg_set_error("RegridStore: the finished handle left the cache before it was collected");
+    return MPG_ERR_HIP;
+  }
   return MPG_SUCCESS;
 }
 
-static void store_worker_drain() {
-  std::unique_lock<std::mutex> lk(SW().mu);
-  SW().cv.wait(lk, [] { return SW().pending.empty(); });
+// the source mesh's points are windowed (mpg_mesh_set_source_window): a new handle indexes relative to the window from the start
+static int rebase_to_window(mpg_handle_s *h, const mpg_mesh_s *m, int loc, hipStream_t s) {
+  return m->win_count[loc] >= 0 ? mpg_k_rebase(h, m->win_first[loc], m->win_count[loc], s, true) : (int)MPG_SUCCESS;
 }
-
-static void store_worker_stop() {   // mpg_finalize
-  if (!SW().thread) return;
-  store_worker_drain();
-  {
-    std::lock_guard<std::mutex> lk(SW().mu);
-    SW().stop = true;
-  }
-  SW().cv.notify_all();
-  SW().thread->join();
-  delete SW().thread;
-  SW().thread = nullptr;
-  (void)hipStreamDestroy(SW().stream);
-  SW().stream = nullptr;
-}
-
-// out == nullptr: start the Store and return (mpg_regrid_store[_grid]_begin); else return the handle, waiting for its Store
-static int store_common(HandleKey key, mpg_handle *out, int (*build)(mpg_handle_s *, void *, hipStream_t), const StoreCtx &ctx) {
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    {
-      CACHE_LOCK();
-      auto it = g_cache.find(key);
-      if (it != g_cache.end()) {   // in use elsewhere, or parked by an earlier release / a finished _begin: the same weights, no device work
-        if (out) {
-          it->second->refcount++;
-          *out = it->second;
-        }
-        return MPG_SUCCESS;
-      }
-    }
-    int rc = store_worker_start(g_device);
-    if (rc) return rc;
-    std::shared_ptr<StoreJob> job;
-    {
-      std::unique_lock<std::mutex> lk(SW().mu);
-      auto pit = SW().pending.find(key);
-      if (pit != SW().pending.end()) {
-        job = pit->second;
-      } else {
-        job = std::make_shared<StoreJob>();
-        job->key = key;
-        job->build = build;
-        job->ctx = ctx;
-        if (hipEventCreateWithFlags(&job->ready, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(job->ready, g_stream);
-        SW().pending[key] = job;
-        SW().queue.push_back(job);
-      }
-      if (!out) {
-        lk.unlock();
-        SW().cv.notify_all();
-        return MPG_SUCCESS;
-      }
-      SW().cv.notify_all();
-      SW().cv.wait(lk, [&] { return job->done; });
-    }
-    if (job->rc) {
-      mpg_set_error("%s", job->err);
-      return job->rc;
-    }
-    // finished: the handle is in the cache now (unless a flood of releases has pushed it out again: then once more)
-  }
-  mpg_set_error("RegridStore: the finished handle left the cache before it was collected");
-  return MPG_ERR_HIP;
-}
-
-static int store_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = x->method;
+static int store_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
   int rc;
-  if (x->method == MPG_REGRIDMETHOD_BILINEAR) rc = mpg_k_store_bilinear_mesh(x->m, x->g, x->stagger, x->meshloc, h, s);
-  else if (x->method == MPG_REGRIDMETHOD_NEAREST_STOD) rc = mpg_k_store_nearest(x->m, x->g, x->stagger, h, s);
-  else rc = mpg_k_store_conserve(x->m, x->g, h, s);
-  if (!rc && x->m->win_count[x->meshloc] >= 0)    // the mesh's sources are windowed: index relative to the window from the start
-    rc = mpg_k_rebase(h, x->m->win_first[x->meshloc], x->m->win_count[x->meshloc], s, true);
-  return rc;
+  if (x.method == MPG_REGRIDMETHOD_BILINEAR) rc = mpg_k_store_bilinear_mesh(x.src_mesh, x.dst_grid, x.dst_loc, x.src_loc, h, s);
+  else if (x.method == MPG_REGRIDMETHOD_NEAREST_STOD) rc = mpg_k_store_nearest(x.src_mesh, x.dst_grid, x.dst_loc, h, s);
+  else rc = mpg_k_store_conserve(x.src_mesh, x.dst_grid, h, s);
+  return rc ? rc : rebase_to_window(h, x.src_mesh, x.src_loc, s);
 }
-static int store_grid_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = x->method;
-  return mpg_k_store_grid_bilinear(x->g, x->stagger, h, s);
+static int store_grid_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  return mpg_k_store_grid_bilinear(x.src_grid, x.dst_loc, h, s);
 }
 
 static int store_mesh_entry(mpg_mesh src, int src_meshloc, mpg_grid dst, int dst_staggerloc, int regridmethod, mpg_handle *out, const char *who) {
@@ -912,13 +803,8 @@ static int store_mesh_entry(mpg_mesh src, int src_meshloc, mpg_grid dst, int dst
     mpg_set_error("%s: conservative regridding is defined on the CENTER stagger only", who);
     return MPG_ERR_UNSUPPORTED;
   }
-  StoreCtx ctx{src, dst, dst_staggerloc, regridmethod, src_meshloc};
-  // the line type in force is part of what a bilinear handle IS: the two never share a cache entry
-  // ... and so is the apex rule of the polygon fans for node-located sources
-  HandleKey key(src, src_meshloc, dst, dst_staggerloc,
-                regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 16 * mpg_bilinear_linetype() : 0) +
-                    (regridmethod == MPG_REGRIDMETHOD_BILINEAR && src_meshloc == MPG_MESHLOC_NODE ? 256 * (mpg_node_fan_origin() + 16) : 0));
-  return store_common(key, out, store_mesh_build, ctx);
+  // the line type in force is part of what a bilinear handle IS, and so is the apex rule of the polygon fans for node-located sources
+  return store_common(StoreKey::mesh_to_grid(src, src_meshloc, dst, dst_staggerloc, regridmethod, mpg_bilinear_linetype(), mpg_node_fan_origin()), out);
 }
 
 int mpg_regrid_store(mpg_mesh src, int src_meshloc, mpg_grid dst, int dst_staggerloc, int regridmethod, mpg_handle *out) {
@@ -937,13 +823,10 @@ int mpg_handle_source_range(mpg_handle h, int64_t *first, int64_t *end) {
   MPG_ARG(!h->localized, "mpg_handle_source_range: the handle was re-indexed (mpg_handle_localize / mpg_handle_rebase)");
   int rc = mpg_k_source_range(h, first, end, g_stream);
   if (rc) return rc;
-  if (h->cached && std::get<1>(h->key) < 100) {   // Mesh -> Grid handle of a windowed mesh: back to global ids
-    mpg_mesh_s *m = (mpg_mesh_s *)std::get<0>(h->key);
-    const int loc = std::get<1>(h->key);
-    if (m->win_count[loc] >= 0 && *end > *first) {
-      *first += m->win_first[loc];
-      *end += m->win_first[loc];
-    }
+  if (*end > *first) {   // a handle of a windowed mesh: back to global ids
+    const int64_t w0 = mpg_handle_window_first(h);
+    *first += w0;
+    *end += w0;
   }
   return MPG_SUCCESS;
 }
@@ -955,33 +838,33 @@ int mpg_mesh_set_source_window(mpg_mesh m, int meshloc, int64_t first, int64_t c
   MPG_ARG(first >= 0 && count >= 0 && first + count <= n_all, "mpg_mesh_set_source_window: the window must lie inside the mesh");
   const int64_t old_first = m->win_count[meshloc] >= 0 ? m->win_first[meshloc] : 0;
   store_worker_drain();
-  CACHE_LOCK();
-  struct Busy { Busy() { g_cache_busy = true; } ~Busy() { g_cache_busy = false; } } busy;
   // every handle of this mesh and location that exists already (in use or parked) moves to the new window -- after ALL of
   // them have been checked: one that references a source outside it fails the call and nothing has changed
-  for (auto &kv : g_cache) {
-    if (std::get<0>(kv.first) != (void *)m || std::get<1>(kv.first) != meshloc) continue;
-    int64_t f = 0, e = 0;
-    int rc = mpg_k_source_range(kv.second, &f, &e, g_stream);
-    if (rc) return rc;
-    if (e > f && (f + old_first < first || e + old_first > first + count)) {
-      mpg_set_error("mpg_mesh_set_source_window: a route handle of this mesh references sources [%lld, %lld), outside the window [%lld, %lld)",
-                    (long long)(f + old_first), (long long)(e + old_first), (long long)first, (long long)(first + count));
-      return MPG_ERR_INVALID_ARG;
+  return cache().with_entries([&](const StoreCache<mpg_handle_s>::Map &entries) -> int {
+    for (auto &kv : entries) {
+      if (!kv.first.source_is(m, meshloc)) continue;
+      int64_t f = 0, e = 0;
+      int rc = mpg_k_source_range(kv.second, &f, &e, g_stream);
+      if (rc) return rc;
+      if (e > f && (f + old_first < first || e + old_first > first + count)) {
+        mpg_set_error("mpg_mesh_set_source_window: a route handle of this mesh references sources [%lld, %lld), outside the window [%lld, %lld)",
+                      (long long)(f + old_first), (long long)(e + old_first), (long long)first, (long long)(first + count));
+        return MPG_ERR_INVALID_ARG;
+      }
     }
-  }
-  for (auto &kv : g_cache) {
-    if (std::get<0>(kv.first) != (void *)m || std::get<1>(kv.first) != meshloc) continue;
-    mpg_handle_s *h = kv.second;
-    h->free_tile_lists();
-    h->lf_choice = 0;
-    h->cf_choice = 0;
-    int rc = mpg_k_rebase(h, first - old_first, count, g_stream, true);
-    if (rc) return rc;
-  }
-  m->win_first[meshloc] = first;
-  m->win_count[meshloc] = first == 0 && count == n_all ? -1 : count;   // the whole mesh: no window any more
-  return MPG_SUCCESS;
+    for (auto &kv : entries) {
+      if (!kv.first.source_is(m, meshloc)) continue;
+      mpg_handle_s *h = kv.second;
+      h->free_tile_lists();
+      h->lf_choice = 0;
+      h->cf_choice = 0;
+      int rc = mpg_k_rebase(h, first - old_first, count, g_stream, true);
+      if (rc) return rc;
+    }
+    m->win_first[meshloc] = first;
+    m->win_count[meshloc] = first == 0 && count == n_all ? -1 : count;   // the whole mesh: no window any more
+    return MPG_SUCCESS;
+  });
 }
 
 static int store_grid_entry(mpg_grid grid, int src_staggerloc, int dst_staggerloc, int regridmethod, mpg_handle *out) {
@@ -992,9 +875,8 @@ static int store_grid_entry(mpg_grid grid, int src_staggerloc, int dst_staggerlo
     mpg_set_error("mpg_regrid_store_grid: only bilinear CENTER -> EDGE1/EDGE2 is used by the reference (interp.F90:298,316)");
     return MPG_ERR_UNSUPPORTED;
   }
-  StoreCtx ctx{nullptr, grid, dst_staggerloc, regridmethod, 0};
-  HandleKey key(grid, 100 + src_staggerloc, grid, dst_staggerloc, regridmethod + 256 * mpg_grid_inside_tol_exp());   // the inside tolerance in force is part of the handle
-  return store_common(key, out, store_grid_build, ctx);
+  // the inside tolerance in force is part of the handle
+  return store_common(StoreKey::grid_to_grid(grid, src_staggerloc, dst_staggerloc, regridmethod, mpg_grid_inside_tol_exp()), out);
 }
 int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc, int regridmethod, mpg_handle *out) {
   MPG_CHECK_INIT();
@@ -1006,15 +888,10 @@ int mpg_regrid_store_grid_begin(mpg_grid grid, int src_staggerloc, int dst_stagg
 }
 
 // ---- Grid -> Mesh Store (k_store_to_mesh.hip) --------------------------------------------------------------------------------
-// Cache key: (grid, 200 + stagger, mesh, meshloc, method | tolerance | direction bit).  The source object comes first, as in the other
-// keys, so everything that looks for "the handles whose SOURCE is this mesh" -- mpg_mesh_set_source_window, the window offset of
+// Everything that looks for "the handles whose SOURCE is this mesh" -- mpg_mesh_set_source_window, the window offset of
 // mpg_handle_source_range / _unique_sources -- passes these handles by: the mesh is their destination, their sources are grid points.
-// The direction bit keeps the key apart from a Mesh -> Grid key even if a grid and a mesh should ever share an address.
-#define MPG_KEY_TO_MESH (1 << 20)
-static int store_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = x->method;
-  return mpg_k_store_to_mesh(x->g, x->stagger, x->m, x->meshloc, x->method, h, s);
+static int store_to_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  return mpg_k_store_to_mesh(x.src_grid, x.src_loc, x.dst_mesh, x.dst_loc, x.method, h, s);
 }
 
 int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out) {
@@ -1051,23 +928,14 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
     mpg_set_error("mpg_regrid_store_to_mesh: the grid holds no coordinates of stagger %d", src_staggerloc);
     return MPG_ERR_INVALID_ARG;
   }
-  StoreCtx ctx{dst, src, src_staggerloc, regridmethod, dst_meshloc};
   // the inside tolerance in force is part of what a bilinear handle is (as for the Grid -> Grid Store)
-  HandleKey key(src, 200 + src_staggerloc, dst, dst_meshloc,
-                regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 256 * mpg_grid_inside_tol_exp() : 0) + MPG_KEY_TO_MESH);
-  return store_common(key, out, store_to_mesh_build, ctx);
+  return store_common(StoreKey::grid_to_mesh(src, src_staggerloc, dst, dst_meshloc, regridmethod, mpg_grid_inside_tol_exp()), out);
 }
 
 // ---- bilinear Grid -> Mesh Store of a periodic grid (k_store_periodic_to_mesh.hip) --------------------------------------------------
-// Cache key: the Grid -> Mesh key of the CENTER stagger with the bilinear method, the inside tolerance and the direction bit, plus a kind
-// bit of its own -- mpg_regrid_store_to_mesh refuses bilinear on a periodic grid, and the bit keeps the key apart whatever that call
-// accepts one day -- and 65536 * pole_method: the two pole methods are two handles.  The grid sits in the first place, so
-// mpg_mesh_set_source_window passes these handles by; cache_purge looks at both places.
-#define MPG_KEY_PERIODIC (1 << 22)
-static int store_periodic_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = MPG_REGRIDMETHOD_BILINEAR;
-  return mpg_k_store_periodic_to_mesh(x->g, x->m, x->meshloc, x->method, h, s);   // (ctx.method carries the pole method)
+// A kind of its own, whatever mpg_regrid_store_to_mesh accepts one day; the two pole methods are two handles.
+static int store_periodic_to_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  return mpg_k_store_periodic_to_mesh(x.src_grid, x.dst_mesh, x.dst_loc, x.pole_method, h, s);
 }
 
 int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshloc, int pole_method, mpg_handle *out) {
@@ -1102,19 +970,12 @@ int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshlo
     mpg_set_error("mpg_regrid_store_periodic_to_mesh: the grid holds no CENTER coordinates");
     return MPG_ERR_INVALID_ARG;
   }
-  StoreCtx ctx{dst, src, MPG_STAGGERLOC_CENTER, pole_method, dst_meshloc};
-  HandleKey key(src, 200 + MPG_STAGGERLOC_CENTER, dst, dst_meshloc,
-                MPG_REGRIDMETHOD_BILINEAR + 256 * mpg_grid_inside_tol_exp() + 65536 * pole_method + MPG_KEY_TO_MESH + MPG_KEY_PERIODIC);
-  return store_common(key, out, store_periodic_to_mesh_build, ctx);
+  return store_common(StoreKey::periodic_to_mesh(src, dst, dst_meshloc, pole_method, mpg_grid_inside_tol_exp()), out);
 }
 
 // ---- conservative Grid -> Mesh Store (k_store_conserve.hip) ---------------------------------------------------------------------
-// Cache key: the Grid -> Mesh key of the CENTER stagger and the element location with the method MPG_REGRIDMETHOD_CONSERVE -- which
-// mpg_regrid_store_to_mesh refuses, so no key of that call has it -- plus 256 * norm_type and the direction bit.
-static int store_conserve_to_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = MPG_REGRIDMETHOD_CONSERVE;
-  return mpg_k_store_conserve_to_mesh(x->g, x->m, x->method, h, s);   // (ctx.method carries the normalisation)
+static int store_conserve_to_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  return mpg_k_store_conserve_to_mesh(x.src_grid, x.dst_mesh, x.norm_type, h, s);
 }
 
 int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type, mpg_handle *out) {
@@ -1132,27 +993,17 @@ int mpg_regrid_store_conserve_to_mesh(mpg_grid src, mpg_mesh dst, int norm_type,
                   (long long)dst->nCells);
     return MPG_ERR_OVERFLOW;
   }
-  StoreCtx ctx{dst, src, MPG_STAGGERLOC_CENTER, norm_type, MPG_MESHLOC_ELEMENT};
-  HandleKey key(src, 200 + MPG_STAGGERLOC_CENTER, dst, MPG_MESHLOC_ELEMENT, MPG_REGRIDMETHOD_CONSERVE + 256 * norm_type + MPG_KEY_TO_MESH);
-  return store_common(key, out, store_conserve_to_mesh_build, ctx);
+  return store_common(StoreKey::conserve_to_mesh(src, dst, norm_type), out);
 }
 
 // ---- Mesh -> Mesh Store (k_store_mesh.hip) -------------------------------------------------------------------------------------
-// Cache key: (src mesh, src_meshloc, dst mesh, dst_meshloc, method | line type | kind bit).  The source mesh and its location come first,
-// as in a Mesh -> Grid key, and on purpose: the sources of these handles ARE that mesh's cells, so everything that looks for "the
-// handles whose source is this mesh" -- mpg_mesh_set_source_window, the window offset of mpg_handle_source_range / _unique_sources,
-// mpg_handle_is_windowed -- finds them and treats them as it treats Mesh -> Grid handles; a window on the DESTINATION mesh does not
-// (the destination sits in the third place).  cache_purge looks at both places: parked entries go when either mesh is destroyed.
-// The kind bit keeps the key apart from a Mesh -> Grid key even if a grid and a mesh should ever share an address, and from the
-// Grid -> Mesh bit.
-#define MPG_KEY_MESH_MESH (1 << 21)
-static int store_mesh_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = x->method;
-  int rc = mpg_k_store_mesh(x->m, x->dst_mesh, x->stagger, x->method, h, s);
-  if (!rc && x->m->win_count[MPG_MESHLOC_ELEMENT] >= 0)   // the source mesh's cells are windowed: index relative to the window from the start
-    rc = mpg_k_rebase(h, x->m->win_first[MPG_MESHLOC_ELEMENT], x->m->win_count[MPG_MESHLOC_ELEMENT], s, true);
-  return rc;
+// The sources of these handles ARE the source mesh's cells (StoreKey::source_is_mesh), so everything that looks for "the handles whose
+// source is this mesh" -- mpg_mesh_set_source_window, the window offset of mpg_handle_source_range / _unique_sources,
+// mpg_handle_is_windowed -- finds them and treats them as it treats Mesh -> Grid handles; a window on the DESTINATION mesh does not.
+// Parked entries go when either mesh is destroyed.
+static int store_mesh_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  const int rc = mpg_k_store_mesh(x.src_mesh, x.dst_mesh, x.dst_loc, x.method, h, s);
+  return rc ? rc : rebase_to_window(h, x.src_mesh, x.src_loc, s);
 }
 
 int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_meshloc, int regridmethod, mpg_handle *out) {
@@ -1185,24 +1036,16 @@ int mpg_regrid_store_mesh(mpg_mesh src, int src_meshloc, mpg_mesh dst, int dst_m
                   (long long)src->nCells, (long long)src->nVertices, (long long)n_dst);
     return MPG_ERR_OVERFLOW;
   }
-  StoreCtx ctx{src, nullptr, dst_meshloc, regridmethod, src_meshloc, dst};
   // the line type in force is part of what a bilinear handle IS (as for the Mesh -> Grid Store)
-  HandleKey key(src, src_meshloc, dst, dst_meshloc,
-                regridmethod + (regridmethod == MPG_REGRIDMETHOD_BILINEAR ? 16 * mpg_bilinear_linetype() : 0) + MPG_KEY_MESH_MESH);
-  return store_common(key, out, store_mesh_mesh_build, ctx);
+  return store_common(StoreKey::mesh_to_mesh(src, src_meshloc, dst, dst_meshloc, regridmethod, mpg_bilinear_linetype()), out);
 }
 
 // ---- conservative Mesh -> Mesh Store (k_store_conserve_mesh.hip) -------------------------------------------------------------------
-// Cache key: the Mesh -> Mesh key of the element locations with the method MPG_REGRIDMETHOD_CONSERVE -- which mpg_regrid_store_mesh
-// refuses, so no key of that call has it -- plus 256 * norm_type.  The source mesh sits in the first place: mpg_mesh_set_source_window on
-// it rebases these handles like every other Mesh -> Mesh handle, a window on the destination mesh passes them by.
-static int store_conserve_mesh_build(mpg_handle_s *h, void *c, hipStream_t s) {
-  StoreCtx *x = (StoreCtx *)c;
-  h->method = MPG_REGRIDMETHOD_CONSERVE;
-  int rc = mpg_k_store_conserve_mesh(x->m, x->dst_mesh, x->method, h, s);   // (ctx.method carries the normalisation)
-  if (!rc && x->m->win_count[MPG_MESHLOC_ELEMENT] >= 0)   // the source mesh's cells are windowed: index relative to the window from the start
-    rc = mpg_k_rebase(h, x->m->win_first[MPG_MESHLOC_ELEMENT], x->m->win_count[MPG_MESHLOC_ELEMENT], s, true);
-  return rc;
+// mpg_mesh_set_source_window on the source mesh rebases these handles like every other Mesh -> Mesh handle, a window on the destination
+// mesh passes them by.
+static int store_conserve_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  const int rc = mpg_k_store_conserve_mesh(x.src_mesh, x.dst_mesh, x.norm_type, h, s);
+  return rc ? rc : rebase_to_window(h, x.src_mesh, x.src_loc, s);
 }
 
 int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mpg_handle *out) {
@@ -1225,9 +1068,13 @@ int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mp
                   (long long)dst->nCells);
     return MPG_ERR_OVERFLOW;
   }
-  StoreCtx ctx{src, nullptr, MPG_MESHLOC_ELEMENT, norm_type, MPG_MESHLOC_ELEMENT, dst};
-  HandleKey key(src, MPG_MESHLOC_ELEMENT, dst, MPG_MESHLOC_ELEMENT, MPG_REGRIDMETHOD_CONSERVE + 256 * norm_type + MPG_KEY_MESH_MESH);
-  return store_common(key, out, store_conserve_mesh_build, ctx);
+  return store_common(StoreKey::conserve_mesh_to_mesh(src, dst, norm_type), out);
+}
+
+static StoreBuildFn store_build_fn(StoreKind kind) {
+  static const StoreBuildFn table[STORE_KIND_COUNT] = {store_mesh_build,             store_grid_build,      store_to_mesh_build, store_periodic_to_mesh_build,
+                                                       store_conserve_to_mesh_build, store_mesh_mesh_build, store_conserve_mesh_build};   // in StoreKind's order
+  return table[kind];
 }
 
 int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
@@ -1241,25 +1088,7 @@ int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
 }
 
 int mpg_handle_release(mpg_handle h) {
-  if (!h) return MPG_SUCCESS;
-  CACHE_LOCK();
-  if (--h->refcount > 0) return MPG_SUCCESS;
-  if (!h->cached) {
-    handle_free(h);
-    return MPG_SUCCESS;
-  }
-  h->parked_at = ++g_park_clock;   // stays in the cache with refcount 0
-  int nparked = 0;
-  for (auto &kv : g_cache) nparked += kv.second->refcount == 0;
-  while (nparked > MPG_MAX_PARKED) {   // drop the one released longest ago
-    auto old = g_cache.end();
-    for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
-      if (it->second->refcount == 0 && (old == g_cache.end() || it->second->parked_at < old->second->parked_at)) old = it;
-    mpg_handle_s *victim = old->second;
-    g_cache.erase(old);
-    handle_free(victim);
-    --nparked;
-  }
+  if (h) cache().release(h);
   return MPG_SUCCESS;
 }
 
@@ -1891,14 +1720,11 @@ static void lf_invalidate(mpg_handle_s *h) {
 // mpg_handle_unique_sources and mpg_handle_source_range report GLOBAL ids whatever the window is.
 }  // extern "C"
 int64_t mpg_handle_window_first(const mpg_handle_s *h) {   // > 0 offset of the handle's indices, 0 when its mesh is not windowed
-  if (!h->cached || std::get<1>(h->key) >= 100) return 0;
-  const mpg_mesh_s *m = (const mpg_mesh_s *)std::get<0>(h->key);
-  const int loc = std::get<1>(h->key);
-  return m->win_count[loc] >= 0 ? m->win_first[loc] : 0;
+  return mpg_handle_is_windowed(h) ? ((const mpg_mesh_s *)h->key.src)->win_first[h->key.source_mesh_loc()] : 0;
 }
 bool mpg_handle_is_windowed(const mpg_handle_s *h) {
-  if (!h->cached || std::get<1>(h->key) >= 100) return false;
-  return ((const mpg_mesh_s *)std::get<0>(h->key))->win_count[std::get<1>(h->key)] >= 0;
+  if (!h->cached || !h->key.source_is_mesh()) return false;
+  return ((const mpg_mesh_s *)h->key.src)->win_count[h->key.source_mesh_loc()] >= 0;
 }
 extern "C" {
 #define MPG_NOT_WINDOWED(h, what)                                                                                                  \
@@ -1930,11 +1756,7 @@ int mpg_handle_localize(mpg_handle h) {
   MPG_ARG(h->n_pole == 0, "mpg_handle_localize: handles with pole terms (periodic Grid -> Grid) cannot be re-indexed");
   MPG_NOT_WINDOWED(h, "mpg_handle_localize");
   // a localized handle no longer matches its cache key: detach it
-  if (h->cached) {
-    CACHE_LOCK();
-    g_cache.erase(h->key);
-    h->cached = false;
-  }
+  cache().detach(h);
   std::vector<int32_t> ids;
   lf_invalidate(h);
   return mpg_k_unique_sources(h, ids, true, g_stream);
@@ -1949,11 +1771,7 @@ int mpg_handle_rebase(mpg_handle h, int64_t base, int64_t n_local) {
   MPG_ARG(h->n_pole == 0, "mpg_handle_rebase: handles with pole terms (periodic Grid -> Grid) cannot be re-indexed");
   MPG_ARG(base >= 0 && n_local >= 0 && n_local < 0x7fffffff, "mpg_handle_rebase: bad range");
   MPG_NOT_WINDOWED(h, "mpg_handle_rebase");
-  if (h->cached) {
-    CACHE_LOCK();
-    g_cache.erase(h->key);
-    h->cached = false;
-  }
+  cache().detach(h);
   lf_invalidate(h);
   return mpg_k_rebase(h, base, n_local, g_stream);
 }

@@ -5,10 +5,10 @@
 #include <functional>
 #include <map>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/mpassit_amd.h"
+#include "store_cache.h"
 #include "tree_walk.h"
 
 // Tiles of the Regrid kernels are txu x tyu target points whose x origin is shifted per grid row so that every segment of a
@@ -205,7 +205,6 @@ struct CellBvhView : BvhView {
 
 struct mpg_handle_s;
 struct mpg_grid_s;
-typedef std::tuple<void *, int, void *, int, int> HandleKey;
 
 struct mpg_mesh_s {
   int64_t nCells = 0, nVertices = 0;
@@ -290,7 +289,7 @@ struct mpg_handle_s {
   int refcount = 1;
   bool cached = false;
   uint64_t parked_at = 0;   // release order of a handle waiting in the cache with refcount 0 (mpg_api.hip)
-  HandleKey key;
+  StoreKey key;             // what it is cached under while `cached` (mpg_api.hip; no other translation unit reads it)
   float store_ms = 0.f;
   int64_t store_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // which branches the Store took (mpg_handle_store_stats; [0] is store_path)
   int store_path = 0;       // candidate search of the Store: 0 hierarchical (pyramid walk / BVH), 1 the grid's index space, 2 index space + BVH for the rest
@@ -358,6 +357,7 @@ void mpg_set_staged_store(int v);            // "staged_store" knob (k_apply_lfu
 void mpg_set_lf_rows_store(int v);          // "lf_rows_store" knob (k_apply_typed.hip; A/B only)
 void mpg_set_staged_lds_pad_kb(int v);      // "staged_lds_pad_kb" knob (k_apply_lfu.hip; A/B only)
 int mpg_staged_lds_pad_kb();
+int64_t mpg_handle_window_first(const mpg_handle_s *h);   // mpg_api.hip: offset of the handle's indices, 0 when its mesh carries no source window
 bool mpg_handle_is_windowed(const mpg_handle_s *h);   // mpg_api.hip: its mesh carries a source window (indices are window-relative)
 void mpg_cache_detach(mpg_handle_s *h);  // mpg_api.hip: a handle about to be re-indexed in place leaves the Store cache
 void mpg_hostpipe_release();  // mpg_hostpipe.hip: device slots / streams of the host-pointer Regrid pipeline, dropped by mpg_finalize

@@ -65,6 +65,98 @@ def test_cache_and_refcount_behave_as_for_plain_stores(gpu_lib, regional_case):
     grid.destroy()
 
 
+def _begun_stores_and_a_window(m, g, serial):
+    """Two begun Stores on (mesh, grid), a windowed mesh cut to the same grid at once, three Stores on it, then the two collected.
+    serial: mpg_warmup_wait (which drains the worker) after every call."""
+    from mpassit_amd import _lib as L, regrid as R
+
+    def step(x=None):
+        if serial:
+            L.check(L.load().mpg_warmup_wait())
+        return x
+    mesh, grid = step(R.Mesh.from_mpas(m)), step(R.Grid.from_target(g))
+    step(R.regrid_store_begin(mesh, grid, R.REGRIDMETHOD_CONSERVE))
+    step(R.regrid_store_begin(mesh, grid, R.REGRIDMETHOD_BILINEAR))
+    wmesh = step(R.Mesh.from_mpas(m, window_grid=grid))
+    got = [wmesh.window_info()]
+    handles = []
+    for o, method in ((wmesh, R.REGRIDMETHOD_BILINEAR), (wmesh, R.REGRIDMETHOD_NEAREST_STOD), (wmesh, R.REGRIDMETHOD_CONSERVE),
+                      (mesh, R.REGRIDMETHOD_CONSERVE), (mesh, R.REGRIDMETHOD_BILINEAR)):
+        handles.append(step(R.regrid_store(o, grid, method)))
+        got.append([np.array(a) for a in _weights(handles[-1])])
+    for rh in handles:
+        rh.release()
+    for o in (wmesh, mesh, grid):
+        o.destroy()
+    return got
+
+
+def test_begun_stores_and_a_window_on_one_grid(gpu_lib, regional_case):
+    """mpg_mesh_create_window builds the grid's point and cell pyramids on the caller's thread; a begun Store on that grid builds them on
+    the worker.  The call drains the worker first, so the window and all five weight sets are those of the same calls made one after
+    the other.  A guard that must pass: without the drain the two threads race, and a race cannot be made to fail on demand."""
+    m, g = regional_case
+    want = _begun_stores_and_a_window(m, g, serial=True)
+    got = _begun_stores_and_a_window(m, g, serial=False)
+    assert got[0] == want[0] and 0 < got[0][1] <= m.nCells
+    assert len(got) == len(want) == 6
+    for a, b in zip(got[1:], want[1:]):
+        assert len(a) == len(b) >= 2 and _same(a, b)
+
+
+def test_one_handle_per_distinct_store(gpu_lib):
+    """Every Store entry point on one mesh pair and one projection-built grid (the periodic Store, which refuses that regional grid, on a
+    small global one): the same call twice returns the same handle, every distinct call a handle of its own.  The line type in force is
+    part of a bilinear handle and of no other."""
+    import _mesh_to_mesh_cases as MC
+    from mpassit_amd import _lib as L, regrid as R, target_grid as tg
+    BIL, CON, NN = R.REGRIDMETHOD_BILINEAR, R.REGRIDMETHOD_CONSERVE, R.REGRIDMETHOD_NEAREST_STOD
+    a, b = R.Mesh.from_mpas(MC.mesh("geo8")), R.Mesh.from_mpas(MC.mesh("vor1500"))
+    grid = R.Grid.from_proj(tg.define_target_grid_params("lambert", 61, 41, dx=30000.0, dy=30000.0, ref_lat=38.5, ref_lon=-97.5, truelat1=38.5,
+                                                         truelat2=38.5, stand_lon=-97.5), fill_target=False)
+    globe = R.Grid.from_target(tg.define_target_grid_params("lat-lon", nx=24, ny=12, stand_lon=0.0, is_regional=False))
+    calls = [lambda m=m, loc=loc, st=st: R.regrid_store(a, grid, m, staggerloc=st, meshloc=loc)
+             for m, loc, st in ((BIL, R.MESHLOC_ELEMENT, R.STAGGERLOC_CENTER), (BIL, R.MESHLOC_NODE, R.STAGGERLOC_CENTER),
+                                (BIL, R.MESHLOC_ELEMENT, R.STAGGERLOC_EDGE1), (NN, R.MESHLOC_ELEMENT, R.STAGGERLOC_CENTER),
+                                (CON, R.MESHLOC_ELEMENT, R.STAGGERLOC_CENTER))]
+    calls += [lambda: R.regrid_store(b, grid, BIL)]
+    calls += [lambda st=st: R.regrid_store_grid(grid, st) for st in (R.STAGGERLOC_EDGE1, R.STAGGERLOC_EDGE2)]
+    calls += [lambda m=m, loc=loc, st=st: R.regrid_store_to_mesh(grid, a, m, staggerloc=st, meshloc=loc)
+              for m, loc, st in ((BIL, R.MESHLOC_ELEMENT, R.STAGGERLOC_CENTER), (NN, R.MESHLOC_ELEMENT, R.STAGGERLOC_CENTER),
+                                 (BIL, R.MESHLOC_NODE, R.STAGGERLOC_CENTER), (BIL, R.MESHLOC_ELEMENT, R.STAGGERLOC_CORNER))]
+    calls += [lambda p=p: R.regrid_store_periodic_to_mesh(globe, a, pole_method=p) for p in (R.POLEMETHOD_ALLAVG, R.POLEMETHOD_NONE)]
+    calls += [lambda n=n: R.regrid_store_conserve_to_mesh(grid, a, norm=n) for n in (R.NORM_DSTAREA, R.NORM_FRACAREA)]
+    calls += [lambda m=m, loc=loc: R.regrid_store_mesh(a, b, m, dst_meshloc=loc)
+              for m, loc in ((BIL, R.MESHLOC_ELEMENT), (NN, R.MESHLOC_ELEMENT), (BIL, R.MESHLOC_NODE))]
+    calls += [lambda: R.regrid_store_mesh(b, a, BIL)]
+    calls += [lambda n=n: R.regrid_store_conserve_mesh(a, b, norm=n) for n in (R.NORM_DSTAREA, R.NORM_FRACAREA)]
+    held = []
+    try:
+        R.regrid_store_begin(a, grid, CON)                      # the two _begin forms: the plain calls below collect their handles
+        R.regrid_store_grid_begin(grid, R.STAGGERLOC_EDGE2)
+        first = [c() for c in calls]
+        held += first
+        again = [c() for c in calls]
+        held += again
+        assert [h._h.value for h in first] == [h._h.value for h in again]
+        assert len({h._h.value for h in first}) == len(calls) == 22
+        # the line type: nearest Stores share their handle across it, bilinear ones do not
+        L.tune("bilinear_linetype", 1)
+        held += [R.regrid_store(a, grid, NN), R.regrid_store_mesh(a, b, NN), R.regrid_store(a, grid, CON), R.regrid_store(a, grid, BIL),
+                 R.regrid_store_mesh(a, b, BIL)]
+        assert [h._h.value for h in held[-5:-2]] == [first[3]._h.value, first[17]._h.value, first[4]._h.value]
+        assert not {h._h.value for h in held[-2:]} & {h._h.value for h in first} and held[-2]._h.value != held[-1]._h.value
+        L.tune("bilinear_linetype", 0)
+        held += [R.regrid_store(a, grid, BIL), R.regrid_store_mesh(a, b, BIL)]
+        assert [h._h.value for h in held[-2:]] == [first[0]._h.value, first[16]._h.value]
+    finally:
+        L.tune("bilinear_linetype", 0)
+        for h in held:
+            h.release()
+        for o in (a, b, grid, globe):
+            o.destroy()
+
+
 def test_refused_arguments_are_refused_at_once(gpu_lib, regional_case):
     from mpassit_amd import _lib as L, regrid as R
     m, g = regional_case
