@@ -220,7 +220,7 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
  * dstField on a Mesh location, regridmethod=BILINEAR, polemethod=) -- a global lat-lon analysis (GFS, ERA5, an SST product) taken onto MPAS
  * cells by the default method.  The grid must have been created with MPG_GRID_PERIODIC_I.
  * Source points: the grid's nx x ny CENTER points, source index = j * nx + i.  Destinations: the mesh's cell centres (MPG_MESHLOC_ELEMENT)
- *   or vertices (MPG_MESHLOC_NODE).
+ *   or vertices (MPG_MESHLOC_NODE), or the edges mpg_mesh_set_edges gave it (MPG_MESHLOC_EDGE; none set -> MPG_ERR_INVALID_ARG).
  * Quads: b in [0, ny - 2], a in [0, nx - 1]; A = (b, a), B = (b, (a + 1) mod nx), C = (b + 1, (a + 1) mod nx), D = (b + 1, a);
  *   quad id = b * nx + a.  A point belongs to the lowest quad id for which the bilinear map of mpg_regrid_store_to_mesh has a solution
  *   with xi, eta in [-tol, 1 + tol], tol = 10^-grid_inside_tol_exp; weights (1-xi)(1-eta), xi (1-eta), xi eta, (1-xi) eta on A, B, C, D.
@@ -264,7 +264,7 @@ int mpg_regrid_store_to_mesh(mpg_grid src, int src_staggerloc, mpg_mesh dst, int
  *   [3] points mapped by a cap, [4] points mapped by a seam quad (a = nx - 1).
  * Everything that takes a CSR handle takes this one, with no kernel of its own: mpg_regrid_csr_to_mesh_dev in both mesh orders,
  *   mpg_regrid_csr_rows_dev, mpg_regrid_typed[_pitched]_dev, mpg_regrid_masked_dev, mpg_regrid_transpose_dev, mpg_handle_get_csr.
- *   mpg_regrid_to_mesh_dev and mpg_regrid_rows_dev refuse it as they refuse every CSR handle. */
+ *   mpg_regrid_to_mesh_dev and mpg_regrid_rows_dev refuse it as they refuse every CSR handle.  Winds: mpg_wind_csr_to_mesh_dev. */
 enum { MPG_POLEMETHOD_NONE = 0, MPG_POLEMETHOD_ALLAVG = 1 };
 int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshloc, int pole_method, mpg_handle *out);
 /* Mesh -> Mesh: ESMF_FieldRegridStore(srcField on a Mesh's elements, dstField on another Mesh's location) -- a global run feeding the
@@ -622,7 +622,7 @@ int mpg_wind_destagger(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *c
  * of the other), for dense and pitched sources, and from call to call.  No atomics.  Stream as mpg_regrid_dev.  The call allocates
  * nothing and synchronises nothing: it can be captured in a hipGraph from the first call.
  * Refusals, each with a message that names the way out.  MPG_ERR_UNSUPPORTED: CSR handles (conservative, periodic, from-weights: winds
- * from a periodic global grid are out of scope), handles with pole caps, 3-slot handles or a pair of mixed nnz_per_row, MPG_TYPE_BE on
+ * from a periodic global grid go through mpg_wind_csr_to_mesh_dev), handles with pole caps, 3-slot handles or a pair of mixed nnz_per_row, MPG_TYPE_BE on
  * either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays, rh_u.n_dst != rh_v.n_dst, nlev < 1, unknown enums.  MPG_ERR_OVERFLOW: more
  * 64-point blocks than one launch holds. */
 int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev,
@@ -670,12 +670,52 @@ int mpg_mesh_edge_rotang_dev(mpg_grid grid, mpg_mesh mesh, double *cn_dev, doubl
  * sources, and from call to call.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it
  * can be captured in a hipGraph from the first call.
  * Refusals, those of mpg_wind_to_mesh_dev under the name mpg_wind_to_edges.  MPG_ERR_UNSUPPORTED: CSR handles (conservative, periodic,
- * from-weights: winds from a periodic global grid are out of scope), handles with pole caps, 3-slot handles or a pair of mixed
+ * from-weights: winds from a periodic global grid go through mpg_wind_csr_to_edges_dev), handles with pole caps, 3-slot handles or a pair of mixed
  * nnz_per_row, MPG_TYPE_BE on either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays (cn_dev / sn_dev included), rh_u.n_dst !=
  * rh_v.n_dst, nlev < 1, unknown enums, aliased arrays.  MPG_ERR_OVERFLOW: more 64-point blocks than one launch holds. */
 int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev,
                           const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev,
                           void *un_dev, void *ut_dev, int dst_type, int dst_layout, void *hip_stream);
+/* Winds through CSR handles: the two calls above for the handles they refuse -- U and V of a periodic global lat-lon or Gaussian
+ * analysis (GFS, ERA5, an IFS product) onto the cells, vertices or edges of a mesh, in ONE pass: the two Regrids of
+ * mpg_regrid_csr_to_mesh_dev, the rotation and the cast, without the two float64 intermediates of nlev * n_dst and with the handle's
+ * indices and weights staged once.  The argument lists are those of mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev and keep their
+ * meaning: cosa_dev / sina_dev both set or both NULL (no rotation; exactly one NULL -> MPG_ERR_INVALID_ARG); cn_dev / sn_dev REQUIRED
+ * (mpg_mesh_edge_rotang_dev; a NULL grid there for winds that are earth-relative already, as a lat-lon analysis has them); ut_dev may
+ * be NULL; u_level_stride / v_level_stride in elements, 0 = dense, below n_src -> MPG_ERR_INVALID_ARG; results in MPG_LAYOUT_CELL_FAST
+ * [lev][point] or MPG_LAYOUT_LEV_FAST [point][lev], fully overwritten.
+ *   rh_u, rh_v           CSR handles (nnz_per_row 0) onto the SAME n_dst points: mpg_regrid_store_periodic_to_mesh,
+ *                        mpg_regrid_store_conserve_to_mesh, mpg_regrid_store_conserve_mesh, mpg_handle_from_weights.  rh_u == rh_v is
+ *                        the main case, a collocated analysis: the kernel then stages ONE run and feeds both accumulators from each
+ *                        staged (col, val).  With two different handles each handle's run is walked for its own component.  The calls
+ *                        do not look at the mesh.
+ * Values, a contract by identity: float64 arithmetic without contraction, per (point, level) and per handle
+ *   acc = fma(val[q], (double)src[col[q]], acc)    from 0.0, the row's entries in stored order, whatever LDS chunk an entry arrives in
+ *   a  = fma(acc_u, 1.0, 0.0)                      exactly mpg_regrid_csr_to_mesh_dev(rh_u, dst F64, scale 1, offset 0)
+ *   b  = fma(acc_v, 1.0, 0.0)                      the same with rh_v, V
+ *   mesh call:   ue = a * ca - b * sa ;  ve = a * sa + b * ca      (no rotation: ue = a, ve = b)
+ *   edges call:  un = a * cn + b * sn ;  ut = b * cn - a * sn      (ut only when ut_dev != NULL)
+ *   store (TD)o0 [, (TD)o1]                        every product and sum rounded; one rounding to the destination type
+ * A point whose row is empty in either handle gets (TD)(+0.0) in every result (0 * c - 0 * s can be -0.0, hence a mask).  The same bits
+ * for both layouts, for dense and pitched sources, for rh_u == rh_v given once or as two equal handles, and from call to call.
+ * No atomics.  Stream as mpg_regrid_dev.  The calls allocate nothing and synchronise nothing: they can be captured in a hipGraph from
+ * the first call.  n_dst == 0 is success; a handle with no entries gives zeroed results.
+ * CAVEAT, pole caps: under MPG_POLEMETHOD_ALLAVG a cap point gets the row mean of each wind COMPONENT -- what two scalar ESMF Regrids
+ * give, and not a wind: for a solid-body rotation of unit speed about an axis tilted 45 degrees, from a 72 x 36 grid onto the 59 994
+ * edges of a 20 000-cell mesh, un is off by at most 1.41e-3 on quad rows and by up to 0.53 on the 57 cap edges (24 x 12: 1.23e-2 and
+ * 0.71).  A host that cares stores with MPG_POLEMETHOD_NONE and fills the cap points itself (mpg_regrid_masked_dev, a nearest handle);
+ * a Cartesian-vector Regrid is the real answer and is not built.
+ * Refusals, each with a message that names the way out, under the names mpg_wind_csr_to_mesh / mpg_wind_csr_to_edges.
+ * MPG_ERR_UNSUPPORTED: a fixed handle on either side (mpg_wind_to_mesh_dev / mpg_wind_to_edges_dev serve those), a handle with pole
+ * terms (mpg_handle_pole_count > 0), MPG_TYPE_BE on either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays, exactly one NULL angle
+ * (mesh call), NULL cn_dev / sn_dev (edges call), rh_u.n_dst != rh_v.n_dst, nlev < 1, unknown enums, a level stride below n_src,
+ * results aliasing each other, a source or the angles.  MPG_ERR_OVERFLOW: more 64-point blocks than one launch holds. */
+int mpg_wind_csr_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev,
+                             const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev,
+                             void *ve_dev, int dst_type, int dst_layout, void *hip_stream);
+int mpg_wind_csr_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev,
+                              const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev,
+                              void *un_dev, void *ut_dev, int dst_type, int dst_layout, void *hip_stream);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

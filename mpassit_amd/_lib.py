@@ -30,6 +30,7 @@ SYMBOLS = [
     "mpg_regrid_store_periodic_to_mesh",
     "mpg_wind_to_mesh_dev", "mpg_mesh_rotang_dev",
     "mpg_mesh_set_edges", "mpg_mesh_edge_count", "mpg_mesh_edge_rotang_dev", "mpg_wind_to_edges_dev",
+    "mpg_wind_csr_to_mesh_dev", "mpg_wind_csr_to_edges_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -238,6 +239,31 @@ def wind_to_edges_dev(*args):
     if "wind_edges" not in _to_mesh_fns:
         _to_mesh_fns["wind_edges"] = _WIND_TO_EDGES_PROTO(("mpg_wind_to_edges_dev", load()))
     return _to_mesh_fns["wind_edges"](*args)
+
+
+# The two wind calls for CSR handles, bound the same way: the argument lists of mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev.
+#   mpg_wind_csr_to_mesh_dev(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev,
+#                            dst_type, dst_layout, hip_stream)
+#   mpg_wind_csr_to_edges_dev(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev,
+#                             dst_type, dst_layout, hip_stream)
+_WIND_CSR_TO_MESH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+_WIND_CSR_TO_EDGES_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+
+
+def wind_csr_to_mesh_dev(*args):
+    """The typed binding of mpg_wind_csr_to_mesh_dev; returns the call's status code."""
+    if "wind_csr" not in _to_mesh_fns:
+        _to_mesh_fns["wind_csr"] = _WIND_CSR_TO_MESH_PROTO(("mpg_wind_csr_to_mesh_dev", load()))
+    return _to_mesh_fns["wind_csr"](*args)
+
+
+def wind_csr_to_edges_dev(*args):
+    """The typed binding of mpg_wind_csr_to_edges_dev; returns the call's status code."""
+    if "wind_csr_edges" not in _to_mesh_fns:
+        _to_mesh_fns["wind_csr_edges"] = _WIND_CSR_TO_EDGES_PROTO(("mpg_wind_csr_to_edges_dev", load()))
+    return _to_mesh_fns["wind_csr_edges"](*args)
 
 
 _lib = None

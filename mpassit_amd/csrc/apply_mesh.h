@@ -1,8 +1,8 @@
 // What the four mesh-order Regrid kernels (k_apply_to_mesh / k_apply_csr_to_mesh / k_apply_rows / k_apply_csr_rows.hip) and the wind
-// kernel on two fixed handles (k_wind_pair.hip) share: the staging of a block's indices and weights or of its CSR run through LDS, the
+// kernels on two fixed handles (k_wind_pair.hip) and on two CSR handles (k_wind_csr.hip) share: the staging of a block's indices and weights or of its CSR run through LDS, the
 // (point, level) cursor along a block's [cell][lev] run, the drain of the [cell][lev] result tile, and on the host the tile plan, the
 // launch grid, the path of a handle without sources and the (src_type, dst_type) dispatch.  One workgroup of 256 threads owns AM_CELLS
-// consecutive destination points and all levels in every one of the five; the LDS arrays are declared by the kernels (dynamic or static)
+// consecutive destination points and all levels in every one of the six; the LDS arrays are declared by the kernels (dynamic or static)
 // and handed in as pointers; the main loops stay there.
 #pragma once
 #include <algorithm>

@@ -271,9 +271,9 @@ int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s) {
 int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s) {
   int rc;
   const PointSet &src = g->pts[MPG_STAGGERLOC_CENTER];
-  const PointSet &dst = meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
+  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
   const int nx = g->nx, ny = g->ny;
-  const int64_t n = meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
   h->kind = MPG_KIND_CSR;
   h->nnz_per_row = 0;
   h->n_src = (int64_t)nx * ny;

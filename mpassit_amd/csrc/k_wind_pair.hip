@@ -25,6 +25,7 @@
 // No atomics, no allocation, no synchronisation with the host: the call is capturable in a hipGraph from the first call.
 #pragma clang fp contract(off)
 #include "apply_mesh.h"
+#include "wind_policies.h"   // CellsRotated, CellsPlain, EdgesNormal, EdgesBoth: shared with k_wind_csr.hip
 
 struct WindPair {
   const int32_t *idx_u, *idx_v;   // [NNZ][P] each, -1 = unmapped; the same pointers for one handle given twice
@@ -34,43 +35,6 @@ struct WindPair {
   void *r0, *r1;                  // nlev * P each, [lev][point] or [point][lev]; r1 only touched by the policies with NOUT 2
   int64_t P, ldu, ldv;
   int nlev, kc, S;
-};
-
-struct CellsRotated {
-  static constexpr int NOUT = 2;
-  static constexpr bool ANGLES = true;
-  static __device__ __forceinline__ void combine(double ra, double rb, double c, double s, double &o0, double &o1) {
-    const double t1 = ra * c, t2 = rb * s, t3 = ra * s, t4 = rb * c;
-    o0 = t1 - t2;
-    o1 = t3 + t4;
-  }
-};
-struct CellsPlain {
-  static constexpr int NOUT = 2;
-  static constexpr bool ANGLES = false;
-  static __device__ __forceinline__ void combine(double ra, double rb, double, double, double &o0, double &o1) {
-    o0 = ra;
-    o1 = rb;
-  }
-};
-struct EdgesNormal {
-  static constexpr int NOUT = 1;
-  static constexpr bool ANGLES = true;
-  static __device__ __forceinline__ void combine(double ra, double rb, double c, double s, double &o0, double &o1) {
-    const double t1 = ra * c, t2 = rb * s;
-    o0 = t1 + t2;
-    o1 = 0.0;   // (not stored)
-  }
-};
-struct EdgesBoth {
-  static constexpr int NOUT = 2;
-  static constexpr bool ANGLES = true;
-  static __device__ __forceinline__ void combine(double ra, double rb, double c, double s, double &o0, double &o1) {
-    const double t1 = ra * c, t2 = rb * s;
-    o0 = t1 + t2;
-    const double t3 = rb * c, t4 = ra * s;
-    o1 = t3 - t4;
-  }
 };
 
 template <typename TS, typename TD, int NNZ, bool LEVF, typename C>

@@ -124,7 +124,8 @@ void mpg_pool_release() {
 #define MPG_ANCHORS(X) X(k_setup) X(k_target_grid) X(k_store_bilinear) X(k_store_nearest) X(k_store_conserve) X(k_store_gridbil) \
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
-  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair)
+  X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
+  X(k_wind_csr)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -941,7 +942,10 @@ static int store_periodic_to_mesh_build(mpg_handle_s *h, const StoreCtx &x, hipS
 int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshloc, int pole_method, mpg_handle *out) {
   MPG_CHECK_INIT();
   MPG_ARG(src && dst && out, "mpg_regrid_store_periodic_to_mesh: NULL argument");
-  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE,
+  MPG_ARG(dst_meshloc != MPG_MESHLOC_EDGE || dst->edge.n > 0,
+          "mpg_regrid_store_periodic_to_mesh: unknown mesh location (MPG_MESHLOC_ELEMENT or MPG_MESHLOC_NODE; MPG_MESHLOC_EDGE needs a mesh that "
+          "mpg_mesh_set_edges gave edges)");
+  MPG_ARG(dst_meshloc == MPG_MESHLOC_ELEMENT || dst_meshloc == MPG_MESHLOC_NODE || dst_meshloc == MPG_MESHLOC_EDGE,
           "mpg_regrid_store_periodic_to_mesh: unknown mesh location (MPG_MESHLOC_ELEMENT or MPG_MESHLOC_NODE)");
   MPG_ARG(pole_method == MPG_POLEMETHOD_NONE || pole_method == MPG_POLEMETHOD_ALLAVG,
           "mpg_regrid_store_periodic_to_mesh: pole_method must be MPG_POLEMETHOD_NONE or MPG_POLEMETHOD_ALLAVG (NPNTAVG and TEETH are not built)");
@@ -961,7 +965,7 @@ int mpg_regrid_store_periodic_to_mesh(mpg_grid src, mpg_mesh dst, int dst_meshlo
     return MPG_ERR_INVALID_ARG;
   }
   const int64_t n_src = (int64_t)src->nx * src->ny;
-  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
+  const int64_t n_dst = dst_meshloc == MPG_MESHLOC_EDGE ? dst->edge.n : dst_meshloc == MPG_MESHLOC_ELEMENT ? dst->nCells : dst->nVertices;
   if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
     mpg_set_error("mpg_regrid_store_periodic_to_mesh: %lld source points / %lld mesh points exceed int32 ids", (long long)n_src, (long long)n_dst);
     return MPG_ERR_OVERFLOW;
@@ -1259,11 +1263,13 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle h, const void *src_dev, int src_type, 
 }
 
 // ---- the wind chain turned round: U / V staggers onto mesh points, one pass (k_wind_pair.hip) -----------------------------------------
-// What mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev check alike, under the caller's name: the handles, the enums, the strides (out:
+// What mpg_wind_to_mesh_dev and mpg_wind_to_edges_dev, and their twins for CSR handles further down, check alike, under the caller's name: the handles, the enums, the strides (out:
 // ldu / ldv in elements) and the aliases of the results r0 / r1 with each other, the sources and the angles a0 / a1.
 struct WindCall {
   const char *who, *results, *angles;   // "mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev"
   bool need_angles, need_r1;            // false: both angles may be NULL together / r1 may be NULL
+  bool csr;                             // the handles this call takes: CSR ones (k_wind_csr.hip) or fixed ones (k_wind_pair.hip)
+  const char *twin;                     // the call that takes the other kind
 };
 static int wind_pair_checks(const WindCall &c, mpg_handle rh_u, mpg_handle rh_v, const double *a0, const double *a1, const void *u_dev,
                             const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *r0, void *r1,
@@ -1284,14 +1290,24 @@ static int wind_pair_checks(const WindCall &c, mpg_handle rh_u, mpg_handle rh_v,
   if ((src_type | dst_type) & MPG_TYPE_BE)
     return fail(MPG_ERR_UNSUPPORTED, "big-endian values (MPG_TYPE_BE) are not supported; mpg_bswap_dev swaps an array in place before or after the call");
   for (mpg_handle h : {rh_u, rh_v}) {
-    if (h->kind != MPG_KIND_FIXED)
-      return fail(MPG_ERR_UNSUPPORTED, "CSR handles (conservative, periodic, from-weights) are not supported: pairs of fixed 4-slot or 1-slot handles are. "
-                                       "mpg_regrid_csr_to_mesh_dev into float64 on each handle, then the rotation, is the route for those.");
+    if (c.csr && h->n_pole > 0)   // (whatever its kind: the message that helps is the one about the pole terms)
+      return fail(MPG_ERR_UNSUPPORTED, "handles with pole-cap terms (periodic Grid -> Grid, mpg_handle_pole_count > 0) are not supported; "
+                                       "mpg_regrid_typed_dev on each handle, then the rotation, serves them");
+    if (!c.csr && h->kind != MPG_KIND_FIXED) {
+      mpg_set_error("%s: CSR handles (conservative, periodic, from-weights) are not supported: pairs of fixed 4-slot or 1-slot handles are. "
+                    "%s serves pairs of CSR handles in one pass.", who, c.twin);
+      return MPG_ERR_UNSUPPORTED;
+    }
+    if (c.csr && h->kind != MPG_KIND_CSR) {
+      mpg_set_error("%s: fixed 1-, 3- and 4-slot handles are not supported: this call takes pairs of CSR handles. %s serves pairs of fixed "
+                    "4-slot or 1-slot handles.", who, c.twin);
+      return MPG_ERR_UNSUPPORTED;
+    }
     if (h->n_pole > 0)
       return fail(MPG_ERR_UNSUPPORTED, "handles with pole-cap terms (periodic Grid -> Grid) are not supported; mpg_regrid_typed_dev on each handle, then "
                                        "the rotation, serves them");
   }
-  if (rh_u->nnz_per_row != rh_v->nnz_per_row || (rh_u->nnz_per_row != 4 && rh_u->nnz_per_row != 1)) {
+  if (!c.csr && (rh_u->nnz_per_row != rh_v->nnz_per_row || (rh_u->nnz_per_row != 4 && rh_u->nnz_per_row != 1))) {
     mpg_set_error("%s: handles of %d and %d slots are not supported (both 4 -- bilinear -- or both 1 -- nearest); "
                   "mpg_regrid_to_mesh_dev into float64 on each handle, then the rotation, serves any fixed pair",
                   who, rh_u->nnz_per_row, rh_v->nnz_per_row);
@@ -1349,7 +1365,7 @@ int mpg_wind_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_de
                          int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev, void *ve_dev, int dst_type,
                          int dst_layout, void *hip_stream) {
   int64_t ldu, ldv;
-  int rc = wind_pair_checks({"mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev", false, true}, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev,
+  int rc = wind_pair_checks({"mpg_wind_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev", false, true, false, "mpg_wind_csr_to_mesh_dev"}, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev,
                             src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev, dst_type, dst_layout, &ldu, &ldv);
   if (rc) return rc;
   return mpg_k_wind_pair(false, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
@@ -1362,11 +1378,36 @@ int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev
                           int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *un_dev, void *ut_dev, int dst_type,
                           int dst_layout, void *hip_stream) {
   int64_t ldu, ldv;
-  int rc = wind_pair_checks({"mpg_wind_to_edges", "un_dev and ut_dev", "cn_dev, sn_dev", true, false}, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev,
+  int rc = wind_pair_checks({"mpg_wind_to_edges", "un_dev and ut_dev", "cn_dev, sn_dev", true, false, false, "mpg_wind_csr_to_edges_dev"}, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev,
                             src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev, dst_type, dst_layout, &ldu, &ldv);
   if (rc) return rc;
   return mpg_k_wind_pair(true, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
                          (hipStream_t)hip_stream);
+}
+
+// ---- the same two calls for CSR handles: winds from a periodic global grid, a conservative Store, from-weights (k_wind_csr.hip) ----------
+int mpg_wind_csr_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cosa_dev, const double *sina_dev, const void *u_dev,
+                             const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *ue_dev,
+                             void *ve_dev, int dst_type, int dst_layout, void *hip_stream) {
+  int64_t ldu, ldv;
+  int rc = wind_pair_checks({"mpg_wind_csr_to_mesh", "ue_dev and ve_dev", "cosa_dev, sina_dev", false, true, true, "mpg_wind_to_mesh_dev"}, rh_u, rh_v,
+                            cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, ue_dev, ve_dev, dst_type, dst_layout,
+                            &ldu, &ldv);
+  if (rc) return rc;
+  return mpg_k_wind_csr(false, rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, ue_dev, ve_dev, dst_type, dst_layout,
+                        (hipStream_t)hip_stream);
+}
+
+int mpg_wind_csr_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev,
+                              const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev, void *un_dev,
+                              void *ut_dev, int dst_type, int dst_layout, void *hip_stream) {
+  int64_t ldu, ldv;
+  int rc = wind_pair_checks({"mpg_wind_csr_to_edges", "un_dev and ut_dev", "cn_dev, sn_dev", true, false, true, "mpg_wind_to_edges_dev"}, rh_u, rh_v,
+                            cn_dev, sn_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, un_dev, ut_dev, dst_type, dst_layout,
+                            &ldu, &ldv);
+  if (rc) return rc;
+  return mpg_k_wind_csr(true, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
+                        (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

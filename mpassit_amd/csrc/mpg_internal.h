@@ -483,6 +483,9 @@ int mpg_k_apply_to_mesh(mpg_handle_s *h, const void *src, int src_type, int64_t 
 // nullptr, (r0, r1) = (ue, ve); edges true: mpg_wind_to_edges_dev, (c, s) = (cn, sn), (r0, r1) = (un, ut), ut may be nullptr
 int mpg_k_wind_pair(bool edges, mpg_handle_s *hu, mpg_handle_s *hv, const double *c, const double *s_, const void *u, const void *v, int src_type,
                     int64_t ldu, int64_t ldv, int nlev, void *r0, void *r1, int dst_type, int layout, hipStream_t s);
+// k_wind_csr.hip: the same for two CSR handles without pole terms (mpg_wind_csr_to_mesh_dev, mpg_wind_csr_to_edges_dev), the same arguments
+int mpg_k_wind_csr(bool edges, mpg_handle_s *hu, mpg_handle_s *hv, const double *c, const double *s_, const void *u, const void *v, int src_type,
+                   int64_t ldu, int64_t ldv, int nlev, void *r0, void *r1, int dst_type, int layout, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

@@ -448,6 +448,24 @@ module mpg
       integer(c_int64_t), value :: u_level_stride, v_level_stride
       integer(c_int) :: rc
     end function mpg_wind_to_edges_dev
+    !> the two wind calls for CSR handles (mpg_regrid_store_periodic_to_mesh: U and V of a global lat-lon or Gaussian analysis; the
+    !! conservative Stores; from-weights), with the argument lists and the meaning of their fixed-handle twins (include/mpassit_amd.h)
+    function mpg_wind_csr_to_mesh_dev(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, &
+                                      ue_dev, ve_dev, dst_type, dst_layout, hip_stream) bind(C, name="mpg_wind_csr_to_mesh_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, ue_dev, ve_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride, v_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_csr_to_mesh_dev
+    function mpg_wind_csr_to_edges_dev(rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, un_dev, &
+                                       ut_dev, dst_type, dst_layout, hip_stream) bind(C, name="mpg_wind_csr_to_edges_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, un_dev, ut_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride, v_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_csr_to_edges_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -24,7 +24,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
            "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
-           "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd"]
+           "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
+           "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd"]
 
 
 def _f64(a):
@@ -933,7 +934,8 @@ def regrid_store_to_mesh(src_grid, dst_mesh, regridmethod=REGRIDMETHOD_BILINEAR,
 def regrid_store_periodic_to_mesh(src_grid, dst_mesh, meshloc=MESHLOC_ELEMENT, pole_method=POLEMETHOD_ALLAVG):
     """ESMF_FieldRegridStore(grid field -> mesh field, regridmethod=BILINEAR, polemethod=pole_method) from a grid that is periodic in i
     (Grid(..., periodic=True), a global Grid.from_target / from_proj): the CENTER points onto the mesh's cells (MESHLOC_ELEMENT) or vertices
-    (MESHLOC_NODE), the seam column between i = nx - 1 and i = 0 and -- under POLEMETHOD_ALLAVG -- the pole caps included; POLEMETHOD_NONE
+    (MESHLOC_NODE) or, on a mesh with edges (Mesh.set_edges; without them rc 2), its edge points (MESHLOC_EDGE: the handle
+    wind_csr_to_edges takes), the seam column between i = nx - 1 and i = 0 and -- under POLEMETHOD_ALLAVG -- the pole caps included; POLEMETHOD_NONE
     leaves the points poleward of the first and last row unmapped.  Each end row closes on the pole of its own hemisphere (the sign of the
     row's mean z), so the rows may be numbered south to north or north to south (GRIB, ERA5, the Gaussian grids); GRID_NO_SOUTH_POLE /
     GRID_NO_NORTH_POLE name the row-0 / row-(ny-1) end of a row block, and two live ends in one hemisphere are refused (rc 2).  A CSR handle without pole terms (n_dst = the mesh count; quad rows of 4
@@ -1114,9 +1116,13 @@ def _wind_pair(who, call, rh_u, rh_v, angles, names, need_angles, u, v, nlev, la
         for rh in (rh_u, rh_v):  # the indices and weights of both handles and the angles (when given) once
             if getattr(rh, "_acc_U", None) is None:
                 rh._acc_U = int(rh.unique_sources().size)
+        if rh_u.nnz_per_row == 0:   # CSR handles: 12 nnz + 4 (P + 1) per DISTINCT handle (one handle given twice is staged once)
+            wbytes = sum(12 * rh.nnz + 4 * (rh.n_dst + 1) for rh in ((rh_u,) if rh_v is rh_u else (rh_u, rh_v)))
+        else:
+            wbytes = rh_u.n_dst * 2 * rh_u.nnz_per_row * 12
         ACCOUNT.append(("%s nnz%d L%d%s" % (who, rh_u.nnz_per_row, nlev, label),
                         nlev * (rh_u._acc_U + rh_v._acc_U) * u.element_size() + nout * rh_u.n_dst * nlev * res[0].element_size()
-                        + rh_u.n_dst * (2 * rh_u.nnz_per_row * 12 + (16 if angles[0] is not None else 0))))
+                        + wbytes + rh_u.n_dst * (16 if angles[0] is not None else 0)))
 
     def p(t):
         return t.data_ptr() if t is not None else None
@@ -1153,9 +1159,11 @@ def mesh_rotang(grid, mesh, meshloc=MESHLOC_ELEMENT):
 
 
 def _unmapped_mask(rh):
-    """The points a fixed handle leaves unmapped (idx[0] < 0) as a bool CUDA tensor [n_dst], downloaded once per handle object."""
+    """The points a handle leaves unmapped -- a fixed one: idx[0] < 0; a CSR one: the row is empty -- as a bool CUDA tensor [n_dst],
+    downloaded once per handle object."""
     if getattr(rh, "_unmapped_dev", None) is None:
-        rh._unmapped_dev = _torch.as_tensor(rh.weights()[0][:, 0] < 0, device="cuda")
+        un = np.diff(rh.csr()[0]) == 0 if rh.nnz_per_row == 0 else rh.weights()[0][:, 0] < 0
+        rh._unmapped_dev = _torch.as_tensor(un, device="cuda")
     return rh._unmapped_dev
 
 
@@ -1273,3 +1281,62 @@ def wind_to_edges_autograd(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FA
     rh_v.regrid_transpose(g_b) are returned in u's and v's shapes and dtypes: the exact adjoint of the forward.  The first backward on a
     handle downloads its indices once for the mask."""
     return WindToEdgesFunction.apply(u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential)
+
+
+def wind_csr_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, outs=None):
+    """mpg_wind_csr_to_mesh_dev: wind_to_mesh for CSR handles -- regrid_store_periodic_to_mesh (U and V of a global lat-lon or Gaussian
+    analysis), regrid_store_conserve_to_mesh, regrid_store_conserve_mesh, RouteHandle.from_weights -- in one pass: ue = a ca - b sa,
+    ve = a sa + b ca with a, b the float64 results of rh_u.regrid_csr_to_mesh(u) and rh_v.regrid_csr_to_mesh(v); cosa / sina both None:
+    no rotation (ue = a, ve = b).  rh_u is rh_v is the main case (a collocated analysis): the handle is staged once.  The arguments and
+    results are wind_to_mesh's; a point whose row is empty in either handle is +0.0 in both results.  Bit-identical to the separate
+    calls.  Under POLEMETHOD_ALLAVG a cap point gets the row mean of each COMPONENT, which is not a wind (include/mpassit_amd.h)."""
+    return _wind_pair("wind_csr_to_mesh", L.wind_csr_to_mesh_dev, rh_u, rh_v, (cosa, sina), "cosa / sina", False, u, v, nlev, layout, out_dtype, outs, 2)
+
+
+def wind_csr_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, tangential=False, outs=None):
+    """mpg_wind_csr_to_edges_dev: wind_to_edges for CSR handles onto the mesh's edges (the typical one:
+    regrid_store_periodic_to_mesh(grid, mesh, meshloc=MESHLOC_EDGE), given as rh_u and rh_v), in one pass: un = a cn + b sn, the
+    edge-normal wind `u` MPAS carries, and with tangential=True ut = b cn - a sn, with a, b the float64 results of
+    rh_u.regrid_csr_to_mesh(u) and rh_v.regrid_csr_to_mesh(v) and cn / sn of mesh_edge_rotang (grid=None for the earth-relative winds of
+    a lat-lon analysis; required).  The arguments and results are wind_to_edges'; a point whose row is empty in either handle is +0.0.
+    Bit-identical to the separate calls.  The cap caveat of wind_csr_to_mesh holds here too."""
+    nout = 2 if tangential else 1
+    if _is_torch(outs):
+        outs = (outs,)
+    res = _wind_pair("wind_csr_to_edges", L.wind_csr_to_edges_dev, rh_u, rh_v, (cn, sn), "cn / sn", True, u, v, nlev, layout, out_dtype, outs, nout,
+                     label=" x%d" % nout)
+    return res if tangential else res[0]
+
+
+if _torch is not None:
+    class WindCsrToMeshFunction(WindToMeshFunction):
+        """wind_csr_to_mesh with a gradient: WindToMeshFunction's backward (the mask of a CSR handle is "row empty") behind the CSR
+        forward.  Use wind_csr_to_mesh_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, v, rh_u, rh_v, cosa, sina, nlev, layout):
+            ctx.rh_u, ctx.rh_v, ctx.cosa, ctx.sina, ctx.nlev, ctx.layout = rh_u, rh_v, cosa, sina, nlev, layout
+            ctx.shapes, ctx.dtypes = (u.shape, v.shape), (u.dtype, v.dtype)
+            return wind_csr_to_mesh(rh_u, rh_v, cosa, sina, u.contiguous(), v.contiguous(), nlev, layout=layout, out_dtype=u.dtype)
+
+    class WindCsrToEdgesFunction(WindToEdgesFunction):
+        """wind_csr_to_edges with a gradient: WindToEdgesFunction's backward behind the CSR forward.  Use wind_csr_to_edges_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential):
+            ctx.rh_u, ctx.rh_v, ctx.cn, ctx.sn, ctx.nlev, ctx.layout, ctx.tangential = rh_u, rh_v, cn, sn, nlev, layout, tangential
+            ctx.shapes, ctx.dtypes = (u.shape, v.shape), (u.dtype, v.dtype)
+            return wind_csr_to_edges(rh_u, rh_v, cn, sn, u.contiguous(), v.contiguous(), nlev, layout=layout, out_dtype=u.dtype, tangential=tangential)
+
+
+def wind_csr_to_mesh_autograd(rh_u, rh_v, cosa, sina, u, v, nlev, layout=LAYOUT_CELL_FAST):
+    """wind_csr_to_mesh(rh_u, rh_v, cosa, sina, u, v, nlev, layout) in u's dtype as a differentiable torch op: the gradients of
+    wind_to_mesh_autograd, with "unmapped" read as "the row is empty" (the first backward on a handle downloads its row pointers once)
+    and each handle's regrid_transpose, which serves CSR handles."""
+    return WindCsrToMeshFunction.apply(u, v, rh_u, rh_v, cosa, sina, nlev, layout)
+
+
+def wind_csr_to_edges_autograd(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CELL_FAST, tangential=False):
+    """wind_csr_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout, tangential=tangential) in u's dtype as a differentiable torch op: the
+    gradients of wind_to_edges_autograd, with "unmapped" read as "the row is empty" and each handle's regrid_transpose."""
+    return WindCsrToEdgesFunction.apply(u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential)
