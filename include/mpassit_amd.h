@@ -336,12 +336,17 @@ int mpg_regrid_pitched_dev(mpg_handle rh, const double *src_dev, int src_layout,
 /* Fused ingest/egress Regrid (the callers either side of the hot path): the source may be
  * float32 (MPAS history variables are single precision; the reference widens them at read, input_data.F90:630-655)
  * and the destination float32 (every output variable is NF90_FLOAT, write_data.F90:779).  The arithmetic stays
- * float64 and  dst = (dst type)( regrid(src) * scale + offset )  reproduces the writer's post-ops (T - 300,
+ * float64 and  dst = (dst type) fma(regrid(src), scale, offset)  reproduces the writer's post-ops (T - 300,
  * write_data.F90:1343; PHB * 9.81, :1418), so float32 results are bit-identical to the reference's file contents.
  * src_type / dst_type: MPG_TYPE_F64 or MPG_TYPE_F32, optionally | MPG_TYPE_BE: the values are big-endian in memory, as a
  * NetCDF classic (CDF-1/2/5) variable stores them -- the bytes of nf90_get_var's source (input_data.F90:630) and of
  * nf90_put_var's destination (write_data.F90:1339-1475) travel file <-> HBM untouched (mpg_file_to_dev / mpg_dev_to_file)
  * and the Regrid reads / writes them as they are: no byte-swap pass over the data exists.
+ * The sum itself, a contract by identity for every call that applies a handle: a fixed handle's slots in stored order -- one slot (nearest)
+ * is a copy of the source value, three slots (w0, a), (w1, b), (w2, e) give fma(w2, e, fma(w1, b, w0 * a)), four give the chain
+ * acc = fma(w[q], src[idx[q]], acc) from 0.0 -- and +0.0 for an unmapped point; a CSR row is that chain over its entries in stored order,
+ * +0.0 when empty.  mpg_regrid_dev stores the sum as it stands (a -0.0 stays -0.0); every typed call stores (dst type) fma(sum, scale, offset),
+ * unmapped points included.
  * Device pointers, stream as in mpg_regrid_dev. */
 enum { MPG_TYPE_F64 = 0, MPG_TYPE_F32 = 1, MPG_TYPE_BE = 2 };
 int mpg_regrid_typed_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields,
@@ -373,8 +378,8 @@ int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, i
  * src_dev: [nfields][nlev][plane], plane = n_src of mpg_handle_info, planes src_level_stride elements apart (0 = dense; below n_src ->
  * MPG_ERR_INVALID_ARG); a pitched result of the *_pitched_dev calls is accepted as it is, its pad is never read.
  * dst_dev: nfields slabs of nlev * n_dst in dst_layout: MPG_LAYOUT_CELL_FAST [lev][cell] or MPG_LAYOUT_LEV_FAST [cell][lev] (MPAS file
- * order: the slab can go into an init or restart file as it is).  Fully overwritten; unmapped points get (dst type)(0.0 * scale + offset).
- * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type)( regrid(src) * scale + offset ) rounded once
+ * order: the slab can go into an init or restart file as it is).  Fully overwritten; unmapped points get (dst type) fma(0.0, scale, offset).
+ * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type) fma(regrid(src), scale, offset) rounded once
  * at the store; MPG_TYPE_BE -> MPG_ERR_UNSUPPORTED.  MPG_ERR_UNSUPPORTED too for CSR handles (conservative, from-weights) and for handles
  * with pole caps.
  * Contract by identity, no tolerance: with MPG_LAYOUT_CELL_FAST the bytes equal what mpg_regrid_typed_dev(rh, src, src_type,
@@ -422,7 +427,7 @@ int mpg_handle_get_dst_frac(mpg_handle rh, double *frac_host);   /* [n_dst]; MPG
  * Contract by identity, no tolerance: a row's value is acc = fma(val[q], src[col[q]], acc) from 0.0 in stored order, then the epilogue
  * -- the expression of the typed Regrid's CSR kernel -- so with MPG_LAYOUT_CELL_FAST the bytes equal what mpg_regrid_typed_dev writes on
  * the same handle from a dense source, and with MPG_LAYOUT_LEV_FAST element [c][k] has the bits of element [k][c] of that result; an
- * empty row gives (dst type)(0.0 * scale + offset).  The same bits across calls, across nfields batching and between a pitched and a
+ * empty row gives (dst type) fma(0.0, scale, offset).  The same bits across calls, across nfields batching and between a pitched and a
  * dense source.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing: it can be captured in a
  * hipGraph from the first call. */
 int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
@@ -433,8 +438,8 @@ int mpg_regrid_csr_to_mesh_dev(mpg_handle rh, const void *src_dev, int src_type,
  * handle with 1, 3 or 4 slots and no pole caps is accepted.
  * src_dev: nfields slabs of [n_src][nlev], n_src the handle's current index space (the window count after mpg_mesh_set_source_window,
  * the local extent after mpg_handle_localize / rebase).  dst_dev: nfields slabs of [n_dst][nlev], fully overwritten; an unmapped point
- * gets (dst type)(0.0 * scale + offset).
- * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type)( regrid(src) * scale + offset ) rounded once
+ * gets (dst type) fma(0.0, scale, offset).
+ * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, dst = (dst type) fma(regrid(src), scale, offset) rounded once
  * at the store.  Refusals.  MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; CSR handles (conservative, from-weights: mpg_regrid_csr_rows_dev serves
  * them); handles with pole caps.
  * MPG_ERR_INVALID_ARG: nlev < 1, nfields < 1, NULL.
@@ -482,7 +487,7 @@ int mpg_regrid_rows_dev(mpg_handle rh, const void *src_dev, int src_type, int nl
  *   MPG_ERR_INVALID_ARG: nlev < 1, nfields < 1, NULL.
  *   Contract by identity, no tolerance: acc = fma(val[q], src[col[q] * nlev + k], acc) from 0.0 in stored order, then
  *   (dst type) fma(acc, scale, offset); element [p][k] has the bits of element [k][p] of what mpg_regrid_typed_dev(rh, src, src_type,
- *   MPG_LAYOUT_LEV_FAST, ...) writes on the same handle; an empty row gives (dst type)(0.0 * scale + offset).  The same bits across
+ *   MPG_LAYOUT_LEV_FAST, ...) writes on the same handle; an empty row gives (dst type) fma(0.0, scale, offset).  The same bits across
  *   calls and across nfields batching.  No atomics.  Stream as mpg_regrid_dev.  The call allocates nothing and synchronises nothing:
  *   it can be captured in a hipGraph from the first call. */
 int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mpg_handle *out);
@@ -505,7 +510,7 @@ int mpg_handle_transpose_build_ms(mpg_handle rh, float *ms);
  *   N          the unmasked Regrid's own expression with weight AND value of every invalid entry replaced by 0.0 (a missing NaN never
  *              enters a product)
  *   defined    the point has at least one stored entry, Wv > 0 and Wv >= min_valid_frac * Wt
- *   result     defined: dst = (dst type)( N * (Wt / Wv) * scale + offset );  undefined -- unmapped points included --:
+ *   result     defined: dst = (dst type) fma(N * (Wt / Wv), scale, offset);  undefined -- unmapped points included --:
  *              dst = (dst type) fill_value, whatever scale and offset are (fill_value for unmapped points: a result can tell
  *              "no data" from 0).  Wt / Wv keeps a partly covered conservative cell scaled as the unmasked Regrid scales it; for
  *              bilinear weights (Wt = 1 up to rounding) it is the usual renormalisation.

@@ -56,7 +56,7 @@ def test_header_states_the_rules():
     for phrase in ("[n_src][nlev]", "[n_dst][nlev]", "ANY CSR handle without pole caps", "mpg_handle_from_weights",
                    "MPG_ERR_UNSUPPORTED: a fixed handle (mpg_regrid_rows_dev serves those); MPG_TYPE_BE", "nlev < 1", "nfields < 1",
                    "Contract by identity, no tolerance", "fma(val[q], src[col[q] * nlev + k], acc)", "stored order",
-                   "element [p][k] has the bits of element [k][p]", "MPG_LAYOUT_LEV_FAST", "(dst type)(0.0 * scale + offset)", "nfields batching",
+                   "element [p][k] has the bits of element [k][p]", "MPG_LAYOUT_LEV_FAST", "(dst type) fma(0.0, scale, offset)", "nfields batching",
                    "No atomics", "allocates nothing and synchronises nothing", "hipGraph from the first call"):
         assert phrase in doc, phrase
 

@@ -50,7 +50,7 @@ def test_header_states_the_rules():
                    "ny_dst = 1", "mpg_regrid_rows_dev"):
         assert phrase in doc, phrase
     doc = _doc(APPLY, "Regrid from rows to rows")
-    for phrase in ("[cell][lev] in and [cell][lev] out", "1, 3 or 4 slots", "no pole caps", "(dst type)(0.0 * scale + offset)",
+    for phrase in ("[cell][lev] in and [cell][lev] out", "1, 3 or 4 slots", "no pole caps", "(dst type) fma(0.0, scale, offset)",
                    "MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; CSR handles", "pole caps", "nlev < 1", "Contract by identity, no tolerance",
                    "element [p][k] has the bits of element [k][p]", "MPG_LAYOUT_LEV_FAST", "mpg_regrid_typed_dev", "nfields batching", "No atomics",
                    "allocates nothing and synchronises nothing", "hipGraph"):
