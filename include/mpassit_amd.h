@@ -709,7 +709,7 @@ int mpg_wind_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev
  * give, and not a wind: for a solid-body rotation of unit speed about an axis tilted 45 degrees, from a 72 x 36 grid onto the 59 994
  * edges of a 20 000-cell mesh, un is off by at most 1.41e-3 on quad rows and by up to 0.53 on the 57 cap edges (24 x 12: 1.23e-2 and
  * 0.71).  A host that cares stores with MPG_POLEMETHOD_NONE and fills the cap points itself (mpg_regrid_masked_dev, a nearest handle);
- * a Cartesian-vector Regrid is the real answer and is not built.
+ * a Cartesian-vector Regrid (ESMF 8.6's vectorRegrid) is the real answer: mpg_wind_vector_dev, below (6.0e-4 on those 57 cap edges).
  * Refusals, each with a message that names the way out, under the names mpg_wind_csr_to_mesh / mpg_wind_csr_to_edges.
  * MPG_ERR_UNSUPPORTED: a fixed handle on either side (mpg_wind_to_mesh_dev / mpg_wind_to_edges_dev serve those), a handle with pole
  * terms (mpg_handle_pole_count > 0), MPG_TYPE_BE on either side.  MPG_ERR_INVALID_ARG: NULL handles or arrays, exactly one NULL angle
@@ -721,6 +721,56 @@ int mpg_wind_csr_to_mesh_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cos
 int mpg_wind_csr_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn_dev, const double *sn_dev, const void *u_dev,
                               const void *v_dev, int src_type, int64_t u_level_stride, int64_t v_level_stride, int nlev,
                               void *un_dev, void *ut_dev, int dst_type, int dst_layout, void *hip_stream);
+/* A wind as a VECTOR through one CSR handle (ESMF 8.6's vectorRegrid): (u, v) at every source point is taken to a Cartesian 3-vector
+ * with the source point's local frame, the three components are regridded with the handle's weights, and the result is projected onto
+ * the destination point's frame.  Under MPG_POLEMETHOD_ALLAVG a cap point then gets the mean of the row's VECTORS as seen from the cap
+ * point, which is a wind (the solid-body case of the caveat above: 6.0e-4 on the 57 cap edges where the two scalar Regrids are off by
+ * 0.53; on quad rows 1.88e-3 against 1.41e-3, because the chord of the interpolated position shrinks the vector, as it does in ESMF:
+ * the calls stand beside mpg_wind_csr_to_mesh_dev / mpg_wind_csr_to_edges_dev, not in their place).  The weights do not depend on the
+ * level, so the three steps fold into one 2 x 2 block per CSR entry, computed once per (handle, frames); the hot path is four fmas and
+ * two gathers per entry and level, for every CSR handle: periodic, conservative Grid -> Mesh, conservative Mesh -> Mesh, from-weights.
+ * None of the three calls allocates, synchronises with the host or uses atomics: all can be captured in a hipGraph from their first
+ * call.  Stream as mpg_regrid_dev.  The calls do not look at the mesh or the grid.
+ *
+ * mpg_sphere_frames_dev: the frames of n points.  lon_dev / lat_dev [n] float64, radians.  frames_dev [6][n] float64, the planes
+ *   D0x D0y D0z D1x D1y D1z.  east = (-sin lon, cos lon, 0), north = (-sin lat cos lon, -sin lat sin lon, cos lat).
+ *   c_dev, s_dev both NULL: D0 = east, D1 = north -- earth-relative winds.  Both set ([n] float64): D0 = c east + s north,
+ *   D1 = c north - s east, every product and sum rounded (fp contract(off)).  cosa / sina for the grid-relative winds of a Lambert
+ *   grid; cos / sin of angleEdge for (normal, tangent) at mesh edges, so that un / ut need no second rotation; what
+ *   mpg_mesh_edge_rotang_dev gives to go straight to un / ut of a projected grid.  Exactly one NULL -> MPG_ERR_INVALID_ARG; so are NULL
+ *   lon_dev / lat_dev / frames_dev (checked before the n == 0 success), n < 0 and frames aliasing an input.
+ *
+ * mpg_wind_vector_weights_dev: the blocks of (handle, frames).  src_frames_dev [6][n_src], dst_frames_dev [6][n_dst], m_dev [4][nnz]:
+ *   the planes m00 m01 m10 m11 in the handle's CSR entry order (mpg_handle_get_csr); the caller owns m_dev, 4 * nnz doubles with nnz
+ *   from mpg_handle_info.  The same bits as numpy: for entry q of row p with c = col[q]
+ *     m00 = val[q] * ((e.x*D0.x + e.y*D0.y) + e.z*D0.z)     e  = source D0 at c,  D0 = destination D0 at p
+ *     m01 = val[q] * ((n.x*D0.x + n.y*D0.y) + n.z*D0.z)     n  = source D1 at c
+ *     m10, m11                                              the same against the destination D1
+ *   every operation rounded, nothing contracted.  A handle with no entries is success and writes nothing.
+ *
+ * mpg_wind_vector_dev: the apply.  The arguments are those of mpg_wind_csr_to_mesh_dev with one handle and m_dev in place of the
+ *   angles: u_level_stride / v_level_stride in elements, 0 = dense, below n_src -> MPG_ERR_INVALID_ARG; results in MPG_LAYOUT_CELL_FAST
+ *   [lev][point] or MPG_LAYOUT_LEV_FAST [point][lev], fully overwritten.  r1_dev may be NULL: then only r0 is computed and only the
+ *   planes m00, m01 are read -- un alone.  Values, a contract by identity, per (point, level):
+ *     acc_kl = fma(m_kl[q], (double)src_l[col[q]], acc_kl)    from 0.0, in stored order, whatever LDS chunk an entry arrives in
+ *     o0 = fma(acc00, 1.0, 0.0) + fma(acc01, 1.0, 0.0)        src_0 = U, src_1 = V
+ *     o1 = fma(acc10, 1.0, 0.0) + fma(acc11, 1.0, 0.0)
+ *     store (TD)o0 [, (TD)o1]                                 one rounding to the destination type
+ *   o0 is bit for bit mpg_regrid_csr_to_mesh_dev of a from-weights handle with values m00 applied to U, plus the same with m01 applied
+ *   to V, both into float64 with scale 1 and offset 0, added once.  An empty row gives (TD)(+0.0).  The same bits for both layouts, for
+ *   dense and pitched sources, and from call to call.  n_dst == 0 is success; a handle with no entries gives zeroed results.
+ * Refusals, each with a message that names the call and the way out, under the names mpg_sphere_frames / mpg_wind_vector_weights /
+ * mpg_wind_vector.  MPG_ERR_UNSUPPORTED: a fixed handle (mpg_handle_get_weights -> mpg_handle_from_weights makes a CSR handle of
+ * it), a handle with pole terms (mpg_handle_pole_count > 0), MPG_TYPE_BE on either side.  MPG_ERR_INVALID_ARG: NULL handle or arrays,
+ * nlev < 1, unknown enums, a level stride below n_src, results aliasing each other, a source or m_dev.  MPG_ERR_OVERFLOW: more
+ * 64-point blocks than one launch holds. */
+int mpg_sphere_frames_dev(int64_t n, const double *lon_dev, const double *lat_dev, const double *c_dev, const double *s_dev,
+                          double *frames_dev, void *hip_stream);
+int mpg_wind_vector_weights_dev(mpg_handle rh, const double *src_frames_dev, const double *dst_frames_dev, double *m_dev,
+                                void *hip_stream);
+int mpg_wind_vector_dev(mpg_handle rh, const double *m_dev, const void *u_dev, const void *v_dev, int src_type,
+                        int64_t u_level_stride, int64_t v_level_stride, int nlev, void *r0_dev, void *r1_dev, int dst_type,
+                        int dst_layout, void *hip_stream);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

@@ -31,6 +31,7 @@ SYMBOLS = [
     "mpg_wind_to_mesh_dev", "mpg_mesh_rotang_dev",
     "mpg_mesh_set_edges", "mpg_mesh_edge_count", "mpg_mesh_edge_rotang_dev", "mpg_wind_to_edges_dev",
     "mpg_wind_csr_to_mesh_dev", "mpg_wind_csr_to_edges_dev",
+    "mpg_sphere_frames_dev", "mpg_wind_vector_weights_dev", "mpg_wind_vector_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -264,6 +265,38 @@ def wind_csr_to_edges_dev(*args):
     if "wind_csr_edges" not in _to_mesh_fns:
         _to_mesh_fns["wind_csr_edges"] = _WIND_CSR_TO_EDGES_PROTO(("mpg_wind_csr_to_edges_dev", load()))
     return _to_mesh_fns["wind_csr_edges"](*args)
+
+
+# A wind as a vector through one CSR handle, bound the same way.
+#   mpg_sphere_frames_dev(n, lon_dev, lat_dev, c_dev, s_dev, frames_dev, hip_stream)
+#   mpg_wind_vector_weights_dev(rh, src_frames_dev, dst_frames_dev, m_dev, hip_stream)
+#   mpg_wind_vector_dev(rh, m_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, r0_dev, r1_dev, dst_type, dst_layout,
+#                       hip_stream)
+_SPHERE_FRAMES_PROTO = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_WIND_VECTOR_WEIGHTS_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_WIND_VECTOR_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+
+
+def sphere_frames_dev(*args):
+    """The typed binding of mpg_sphere_frames_dev; returns the call's status code."""
+    if "frames" not in _to_mesh_fns:
+        _to_mesh_fns["frames"] = _SPHERE_FRAMES_PROTO(("mpg_sphere_frames_dev", load()))
+    return _to_mesh_fns["frames"](*args)
+
+
+def wind_vector_weights_dev(*args):
+    """The typed binding of mpg_wind_vector_weights_dev; returns the call's status code."""
+    if "vector_weights" not in _to_mesh_fns:
+        _to_mesh_fns["vector_weights"] = _WIND_VECTOR_WEIGHTS_PROTO(("mpg_wind_vector_weights_dev", load()))
+    return _to_mesh_fns["vector_weights"](*args)
+
+
+def wind_vector_dev(*args):
+    """The typed binding of mpg_wind_vector_dev; returns the call's status code."""
+    if "vector" not in _to_mesh_fns:
+        _to_mesh_fns["vector"] = _WIND_VECTOR_PROTO(("mpg_wind_vector_dev", load()))
+    return _to_mesh_fns["vector"](*args)
 
 
 _lib = None

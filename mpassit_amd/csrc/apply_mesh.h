@@ -3,7 +3,8 @@
 // (point, level) cursor along a block's [cell][lev] run, the drain of the [cell][lev] result tile, and on the host the tile plan, the
 // launch grid, the path of a handle without sources and the (src_type, dst_type) dispatch.  One workgroup of 256 threads owns AM_CELLS
 // consecutive destination points and all levels in every one of the six; the LDS arrays are declared by the kernels (dynamic or static)
-// and handed in as pointers; the main loops stay there.
+// and handed in as pointers; the main loops stay there.  k_wind_vector.hip is the seventh: it stages its run through CsrRunN, which stands
+// beside CsrRun and changes nothing the six compile.
 #pragma once
 #include <algorithm>
 
@@ -64,6 +65,50 @@ __device__ __forceinline__ CsrRun am_csr_run(const int32_t *__restrict__ rowptr,
   __syncthreads();
   CsrRun r{col, val, scol, sval, t, srp[0], srp[AM_CELLS], 0};
   r.nchunk = (int)(((int64_t)r.r1 - r.r0 + AM_CHUNK - 1) / AM_CHUNK);
+  if (r.nchunk == 1) {
+    r.stage(r.r0);
+    __syncthreads();
+  }
+  return r;
+}
+
+// The same run with NV value planes per entry, vstride elements apart in memory (k_wind_vector.hip: the 2 x 2 block of an entry), CH
+// entries resident at a time: sval[NV][CH].  What CsrRun says about nchunk and the barriers of enter() holds here.
+template <int NV, int CH>
+struct CsrRunN {
+  const int32_t *col;
+  const double *val;
+  int64_t vstride;
+  int32_t *scol;
+  double *sval;
+  int t, r0, r1, nchunk;
+  __device__ __forceinline__ void stage(int qa) const {
+    const int n = min(CH, r1 - qa);
+    for (int i = t; i < n; i += 256) {
+      scol[i] = col[qa + i];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sval[k * CH + i] = val[k * vstride + qa + i];
+    }
+  }
+  // chunk ch (ch * CH < r1 - r0) is resident on return; its first entry qa: plane k of entry q of the run is sval[k * CH + q - qa]
+  __device__ __forceinline__ int enter(int ch) const {
+    const int qa = r0 + ch * CH;
+    if (nchunk > 1) {
+      __syncthreads();   // the chunk before has been walked by every wave
+      stage(qa);
+      __syncthreads();
+    }
+    return qa;
+  }
+};
+template <int NV, int CH>
+__device__ __forceinline__ CsrRunN<NV, CH> am_csr_run_n(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                        const double *__restrict__ val, int64_t vstride, int64_t P, int64_t p0, int t,
+                                                        int32_t *srp, int32_t *scol, double *sval) {
+  if (t <= AM_CELLS) srp[t] = rowptr[min(p0 + t, P)];   // rows past the end are empty
+  __syncthreads();
+  CsrRunN<NV, CH> r{col, val, vstride, scol, sval, t, srp[0], srp[AM_CELLS], 0};
+  r.nchunk = (int)(((int64_t)r.r1 - r.r0 + CH - 1) / CH);
   if (r.nchunk == 1) {
     r.stage(r.r0);
     __syncthreads();

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mpg_internal.h"
+#include "wind_vector_checks.h"
 
 static thread_local char g_err[1024] = "";
 static bool g_init = false;
@@ -125,7 +126,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr)
+  X(k_wind_csr) X(k_wind_vector)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1408,6 +1409,48 @@ int mpg_wind_csr_to_edges_dev(mpg_handle rh_u, mpg_handle rh_v, const double *cn
   if (rc) return rc;
   return mpg_k_wind_csr(true, rh_u, rh_v, cn_dev, sn_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, un_dev, ut_dev, dst_type, dst_layout,
                         (hipStream_t)hip_stream);
+}
+
+// ---- a wind as a vector through one CSR handle: frames, 2 x 2 blocks, apply (k_wind_vector.hip) ------------------------------------------
+// The checks are host-only text of their own (wind_vector_checks.h), so that a stand-alone program can run them.
+static int wv_refused(int rc, const WvErr &e) {
+  mpg_set_error("%s", e.msg);
+  return rc;
+}
+static WvHandle wv_handle(mpg_handle rh) { return WvHandle{rh->kind == MPG_KIND_CSR, rh->n_pole, rh->n_src, rh->n_dst, rh->nnz}; }
+
+int mpg_sphere_frames_dev(int64_t n, const double *lon_dev, const double *lat_dev, const double *c_dev, const double *s_dev,
+                          double *frames_dev, void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  int rc = wv_check_frames(n, lon_dev, lat_dev, c_dev, s_dev, frames_dev, e);
+  if (rc) return wv_refused(rc, e);
+  return mpg_k_sphere_frames(n, lon_dev, lat_dev, c_dev, s_dev, frames_dev, (hipStream_t)hip_stream);
+}
+
+int mpg_wind_vector_weights_dev(mpg_handle rh, const double *src_frames_dev, const double *dst_frames_dev, double *m_dev, void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  WvHandle h{};
+  if (rh) h = wv_handle(rh);
+  bool nothing;
+  int rc = wv_check_weights(rh ? &h : nullptr, src_frames_dev, dst_frames_dev, m_dev, &nothing, e);
+  if (rc) return wv_refused(rc, e);
+  if (nothing) return MPG_SUCCESS;   // no entries: nothing to write
+  return mpg_k_wind_vector_weights(rh, src_frames_dev, dst_frames_dev, m_dev, (hipStream_t)hip_stream);
+}
+
+int mpg_wind_vector_dev(mpg_handle rh, const double *m_dev, const void *u_dev, const void *v_dev, int src_type, int64_t u_level_stride,
+                        int64_t v_level_stride, int nlev, void *r0_dev, void *r1_dev, int dst_type, int dst_layout, void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  WvHandle h{};
+  if (rh) h = wv_handle(rh);
+  int64_t ldu, ldv;
+  int rc = wv_check_apply(rh ? &h : nullptr, m_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, r0_dev, r1_dev, dst_type, dst_layout,
+                          &ldu, &ldv, e);
+  if (rc) return wv_refused(rc, e);
+  return mpg_k_wind_vector(rh, m_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, r0_dev, r1_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

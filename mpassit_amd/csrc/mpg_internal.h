@@ -486,6 +486,13 @@ int mpg_k_wind_pair(bool edges, mpg_handle_s *hu, mpg_handle_s *hv, const double
 // k_wind_csr.hip: the same for two CSR handles without pole terms (mpg_wind_csr_to_mesh_dev, mpg_wind_csr_to_edges_dev), the same arguments
 int mpg_k_wind_csr(bool edges, mpg_handle_s *hu, mpg_handle_s *hv, const double *c, const double *s_, const void *u, const void *v, int src_type,
                    int64_t ldu, int64_t ldv, int nlev, void *r0, void *r1, int dst_type, int layout, hipStream_t s);
+// k_wind_vector.hip: a wind as a vector through ONE CSR handle without pole terms (arguments checked by the API entry points): the
+// frames [6][n] of n points (c, s both nullptr: east / north), the 2 x 2 blocks m[4][nnz] of (handle, frames), and the apply of the
+// blocks to (u, v), r1 == nullptr: r0 alone
+int mpg_k_sphere_frames(int64_t n, const double *lon, const double *lat, const double *c, const double *s_, double *frames, hipStream_t s);
+int mpg_k_wind_vector_weights(mpg_handle_s *h, const double *src_frames, const double *dst_frames, double *m, hipStream_t s);
+int mpg_k_wind_vector(mpg_handle_s *h, const double *m, const void *u, const void *v, int src_type, int64_t ldu, int64_t ldv, int nlev,
+                      void *r0, void *r1, int dst_type, int layout, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

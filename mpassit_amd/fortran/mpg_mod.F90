@@ -466,6 +466,27 @@ module mpg
       integer(c_int64_t), value :: u_level_stride, v_level_stride
       integer(c_int) :: rc
     end function mpg_wind_csr_to_edges_dev
+    !> a wind as a vector through one CSR handle (vectorRegrid): frames, the 2 x 2 blocks of (handle, frames), the apply
+    function mpg_sphere_frames_dev(n, lon_dev, lat_dev, c_dev, s_dev, frames_dev, hip_stream) bind(C, name="mpg_sphere_frames_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: n
+      type(c_ptr), value :: lon_dev, lat_dev, c_dev, s_dev, frames_dev, hip_stream
+      integer(c_int) :: rc
+    end function mpg_sphere_frames_dev
+    function mpg_wind_vector_weights_dev(rh, src_frames_dev, dst_frames_dev, m_dev, hip_stream) &
+        bind(C, name="mpg_wind_vector_weights_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: rh, src_frames_dev, dst_frames_dev, m_dev, hip_stream
+      integer(c_int) :: rc
+    end function mpg_wind_vector_weights_dev
+    function mpg_wind_vector_dev(rh, m_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, r0_dev, r1_dev, dst_type, &
+                                 dst_layout, hip_stream) bind(C, name="mpg_wind_vector_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh, m_dev, u_dev, v_dev, r0_dev, r1_dev, hip_stream
+      integer(c_int), value :: src_type, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride, v_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_vector_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -25,7 +25,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
            "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
            "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
-           "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd"]
+           "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
+           "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd"]
 
 
 def _f64(a):
@@ -1340,3 +1341,152 @@ def wind_csr_to_edges_autograd(rh_u, rh_v, cn, sn, u, v, nlev, layout=LAYOUT_CEL
     """wind_csr_to_edges(rh_u, rh_v, cn, sn, u, v, nlev, layout, tangential=tangential) in u's dtype as a differentiable torch op: the
     gradients of wind_to_edges_autograd, with "unmapped" read as "the row is empty" and each handle's regrid_transpose."""
     return WindCsrToEdgesFunction.apply(u, v, rh_u, rh_v, cn, sn, nlev, layout, tangential)
+
+
+# ---- a wind as a vector through one CSR handle (ESMF 8.6's vectorRegrid) --------------------------------------------------------------
+def sphere_frames(lon, lat, c=None, s=None):
+    """mpg_sphere_frames_dev: the local frames of n points (lon, lat: float64 CUDA tensors or numpy arrays, RADIANS) as a [6][n] float64
+    CUDA tensor, the planes D0x D0y D0z D1x D1y D1z.  c, s both None: D0 = east, D1 = north (earth-relative winds); else D0 = c east +
+    s north, D1 = c north - s east: mesh_rotang's (cosa, sina) for the grid-relative winds of a Lambert grid, cos / sin of angleEdge for
+    (normal, tangent) at mesh edges, mesh_edge_rotang's (cn, sn) for both at once.  target_grid.sphere_frames_at is the numpy mirror."""
+    import torch
+    if (c is None) != (s is None):
+        raise ValueError("sphere_frames: c and s come together (both None: east and north)")
+
+    def dev(x):
+        return x if x is None or _is_torch(x) else torch.as_tensor(_f64(x).reshape(-1), device="cuda")
+    lon, lat, c, s = (dev(x) for x in (lon, lat, c, s))
+    n = lon.numel()
+    for t in (lon, lat, c, s):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError("sphere_frames: lon, lat, c and s must be contiguous float64 CUDA tensors (or numpy arrays) of one length")
+    frames = torch.empty((6, n), dtype=torch.float64, device="cuda")
+    check(L.sphere_frames_dev(n, lon.data_ptr(), lat.data_ptr(), c.data_ptr() if c is not None else None, s.data_ptr() if s is not None else None,
+                              frames.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return frames
+
+
+def _frames_ok(t, n):
+    import torch
+    return _is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == 6 * n
+
+
+def wind_vector_weights(rh, src_frames, dst_frames):
+    """mpg_wind_vector_weights_dev: the 2 x 2 blocks of (rh, frames) as a [4][nnz] float64 CUDA tensor, the planes m00 m01 m10 m11 in the
+    order of rh.csr()'s entries -- computed once, applied by wind_vector to any number of levels and fields.  rh: a CSR handle without
+    pole terms; src_frames [6][n_src], dst_frames [6][n_dst] as sphere_frames makes.  The bits of target_grid.wind_vector_blocks."""
+    import torch
+    if not (_frames_ok(src_frames, rh.n_src) and _frames_ok(dst_frames, rh.n_dst)):
+        raise ValueError("wind_vector_weights: the frames must be contiguous float64 CUDA tensors [6][n_src = %d] and [6][n_dst = %d]"
+                         % (rh.n_src, rh.n_dst))
+    m = torch.empty((4, rh.nnz), dtype=torch.float64, device="cuda")
+    check(L.wind_vector_weights_dev(rh._h, src_frames.data_ptr(), dst_frames.data_ptr(), m.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return m
+
+
+def wind_vector(rh, m, u, v, nlev, layout=LAYOUT_CELL_FAST, out_dtype=None, second=True, outs=None):
+    """mpg_wind_vector_dev: (u, v) through the CSR handle rh as a VECTOR, in one pass -- per point r0 = sum_q m00 u[col] + m01 v[col],
+    r1 = sum_q m10 u[col] + m11 v[col] with the blocks m of wind_vector_weights(rh, src_frames, dst_frames): with (east, north) frames on
+    both sides (r0, r1) = (ue, ve); with (normal, tangent) frames at mesh edges (un, ut).  Under POLEMETHOD_ALLAVG a cap point gets the
+    mean of the row's vectors, which is a wind (wind_csr_to_mesh gives the mean of each component there, which is not).  u, v: float32 /
+    float64 CUDA tensors of one dtype, [nlev][n_src], contiguous or plane-pitched views (nlev, ny, nx).  Returns (r0, r1), or r0 alone
+    with second=False (only m00, m01 are read), of out_dtype (default: u's): (nlev, n_dst) for LAYOUT_CELL_FAST, (n_dst, nlev) for
+    LAYOUT_LEV_FAST; an empty row is +0.0.  outs: the pair (second=False: the tensor) to write into, contiguous, nlev * n_dst elements.
+    Bit-identical to four regrid_csr_to_mesh calls of from-weights handles with the values m[k], added in float64 and cast once."""
+    import torch
+    who = "wind_vector"
+    ldu, ldv = _wind_source(u, rh, nlev, who), _wind_source(v, rh, nlev, who)
+    if u.dtype != v.dtype:
+        raise ValueError(who + ": u and v must have one dtype")
+    if not (_is_torch(m) and m.is_cuda and m.is_contiguous() and m.dtype == torch.float64 and m.numel() == 4 * rh.nnz):
+        raise ValueError("%s: m must be a contiguous float64 CUDA tensor [4][nnz = %d] (wind_vector_weights)" % (who, rh.nnz))
+    nout = 2 if second else 1
+    if _is_torch(outs):
+        outs = (outs,)
+    outs = tuple(outs) if outs is not None else (None,) * nout
+    if len(outs) != nout:
+        raise ValueError(who + ": outs must hold %d tensor(s)" % nout)
+    given = [t for t in outs if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
+    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+    shape = (nlev, rh.n_dst) if layout == LAYOUT_CELL_FAST else (rh.n_dst, nlev)
+    res = [t if t is not None else torch.empty(shape, dtype=out_dtype, device=u.device) for t in outs]
+    for t in res:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh.n_dst):
+            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh.n_dst))
+    if ACCOUNT is not None:     # 2 L U e_s + n_out P L e_d + (4 + 16 n_out) nnz + 4 (P + 1): both sources, every result, col and the blocks once
+        if getattr(rh, "_acc_U", None) is None:
+            rh._acc_U = int(rh.unique_sources().size)
+        ACCOUNT.append(("%s L%d x%d" % (who, nlev, nout), 2 * nlev * rh._acc_U * u.element_size() + nout * rh.n_dst * nlev * res[0].element_size()
+                        + (4 + 16 * nout) * rh.nnz + 4 * (rh.n_dst + 1)))
+    check(L.wind_vector_dev(rh._h, m.data_ptr(), u.data_ptr(), v.data_ptr(), int(u.dtype == torch.float32), ldu, ldv, int(nlev), res[0].data_ptr(),
+                            res[1].data_ptr() if second else None, int(out_dtype == torch.float32), int(layout),
+                            torch.cuda.current_stream().cuda_stream))
+    return tuple(res) if second else res[0]
+
+
+class _VectorAdjoint:
+    """The four from-weights handles A_kl of one (rh, m), values m[k] on rh's pattern: what wind_vector's backward applies the transposes
+    of.  Built on the first backward, kept on the tensor m, rebuilt when m has been written since; releases its handles with itself."""
+
+    def __init__(self, rh, m, nplanes):
+        rowptr, col, _ = rh.csr()
+        row = np.repeat(np.arange(1, rh.n_dst + 1, dtype=np.int32), np.diff(rowptr).astype(np.int64))
+        mh = m.detach().cpu().numpy()
+        self.key = (rh._h.value if hasattr(rh._h, "value") else rh._h, m.data_ptr(), m._version, nplanes)
+        self.handles = [RouteHandle.from_weights(rh.n_src, rh.n_dst, 1, row, (col + 1).astype(np.int32), mh[k]) for k in range(nplanes)]
+
+    def __del__(self):
+        for h in self.handles:
+            try:
+                h.release()
+            except Exception:     # the library may be gone at interpreter exit
+                pass
+
+    @classmethod
+    def of(cls, rh, m, nplanes):
+        held = getattr(m, "_mpg_vector_adjoint", None)
+        key = (rh._h.value if hasattr(rh._h, "value") else rh._h, m.data_ptr(), m._version)
+        if held is None or held.key[:3] != key or held.key[3] < nplanes:
+            held = cls(rh, m, nplanes)
+            m._mpg_vector_adjoint = held
+        return held.handles
+
+
+if _torch is not None:
+    class WindVectorFunction(_torch.autograd.Function):
+        """wind_vector with a gradient with respect to u and v (m is a constant): forward is wind_vector in u's dtype; backward takes the
+        incoming gradients back to [lev][point] planes and applies regrid_transpose of the from-weights handles A_kl (values m[k]):
+        gu = A00^T g0 + A10^T g1, gv = A01^T g0 + A11^T g1.  Use wind_vector_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, v, rh, m, nlev, layout, second):
+            ctx.rh, ctx.m, ctx.nlev, ctx.layout, ctx.second = rh, m, nlev, layout, second
+            ctx.shapes, ctx.dtypes = (u.shape, v.shape), (u.dtype, v.dtype)
+            return wind_vector(rh, m, u.contiguous(), v.contiguous(), nlev, layout=layout, out_dtype=u.dtype, second=second)
+
+        @staticmethod
+        def backward(ctx, g0, g1=None):
+            n, nlev = ctx.rh.n_dst, ctx.nlev
+            A = _VectorAdjoint.of(ctx.rh, ctx.m, 4 if ctx.second else 2)
+            grads = []
+            for g in ((g0, g1) if ctx.second else (g0,)):     # regrid_transpose reads [nlev][n_dst] planes
+                if ctx.layout == LAYOUT_LEV_FAST:
+                    g = g.reshape(n, nlev).t()
+                grads.append(g.reshape(nlev, n).contiguous())
+            out = []
+            for l in range(2):                                 # l = 0: u, 1: v
+                g = A[l].regrid_transpose(grads[0], nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[l])
+                if ctx.second:
+                    g = g + A[2 + l].regrid_transpose(grads[1], nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtypes[l])
+                out.append(g.reshape(ctx.shapes[l]))
+            return tuple(out) + (None,) * 5
+
+
+def wind_vector_autograd(rh, m, u, v, nlev, layout=LAYOUT_CELL_FAST, second=True):
+    """wind_vector(rh, m, u, v, nlev, layout, second=second) in u's dtype as a differentiable torch op.  The gradients with respect to u
+    and v (m is a constant of the op): gu = A00^T g0 + A10^T g1 and gv = A01^T g0 + A11^T g1 with A_kl the handle's pattern with the values
+    m[k], through regrid_transpose of four from-weights handles (two with second=False) that the first backward builds from a download
+    of rh.csr() and m and that stay with m; returned in u's and v's shapes and dtypes: the exact adjoint of the forward."""
+    return WindVectorFunction.apply(u, v, rh, m, nlev, layout, second)

@@ -290,6 +290,52 @@ def edge_rotang_at(proj, lon_deg, angle_edge):
     return np.cos(phi), np.sin(phi)
 
 
+def sphere_frames_at(lon, lat, c=None, s=None):
+    """The local frames of n points on the sphere (lon, lat in RADIANS) as a [6][n] float64 array, the planes D0x D0y D0z D1x D1y D1z:
+    east = (-sin lon, cos lon, 0), north = (-sin lat cos lon, -sin lat sin lon, cos lat).  c, s both None: D0 = east, D1 = north
+    (earth-relative winds); else D0 = c east + s north, D1 = c north - s east, every product and sum an operation of its own -- rotang_at's
+    (cosa, sina) for the grid-relative winds of a Lambert grid, cos / sin of angleEdge for (normal, tangent) at mesh edges,
+    edge_rotang_at's (cn, sn) for both at once.  The host mirror of mpg_sphere_frames_dev (which it meets to the device's sin / cos)."""
+    if (c is None) != (s is None):
+        raise ValueError("sphere_frames_at: c and s come together (both None: east and north)")
+    lon, lat = np.asarray(lon, dtype=np.float64).reshape(-1), np.asarray(lat, dtype=np.float64).reshape(-1)
+    sl, cl, sp, cp = np.sin(lon), np.cos(lon), np.sin(lat), np.cos(lat)
+    east = np.stack([-sl, cl, np.zeros_like(sl)])
+    north = np.stack([-sp * cl, -sp * sl, cp])
+    if c is None:
+        return np.concatenate([east, north])
+    c, s = np.asarray(c, dtype=np.float64).reshape(1, -1), np.asarray(s, dtype=np.float64).reshape(1, -1)
+    return np.concatenate([c * east + s * north, c * north - s * east])
+
+
+def wind_vector_blocks(rowptr, col, val, src_frames, dst_frames):
+    """The 2 x 2 blocks m[4][nnz] (planes m00 m01 m10 m11, CSR entry order) of a Cartesian-vector Regrid through the CSR weights
+    (rowptr, col, val): for entry q of row p with c = col[q], e / n the source frame at c and D0 / D1 the destination frame at p,
+        m00 = val[q] * ((e.x*D0.x + e.y*D0.y) + e.z*D0.z)      m01 = val[q] * ((n.x*D0.x + n.y*D0.y) + n.z*D0.z)
+    and m10, m11 the same against D1 -- (r0, r1) at p = sum_q M_q (u, v)[col[q]].  numpy rounds every operation and contracts nothing:
+    mpg_wind_vector_weights_dev gives these bits."""
+    rowptr, col = np.asarray(rowptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
+    val, sf, df = np.asarray(val, dtype=np.float64), np.asarray(src_frames, dtype=np.float64), np.asarray(dst_frames, dtype=np.float64)
+    row = np.repeat(np.arange(rowptr.size - 1), np.diff(rowptr))
+    e, n = sf[0:3][:, col], sf[3:6][:, col]
+    m = np.empty((4, col.size))
+    for k, d in enumerate((df[0:3][:, row], df[3:6][:, row])):
+        m[2 * k] = val * ((e[0] * d[0] + e[1] * d[1]) + e[2] * d[2])
+        m[2 * k + 1] = val * ((n[0] * d[0] + n[1] * d[1]) + n[2] * d[2])
+    return m
+
+
+def wind_vector_apply(rowptr, col, m, u, v):
+    """(r0, r1) [n_dst] of one level: r_k = sum over the row's entries of m_k0 u[col] + m_k1 v[col] (the blocks of wind_vector_blocks; float64
+    sums by np.bincount, not in the device's order: a reference for values, not for bits)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    n = rowptr.size - 1
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    uu, vv = np.asarray(u, dtype=np.float64).reshape(-1)[col], np.asarray(v, dtype=np.float64).reshape(-1)[col]
+    return tuple(np.bincount(row, weights=m[2 * k] * uu, minlength=n) + np.bincount(row, weights=m[2 * k + 1] * vv, minlength=n)
+                 for k in range(2))
+
+
 @dataclass
 class TargetGrid:
     """Host copy of what `define_target_grid_params` leaves in the ESMF Grid (all [nj][ni], degrees)."""
