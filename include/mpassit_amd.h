@@ -771,6 +771,60 @@ int mpg_wind_vector_weights_dev(mpg_handle rh, const double *src_frames_dev, con
 int mpg_wind_vector_dev(mpg_handle rh, const double *m_dev, const void *u_dev, const void *v_dev, int src_type,
                         int64_t u_level_stride, int64_t v_level_stride, int nlev, void *r0_dev, void *r1_dev, int dst_type,
                         int dst_layout, void *hip_stream);
+/* Winds FROM the edge-normal u a mesh carries: MPAS's mpas_reconstruct.  Restart, LBC and many init files hold only the prognostic
+ * u(nEdges, nVertLevels) and the mesh's coeffs_reconstruct; at cell c
+ *     V(k, c) = sum_i coeffs_reconstruct(:, i, c) * u(k, edgesOnCell(i, c))
+ * is the Cartesian wind, and its projection on east / north at the cell is uReconstructZonal / uReconstructMeridional.  The
+ * coefficients do not depend on the level, so the projection folds into 2 or 3 values per entry of the CSR pattern of edgesOnCell,
+ * computed once per (handle, coefficients, frames); the hot path is one gather and nout fmas per entry and level, with col staged once
+ * and u gathered once for all results.  The two device calls neither allocate, synchronise with the host nor use atomics: both can be
+ * captured in a hipGraph from their first call.  Stream as mpg_regrid_dev.
+ *
+ * mpg_reconstruct_store: the pattern as an ordinary from-weights CSR handle, n_src = nEdges, n_dst = nx_dst = nCells, ny_dst = 1.
+ *   nEdgesOnCell_host [nCells], edgesOnCell_host [nCells][maxEdges] int32 as in the file: ids are 1-based, slots past the count are not
+ *   read.  Row c holds the first nEdgesOnCell[c] entries of edgesOnCell[c][0..maxEdges) in the file's slot order, which is the
+ *   summation order; every value is 1.0.  A cell with nEdgesOnCell = 0 has an empty row; duplicate edge ids in a row are allowed.  The
+ *   handle goes through mpg_handle_from_weights's machinery (always CSR) and every CSR consumer takes it, mpg_handle_get_csr and
+ *   mpg_regrid_transpose_dev included.  Not cached: pair it with mpg_handle_release.  The handle keeps its longest row, taken on the
+ *   host at Store time.  MPG_ERR_INVALID_ARG with the offending cell: a count outside [0, maxEdges], an id outside [1, nEdges] among
+ *   the counted slots; NULL arrays, nCells < 1, nEdges < 1, maxEdges < 0.  MPG_ERR_OVERFLOW: nCells, nEdges or the entries beyond int32.
+ *
+ * mpg_reconstruct_weights_dev: the values of (handle, coefficients, frames).  coeffs_dev [nCells][maxEdges][3] float64, the file's
+ *   coeffs_reconstruct(nCells, maxEdges, R3), padding included.  dst_frames_dev [6][nCells] from mpg_sphere_frames_dev, or NULL.
+ *   m_dev [nout][nnz] in the handle's entry order, nout = 2 with frames, 3 without; the caller owns it.  The same bits as numpy, every
+ *   operation rounded, nothing contracted (fp contract(off)): for entry q of row c, slot i = q - rowptr[c], (cx, cy, cz) = coeffs[c][i][:]
+ *     frames:  m0 = val[q] * ((cx*D0.x + cy*D0.y) + cz*D0.z)      m1: the same against D1
+ *     NULL:    m_k = val[q] * c_k                                  k = X, Y, Z
+ *   Frames of (lonCell, latCell) with no turn give uReconstructZonal / uReconstructMeridional; frames turned by cosa / sina at the
+ *   cells (mpg_mesh_rotang_dev) give grid-relative winds; NULL gives uReconstructX / Y / Z.  A handle without entries is success and
+ *   writes nothing.  Refused under the name mpg_reconstruct_weights: MPG_ERR_UNSUPPORTED for a fixed handle and for a handle with pole
+ *   terms; MPG_ERR_INVALID_ARG for a handle whose longest row exceeds maxEdges (the message says so; no device read-back is used: the
+ *   handle must record its longest row, as those of mpg_reconstruct_store and mpg_handle_from_weights do), NULL arrays, m_dev
+ *   aliasing an input.
+ *
+ * mpg_wind_reconstruct_dev: the apply.  nout is 2 or 3 and r2_dev is non-NULL exactly when nout == 3; nout == 1 is refused
+ *   (mpg_regrid_csr_to_mesh_dev / mpg_regrid_csr_rows_dev of a from-weights handle serve one result).  src_layout:
+ *   MPG_LAYOUT_LEV_FAST is u[nEdges][nlev], MPAS file order, dense (u_level_stride must be 0); MPG_LAYOUT_CELL_FAST is nlev planes
+ *   u_level_stride elements apart, 0 = dense, below n_src -> MPG_ERR_INVALID_ARG.  dst_layout: MPG_LAYOUT_CELL_FAST [lev][cell] or
+ *   MPG_LAYOUT_LEV_FAST [cell][lev]; results are fully overwritten.  src_type / dst_type: float32 or float64 in any pairing.
+ *   Values, a contract by identity, per (cell, level, k < nout):
+ *     acc_k = fma(m_k[q], (double)u[col[q]], acc_k)     from 0.0, the row's entries in stored order, whatever LDS chunk an entry arrives in
+ *     store (TD) fma(acc_k, 1.0, 0.0)                   one rounding to the destination type; an empty row gives (TD)(+0.0)
+ *   Result k is bit for bit mpg_regrid_csr_to_mesh_dev of a from-weights handle with the values m_k, at scale 1 and offset 0.  The
+ *   same bits for all four layout pairs, for dense and pitched sources, and from call to call.  n_dst == 0 is success; a handle
+ *   without entries gives zeroed results.
+ * Refusals of the apply, each with a message that names the call, under the name mpg_wind_reconstruct.  MPG_ERR_UNSUPPORTED: a fixed
+ * handle, a handle with pole terms (mpg_handle_pole_count > 0), MPG_TYPE_BE on either side (mpg_bswap_dev swaps an array in place).
+ * MPG_ERR_INVALID_ARG: NULL handle or arrays, nout outside {2, 3}, r2_dev not matching nout, nlev < 1, unknown enums, a non-zero
+ * stride with MPG_LAYOUT_LEV_FAST sources, a level stride below n_src, results aliasing each other, the source or m_dev.
+ * MPG_ERR_OVERFLOW: more 64-row blocks than one launch holds. */
+int mpg_reconstruct_store(int64_t nCells, int64_t nEdges, int maxEdges, const int32_t *nEdgesOnCell_host,
+                          const int32_t *edgesOnCell_host, mpg_handle *out);
+int mpg_reconstruct_weights_dev(mpg_handle rh, int maxEdges, const double *coeffs_dev, const double *dst_frames_dev,
+                                double *m_dev, void *hip_stream);
+int mpg_wind_reconstruct_dev(mpg_handle rh, const double *m_dev, int nout, const void *u_dev, int src_type, int src_layout,
+                             int64_t u_level_stride, int nlev, void *r0_dev, void *r1_dev, void *r2_dev, int dst_type,
+                             int dst_layout, void *hip_stream);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

@@ -32,6 +32,7 @@ SYMBOLS = [
     "mpg_mesh_set_edges", "mpg_mesh_edge_count", "mpg_mesh_edge_rotang_dev", "mpg_wind_to_edges_dev",
     "mpg_wind_csr_to_mesh_dev", "mpg_wind_csr_to_edges_dev",
     "mpg_sphere_frames_dev", "mpg_wind_vector_weights_dev", "mpg_wind_vector_dev",
+    "mpg_reconstruct_store", "mpg_reconstruct_weights_dev", "mpg_wind_reconstruct_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -297,6 +298,38 @@ def wind_vector_dev(*args):
     if "vector" not in _to_mesh_fns:
         _to_mesh_fns["vector"] = _WIND_VECTOR_PROTO(("mpg_wind_vector_dev", load()))
     return _to_mesh_fns["vector"](*args)
+
+
+# Winds from edge-normal u, bound the same way.
+#   mpg_reconstruct_store(nCells, nEdges, maxEdges, nEdgesOnCell_host, edgesOnCell_host, out)
+#   mpg_reconstruct_weights_dev(rh, maxEdges, coeffs_dev, dst_frames_dev, m_dev, hip_stream)
+#   mpg_wind_reconstruct_dev(rh, m_dev, nout, u_dev, src_type, src_layout, u_level_stride, nlev, r0_dev, r1_dev, r2_dev, dst_type,
+#                            dst_layout, hip_stream)
+_RECONSTRUCT_STORE_PROTO = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+_RECONSTRUCT_WEIGHTS_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_WIND_RECONSTRUCT_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
+
+
+def reconstruct_store(*args):
+    """The typed binding of mpg_reconstruct_store; returns the call's status code."""
+    if "reconstruct_store" not in _to_mesh_fns:
+        _to_mesh_fns["reconstruct_store"] = _RECONSTRUCT_STORE_PROTO(("mpg_reconstruct_store", load()))
+    return _to_mesh_fns["reconstruct_store"](*args)
+
+
+def reconstruct_weights_dev(*args):
+    """The typed binding of mpg_reconstruct_weights_dev; returns the call's status code."""
+    if "reconstruct_weights" not in _to_mesh_fns:
+        _to_mesh_fns["reconstruct_weights"] = _RECONSTRUCT_WEIGHTS_PROTO(("mpg_reconstruct_weights_dev", load()))
+    return _to_mesh_fns["reconstruct_weights"](*args)
+
+
+def wind_reconstruct_dev(*args):
+    """The typed binding of mpg_wind_reconstruct_dev; returns the call's status code."""
+    if "wind_reconstruct" not in _to_mesh_fns:
+        _to_mesh_fns["wind_reconstruct"] = _WIND_RECONSTRUCT_PROTO(("mpg_wind_reconstruct_dev", load()))
+    return _to_mesh_fns["wind_reconstruct"](*args)
 
 
 _lib = None

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mpg_internal.h"
+#include "wind_reconstruct_checks.h"
 #include "wind_vector_checks.h"
 
 static thread_local char g_err[1024] = "";
@@ -126,7 +127,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1453,6 +1454,60 @@ int mpg_wind_vector_dev(mpg_handle rh, const double *m_dev, const void *u_dev, c
   return mpg_k_wind_vector(rh, m_dev, u_dev, v_dev, src_type, ldu, ldv, nlev, r0_dev, r1_dev, dst_type, dst_layout, (hipStream_t)hip_stream);
 }
 
+// ---- winds from edge-normal u: the pattern of edgesOnCell, the values of (coeffs_reconstruct, frames), apply (k_wind_reconstruct.hip) ----
+// The checks are host-only text of their own (wind_reconstruct_checks.h), so that a stand-alone program can run them.
+static int handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, const int32_t *row_host, const int32_t *col_host,
+                               const double *S_host, bool force_csr, mpg_handle *out);
+static WrHandle wr_handle(mpg_handle rh) { return WrHandle{wv_handle(rh), rh->max_row}; }
+
+int mpg_reconstruct_store(int64_t nCells, int64_t nEdges, int maxEdges, const int32_t *nEdgesOnCell_host, const int32_t *edgesOnCell_host,
+                          mpg_handle *out) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  int64_t nnz, max_row;
+  int rc = wr_check_store(nCells, nEdges, maxEdges, nEdgesOnCell_host, edgesOnCell_host, out, &nnz, &max_row, e);
+  if (rc) return wv_refused(rc, e);
+  // the first nEdgesOnCell[c] slots of every cell in the file's order (the summation order), every value 1.0
+  std::vector<int32_t> row((size_t)nnz + 1), col((size_t)nnz + 1);
+  std::vector<double> one((size_t)nnz + 1, 1.0);
+  size_t q = 0;
+  for (int64_t c = 0; c < nCells; ++c)
+    for (int32_t i = 0; i < nEdgesOnCell_host[c]; ++i, ++q) {
+      row[q] = (int32_t)(c + 1);
+      col[q] = edgesOnCell_host[c * (int64_t)maxEdges + i];
+    }
+  rc = handle_from_weights(nEdges, (int)nCells, 1, nnz, row.data(), col.data(), one.data(), true, out);
+  if (!rc) (*out)->max_row = max_row;
+  return rc;
+}
+
+int mpg_reconstruct_weights_dev(mpg_handle rh, int maxEdges, const double *coeffs_dev, const double *dst_frames_dev, double *m_dev,
+                                void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  WrHandle h{};
+  if (rh) h = wr_handle(rh);
+  bool nothing;
+  int rc = wr_check_weights(rh ? &h : nullptr, maxEdges, coeffs_dev, dst_frames_dev, m_dev, &nothing, e);
+  if (rc) return wv_refused(rc, e);
+  if (nothing) return MPG_SUCCESS;   // no entries: nothing to write
+  return mpg_k_reconstruct_weights(rh, maxEdges, coeffs_dev, dst_frames_dev, m_dev, (hipStream_t)hip_stream);
+}
+
+int mpg_wind_reconstruct_dev(mpg_handle rh, const double *m_dev, int nout, const void *u_dev, int src_type, int src_layout, int64_t u_level_stride,
+                             int nlev, void *r0_dev, void *r1_dev, void *r2_dev, int dst_type, int dst_layout, void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  WrHandle h{};
+  if (rh) h = wr_handle(rh);
+  int64_t ldu;
+  int rc = wr_check_apply(rh ? &h : nullptr, m_dev, nout, u_dev, src_type, src_layout, u_level_stride, nlev, r0_dev, r1_dev, r2_dev, dst_type,
+                          dst_layout, &ldu, e);
+  if (rc) return wv_refused(rc, e);
+  return mpg_k_wind_reconstruct(rh, m_dev, nout, u_dev, src_type, src_layout, ldu, nlev, r0_dev, r1_dev, r2_dev, dst_type, dst_layout,
+                                (hipStream_t)hip_stream);
+}
+
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------
 int mpg_regrid_masked_dev(mpg_handle h, const void *src_dev, int src_type, int src_layout, int nlev, int nfields, void *dst_dev, int dst_type,
                           int64_t dst_level_stride, const mpg_mask_opts *opts, void *hip_stream) {
@@ -1614,8 +1669,9 @@ int mpg_rotate_winds(int64_t npts, int nlev, const double *cosa_host, const doub
 }
 
 // ---- introspection ----------------------------------------------------------------------------------
-int mpg_handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, const int32_t *row_host, const int32_t *col_host,
-                            const double *S_host, mpg_handle *out) {
+// force_csr: a CSR handle even where every mapped row has exactly 3 entries (mpg_reconstruct_store: its consumers take CSR handles only)
+static int handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, const int32_t *row_host, const int32_t *col_host,
+                               const double *S_host, bool force_csr, mpg_handle *out) {
   MPG_CHECK_INIT();
   MPG_ARG(out && (nnz == 0 || (row_host && col_host && S_host)), "mpg_handle_from_weights: NULL argument");
   MPG_ARG(n_src > 0 && n_src < 0x7fffffff && nx_dst > 0 && ny_dst > 0 && nnz >= 0 && nnz < 0x7fffffff,
@@ -1655,7 +1711,8 @@ int mpg_handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, 
   h->nnz = nnz;
   h->method = -1;
   int rc = MPG_SUCCESS;
-  if (maxlen == 3 && minlen_nonempty == 3) {
+  h->max_row = maxlen;
+  if (maxlen == 3 && minlen_nonempty == 3 && !force_csr) {
     // every mapped destination has exactly 3 sources (bilinear on triangles): the fast fixed-3 layout
     h->kind = MPG_KIND_FIXED;
     h->nnz_per_row = 3;
@@ -1686,6 +1743,11 @@ int mpg_handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, 
   }
   *out = h;
   return MPG_SUCCESS;
+}
+
+int mpg_handle_from_weights(int64_t n_src, int nx_dst, int ny_dst, int64_t nnz, const int32_t *row_host, const int32_t *col_host,
+                            const double *S_host, mpg_handle *out) {
+  return handle_from_weights(n_src, nx_dst, ny_dst, nnz, row_host, col_host, S_host, false, out);
 }
 
 int mpg_handle_info(mpg_handle h, int64_t *n_src, int64_t *n_dst, int *nx_dst, int *ny_dst, int *nnz_per_row, int64_t *nnz) {

@@ -285,6 +285,7 @@ struct mpg_handle_s {
   DevBuf<int32_t> col;
   DevBuf<double> val;
   int64_t nnz = 0;
+  int64_t max_row = -1;      // longest CSR row as the Store counted it on the host (mpg_handle_from_weights, mpg_reconstruct_store); -1: not recorded
   DevBuf<double> dst_frac;   // [n_dst] covered fraction of every destination cell (conservative Grid -> Mesh and Mesh -> Mesh Stores; absent otherwise)
   int refcount = 1;
   bool cached = false;
@@ -493,6 +494,11 @@ int mpg_k_sphere_frames(int64_t n, const double *lon, const double *lat, const d
 int mpg_k_wind_vector_weights(mpg_handle_s *h, const double *src_frames, const double *dst_frames, double *m, hipStream_t s);
 int mpg_k_wind_vector(mpg_handle_s *h, const double *m, const void *u, const void *v, int src_type, int64_t ldu, int64_t ldv, int nlev,
                       void *r0, void *r1, int dst_type, int layout, hipStream_t s);
+// k_wind_reconstruct.hip: winds from edge-normal u through the CSR pattern of edgesOnCell (arguments checked by the API entry points): the
+// values m[nout][nnz] of (handle, coeffs_reconstruct, frames; dst_frames == nullptr: X, Y, Z) and their apply to u, nout = 2 or 3 results
+int mpg_k_reconstruct_weights(mpg_handle_s *h, int maxEdges, const double *coeffs, const double *dst_frames, double *m, hipStream_t s);
+int mpg_k_wind_reconstruct(mpg_handle_s *h, const double *m, int nout, const void *u, int src_type, int src_layout, int64_t ldu, int nlev,
+                           void *r0, void *r1, void *r2, int dst_type, int dst_layout, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

@@ -487,6 +487,31 @@ module mpg
       integer(c_int64_t), value :: u_level_stride, v_level_stride
       integer(c_int) :: rc
     end function mpg_wind_vector_dev
+    !> winds from the edge-normal u (mpas_reconstruct): the pattern of edgesOnCell, the values of (handle, coeffs_reconstruct, frames), the apply
+    function mpg_reconstruct_store(nCells, nEdges, maxEdges, nEdgesOnCell_host, edgesOnCell_host, out) &
+        bind(C, name="mpg_reconstruct_store") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: nCells, nEdges
+      integer(c_int), value :: maxEdges
+      type(c_ptr), value :: nEdgesOnCell_host, edgesOnCell_host
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_reconstruct_store
+    function mpg_reconstruct_weights_dev(rh, maxEdges, coeffs_dev, dst_frames_dev, m_dev, hip_stream) &
+        bind(C, name="mpg_reconstruct_weights_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: rh, coeffs_dev, dst_frames_dev, m_dev, hip_stream
+      integer(c_int), value :: maxEdges
+      integer(c_int) :: rc
+    end function mpg_reconstruct_weights_dev
+    function mpg_wind_reconstruct_dev(rh, m_dev, nout, u_dev, src_type, src_layout, u_level_stride, nlev, r0_dev, r1_dev, r2_dev, dst_type, &
+                                      dst_layout, hip_stream) bind(C, name="mpg_wind_reconstruct_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh, m_dev, u_dev, r0_dev, r1_dev, r2_dev, hip_stream
+      integer(c_int), value :: nout, src_type, src_layout, nlev, dst_type, dst_layout
+      integer(c_int64_t), value :: u_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_reconstruct_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -26,7 +26,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
            "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
            "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
-           "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd"]
+           "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
+           "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd"]
 
 
 def _f64(a):
@@ -1490,3 +1491,117 @@ def wind_vector_autograd(rh, m, u, v, nlev, layout=LAYOUT_CELL_FAST, second=True
     m[k], through regrid_transpose of four from-weights handles (two with second=False) that the first backward builds from a download
     of rh.csr() and m and that stay with m; returned in u's and v's shapes and dtypes: the exact adjoint of the forward."""
     return WindVectorFunction.apply(u, v, rh, m, nlev, layout, second)
+
+
+# ---- winds from the edge-normal u a mesh carries (MPAS's mpas_reconstruct) -------------------------------------------------------------
+def reconstruct_store(nEdgesOnCell, edgesOnCell, nEdges):
+    """mpg_reconstruct_store: the pattern of edgesOnCell as a from-weights CSR RouteHandle, n_src = nEdges, n_dst = nCells.  nEdgesOnCell
+    [nCells] and edgesOnCell [nCells][maxEdges] as an MPAS file holds them (1-based ids; slots past the count are not read): row c is the
+    first nEdgesOnCell[c] slots of cell c in the file's order, which is the summation order; every value is 1.0.  Not cached: release()
+    it.  Every CSR consumer takes the handle (csr(), regrid_csr_to_mesh, regrid_csr_rows, regrid_transpose)."""
+    n_on = np.ascontiguousarray(nEdgesOnCell, np.int32).reshape(-1)
+    eoc = np.ascontiguousarray(edgesOnCell, np.int32)
+    if eoc.ndim != 2 or eoc.shape[0] != n_on.size:
+        raise ValueError("reconstruct_store: edgesOnCell must be [nCells = %d][maxEdges]" % n_on.size)
+    h = C.c_void_p()
+    check(L.reconstruct_store(n_on.size, int(nEdges), int(eoc.shape[1]), _ptr(n_on), _ptr(eoc), C.byref(h)))
+    return RouteHandle(h)
+
+
+def reconstruct_weights(rh, coeffs, dst_frames=None):
+    """mpg_reconstruct_weights_dev: the values of (rh, coeffs, frames) as a [nout][nnz] float64 CUDA tensor in the order of rh.csr()'s
+    entries -- computed once, applied by wind_reconstruct to any number of levels and time levels.  coeffs: the file's coeffs_reconstruct
+    [nCells][maxEdges][3] (a float64 CUDA tensor or a numpy array), padding included.  dst_frames [6][nCells] as sphere_frames makes:
+    nout = 2, (lonCell, latCell) unturned for uReconstructZonal / uReconstructMeridional, turned by mesh_rotang's (cosa, sina) for
+    grid-relative winds; None: nout = 3, uReconstructX / Y / Z.  The bits of target_grid.reconstruct_blocks."""
+    import torch
+    if not _is_torch(coeffs):
+        coeffs = torch.as_tensor(_f64(coeffs), device="cuda")
+    if not (coeffs.is_cuda and coeffs.is_contiguous() and coeffs.dtype == torch.float64 and coeffs.dim() == 3 and coeffs.shape[0] == rh.n_dst
+            and coeffs.shape[2] == 3):
+        raise ValueError("reconstruct_weights: coeffs must be a contiguous float64 [nCells = %d][maxEdges][3]" % rh.n_dst)
+    if dst_frames is not None and not _frames_ok(dst_frames, rh.n_dst):
+        raise ValueError("reconstruct_weights: dst_frames must be a contiguous float64 CUDA tensor [6][nCells = %d]" % rh.n_dst)
+    m = torch.empty((2 if dst_frames is not None else 3, rh.nnz), dtype=torch.float64, device="cuda")
+    check(L.reconstruct_weights_dev(rh._h, int(coeffs.shape[1]), coeffs.data_ptr(), dst_frames.data_ptr() if dst_frames is not None else None,
+                                    m.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return m
+
+
+def wind_reconstruct(rh, m, u, nlev, src_layout=LAYOUT_LEV_FAST, layout=LAYOUT_CELL_FAST, out_dtype=None, outs=None):
+    """mpg_wind_reconstruct_dev: the winds at the cells from the edge-normal u, in one pass -- per cell and level r_k = sum_q m_k[q]
+    u[col[q]] with the values m [nout][nnz] of reconstruct_weights (nout = 2: the frame's two components, 3: X, Y, Z).  u: a float32 /
+    float64 CUDA tensor; src_layout LAYOUT_LEV_FAST: [nEdges][nlev], MPAS file order, contiguous; LAYOUT_CELL_FAST: [nlev][nEdges],
+    contiguous or a plane-pitched view (nlev, ny, nx).  Returns nout tensors of out_dtype (default: u's): (nlev, nCells) for layout
+    LAYOUT_CELL_FAST, (nCells, nlev) for LAYOUT_LEV_FAST; an empty row is +0.0.  outs: the nout tensors to write into, contiguous, nlev *
+    nCells elements each.  Bit-identical to nout regrid_csr_to_mesh calls of from-weights handles with the values m[k]."""
+    import torch
+    who = "wind_reconstruct"
+    if not (_is_torch(m) and m.is_cuda and m.is_contiguous() and m.dtype == torch.float64 and m.dim() == 2 and m.shape[1] == rh.nnz):
+        raise ValueError("%s: m must be a contiguous float64 CUDA tensor [nout][nnz = %d] (reconstruct_weights)" % (who, rh.nnz))
+    nout = int(m.shape[0])
+    if src_layout == LAYOUT_LEV_FAST:
+        if not (_is_torch(u) and u.is_cuda and u.dtype in (torch.float32, torch.float64) and u.is_contiguous() and u.numel() == nlev * rh.n_src):
+            raise ValueError("%s: a LAYOUT_LEV_FAST source is a contiguous float32/float64 CUDA tensor [nEdges = %d][nlev = %d]" % (who, rh.n_src, nlev))
+        ldu = 0
+    else:
+        ldu = _wind_source(u, rh, nlev, who)
+    outs = tuple(outs) if outs is not None else (None,) * nout
+    if len(outs) != nout:
+        raise ValueError(who + ": outs must hold %d tensors" % nout)
+    given = [t for t in outs if t is not None]
+    out_dtype = out_dtype or (given[0].dtype if given else u.dtype)
+    if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+        out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+    shape = (nlev, rh.n_dst) if layout == LAYOUT_CELL_FAST else (rh.n_dst, nlev)
+    res = [t if t is not None else torch.empty(shape, dtype=out_dtype, device=u.device) for t in outs]
+    for t in res:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == out_dtype and t.dtype in (torch.float32, torch.float64) and t.numel() == nlev * rh.n_dst):
+            raise ValueError(who + ": outs must be contiguous float32/float64 CUDA tensors of %d elements and one dtype" % (nlev * rh.n_dst))
+    if ACCOUNT is not None:     # nEdges L e_s + nout nCells L e_d + (4 + 8 nout) nnz: the source, every result, col and the values once
+        ACCOUNT.append(("%s L%d x%d" % (who, nlev, nout), nlev * rh.n_src * u.element_size() + nout * rh.n_dst * nlev * res[0].element_size()
+                        + (4 + 8 * nout) * rh.nnz))
+    check(L.wind_reconstruct_dev(rh._h, m.data_ptr(), nout, u.data_ptr(), int(u.dtype == torch.float32), int(src_layout), ldu, int(nlev),
+                                 res[0].data_ptr(), res[1].data_ptr() if nout > 1 else None, res[2].data_ptr() if nout > 2 else None,
+                                 int(out_dtype == torch.float32), int(layout), torch.cuda.current_stream().cuda_stream))
+    return tuple(res)
+
+
+if _torch is not None:
+    class WindReconstructFunction(_torch.autograd.Function):
+        """wind_reconstruct with a gradient with respect to u (m is a constant): forward is wind_reconstruct in u's dtype; backward takes
+        the incoming gradients back to [lev][cell] planes and applies regrid_transpose of the from-weights handles A_k (values m[k],
+        _VectorAdjoint): gu = sum_k A_k^T g_k, returned in u's layout.  Use wind_reconstruct_autograd()."""
+
+        @staticmethod
+        def forward(ctx, u, rh, m, nlev, src_layout, layout):
+            ctx.rh, ctx.m, ctx.nlev, ctx.src_layout, ctx.layout = rh, m, nlev, src_layout, layout
+            ctx.shape, ctx.dtype = u.shape, u.dtype
+            return wind_reconstruct(rh, m, u.contiguous(), nlev, src_layout=src_layout, layout=layout, out_dtype=u.dtype)
+
+        @staticmethod
+        def backward(ctx, *gs):
+            n, ns, nlev = ctx.rh.n_dst, ctx.rh.n_src, ctx.nlev
+            A = _VectorAdjoint.of(ctx.rh, ctx.m, len(gs))
+            gu = None
+            for k, g in enumerate(gs):                          # regrid_transpose reads [nlev][n_dst] planes
+                if g is None:
+                    continue
+                if ctx.layout == LAYOUT_LEV_FAST:
+                    g = g.reshape(n, nlev).t()
+                t = A[k].regrid_transpose(g.reshape(nlev, n).contiguous(), nlev=nlev, layout=LAYOUT_CELL_FAST, out_dtype=ctx.dtype)
+                gu = t if gu is None else gu + t
+            if gu is None:
+                return (None,) * 6
+            gu = gu.reshape(nlev, ns)
+            if ctx.src_layout == LAYOUT_LEV_FAST:
+                gu = gu.t().contiguous()
+            return (gu.reshape(ctx.shape),) + (None,) * 5
+
+
+def wind_reconstruct_autograd(rh, m, u, nlev, src_layout=LAYOUT_LEV_FAST, layout=LAYOUT_CELL_FAST):
+    """wind_reconstruct(rh, m, u, nlev, src_layout, layout) in u's dtype as a differentiable torch op.  The gradient with respect to u (m
+    is a constant of the op): gu = sum_k A_k^T g_k with A_k the handle's pattern with the values m[k], through regrid_transpose of nout
+    from-weights handles that the first backward builds from a download of rh.csr() and m and that stay with m; returned in u's shape,
+    layout and dtype: the exact adjoint of the forward."""
+    return WindReconstructFunction.apply(u, rh, m, nlev, src_layout, layout)

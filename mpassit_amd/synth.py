@@ -429,3 +429,47 @@ def snow_field(lat_rad, lon_rad, lat0=np.deg2rad(45.0), lon0=np.deg2rad(-100.0 %
     c = latlon_rad_to_xyz(np.array(lat0), np.array(lon0))
     d2 = np.sum((x - c) ** 2, axis=-1)
     return np.exp(-d2 / 0.02)[None, :]
+
+
+def edges_on_cell(m):
+    """(nEdgesOnCell [nCells] int32, edgesOnCell [nCells][maxEdges] int32) of a mesh with edges (mesh_edges), derived from cellsOnEdge:
+    a cell lists every edge that names it, ids 1-based and ascending within the cell, 0-padded; maxEdges is the longest list."""
+    coe = np.asarray(m.cellsOnEdge, np.int64)
+    nc = int(m.nCells)
+    edge = np.repeat(np.arange(1, coe.shape[0] + 1, dtype=np.int64), 2)
+    cell = coe.reshape(-1)
+    keep = cell > 0
+    edge, cell = edge[keep], cell[keep] - 1
+    order = np.lexsort((edge, cell))
+    edge, cell = edge[order], cell[order]
+    n = np.bincount(cell, minlength=nc)
+    start = np.concatenate([[0], np.cumsum(n)[:-1]])
+    eoc = np.zeros((nc, int(n.max()) if nc else 0), np.int32)
+    eoc[cell, np.arange(cell.size) - start[cell]] = edge
+    return n.astype(np.int32), eoc
+
+
+def reconstruct_coeffs(m, nEdgesOnCell, edgesOnCell):
+    """A least-squares stand-in [nCells][maxEdges][3] for an MPAS file's coeffs_reconstruct: with r the cell centre, n_i = cos(angleEdge)
+    east + sin(angleEdge) north at the edge point, n_i' = n_i - (n_i . r) r its part tangent at the centre and M = sum_i n_i' n_i'^T +
+    r r^T, coeffs[c][i] = M^-1 n_i' -- the tangent vector V at the centre that fits u_i = V . n_i' best is sum_i coeffs[c][i] u_i.
+    Where the smallest eigenvalue of M is below 1e-6 of the largest (too few or parallel edges), the coefficients are zero.
+    These are NOT MPAS's radial-basis-function coefficients: real files carry coeffs_reconstruct, and the reconstruction kernel does not
+    care which it gets."""
+    n_on, eoc = np.asarray(nEdgesOnCell, np.int64), np.asarray(edgesOnCell, np.int64)
+    nc, me = eoc.shape
+    lat, lon, ang = np.asarray(m.latEdge), np.asarray(m.lonEdge), np.asarray(m.angleEdge)
+    east = np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)], axis=1)
+    north = np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)], axis=1)
+    nrm = np.cos(ang)[:, None] * east + np.sin(ang)[:, None] * north
+    r = latlon_rad_to_xyz(np.asarray(m.latCell), np.asarray(m.lonCell))
+    valid = np.arange(me)[None, :] < n_on[:, None]
+    ni = nrm[np.maximum(eoc, 1) - 1]                                    # [nc][me][3]
+    ni = ni - np.einsum("cik,ck->ci", ni, r)[:, :, None] * r[:, None, :]
+    ni = np.where(valid[:, :, None], ni, 0.0)
+    M = np.einsum("cik,cil->ckl", ni, ni) + r[:, :, None] * r[:, None, :]
+    ev = np.linalg.eigvalsh(M)
+    good = ev[:, 0] >= 1e-6 * ev[:, 2]
+    Minv = np.linalg.inv(np.where(good[:, None, None], M, np.eye(3)[None]))
+    coeffs = np.einsum("ckl,cil->cik", Minv, ni)
+    return np.ascontiguousarray(np.where(good[:, None, None], coeffs, 0.0))

@@ -336,6 +336,37 @@ def wind_vector_apply(rowptr, col, m, u, v):
                  for k in range(2))
 
 
+def reconstruct_blocks(rowptr, coeffs, val, dst_frames):
+    """The values m[nout][nnz] (CSR entry order) of the wind reconstruction from edge-normal u (MPAS's mpas_reconstruct) through the
+    pattern rowptr of edgesOnCell: for entry q of row c, slot i = q - rowptr[c] and (cx, cy, cz) = coeffs[c][i][:] (coeffs
+    [nCells][maxEdges][3], the file's coeffs_reconstruct),
+        frames [6][nCells]:  m0 = val[q] * ((cx*D0.x + cy*D0.y) + cz*D0.z)     m1 the same against D1          (nout = 2)
+        dst_frames None:     m_k = val[q] * c_k,  k = X, Y, Z                                                   (nout = 3)
+    numpy rounds every operation and contracts nothing: mpg_reconstruct_weights_dev gives these bits."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    coeffs, val = np.asarray(coeffs, dtype=np.float64), np.asarray(val, dtype=np.float64)
+    n = np.diff(rowptr)
+    if n.size and n.max(initial=0) > coeffs.shape[1]:
+        raise ValueError("reconstruct_blocks: the longest row has %d entries, coeffs has %d slots" % (n.max(), coeffs.shape[1]))
+    row = np.repeat(np.arange(rowptr.size - 1), n)
+    slot = np.arange(row.size) - rowptr[row]
+    c = coeffs[row, slot].T                                   # [3][nnz]
+    if dst_frames is None:
+        return np.stack([val * c[0], val * c[1], val * c[2]])
+    df = np.asarray(dst_frames, dtype=np.float64)
+    return np.stack([val * ((c[0] * d[0] + c[1] * d[1]) + c[2] * d[2]) for d in (df[0:3][:, row], df[3:6][:, row])])
+
+
+def reconstruct_apply(rowptr, col, m, u):
+    """The results [nout][n_dst] of one level: r_k = sum over the row's entries of m_k u[col] (float64 sums by np.bincount, not in the
+    device's order: a reference for values, not for bits)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    n = rowptr.size - 1
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    uu = np.asarray(u, dtype=np.float64).reshape(-1)[col]
+    return np.stack([np.bincount(row, weights=mk * uu, minlength=n) for mk in m])
+
+
 @dataclass
 class TargetGrid:
     """Host copy of what `define_target_grid_params` leaves in the ESMF Grid (all [nj][ni], degrees)."""
