@@ -826,6 +826,54 @@ int mpg_wind_reconstruct_dev(mpg_handle rh, const double *m_dev, int nout, const
                              int64_t u_level_stride, int nlev, void *r0_dev, void *r1_dev, void *r2_dev, int dst_type,
                              int dst_layout, void *hip_stream);
 
+/* ---- handle composition: two Regrids folded into ONE CSR handle ----------------------------------------------------------------------
+ * Every operator of this library is a sparse matrix behind a route handle.  A job that needs "A after B" -- edges -> cells -> grid, global
+ * grid -> global mesh -> limited-area mesh, a destagger in front of a Grid -> Mesh handle -- pays an intermediate array between two
+ * applies, and the rounding of that array.  mpg_handle_compose builds C = A . B on the device (a sparse-matrix x sparse-matrix product with
+ * a stated pattern and a stated summation order) as an ordinary CSR handle: every CSR consumer takes it without new apply code
+ * (mpg_regrid_typed_dev, mpg_regrid_csr_to_mesh_dev, mpg_regrid_csr_rows_dev, mpg_regrid_masked_dev, mpg_regrid_transpose_dev,
+ * mpg_wind_vector_weights_dev, mpg_wind_reconstruct_dev, mpg_handle_get_csr).
+ *
+ * mpg_handle_compose: A = outer (n_dst_A x n_src_A), B = inner (n_dst_B x n_src_B), n_dst_B == n_src_A.
+ *   Shape: n_src = n_src_B; n_dst, nx_dst and ny_dst are those of outer.  Always a CSR handle, method -1 as from-weights handles, not
+ *   cached: pair it with mpg_handle_release.  It records its longest row (mpg_reconstruct_weights_dev accepts it).  It owns its arrays:
+ *   outer and inner may be released right after the call.  No destination fraction is carried.  The call is blocking: it allocates and
+ *   reads the entry count back; mpg_handle_store_ms gives the GPU time of the build.  It orders itself after whatever produced the two
+ *   handles, as mpg_handle_get_csr does.
+ *   Operands: either may be fixed (3, 4 or 1 slots per row) or CSR.  An entry of a fixed handle with idx = -1 is skipped; a nearest handle
+ *   without a weight array has weight 1.0.
+ *   Pattern: row i of C holds the distinct source ids reachable from row i of A through the rows of B -- column e appears if at least one
+ *   pair (p in A's row i, q in B's row col_A[p]) has col_B[q] == e -- in ascending order.  Entries are structural: one whose value comes
+ *   out 0.0 stays.  A row of A that is empty or unmapped gives an empty row of C, and so does a row that reaches only empty rows of B:
+ *   Regrid gives 0.0 there, as the chain does.
+ *   Values, a contract by identity, bit for bit those of the numpy mirror (target_grid.compose_csr): c[i,e] starts from 0.0; over A's
+ *   entries p of row i in stored order, and within each p over B's entries q of row col_A[p] in stored order with col_B[q] == e,
+ *     acc = acc + (a_p * b_q)
+ *   the product and the sum rounded separately, nothing contracted (fp contract(off)).  Duplicate columns in a row of either operand
+ *   are allowed: each occurrence is one term.  The same bytes from run to run: no floating-point atomics, and the result does not depend
+ *   on the blocks of destination rows the build works in (mpg_tune "compose_block_rows").
+ *   Limits: rows of any length are served (nothing is held per row in LDS).  The temporaries of the pattern are bounded by a fixed byte
+ *   budget per block of rows; one row alone may reach at most 2^31 - 2 pairs before de-duplication.
+ *   Refusals, each with a message that names the call and the way out.  MPG_ERR_INVALID_ARG: NULL outer, inner or out; n_dst of inner
+ *   != n_src of outer (both numbers are printed; a localized or rebased outer fails here).  MPG_ERR_UNSUPPORTED: a handle with pole terms
+ *   (mpg_handle_pole_count > 0) on either side.  MPG_ERR_OVERFLOW: a composite of more than 2^31 - 2 entries (rowptr is int32); the
+ *   candidate count before de-duplication is a 64-bit quantity and is not what overflows.  A failed allocation returns its error and
+ *   leaks nothing.
+ *
+ * mpg_compose_weights_dev: the same product for caller-owned value planes of B -- how the blocks of mpg_reconstruct_weights_dev or
+ *   mpg_wind_vector_weights_dev pass through a composition.  inner_m_dev [nplanes][nnz_B] in inner's CSR entry order; m_dev
+ *   [nplanes][nnz_C] in composed's entry order; m_k[i,e] follows the rule above with b_q = inner_m[k][q]; nplanes in 1..4.  It neither
+ *   allocates nor synchronises with the host, uses no atomics and can be captured in a hipGraph from its first call.  Memory-safe for any
+ *   three handles whose sizes agree: a pair that does not occur contributes nothing.  With nplanes = 1 and inner's own values it writes
+ *   exactly composed's values.  A composite without entries is success and writes nothing.  Stream as mpg_regrid_dev.
+ *   Refused under the name mpg_compose_weights.  MPG_ERR_UNSUPPORTED: a fixed inner (the planes are defined on CSR entries:
+ *   mpg_handle_get_weights, then mpg_handle_from_weights, makes a CSR handle of it), a fixed composed, pole terms on any handle.
+ *   MPG_ERR_INVALID_ARG: NULL arguments, nplanes outside 1..4, sizes that do not chain (composed.n_dst != outer.n_dst, composed.n_src !=
+ *   inner.n_src, inner.n_dst != outer.n_src), m_dev aliasing inner_m_dev. */
+int mpg_handle_compose(mpg_handle outer, mpg_handle inner, mpg_handle *out);
+int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle inner, int nplanes, const double *inner_m_dev,
+                            double *m_dev, void *hip_stream);
+
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the
@@ -1043,6 +1091,8 @@ int mpg_halo_plan_owned_host(int rank, int nranks, const int64_t *n_needed, cons
  *                 fields of a band of n tiles before the next band
  *   "store_boxes" Stores on a grid that knows its projection: 1 (default) candidates through the grid's index space, 0 the
  *                 hierarchical search always
+ *   "compose_block_rows"  mpg_handle_compose: 0 (default) blocks of destination rows by the byte budget alone, n > 0 of at most n rows
+ *                 as well (tests force many blocks at toy size; the composite is the same)
  * and one that does NOT (it selects between two readings of ESMF's undocumented-here behaviour):
  *   "bilinear_linetype"   Mesh -> Grid bilinear Store: 0 (default) the target point meets the plane of its source triangle
  *                 along the ray from the sphere's centre; 1 along the plane's normal (ESMF_LINETYPE_CART read literally).

@@ -33,6 +33,7 @@ SYMBOLS = [
     "mpg_wind_csr_to_mesh_dev", "mpg_wind_csr_to_edges_dev",
     "mpg_sphere_frames_dev", "mpg_wind_vector_weights_dev", "mpg_wind_vector_dev",
     "mpg_reconstruct_store", "mpg_reconstruct_weights_dev", "mpg_wind_reconstruct_dev",
+    "mpg_handle_compose", "mpg_compose_weights_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -330,6 +331,27 @@ def wind_reconstruct_dev(*args):
     if "wind_reconstruct" not in _to_mesh_fns:
         _to_mesh_fns["wind_reconstruct"] = _WIND_RECONSTRUCT_PROTO(("mpg_wind_reconstruct_dev", load()))
     return _to_mesh_fns["wind_reconstruct"](*args)
+
+
+# Handle composition, bound the same way.
+#   mpg_handle_compose(outer, inner, out)
+#   mpg_compose_weights_dev(composed, outer, inner, nplanes, inner_m_dev, m_dev, hip_stream)
+_HANDLE_COMPOSE_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+_COMPOSE_WEIGHTS_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def handle_compose(*args):
+    """The typed binding of mpg_handle_compose; returns the call's status code."""
+    if "handle_compose" not in _to_mesh_fns:
+        _to_mesh_fns["handle_compose"] = _HANDLE_COMPOSE_PROTO(("mpg_handle_compose", load()))
+    return _to_mesh_fns["handle_compose"](*args)
+
+
+def compose_weights_dev(*args):
+    """The typed binding of mpg_compose_weights_dev; returns the call's status code."""
+    if "compose_weights" not in _to_mesh_fns:
+        _to_mesh_fns["compose_weights"] = _COMPOSE_WEIGHTS_PROTO(("mpg_compose_weights_dev", load()))
+    return _to_mesh_fns["compose_weights"](*args)
 
 
 _lib = None

@@ -125,6 +125,11 @@ int mpg_k_tune(const char *key, int value) {
     mpg_set_lf_rows_store(value);
     return MPG_SUCCESS;
   }
+  if (!strcmp(key, "compose_block_rows")) {   // mpg_handle_compose: 0 = blocks of destination rows by the byte budget alone, n > 0 = of at most n rows as well (the same result)
+    if (value < 0) return MPG_ERR_INVALID_ARG;
+    mpg_set_compose_block_rows(value);
+    return MPG_SUCCESS;
+  }
   if (!strcmp(key, "lfu_min_reuse_x10")) {
     if (value < 0 || value > 1000) return MPG_ERR_INVALID_ARG;
     mpg_lfu_set_min_reuse_x10(value);

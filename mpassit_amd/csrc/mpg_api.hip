@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "compose_checks.h"
 #include "mpg_internal.h"
 #include "wind_reconstruct_checks.h"
 #include "wind_vector_checks.h"
@@ -127,7 +128,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1506,6 +1507,76 @@ int mpg_wind_reconstruct_dev(mpg_handle rh, const double *m_dev, int nout, const
   if (rc) return wv_refused(rc, e);
   return mpg_k_wind_reconstruct(rh, m_dev, nout, u_dev, src_type, src_layout, ldu, nlev, r0_dev, r1_dev, r2_dev, dst_type, dst_layout,
                                 (hipStream_t)hip_stream);
+}
+
+// ---- handle composition: two Regrids folded into one CSR handle (k_compose.hip) -----------------------------------------------------------
+// The checks are host-only text of their own (compose_checks.h), so that a stand-alone program can run them.
+static CoHandle co_handle(mpg_handle rh) { return CoHandle{rh->kind == MPG_KIND_CSR, rh->n_pole, rh->n_src, rh->n_dst, rh->nnz}; }
+
+int mpg_handle_compose(mpg_handle outer, mpg_handle inner, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  CoHandle a{}, b{};
+  if (outer) a = co_handle(outer);
+  if (inner) b = co_handle(inner);
+  int rc = co_check_compose(outer ? &a : nullptr, inner ? &b : nullptr, out, e);
+  if (rc) return wv_refused(rc, e);
+  // Both handles are finished: a Store waits for its build before it hands its handle out, and from-weights handles are uploaded with
+  // blocking copies.  The build runs on the set-up stream, as mpg_handle_get_csr's copies follow whatever produced the handle.
+  mpg_handle_s *h = new mpg_handle_s();
+  h->kind = MPG_KIND_CSR;
+  h->method = -1;
+  h->nnz_per_row = 0;
+  h->n_src = inner->n_src;
+  h->n_dst = outer->n_dst;
+  h->nx_dst = outer->nx_dst;
+  h->ny_dst = outer->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("mpg_handle_compose: hipEventCreate failed");
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_compose(outer, inner, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("mpg_handle_compose: %s", hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle inner, int nplanes, const double *inner_m_dev, double *m_dev,
+                            void *hip_stream) {
+  MPG_CHECK_INIT();
+  WvErr e;
+  CoHandle c{}, a{}, b{};
+  if (composed) c = co_handle(composed);
+  if (outer) a = co_handle(outer);
+  if (inner) b = co_handle(inner);
+  bool nothing;
+  int rc = co_check_weights(composed ? &c : nullptr, outer ? &a : nullptr, inner ? &b : nullptr, nplanes, inner_m_dev, m_dev, &nothing, e);
+  if (rc) return wv_refused(rc, e);
+  if (nothing) return MPG_SUCCESS;   // no entries: nothing to write
+  if (!inner_m_dev) {                // (inner has no entries: every sum is empty)
+    MPG_HIP(hipMemsetAsync(m_dev, 0, sizeof(double) * (size_t)nplanes * (size_t)composed->nnz, (hipStream_t)hip_stream));
+    return MPG_SUCCESS;
+  }
+  return mpg_k_compose_values(composed, outer, inner, nplanes, inner_m_dev, m_dev, (hipStream_t)hip_stream);
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

@@ -499,6 +499,12 @@ int mpg_k_wind_vector(mpg_handle_s *h, const double *m, const void *u, const voi
 int mpg_k_reconstruct_weights(mpg_handle_s *h, int maxEdges, const double *coeffs, const double *dst_frames, double *m, hipStream_t s);
 int mpg_k_wind_reconstruct(mpg_handle_s *h, const double *m, int nout, const void *u, int src_type, int src_layout, int64_t ldu, int nlev,
                            void *r0, void *r1, void *r2, int dst_type, int dst_layout, hipStream_t s);
+// k_compose.hip: c = a . b as one CSR handle (arguments checked by the API entry points).  mpg_k_compose fills c's rowptr, col, val, nnz and
+// max_row (c's shape is the caller's; blocking: it allocates and reads counts back); mpg_k_compose_values writes the values of c's pattern
+// for nplanes planes bm [nplanes][nnz_b] of b's entries into m [nplanes][nnz_c] (bm == nullptr: b's own values, one plane) and only launches
+int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t s);
+int mpg_k_compose_values(mpg_handle_s *c, mpg_handle_s *a, mpg_handle_s *b, int nplanes, const double *bm, double *m, hipStream_t s);
+void mpg_set_compose_block_rows(int v);     // "compose_block_rows" knob (k_compose.hip)
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

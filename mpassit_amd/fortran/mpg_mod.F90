@@ -512,6 +512,20 @@ module mpg
       integer(c_int64_t), value :: u_level_stride
       integer(c_int) :: rc
     end function mpg_wind_reconstruct_dev
+    !> handle composition: C = outer . inner as one CSR handle, and caller-owned value planes of inner taken through it
+    function mpg_handle_compose(outer, inner, out) bind(C, name="mpg_handle_compose") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: outer, inner
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_compose
+    function mpg_compose_weights_dev(composed, outer, inner, nplanes, inner_m_dev, m_dev, hip_stream) &
+        bind(C, name="mpg_compose_weights_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: composed, outer, inner, inner_m_dev, m_dev, hip_stream
+      integer(c_int), value :: nplanes
+      integer(c_int) :: rc
+    end function mpg_compose_weights_dev
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -27,7 +27,7 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
            "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
-           "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd"]
+           "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights"]
 
 
 def _f64(a):
@@ -1605,3 +1605,31 @@ def wind_reconstruct_autograd(rh, m, u, nlev, src_layout=LAYOUT_LEV_FAST, layout
     from-weights handles that the first backward builds from a download of rh.csr() and m and that stay with m; returned in u's shape,
     layout and dtype: the exact adjoint of the forward."""
     return WindReconstructFunction.apply(u, rh, m, nlev, src_layout, layout)
+
+
+# ---- handle composition: two Regrids folded into one CSR handle ---------------------------------------------------------------------------
+def compose(outer, inner):
+    """mpg_handle_compose: C = outer . inner as ONE CSR RouteHandle -- "outer after inner" without the intermediate array.  n_src is
+    inner's, n_dst / nx_dst / ny_dst are outer's; inner.n_dst must equal outer.n_src.  Either operand may be fixed or CSR (no pole terms).
+    Row i holds the distinct sources reachable from outer's row i through inner's rows, ascending; the values are the ordered sums of
+    target_grid.compose_csr, bit for bit.  The handle owns its arrays (outer and inner may be released), is not cached -- release() it --
+    and every CSR consumer takes it: regrid_typed, regrid_csr_to_mesh, regrid_csr_rows, regrid_masked, regrid_transpose, the autograd
+    ops, wind_vector_weights, wind_reconstruct, csr() and to_esmf_weights()."""
+    h = C.c_void_p()
+    check(L.handle_compose(outer._h if outer is not None else None, inner._h if inner is not None else None, C.byref(h)))
+    return RouteHandle(h)
+
+
+def compose_weights(composed, outer, inner, m_inner):
+    """mpg_compose_weights_dev: caller-owned value planes of inner taken through the composition -- m_inner [K][inner.nnz] (K in 1..4, a
+    float64 CUDA tensor in the order of inner.csr()'s entries, e.g. reconstruct_weights' or wind_vector_weights' blocks) -> [K][composed.nnz]
+    float64 CUDA tensor in the order of composed.csr()'s entries, by compose's value rule with b_q = m_inner[k][q].  inner must be a CSR
+    handle.  Neither allocates on the device side nor synchronises: capturable in a graph.  The bits of target_grid.compose_csr."""
+    import torch
+    if not (_is_torch(m_inner) and m_inner.is_cuda and m_inner.is_contiguous() and m_inner.dtype == torch.float64 and m_inner.dim() == 2
+            and m_inner.shape[1] == inner.nnz):
+        raise ValueError("compose_weights: m_inner must be a contiguous float64 CUDA tensor [K][nnz of inner = %d]" % inner.nnz)
+    m = torch.empty((int(m_inner.shape[0]), composed.nnz), dtype=torch.float64, device=m_inner.device)
+    check(L.compose_weights_dev(composed._h, outer._h, inner._h, int(m_inner.shape[0]), m_inner.data_ptr(), m.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream))
+    return m

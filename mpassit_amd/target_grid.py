@@ -367,6 +367,65 @@ def reconstruct_apply(rowptr, col, m, u):
     return np.stack([np.bincount(row, weights=mk * uu, minlength=n) for mk in m])
 
 
+def fixed_to_csr(idx, w=None):
+    """(rowptr, col, val) of a fixed handle's weights() -- idx [n_dst][nnz_per_row] with -1 = no entry, w the same shape or None (a nearest
+    handle: every value 1.0): the slots of a row in their order, the -1 entries dropped.  What mpg_handle_compose reads of a fixed operand."""
+    idx = np.asarray(idx, dtype=np.int64)
+    idx = idx.reshape(idx.shape[0], -1)
+    keep = idx >= 0
+    rowptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64)
+    val = np.ones(idx.shape) if w is None else np.asarray(w, dtype=np.float64).reshape(idx.shape)
+    return rowptr, idx[keep].astype(np.int32), np.ascontiguousarray(val[keep])
+
+
+_COMPOSE_VECTOR_PASSES = 64   # terms of an entry of C summed by vectorised passes; what lies behind them is summed by a plain loop
+
+
+def compose_csr(a_rowptr, a_col, a_val, b_rowptr, b_col, b_vals):
+    """C = A . B of two CSR matrices, the bit-exact mirror of mpg_handle_compose and mpg_compose_weights_dev -> (rowptr int64, col int32,
+    vals [K][nnz_C]) for b_vals [K][nnz_B] (a 1-D b_vals is one plane).  Pattern: row i holds the distinct columns reachable from A's row
+    i through B's rows, ascending; structural (a value of 0.0 stays); rows that reach nothing are empty.  Values: c[i,e] from 0.0, over
+    A's entries p of row i in stored order and within each over B's entries q of row a_col[p] in stored order with b_col[q] == e,
+    acc = acc + (a_p * b_q), the product and the sum each rounded (numpy contracts nothing); duplicates are one term per occurrence.
+    The (p, q) pairs are laid out in that order once; pass t adds the t-th term of every entry, so no index repeats within a pass and
+    each entry sees its terms in order.  Entries with more than _COMPOSE_VECTOR_PASSES terms (long rows, heavy duplicates) finish in a
+    plain loop over their remaining pairs, in the same order."""
+    a_rowptr, b_rowptr = np.asarray(a_rowptr, dtype=np.int64), np.asarray(b_rowptr, dtype=np.int64)
+    a_col, b_col = np.asarray(a_col, dtype=np.int64).reshape(-1), np.asarray(b_col, dtype=np.int64).reshape(-1)
+    a_val = np.asarray(a_val, dtype=np.float64).reshape(-1)
+    b_vals = np.asarray(b_vals, dtype=np.float64)
+    b_vals = b_vals.reshape(1, -1) if b_vals.ndim <= 1 else b_vals
+    K, n = b_vals.shape[0], a_rowptr.size - 1
+    if a_col.size and (a_col.min() < 0 or a_col.max() >= b_rowptr.size - 1):
+        raise ValueError("compose_csr: a column of A lies outside B's rows")
+    # every (p, q) pair, p ascending and q ascending inside p: the summation order
+    blen = np.diff(b_rowptr)[a_col]
+    pair_p = np.repeat(np.arange(a_col.size), blen)
+    first = np.cumsum(blen) - blen                                    # of each p among the pairs
+    pair_q = b_rowptr[a_col][pair_p] + (np.arange(pair_p.size) - first[pair_p])
+    pair_row = np.repeat(np.repeat(np.arange(n), np.diff(a_rowptr)), blen)
+    key = (pair_row << 32) | b_col[pair_q]
+    ukey, entry = np.unique(key, return_inverse=True)                 # sorted: rows together, columns ascending inside a row
+    rowptr = np.searchsorted(ukey >> 32, np.arange(n + 1)).astype(np.int64)
+    col = (ukey & 0xFFFFFFFF).astype(np.int32)
+    vals = np.zeros((K, ukey.size))
+    if pair_p.size == 0:
+        return rowptr, col, vals
+    entry = entry.reshape(-1)
+    order = np.argsort(entry, kind="stable")                          # an entry's pairs, still in summation order
+    start = np.searchsorted(entry[order], np.arange(ukey.size))
+    rank = np.empty(pair_p.size, np.int64)
+    rank[order] = np.arange(pair_p.size) - start[entry[order]]
+    term = a_val[pair_p][None, :] * b_vals[:, pair_q]                 # [K][pairs], each product rounded
+    for t in range(min(int(rank.max()) + 1, _COMPOSE_VECTOR_PASSES)):
+        sel = np.nonzero(rank == t)[0]
+        vals[:, entry[sel]] = vals[:, entry[sel]] + term[:, sel]
+    for s in np.nonzero(rank >= _COMPOSE_VECTOR_PASSES)[0]:           # ascending pair index: ascending rank inside every entry
+        for k in range(K):
+            vals[k, entry[s]] = vals[k, entry[s]] + term[k, s]
+    return rowptr, col, vals
+
+
 @dataclass
 class TargetGrid:
     """Host copy of what `define_target_grid_params` leaves in the ESMF Grid (all [nj][ni], degrees)."""
