@@ -366,9 +366,16 @@ int mpg_regrid_typed_pitched_dev(mpg_handle rh, const void *src_dev, int src_typ
  * rebase).  dst is fully overwritten; a source no entry references gets exactly 0.0 (zeroregion=TOTAL).
  * Types: MPG_TYPE_F64 / MPG_TYPE_F32 on either side, float64 arithmetic, float32 rounded once at the store; MPG_TYPE_BE ->
  * MPG_ERR_UNSUPPORTED.  The linear part only: no scale / offset (the transpose of an affine epilogue is not defined).
- * Determinism: a source's sum runs in ascending (destination point, slot) order, the pole term last, without floating-point
- * atomics: the bits are the same across calls, nfields batching, float32 / float64 inputs that hold the same values and the two
- * layouts.  Stream as mpg_regrid_dev: the first call on a handle builds the transposed index (allocates and synchronises; it is
+ * Values, a contract by identity, per (source c, level k):
+ *   acc = fma(w_j, (double)g[k][row_j], acc) from +0.0 over the stored entries j that reference c, in ascending (destination point,
+ *   slot) order -- for a CSR handle ascending CSR position, duplicates each in their place; w_j of a nearest-neighbour handle is 1.0;
+ *   dst = (dst type)acc, one rounding; a source no entry references gets +0.0.
+ *   With pole caps the sources of the two CENTER rows get (dst type)(acc + term / row_len), the pole term last, where term is reduced in
+ *   a fixed order of its own: thread t of 256 sums w_pole[q] * g[pole_dst[q]] over q = t, t + 256, ... ascending (caps of weight 0
+ *   skipped; whether that product is fused into the sum is not promised), the 256 partial sums are combined by a binary tree
+ *   (p[t] += p[t + s] for s = 128, 64, ..., 1), one sum per row; where the two rows coincide the first row's term is added first.
+ * Determinism: no floating-point atomics; the bits are the same across calls, nfields batching, float32 / float64 inputs that hold the
+ * same values and the two layouts.  Stream as mpg_regrid_dev: the first call on a handle builds the transposed index (allocates and synchronises; it is
  * dropped whenever the handle is re-indexed); every later call only enqueues and can be captured in a hipGraph. */
 int mpg_regrid_transpose_dev(mpg_handle rh, const void *src_dev, int src_type, int64_t src_level_stride, int nlev, int nfields,
                              void *dst_dev, int dst_type, int dst_layout, void *hip_stream);
@@ -567,7 +574,11 @@ int mpg_regrid_bundle_typed(mpg_handle rh, int nfields, const void *const *src_h
 int mpg_handle_release(mpg_handle rh);
 
 /* ---- rotate_winds_cgrid (interp.F90:689-749): in place on CENTER-stagger u, v [nlev][ny][nx] with
- * cosalpha/sinalpha [ny][nx] (model_grid.F90:1154).  */
+ * cosalpha/sinalpha [ny][nx] (model_grid.F90:1154).  Values, a contract by identity (interp.F90:737-748 as written): per point
+ *   tana = sa / ca;  den = ca + sa * tana                       and per level, from the old uo, vo
+ *   un = (uo + vo * tana) / den;  vn = (vo - un * sa) / ca      (vn uses the NEW un)
+ * seven float64 operations, each rounded, nothing contracted or reordered; ca == +-0.0 and non-finite winds give what IEEE 754 gives.
+ * The host form uploads, runs the same kernel and downloads: the same bits. */
 int mpg_rotate_winds(int64_t npts, int nlev, const double *cosa_host, const double *sina_host,
                      double *u_host, double *v_host);
 int mpg_rotate_winds_dev(int64_t npts, int nlev, const double *cosa_dev, const double *sina_dev,
@@ -879,8 +890,11 @@ int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle in
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the
  * conversion nf90_put_var applies (round to nearest).  Device pointers; hip_stream as in mpg_regrid_dev.  dst_be != 0
  * stores the float32 results big-endian (the variable's bytes in a NetCDF classic file), as MPG_TYPE_BE does for Regrid.
- *   mpg_post_cast_dev        dst = (float)(src*scale + offset): plain fields (scale 1, offset 0), T - 300 (:1339-1347,
- *                            the `continue` in that loop is a no-op statement, so every point is shifted), PHB*9.81 (:1418)
+ *   mpg_post_cast_dev        dst = (float)fma(src, scale, offset), one float64 rounding and the conversion: plain fields (scale 1,
+ *                            offset 0), T - 300 (:1339-1347, the `continue` in that loop is a no-op statement, so every point is
+ *                            shifted), PHB*9.81 (:1418).  The writer uses scale or offset, never both: fma(src, 1, offset) is
+ *                            src + offset and fma(src, scale, 0) is src * scale rounded once, the reference's single operation;
+ *                            with both set the product is NOT rounded before the sum
  *   mpg_post_layer_mean_dev  Z_C(k) = 0.5*(PHB(k+1) + PHB(k)), src [nlevp1][n_pts] -> dst [nlevp1-1][n_pts] (:1406-1415)
  *   mpg_post_ptop_dev        P_TOP from P_HYD [nlev][n_pts]: min(maxval(P_HYD), 0.8*P_HYD(top) over columns whose top
  *                            value is >= 10) (:1362-1371); float64 result returned to the host, blocks on the stream */

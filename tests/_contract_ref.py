@@ -5,7 +5,11 @@ The C file is written from the header's text -- explicit fma() where the header 
 elsewhere -- and built at first use with  gcc -O2 -fPIC -shared -ffp-contract=off  into a temporary directory.  It takes a handle's
 own exported pattern (RouteHandle.weights(), .csr(), .pole()) and host arrays; nothing here touches a GPU.
 
-`variant` (REVERSED, MULADD, EPI_MULADD, EPI_SKIP, COLSORT) selects a deliberately wrong recipe; 0 is the contract."""
+`variant` (REVERSED, MULADD, EPI_MULADD, EPI_SKIP, COLSORT) selects a deliberately wrong recipe; 0 is the contract.
+
+Besides the forward Regrids, the masked recipe and the mesh wind products: the transpose (transpose, transposed, special_g,
+transpose_shares, synthetic_transpose_case), the rotation (rotate) and the Grid -> Grid wind chain (wind_destagger, mass_winds,
+winds_are_informative)."""
 import atexit
 import ctypes as C
 import math
@@ -42,6 +46,12 @@ def lib():
                                       C.c_double, C.c_double]
         L.cr_wind_pair.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_int]
+        L.cr_apply_transpose.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int]
+        L.cr_rotate.restype = None
+        L.cr_rotate.argtypes = [C.c_int64, C.c_int] + [C.c_void_p] * 4
+        L.cr_wind_destagger.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [
+            C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -215,6 +225,224 @@ def pole_caps(pat, src, nlev, nfields, src_lev_fast, dst_dtype, epilogue, scale,
     with np.errstate(invalid="ignore", over="ignore"):
         bound = (row_len + 3) * 2.0 ** -53 * np.abs(wp)[None, None, :] * ma * abs(scale if epilogue else 1.0)
     return dst, want, bound, must_nan, free
+
+
+# ---- the transpose, the rotation and the Grid -> Grid wind chain -------------------------------------------------------------------
+def transposed(pat):
+    """The pattern of A^T as a CSR Pattern: one row per source of `pat`, its entries in ascending (destination point, slot or CSR
+    position) order, a nearest handle's weight 1.0.  Built with a stable sort, not with cr_apply_transpose's dealing loop: cr.apply on
+    it (the CSR chain in stored order, no epilogue) is a second statement of the transpose's sum, and the source generators (special,
+    special_is_informative) work on it as they do on a forward pattern.  Pole caps are not part of it."""
+    if pat.nnz:
+        keep = (pat.idx >= 0).reshape(-1)
+        c = pat.idx.reshape(-1)[keep].astype(np.int64)
+        p = np.repeat(np.arange(pat.n_dst, dtype=np.int64), pat.nnz)[keep]
+        w = np.ones(c.size) if pat.nnz == 1 else pat.w.reshape(-1)[keep]
+    else:
+        c = pat.col.astype(np.int64)
+        p = np.repeat(np.arange(pat.n_dst, dtype=np.int64), np.diff(pat.rowptr))
+        w = pat.val
+    order = np.argsort(c, kind="stable")
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(c, minlength=pat.n_src))])
+    return Pattern(pat.n_dst, pat.n_src, 0, rowptr=rowptr, col=p[order], val=w[order])
+
+
+def transpose(pat, g, nlev=1, nfields=1, dst_dtype=np.float64, dst_lev_fast=False, g_level_stride=0, variant=0):
+    """mpg_regrid_transpose_dev without the pole term.  g: float32 / float64, nfields * nlev planes of n_dst, g_level_stride elements
+    apart (0: dense).  Returns ((nfields, nlev, n_src) or, dst_lev_fast, (nfields, n_src, nlev) of dst_dtype, cap [n_src] bool: the
+    sources of the CENTER rows that a pole cap adds its term to -- there the result is the segment sum alone)."""
+    g = np.ascontiguousarray(g)
+    ld = g_level_stride or pat.n_dst
+    assert g.dtype in (np.float32, np.float64) and g.size >= (nfields * nlev - 1) * ld + pat.n_dst, (g.dtype, g.size, nfields, nlev, ld)
+    dst = _dst(pat.n_src, nlev, nfields, dst_dtype, dst_lev_fast)
+    cap = np.zeros(pat.n_src, np.uint8)
+    p = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    if pat.nnz:
+        w = None if pat.nnz == 1 else pat.w
+        handle = (p(pat.idx), p(w), None, None, None)
+    else:
+        handle = (None, None, p(pat.rowptr), p(pat.col), p(pat.val))
+    if pat.pole is not None:
+        _, src0, wp, row_len = pat.pole
+        src0, wp = np.ascontiguousarray(src0, np.int32), np.ascontiguousarray(wp, np.float64)
+        pole = (p(src0), p(wp), src0.size, int(row_len))
+    else:
+        pole = (None, None, 0, 0)
+    rc = lib().cr_apply_transpose(pat.nnz, *handle, pat.n_src, pat.n_dst, g.ctypes.data, int(g.dtype == np.float32), int(g_level_stride), nlev, nfields,
+                                  dst.ctypes.data, int(dst.dtype == np.float32), int(dst_lev_fast), *pole, cap.ctypes.data, int(variant))
+    assert rc == 0, "contract_ref: rc %d" % rc
+    return dst, cap.astype(bool)
+
+
+def rotate(cosa, sina, u, v):
+    """mpg_rotate_winds on copies: (u', v') of u, v [nlev][npts] float64"""
+    cosa, sina = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (cosa, sina))
+    u, v = (np.array(a, np.float64, order="C") for a in (u, v))
+    assert u.shape == v.shape and u.size % cosa.size == 0 and cosa.size == sina.size
+    lib().cr_rotate(cosa.size, u.size // cosa.size, cosa.ctypes.data, sina.ctypes.data, u.ctypes.data, v.ctypes.data)
+    return u, v
+
+
+def wind_destagger(pat1, pat2, cosa, sina, umass, vmass, nlev, dst_type=0, dst_level_stride=0, keep_mass=False):
+    """The Grid -> Grid wind chain.  pat1 / pat2: the EDGE1 / EDGE2 patterns (4 slots) or None; cosa / sina [n_mass] or None; umass / vmass
+    [nlev][n_mass] float64.  dst_type as MPG_TYPE_*: 0 float64 (the sum as it stands), 1 float32, 2 float64 big-endian, 3 float32
+    big-endian.  Returns (U, V, umass', vmass'): U / V (nlev, ld) of float64 / float32 with ld = dst_level_stride or the component's n_dst,
+    elements past n_dst NaN (never written); None for a component without a pattern; the rotated mass winds only with keep_mass."""
+    n_mass = (pat1 or pat2).n_src
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)   # noqa: E731
+    cosa, sina, umass, vmass = f(cosa), f(sina), f(umass), f(vmass)
+    dt = np.float32 if dst_type & 1 else np.float64
+    outs = [None if pat is None else np.full((nlev, dst_level_stride or pat.n_dst), np.nan, dt) for pat in (pat1, pat2)]
+    rots = [np.empty((nlev, n_mass)) if keep_mass and cosa is not None else None for _ in range(2)]
+    p = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    args = []
+    for pat in (pat1, pat2):
+        assert pat is None or (pat.nnz == 4 and pat.n_src == n_mass)
+        args += [None, None, 0] if pat is None else [p(pat.idx), p(pat.w), pat.n_dst]
+    rc = lib().cr_wind_destagger(*args, n_mass, p(cosa), p(sina), p(umass), p(vmass), nlev, p(outs[0]), p(outs[1]), int(dst_type), int(dst_level_stride),
+                                 p(rots[0]), p(rots[1]))
+    assert rc == 0, "contract_ref: rc %d" % rc
+    return outs[0], outs[1], rots[0], rots[1]
+
+
+# the segment lengths the synthetic transpose handle must hold: they bracket the 4-slot form, TR_SHORT = 16 and a wave of 64 lanes
+SYN_LENGTHS = (0, 1, 2, 3, 4, 5, 15, 16, 17, 18, 63, 64, 65, 300)
+SYN_N_SRC, SYN_NX, SYN_NY = 41, 401, 1
+
+
+def synthetic_transpose_case():
+    """(row, col, S) 1-based for RouteHandle.from_weights(SYN_N_SRC, SYN_NX, SYN_NY, ...) and the Pattern it must give: 401 destination
+    points over 41 sources (not a multiple of 64) whose transposed segments have exactly the SYN_LENGTHS, on sources spread over the
+    index range, and 1 to 8 entries on each of the others; a destination's entries are drawn with replacement, so (row, col) pairs repeat
+    (the 300-entry source has fewer than 300 distinct rows by construction, and one pair is repeated on purpose in adjacent and in
+    separated positions); the entries come in shuffled order, so a row's stored order is not its column order.  Destination point 0
+    holds one entry: the padded slots of the register kernels load row 0."""
+    rng = np.random.default_rng(77)
+    n_dst = SYN_NX * SYN_NY
+    special_src = rng.permutation(SYN_N_SRC)[:len(SYN_LENGTHS)]
+    length = rng.integers(1, 9, SYN_N_SRC)
+    length[special_src] = SYN_LENGTHS
+    rows, cols = [], []
+    for c in range(SYN_N_SRC):
+        r = rng.integers(1, n_dst, int(length[c]))                 # point 0 is given its one entry below
+        if length[c] == 5:
+            r[:] = (200, 200, 7, 200, 390)                          # one pair three times: adjacent and separated
+        rows.append(r)
+        cols.append(np.full(r.size, c))
+    row, col = np.concatenate(rows), np.concatenate(cols)
+    one = int(np.nonzero(length == 1)[0][0])                        # the one-entry source sits on destination point 0
+    row[np.nonzero(col == one)[0][0]] = 0
+    S = rng.uniform(0.0, 1.0, row.size)
+    shuffle = rng.permutation(row.size)
+    row, col, S = row[shuffle], col[shuffle], S[shuffle]
+    order = np.argsort(row, kind="stable")                          # from_weights keeps the caller's order inside a row
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=n_dst))]).astype(np.int64)
+    pat = Pattern(SYN_N_SRC, n_dst, 0, rowptr=rowptr, col=col[order], val=S[order])
+    return ((row + 1).astype(np.int32), (col + 1).astype(np.int32), S), pat
+
+
+def segment_lengths(pat):
+    """entries per source of the transposed index, [n_src]"""
+    return _row_counts(pat)
+
+
+def special_g(pat, nlev, nfields, seed=0):
+    """Grid values for the transpose of `pat`, (nfields, nlev, n_dst): `special` on the transposed pattern, and a NaN at destination
+    point 0 of every plane -- the row the padded slots of the register kernels load.  Returns (g, where, the transposed pattern):
+    special_is_informative(transposed pattern, g, where, ...) is the check of the result.
+
+    A handle with fewer than 1000 destination points cannot take `special`'s placements: with 40 sources (the synthetic handle) one
+    level of one field has 40 outputs, four may be non-finite, and five kinds of a float32 source are (NaN, the infinities,
+    +-3.5e38); with 180 points read by six sources each (the composed handle) every non-finite element costs six outputs.  There each
+    kind sits once per field, kind j at level (j + f) % nlev, on the points that cost least: points that only the LONGEST segment reads
+    where it has eleven of them (one output of a level is lost however many kinds share it; from 17 levels on every kind has a level
+    to itself, below that an infinity beside a NaN shows nothing of its own), else the points with the fewest readers.  The random
+    picks (_special_share of the elements, any point, no minimum) add the rest."""
+    pt = transposed(pat)
+    if pt.n_src >= 1000:
+        x, where = special(pt, nlev, nfields, seed)
+    else:
+        x = ordinary(pt.n_src, nlev, nfields, seed)
+        rng = np.random.default_rng(991 + 31 * nlev + seed)
+        where = {name: np.zeros(x.shape, bool) for name, _ in SPECIALS}
+        readers = _row_counts(pt)
+        longest = int(np.diff(pt.rowptr).argmax())
+        own = pt.col[pt.rowptr[longest]:pt.rowptr[longest + 1]]
+        own = rng.permutation(np.unique(own[(readers[own] == 1) & (own != 0)]))
+        if own.size < len(SPECIALS):
+            read = np.nonzero(readers > 0)[0]
+            read = rng.permutation(read[read != 0])
+            own = read[np.argsort(readers[read], kind="stable")]
+        assert own.size >= len(SPECIALS)
+        pick = rng.choice(x.size, size=int(x.size * _special_share(pt)), replace=False)
+        for j, e in enumerate(pick):
+            name, v = SPECIALS[j % len(SPECIALS)]
+            f, k, c = np.unravel_index(e, x.shape)
+            _place(x, where, name, v, f, k, c)
+        for f in range(nfields):
+            for j, (name, v) in enumerate(SPECIALS):
+                _place(x, where, name, v, f, (j + f) % nlev, int(own[j]))
+    for f in range(nfields):
+        for k in range(nlev):
+            _place(x, where, "nan", float("nan"), f, k, 0)
+    return x, where, pt
+
+
+def transpose_shares(pat, g, nlev, nfields):
+    """{wrong recipe: share of the outputs that can differ whose bits do differ}, reference against reference.  Reversing a segment can
+    change a source with two entries or more (fma(w1, x1, round(w0 x0)) against fma(w0, x0, round(w1 x1))) -- three or more where all its
+    weights are 1.0 (a nearest handle, mpg_reconstruct_store's values), where two terms add exactly either way; a separate multiply
+    and add can change a source with two entries or more, and none whose weights are all 1.0 (every product is exact).  A recipe that can
+    change no source of the pattern is not listed."""
+    pt = transposed(pat)
+    n = np.diff(pt.rowptr)
+    unit = np.ones(pat.n_src, bool)
+    unit[np.repeat(np.arange(pat.n_src), n)[pt.val != 1.0]] = False
+    want, _ = transpose(pat, g, nlev, nfields)
+    out = {}
+    for name, variant, can in (("segment reversed", REVERSED, n >= np.where(unit, 3, 2)), ("separate multiply and add", MULADD, (n >= 2) & ~unit)):
+        if can.any():
+            out[name] = float(differs(want, transpose(pat, g, nlev, nfields, variant=variant)[0])[:, :, can].mean())
+    return out
+
+
+def mass_winds(nx, ny, nlev, kind, seed=0):
+    """(umass, vmass, {kind: (mask in umass, mask in vmass)}) for the wind chain and the rotation, [nlev][ny * nx] float64: N(0, 12)
+    winds kept away from zero.  "special": 0.3 % of the elements replaced by the SPECIALS, and every kind once on the rim of each
+    array -- kind j of array a on side (j + 2 a) % 4 of first row, last row, first column, last column, so NaN and both infinities
+    sit on every side between the two arrays; the NaN of umass on the first corner and the +Inf of vmass on the last -- so that the halo
+    of the first and of the last tile sees them.  One placement per kind and array, no more: a mass point is read by up to four U and
+    four V points, and rotated by both components, so on the 19 x 11 grid at one level six non-finite elements already cost 8 % of
+    the outputs."""
+    rng = np.random.default_rng(515 + 7 * nx + 3 * nlev + seed)
+    uv = rng.normal(0.0, 12.0, (2, nlev, ny * nx))
+    uv = np.where(np.abs(uv) < 0.5, 0.5, uv)
+    where = {name: np.zeros(uv.shape, bool) for name, _ in SPECIALS}
+    if kind == "special":
+        for j, e in enumerate(rng.choice(uv.size, size=int(0.003 * uv.size), replace=False)):
+            a, k, c = np.unravel_index(e, uv.shape)
+            _place(uv, where, SPECIALS[j % len(SPECIALS)][0], SPECIALS[j % len(SPECIALS)][1], a, k, c)
+        for a in range(2):
+            for j, (name, v) in enumerate(SPECIALS):
+                t = 3 * j + a
+                y, x = ((0, t % nx), (ny - 1, nx - 1 - t % nx), (t % ny, 0), (ny - 1 - t % ny, nx - 1))[(j + 2 * a) % 4]
+                if (a, name) == (1, "+inf"):
+                    y, x = ny - 1, nx - 1
+                _place(uv, where, name, v, a, (j + a) % nlev, y * nx + x)
+    return uv[0].copy(), uv[1].copy(), {k: (m[0], m[1]) for k, m in where.items() if m.any()}
+
+
+def winds_are_informative(pat1, pat2, rotated, where, u, v):
+    """Every special kind placed in the mass winds reaches an output of every field it can (rotated: U and V from either array; else U
+    from umass, V from vmass), and at least 90 % of the mapped outputs of the reference (float64) are finite.  Returns that share."""
+    assert set(where) == set(k for k, _ in SPECIALS), sorted(where)
+    for name, (mu, mv) in where.items():
+        for pat, masks in ((pat1, (mu, mv) if rotated else (mu,)), (pat2, (mu, mv) if rotated else (mv,))):
+            for m in masks:
+                assert pat is None or (m.any() and reaches(pat, m)), "special kind %r reaches no output of a component" % name
+    fin = float(np.concatenate([np.isfinite(a[:, :pat.n_dst][:, ~pat.unmapped]).reshape(-1) for a, pat in ((u, pat1), (v, pat2)) if pat is not None]).mean())
+    assert fin >= 0.9, "only %.1f %% of the special winds' outputs are finite" % (100.0 * fin)
+    return fin
 
 
 # ---- comparison by bits -------------------------------------------------------------------------------------------------------

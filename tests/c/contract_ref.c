@@ -215,3 +215,154 @@ int cr_wind_pair(int mode, const double *a, const double *b, const double *c, co
     }
   return 0;
 }
+
+/* mpg_regrid_transpose_dev, per (source c, level k): acc = fma(w_j, (double)g[k][row_j], acc) from +0.0 over the stored entries that
+ * reference c, ascending by (destination point, slot) -- for a CSR handle by position, duplicates included --, then (dst type)acc, one
+ * rounding; a source nothing references gets +0.0.  nnz > 0: a fixed handle (idx / w [n_dst][nnz], idx < 0 skipped; w NULL: weight 1,
+ * a nearest handle); nnz == 0: a CSR handle.  g: nfields * nlev planes of n_dst, g_level_stride elements apart (0 = dense).
+ * The pole term is NOT restated: cap_row [n_src] (may be NULL) comes back 1 on the sources of the CENTER rows that a cap with a non-zero
+ * weight adds its term to, 0 elsewhere; those sources hold the segment sum alone here.
+ * variant: CR_MULADD, and CR_REVERSED (the segment last entry first). */
+int cr_apply_transpose(int nnz, const int32_t *idx, const double *w, const int64_t *rowptr, const int32_t *col, const double *val, int64_t n_src,
+                       int64_t n_dst, const void *g, int g_f32, int64_t g_level_stride, int nlev, int nfields, void *dst, int dst_f32,
+                       int dst_lev_fast, const int32_t *pole_src0, const double *pole_w, int64_t n_pole, int row_len, uint8_t *cap_row, int variant) {
+  if (nnz != 0 && nnz != 1 && nnz != 3 && nnz != 4) return 1;
+  const int64_t ld = g_level_stride ? g_level_stride : n_dst;
+  if (ld < n_dst) return 3;
+  const int64_t ne = nnz ? n_dst * nnz : rowptr[n_dst];
+  int64_t *ptr = (int64_t *)calloc((size_t)n_src + 2, sizeof(int64_t));
+  int64_t *rows = (int64_t *)malloc(sizeof(int64_t) * (size_t)(ne + 1));
+  double *wts = (double *)malloc(sizeof(double) * (size_t)(ne + 1));
+  int rc = 0;
+  /* entries in (point, slot) order, dealt to their sources: each source's list is ascending by construction */
+  for (int pass = 0; pass < 2 && !rc; ++pass) {
+    for (int64_t p = 0; p < n_dst && !rc; ++p) {
+      const int64_t b = nnz ? p * nnz : rowptr[p], e = nnz ? b + nnz : rowptr[p + 1];
+      for (int64_t j = b; j < e; ++j) {
+        const int32_t c = nnz ? idx[j] : col[j];
+        if (c < 0 && nnz) continue;
+        if (c < 0 || c >= n_src) { rc = 2; break; }
+        if (pass == 0) ptr[c + 2]++;
+        else {
+          const int64_t at = ptr[c + 1]++;
+          rows[at] = p;
+          wts[at] = nnz ? (w ? w[j] : 1.0) : val[j];
+        }
+      }
+    }
+    if (pass == 0)
+      for (int64_t c = 0; c < n_src; ++c) ptr[c + 2] += ptr[c + 1];   /* ptr[c + 1] = start of c; after the fill, ptr[c + 1] = its end */
+  }
+  /* now the segment of c is [ptr[c], ptr[c + 1]) */
+  for (int f = 0; f < nfields && !rc; ++f)
+    for (int k = 0; k < nlev; ++k) {
+      const int64_t gb = ((int64_t)f * nlev + k) * ld, db = (int64_t)f * nlev * n_src;
+      for (int64_t c = 0; c < n_src; ++c) {
+        double acc = 0.0;
+        if (variant & CR_REVERSED)
+          for (int64_t j = ptr[c + 1] - 1; j >= ptr[c]; --j) acc = accum(wts[j], load(g, g_f32, gb + rows[j]), acc, variant);
+        else
+          for (int64_t j = ptr[c]; j < ptr[c + 1]; ++j) acc = accum(wts[j], load(g, g_f32, gb + rows[j]), acc, variant);
+        store(dst, dst_f32, db + dst_at(dst_lev_fast, n_src, nlev, c, k), acc);
+      }
+    }
+  if (cap_row) {
+    for (int64_t c = 0; c < n_src; ++c) cap_row[c] = 0;
+    for (int64_t q = 0; q < n_pole; ++q) {
+      if (pole_w[q] == 0.0) continue;
+      if (pole_src0[q] < 0 || pole_src0[q] + (int64_t)row_len > n_src) { rc = 2; break; }
+      for (int i = 0; i < row_len; ++i) cap_row[pole_src0[q] + i] = 1;
+    }
+  }
+  free(ptr);
+  free(rows);
+  free(wts);
+  return rc;
+}
+
+/* mpg_rotate_winds[_dev], in place on u, v [nlev][npts]: the seven operations of the header, each rounded and nothing contracted */
+void cr_rotate(int64_t npts, int nlev, const double *cosa, const double *sina, double *u, double *v) {
+  for (int64_t p = 0; p < npts; ++p) {
+    const double ca = cosa[p], sa = sina[p];
+    const double tana = sa / ca;
+    const double sat = sa * tana;
+    const double den = ca + sat;
+    for (int k = 0; k < nlev; ++k) {
+      const int64_t q = (int64_t)k * npts + p;
+      const double uo = u[q], vo = v[q];
+      const double t1 = vo * tana;
+      const double s1 = uo + t1;
+      const double un = s1 / den;
+      const double t2 = un * sa;
+      const double d2 = vo - t2;
+      u[q] = un;
+      v[q] = d2 / ca;
+    }
+  }
+}
+
+static void swap_bytes(void *p, int n) {
+  unsigned char *b = (unsigned char *)p;
+  for (int i = 0; i < n / 2; ++i) {
+    const unsigned char t = b[i];
+    b[i] = b[n - 1 - i];
+    b[n - 1 - i] = t;
+  }
+}
+
+/* mpg_wind_destagger[_pitched]_dev / mpg_wind_destagger: cr_rotate on copies of the mass winds [nlev][n_mass] (cosa NULL: none), then
+ * the 4-slot chain of cr_apply_fixed on the EDGE1 handle (idx1 / w1 [n1][4], U from the rotated umass) and the EDGE2 handle (idx2 / w2
+ * [n2][4], V from the rotated vmass); a NULL idx: that component is not produced.  dst_type 0 (float64): the sum as it stands; 1 (float32),
+ * 2 (float64 big-endian), 3 (float32 big-endian): (TD)fma(sum, 1.0, 0.0), a big-endian result being the byte-reversed bits.  u / v:
+ * nlev planes, dst_level_stride elements apart (0 = dense); elements between the planes are not written.  urot / vrot (may be NULL):
+ * the rotated mass winds. */
+int cr_wind_destagger(const int32_t *idx1, const double *w1, int64_t n1, const int32_t *idx2, const double *w2, int64_t n2, int64_t n_mass,
+                      const double *cosa, const double *sina, const double *umass, const double *vmass, int nlev, void *u, void *v, int dst_type,
+                      int64_t dst_level_stride, double *urot, double *vrot) {
+  const size_t nl = (size_t)n_mass * (size_t)nlev;
+  double *um = NULL, *vm = NULL;
+  if (cosa) {
+    if (!sina || !umass || !vmass) return 1;
+    um = (double *)malloc(sizeof(double) * (nl + 1));
+    vm = (double *)malloc(sizeof(double) * (nl + 1));
+    for (size_t i = 0; i < nl; ++i) {
+      um[i] = umass[i];
+      vm[i] = vmass[i];
+    }
+    cr_rotate(n_mass, nlev, cosa, sina, um, vm);
+    if (urot) for (size_t i = 0; i < nl; ++i) urot[i] = um[i];
+    if (vrot) for (size_t i = 0; i < nl; ++i) vrot[i] = vm[i];
+  }
+  const int f32 = dst_type & 1, be = dst_type & 2, typed = dst_type != 0;
+  int rc = 0;
+  for (int comp = 0; comp < 2 && !rc; ++comp) {
+    const int32_t *idx = comp ? idx2 : idx1;
+    const double *w = comp ? w2 : w1;
+    const int64_t n = comp ? n2 : n1;
+    const double *src = comp ? (vm ? vm : vmass) : (um ? um : umass);
+    void *out = comp ? v : u;
+    if (!idx) continue;
+    if (!src || !out) { rc = 1; break; }
+    const int64_t ld = dst_level_stride ? dst_level_stride : n;
+    if (ld < n) { rc = 3; break; }
+    double *plane = (double *)malloc(sizeof(double) * (size_t)(n + 1));
+    const double zero = 0.0;
+    for (int k = 0; k < nlev && !rc; ++k) {
+      rc = cr_apply_fixed(idx, w, 4, n_mass, n, src + (size_t)k * (size_t)n_mass, 0, 0, 1, 1, plane, 0, 0, typed, 1.0, &zero, 0);
+      for (int64_t p = 0; p < n && !rc; ++p) {
+        const int64_t at = (int64_t)k * ld + p;
+        if (f32) {
+          ((float *)out)[at] = (float)plane[p];
+          if (be) swap_bytes((float *)out + at, 4);
+        } else {
+          ((double *)out)[at] = plane[p];
+          if (be) swap_bytes((double *)out + at, 8);
+        }
+      }
+    }
+    free(plane);
+  }
+  free(um);
+  free(vm);
+  return rc;
+}

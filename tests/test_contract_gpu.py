@@ -13,13 +13,21 @@ Levels 1, 2, 17 and 65, two fields.  Sources: ordinary N(280, 30) data and the s
 subnormals of both types, values whose sums overflow or whose float32 cast does), each as float64 and as float32.  Epilogues (1, 0),
 (9.81, -300) and (9.81, -2700): the last one is where a multiply-then-add epilogue shows in nearly every result (_contract_ref.recipe_shares).
 
-Out of scope and not held here: mpg_regrid_transpose_dev, mpg_rotate_winds and the Grid -> Grid wind chain.
+The transpose (mpg_regrid_transpose_dev) on ten of those handles, on one from mpg_reconstruct_store, one from mpg_handle_compose and a
+synthetic from_weights handle whose transposed segments bracket every kernel's thresholds (_contract_ref.synthetic_transpose_case), with
+ordinary and special grid values (a NaN at destination point 0, the row the padded slots load), dense and pitched with NaN in the pad;
+the rotation (mpg_rotate_winds_dev and mpg_rotate_winds) with cos(alpha) entries of 0.0 and -0.0; the Grid -> Grid wind chain
+(mpg_wind_destagger_dev, _pitched_dev and the host mpg_wind_destagger) on mass grids of 19 x 11, 65 x 17 and 203 x 35 points.  Two derived
+bounds besides test_pole_caps': the cap-row sources of the periodic handle's transpose (_transpose_ref.transpose_ref's), and the pole
+rows of V in the wind chain on the periodic grid (test_pole_caps' own).  The only arithmetic the header does not pin, and so the only
+values not held by bits here, are those two pole terms: the summation order of a cap's row mean and of the transpose's cap reduction.
 
 Every input is a CUDA tensor: nothing goes through the host pipeline."""
 import numpy as np
 import pytest
 
 import _contract_ref as cr
+import _wind_reconstruct_helpers as H
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +68,28 @@ class Case:
             self._src[key] = dict(np=x, cf=cf, lf=cf.transpose(1, 2).contiguous(), where=where)
         return self._src[key]
 
+    def grid_values(self, name, kind, nlev, sdt):
+        """grid values for the transpose of a handle: {'np': (NF, nlev, n_dst) of sdt, 'cf': the same on the GPU, 'pitched': a view
+        (NF, nlev, ny_dst, nx_dst) of it whose planes lie a padded stride apart in a NaN-filled buffer}"""
+        import torch
+        key = (name, "g " + kind, nlev, sdt, 0)
+        if key not in self._src:
+            pat, rh = self.pat[name], self.rh[name]
+            if kind == "ordinary":
+                x = cr.ordinary(pat.n_dst, nlev, NF)
+            else:
+                x, where, pt = cr.special_g(pat, nlev, NF)
+            x = cr.to_f32(x) if sdt == F32 else x
+            if kind != "ordinary":      # every kind reaches an output of each field, >= 90 % of the referenced outputs finite
+                cr.special_is_informative(pt, x, where, nlev, NF)
+            cf = torch.from_numpy(x).cuda()
+            ld = (pat.n_dst + 15) // 16 * 16 + 16
+            buf = torch.full((NF * nlev * ld,), float("nan"), dtype=cf.dtype, device="cuda")
+            view = buf.as_strided((NF, nlev, rh.ny_dst, rh.nx_dst), (nlev * ld, ld, rh.nx_dst, 1))
+            view.copy_(cf.reshape(NF, nlev, rh.ny_dst, rh.nx_dst))
+            self._src[key] = dict(np=x, cf=cf, pitched=view)
+        return self._src[key]
+
     def drop_sources(self):
         self._src.clear()
 
@@ -82,6 +112,7 @@ def case(gpu_lib, regional_case, global_mesh, conus_grid_30km):
     c.add("narrow csr", R.regrid_store(mesh_t, grid_n, R.REGRIDMETHOD_CONSERVE))
     gp = R.Grid.from_target(T.define_target_grid_params("lat-lon", nx=73, ny=37, stand_lon=0.0, is_regional=False))
     c.add("pole 4", R.regrid_store_grid(gp, R.STAGGERLOC_EDGE2))
+    c.add("periodic E1", R.regrid_store_grid(gp, R.STAGGERLOC_EDGE1))
     gm = synth.mesh_edges(global_mesh)
     mesh_g, grid_c = R.Mesh.from_mpas(gm), R.Grid.from_target(conus_grid_30km)
     c.mesh_g, c.grid_c = mesh_g, grid_c
@@ -93,10 +124,18 @@ def case(gpu_lib, regional_case, global_mesh, conus_grid_30km):
     (row, col, S), fw = cr.from_weights_case()
     c.add("fw csr", R.RouteHandle.from_weights(cr.FW_N_SRC, cr.FW_NX, cr.FW_NY, row, col, S))
     c.fw = fw
+    (row, col, S), c.syn = cr.synthetic_transpose_case()
+    c.add("syn csr", R.RouteHandle.from_weights(cr.SYN_N_SRC, cr.SYN_NX, cr.SYN_NY, row, col, S))
+    mc = H.mesh_case(synth.icosahedral_mesh(3))
+    rec = c.add("rec csr", R.reconstruct_store(mc["n_on"], mc["eoc"], mc["m"].nEdges))
+    rng = np.random.default_rng(31)            # 300 points that each take one cell of their own, with a weight: 300 rows of that cell's edges
+    c.pick_i = R.RouteHandle.from_weights(rec.n_dst, 300, 1, np.arange(1, 301, dtype=np.int32), (rng.permutation(rec.n_dst)[:300] + 1).astype(np.int32),
+                                          rng.uniform(0.5, 1.5, 300))
+    c.add("comp csr", R.compose(c.pick_i, rec))
     c.obj = [mesh, grid, mesh_t, grid_n, gp, mesh_g, grid_c]
     yield c
     c.drop_sources()
-    for rh in c.rh.values():
+    for rh in list(c.rh.values()) + [c.pick_i]:
         rh.release()
     for o in c.obj:
         o.destroy()
@@ -519,3 +558,317 @@ def test_wind_csr_to_edges(case, twins, twice):
     c, s = R.mesh_edge_rotang(None, case.mesh_g)
     _winds(case, "edges", "p2m csr edges", name_v, R.wind_csr_to_edges, c, s, (1, 2, 17), ("special",), (True, False))
     _winds(case, "edges", "p2m csr edges", name_v, R.wind_csr_to_edges, c, s, (65,), ("ordinary",), (True, False))
+
+
+# ---- the transpose: mpg_regrid_transpose_dev ---------------------------------------------------------------------------------------------
+TRANSPOSED = ("m2g 3", "m2g 1", "m2g csr", "g2g 4", "narrow 3", "fw csr", "g2m 4 C cells", "p2m csr cells", "rec csr", "comp csr", "syn csr")
+
+
+def test_the_transposed_handles_exercise_what_they_should(case):
+    """on the host, before anything is launched: the synthetic handle's segments bracket TR_SHORT = 16, the 4-slot form and a wave"""
+    p = case.pat
+    lens = cr.segment_lengths(p["syn csr"])
+    assert set(cr.SYN_LENGTHS) <= set(lens.tolist()) and lens.max() == 300 and p["syn csr"].n_src % 64 != 0 and p["syn csr"].nnz == 0
+    for a, b in zip((p["syn csr"].rowptr, p["syn csr"].col, p["syn csr"].val), (case.syn.rowptr, case.syn.col, case.syn.val)):
+        assert np.array_equal(a, b), "from_weights keeps the stored order"
+    assert cr.segment_lengths(p["p2m csr cells"]).max() > 16 and cr.segment_lengths(p["m2g 1"]).max() >= 1
+    assert p["rec csr"].nnz == 0 and (p["rec csr"].val == 1.0).all() and p["rec csr"].n_src == 1920 and p["rec csr"].n_dst == 642
+    assert p["comp csr"].nnz == 0 and p["comp csr"].n_src == 1920 and p["comp csr"].n_dst == 300 and (p["comp csr"].val != 1.0).all()
+    for name in TRANSPOSED:
+        n = cr.segment_lengths(p[name])
+        print("%-16s %6d sources, %6d referenced, segments up to %4d, %5d beyond 16, %6d of at most 4" % (
+            name, p[name].n_src, int((n > 0).sum()), int(n.max()), int((n > 16).sum()), int(((n > 0) & (n <= 4)).sum())))
+        assert p[name].pole is None
+
+
+@pytest.mark.parametrize("name", TRANSPOSED)
+def test_transpose_inputs_can_tell_the_difference(case, name):
+    """reference against reference on the ordinary grid values of 17 levels: a reversed segment and a separate multiply and add each
+    change at least 1 % of the outputs they can change at all (_contract_ref.transpose_shares); the special grid values are checked
+    where they are made (Case.grid_values), here for every level count and both types"""
+    pat = case.pat[name]
+    shares = cr.transpose_shares(pat, case.grid_values(name, "ordinary", 17, F64)["np"], 17, NF)
+    for k, v in shares.items():
+        print("%-16s transpose: %-40s %6.2f %%" % (name, k, 100.0 * v))
+    low = {k: v for k, v in shares.items() if v < 0.01}
+    assert not low, (name, low)
+    if name == "syn csr":
+        assert set(shares) == {"segment reversed", "separate multiply and add"}
+    for nlev in NLEVS:
+        for sdt in (F64, F32):
+            assert np.isnan(case.grid_values(name, "special", nlev, sdt)["np"][:, :, 0]).all()
+
+
+def _transposes(R, rh, s, nlev, ddt):
+    """every way to the same result: both layouts, dense and pitched grid values; yields (what, result as (NF, nlev, n_src))"""
+    for lname, layout in (("[lev][cell]", R.LAYOUT_CELL_FAST), ("[cell][lev]", R.LAYOUT_LEV_FAST)):
+        for sname, src in (("dense", s["cf"]), ("pitched", s["pitched"])):
+            got = rh.regrid_transpose(src, nlev=nlev, nfields=NF, layout=layout, out_dtype=tdt(ddt))
+            yield (lname, sname), got if layout == R.LAYOUT_CELL_FAST else got.transpose(1, 2)
+
+
+@pytest.mark.parametrize("name", TRANSPOSED)
+def test_regrid_transpose(case, name):
+    """acc = fma(w_j, (double)g[k][row_j], acc) from +0.0 in ascending (destination point, slot) order, (dst type)acc, +0.0 for a source
+    nothing references: the bits of cr_apply_transpose on every source, level, field, type pair, layout and pitch"""
+    from mpassit_amd import regrid as R
+    rh, pat = case.rh[name], case.pat[name]
+    unref = cr.segment_lengths(pat) == 0
+    for nlev in NLEVS:
+        for kind in KINDS:
+            for sdt in (F64, F32):
+                s = case.grid_values(name, kind, nlev, sdt)
+                want64, cap = cr.transpose(pat, s["np"], nlev, NF)
+                assert not cap.any() and (cr.bits(want64[:, :, unref]) == 0).all()
+                for ddt in (F64, F32):
+                    with np.errstate(over="ignore"):
+                        want = want64.astype(ddt)                         # one rounding at the store
+                    for how, got in _transposes(R, rh, s, nlev, ddt):
+                        held(got, want, (name, "transpose", nlev, kind, sdt, ddt) + how)
+
+
+def test_regrid_transpose_pole_caps(case):
+    """The periodic 72 x 36 grid, CENTER -> EDGE2.  Off the two CENTER rows under the caps: the bits of the restatement.  On them the
+    kernel adds its cap term last, a reduction whose order the header states but the restatement does not follow: those 2 * row_len
+    sources -- counted, and no more -- are held to _transpose_ref.transpose_ref's derived bound on the ordinary grid values.  On the
+    special ones a cap-row source is held where its bound is finite; where a NaN or infinities of both signs enter its terms it must
+    be NaN; infinities of one sign alone: that infinity; the rest (finite terms whose bound is beyond the largest float64: one order
+    can overflow where another does not) is left free and counted."""
+    from _transpose_ref import EPS, transpose_ref
+    from mpassit_amd import regrid as R
+    rh, pat = case.rh["pole 4"], case.pat["pole 4"]
+    dst, src0, wp, row_len = pat.pole
+    n_held = n_free = n_forced = 0
+    for nlev in NLEVS:
+        for kind in KINDS:
+            for sdt in (F64, F32):
+                key = ("pole 4", "g " + kind, nlev, sdt, 0)
+                s = case.grid_values("pole 4", kind, nlev, sdt)
+                g = s["np"].astype(F64)
+                want64, cap = cr.transpose(pat, s["np"], nlev, NF)
+                assert int(cap.sum()) == 2 * row_len == 144 and cap[:row_len].all() and cap[-row_len:].all(), key
+                capd, offd = np.nonzero(cap)[0], np.nonzero(~cap)[0]
+                with np.errstate(all="ignore"):
+                    ref = [transpose_ref(rh, g[f]) for f in range(NF)]
+                    exact = np.stack([r[0] for r in ref])[:, :, capd]
+                    bound = np.stack([r[1] for r in ref])[:, :, capd]
+                    # the terms of a cap-row source: its own entries and the cap's, as products
+                    pt = cr.transposed(pat)
+                    nan_in = np.zeros(exact.shape, bool)
+                    pos_in, neg_in = nan_in.copy(), nan_in.copy()
+                    for i, c in enumerate(capd):
+                        q = (src0 == (0 if c < row_len else pat.n_src - row_len)) & (wp != 0.0)
+                        e = slice(pt.rowptr[c], pt.rowptr[c + 1])
+                        terms = np.concatenate([pt.val[e] * g[:, :, pt.col[e]], wp[q] * g[:, :, dst[q]]], axis=2)
+                        nan_in[:, :, i] = np.isnan(terms).any(axis=2)
+                        pos_in[:, :, i], neg_in[:, :, i] = np.isposinf(terms).any(axis=2), np.isneginf(terms).any(axis=2)
+                must_nan = nan_in | (pos_in & neg_in)
+                must_inf = (pos_in | neg_in) & ~must_nan
+                checked = ~must_nan & ~must_inf & np.isfinite(bound)
+                free = ~must_nan & ~must_inf & ~checked
+                if kind == "ordinary":
+                    assert checked.all(), key
+                for ddt in (F64, F32):
+                    with np.errstate(over="ignore"):
+                        want = want64.astype(ddt)
+                    for how, got in _transposes(R, rh, s, nlev, ddt):
+                        what = ("pole 4", "transpose", nlev, kind, sdt, ddt) + how
+                        held(got[:, :, offd], want[:, :, offd], what)
+                        gc = got[:, :, capd].cpu().numpy().astype(F64)
+                        with np.errstate(all="ignore"):
+                            w = exact.astype(ddt).astype(F64)
+                            tol = 8 * EPS * bound + (np.spacing(np.abs(exact.astype(F32))).astype(F64) if ddt == F32 else 0.0)
+                            over = (ddt == F32) & (np.abs(exact) > 3.0e38)          # the float32 store of such a value may overflow
+                            ok = np.where(must_nan, np.isnan(gc), np.where(must_inf, gc == np.where(pos_in, np.inf, -np.inf),
+                                          np.where(checked & ~over, np.abs(gc - w) <= tol, True)))
+                        assert ok.all(), (what, "cap rows", int((~ok).sum()), gc[~ok][:3], w[~ok][:3], tol[~ok][:3])
+                n_held += int(checked.sum())
+                n_free += int(free.sum())
+                n_forced += int((must_nan | must_inf).sum())
+    print("transpose pole caps: %d cap-row outputs held to the bound, %d forced non-finite, %d left free" % (n_held, n_forced, n_free))
+    assert n_held > 10000 and n_forced > 0 and n_free < n_held
+
+
+# ---- the rotation: mpg_rotate_winds_dev, mpg_rotate_winds ------------------------------------------------------------------------------
+@pytest.mark.parametrize("nlev", (1, 65))
+@pytest.mark.parametrize("npts", (1, 255, 256, 257))
+def test_rotate_winds(gpu_lib, npts, nlev):
+    """tana = sa / ca; den = ca + sa * tana; un = (uo + vo * tana) / den; vn = (vo - un * sa) / ca, seven rounded operations, in place;
+    cos(alpha) entries of exactly 0.0 and -0.0 (a quotient by zero, an infinity times zero) come out as IEEE 754 has them"""
+    import torch
+    from mpassit_amd import regrid as R
+    rng = np.random.default_rng(40 + npts)
+    phi = rng.uniform(0.0, 2.0 * np.pi, npts)
+    angles = []
+    for zero in ((), (0.0,), (-0.0,)) if npts == 1 else ((0.0, -0.0),):
+        ca, sa = np.cos(phi), np.sin(phi)
+        for i, z in enumerate(zero):
+            ca[(3 + 100 * i) % npts::131] = z
+        if npts > 1:
+            ca[npts - 1] = 0.0
+            assert (ca == 0.0).sum() >= 3 and np.signbit(ca[ca == 0.0]).any() and not np.signbit(ca[ca == 0.0]).all()
+        angles.append((ca, sa))
+    for ca, sa in angles:
+        for kind in KINDS:
+            um, vm, _ = cr.mass_winds(npts, 1, nlev, kind)
+            with np.errstate(all="ignore"):
+                wu, wv = cr.rotate(ca, sa, um, vm)
+            ut, vt = torch.from_numpy(um).cuda(), torch.from_numpy(vm).cuda()
+            R.rotate_winds_cgrid(torch.from_numpy(ca).cuda(), torch.from_numpy(sa).cuda(), ut, vt)
+            held(ut, wu, ("rotate, device", npts, nlev, kind, "u"))
+            held(vt, wv, ("rotate, device", npts, nlev, kind, "v"))
+            uh, vh = um.copy(), vm.copy()
+            R.rotate_winds_cgrid(ca, sa, uh, vh)
+            assert cr.same(uh, wu) and cr.same(vh, wv), ("rotate, host", npts, nlev, kind)
+
+
+# ---- the Grid -> Grid wind chain: mpg_wind_destagger_dev, _pitched_dev, mpg_wind_destagger --------------------------------------------------
+WIND_GRIDS = ((19, 11, 300000.0), (65, 17, 80000.0), (203, 35, 25000.0))      # mass points: narrower than a 64-point tile, one past it, 203 = 12 * 16 + 11
+WIND_NLEVS = (1, 2, 17)
+
+
+@pytest.fixture(scope="module")
+def wind_grids(gpu_lib):
+    from mpassit_amd import regrid as R, target_grid as T
+    out = {}
+    for nx, ny, dx in WIND_GRIDS:
+        t = T.define_target_grid_params("lambert", nx + 1, ny + 1, dx=dx, dy=dx, **LAMBERT)
+        grid = R.Grid.from_target(t)
+        rh1, rh2 = R.regrid_store_grid(grid, R.STAGGERLOC_EDGE1), R.regrid_store_grid(grid, R.STAGGERLOC_EDGE2)
+        ca, sa = (np.ascontiguousarray(a, F64).reshape(-1).copy() for a in (t.cosa, t.sina))
+        assert ca.size == nx * ny and (rh1.nx_dst, rh1.ny_dst, rh2.nx_dst, rh2.ny_dst) == (nx + 1, ny, nx, ny + 1)
+        # two points whose rotation divides by zero, on the first and the last row: a rim point is read by half the outputs an interior
+        # one is, and on 19 x 11 at one level every non-finite mass point already costs 1 to 2 % of them
+        ca[nx // 2], ca[(ny - 1) * nx + 1] = 0.0, -0.0
+        out[nx] = dict(grid=grid, rh=(rh1, rh2), pat=(cr.Pattern.of(rh1), cr.Pattern.of(rh2)), ca=ca, sa=sa, nx=nx, ny=ny)
+    yield out
+    for d in out.values():
+        for rh in d["rh"]:
+            rh.release()
+        d["grid"].destroy()
+
+
+def _wind_dev(rh1, rh2, ca, sa, um, vm, nlev, dst_type, keep, ld):
+    """mpg_wind_destagger_dev (ld 0) or mpg_wind_destagger_pitched_dev through the library itself, into NaN-filled results;
+    returns (U, V, umass', vmass') as numpy arrays, U / V (nlev, ld or n_dst)"""
+    import ctypes as C
+    import torch
+    from mpassit_amd import _lib as L
+    dt = torch.float32 if dst_type & 1 else torch.float64
+    new = lambda rh: None if rh is None else torch.full((nlev, ld or rh.n_dst), float("nan"), dtype=dt, device="cuda")   # noqa: E731
+    U, V = new(rh1), new(rh2)
+    ur, vr = (torch.full_like(um, float("nan")), torch.full_like(vm, float("nan"))) if keep else (None, None)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())       # noqa: E731
+    h = lambda rh: None if rh is None else rh._h                         # noqa: E731
+    head = (h(rh1), h(rh2), p(ca), p(sa), p(um), p(vm), C.c_int(nlev), p(U), p(V), C.c_int(dst_type), p(ur), p(vr))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if ld:
+        L.check(L.load().mpg_wind_destagger_pitched_dev(*head, C.c_int64(ld), stream))
+    else:
+        L.check(L.load().mpg_wind_destagger_dev(*head, stream))
+    torch.cuda.synchronize()
+    return tuple(None if t is None else t.cpu().numpy() for t in (U, V, ur, vr))
+
+
+def _same_result(got, want, dst_type, what):
+    """equal bits, or NaN on both sides -- of a big-endian result after turning both round"""
+    if got is None or want is None:
+        assert got is None and want is None, what
+        return
+    g, w = (cr.swap(got), cr.swap(want)) if dst_type & 2 else (got, want)
+    bad = cr.differs(g.reshape(w.shape), w)
+    assert not bad.any(), (what, int(bad.sum()), bad.size, np.argwhere(bad)[0], g[bad][:2], w[bad][:2])
+
+
+def _ring_is_plus_zero(d, U, V):
+    """the outer half-cell ring -- U's first and last column, V's first and last row -- is unmapped: +0.0, the sign bit clear"""
+    nx, ny = d["nx"], d["ny"]
+    if U is not None:
+        u = U[:, :ny * (nx + 1)].reshape(-1, ny, nx + 1)
+        assert (cr.bits(u[:, :, [0, nx]]) == 0).all(), "U ring"
+    if V is not None:
+        v = V[:, :(ny + 1) * nx].reshape(-1, ny + 1, nx)
+        assert (cr.bits(v[:, [0, ny], :]) == 0).all(), "V ring"
+
+
+@pytest.mark.parametrize("rot", (True, False), ids=("rotated", "unrotated"))
+@pytest.mark.parametrize("nx", [g[0] for g in WIND_GRIDS])
+def test_wind_destagger(wind_grids, nx, rot):
+    """cr_rotate on copies of the mass winds, the 4-slot chain on each handle's own idx / w, the float64 entry storing the sum as it
+    stands and every typed result (TD)fma(sum, 1, 0): the bits of cr_wind_destagger from the device entry, the pitched one (one odd
+    stride for both, NaN between the planes untouched) and the host entry; both components, U only, V only; the rotated mass winds asked
+    for and left out; specials on the first and last row and column of the mass winds"""
+    import torch
+    from mpassit_amd import regrid as R
+    d = wind_grids[nx]
+    (rh1, rh2), (p1, p2), ny = d["rh"], d["pat"], d["ny"]
+    ring1, ring2 = np.zeros((ny, nx + 1), bool), np.zeros((ny + 1, nx), bool)
+    ring1[:, [0, nx]], ring2[[0, ny], :] = True, True
+    assert p1.unmapped[ring1.reshape(-1)].all() and p2.unmapped[ring2.reshape(-1)].all() and not p1.unmapped[~ring1.reshape(-1)].any()
+    ca, sa = (d["ca"], d["sa"]) if rot else (None, None)
+    cat, sat = (torch.from_numpy(ca).cuda(), torch.from_numpy(sa).cuda()) if rot else (None, None)
+    which = ((p1, p2, rh1, rh2),) if rot else ((p1, p2, rh1, rh2), (p1, None, rh1, None), (None, p2, None, rh2))
+    ld = max(p1.n_dst, p2.n_dst) + 5
+    for nlev in WIND_NLEVS:
+        for kind in KINDS:
+            um, vm, where = cr.mass_winds(nx, ny, nlev, kind)
+            umt, vmt = torch.from_numpy(um).cuda(), torch.from_numpy(vm).cuda()
+            if kind == "special":
+                with np.errstate(all="ignore"):
+                    U, V, _, _ = cr.wind_destagger(p1, p2, ca, sa, um, vm, nlev)
+                fin = cr.winds_are_informative(p1, p2, rot, where, U, V)
+                print("%3d x %2d, %2d levels, %s: %.2f %% of the outputs of the special mass winds finite" % (nx, ny, nlev, "rotated" if rot else "unrotated", 100 * fin))
+            for q1, q2, h1, h2 in which:
+                for dst_type in (0, 1, 2, 3):
+                    for keep in ((True, False) if rot else (False,)):
+                        with np.errstate(all="ignore"):
+                            dense = cr.wind_destagger(q1, q2, ca, sa, um, vm, nlev, dst_type, 0, keep)
+                            pitched = cr.wind_destagger(q1, q2, ca, sa, um, vm, nlev, dst_type, ld, keep)
+                        what = (nx, nlev, kind, rot, dst_type, keep, q1 is not None, q2 is not None)
+                        a, b = (umt if (q1 is not None or rot) else None), (vmt if (q2 is not None or rot) else None)
+                        for entry, want, got in (("device", dense, _wind_dev(h1, h2, cat, sat, a, b, nlev, dst_type, keep, 0)),
+                                                 ("pitched", pitched, _wind_dev(h1, h2, cat, sat, a, b, nlev, dst_type, keep, ld))):
+                            for i in range(4):
+                                _same_result(got[i], want[i], dst_type if i < 2 else 0, what + (entry, i))
+                            _ring_is_plus_zero(d, got[0], got[1])
+                        ha, hb = (um.copy() if a is not None else None), (vm.copy() if b is not None else None)
+                        got = R.wind_destagger(h1, h2, ca, sa, ha, hb, nlev, out_dtype=F32 if dst_type & 1 else F64, dst_be=bool(dst_type & 2), keep_mass=keep)
+                        for i in range(4):
+                            _same_result(got[i], dense[i], dst_type if i < 2 else 0, what + ("host", i))
+                        assert (ha is None or cr.same(ha, um)) and (hb is None or cr.same(hb, vm)), "the host entry leaves its inputs alone"
+
+
+def test_wind_destagger_periodic(case):
+    """The periodic 72 x 36 grid, unrotated.  U, and V off its two pole rows: the bits of cr_wind_destagger.  The pole rows of V -- counted:
+    2 * 72 points, rows 0 and ny -- are cap points and held as test_pole_caps holds them: must-be-NaN rows, bits where the reference is
+    not finite, its bound plus one unit in the last place elsewhere."""
+    import torch
+    rh1, rh2, p1, p2 = case.rh["periodic E1"], case.rh["pole 4"], case.pat["periodic E1"], case.pat["pole 4"]
+    nx, ny = 72, 36
+    assert (p1.pole is None or not (p1.pole[2] != 0.0).any()) and p2.pole is not None and (rh1.nx_dst, rh1.ny_dst, rh2.nx_dst, rh2.ny_dst) == (nx + 1, ny, nx, ny + 1)
+    n_cap = 0
+    for nlev in WIND_NLEVS:
+        for kind in KINDS:
+            um, vm, _ = cr.mass_winds(nx, ny, nlev, kind)
+            umt, vmt = torch.from_numpy(um).cuda(), torch.from_numpy(vm).cuda()
+            for dst_type in (0, 1, 2, 3):
+                dt = F32 if dst_type & 1 else F64
+                with np.errstate(all="ignore"):
+                    wu, wv, _, _ = cr.wind_destagger(p1, p2, None, None, um, vm, nlev, dst_type)
+                    pts, want, bound, must_nan, free = cr.pole_caps(p2, vm[None], nlev, 1, False, dt, dst_type != 0, 1.0, 0.0)
+                assert pts.size == 2 * nx and set((pts // nx).tolist()) == {0, ny}, "the excluded points are V's two pole rows and no more"
+                other = np.ones(p2.n_dst, bool)
+                other[pts] = False
+                U, V, _, _ = _wind_dev(rh1, rh2, None, None, umt, vmt, nlev, dst_type, False, 0)
+                what = ("periodic", nlev, kind, dst_type)
+                _same_result(U, wu, dst_type, what + ("U",))
+                _same_result(V[:, other], wv[:, other], dst_type, what + ("V off the pole rows",))
+                g = (cr.swap(V) if dst_type & 2 else V)[:, pts][None]
+                with np.errstate(all="ignore"):
+                    w = want.astype(dt)
+                    exact = ~np.isfinite(w) & ~must_nan & ~free
+                    tol = bound + np.spacing(np.abs(w)).astype(F64)
+                    ok = np.where(must_nan, np.isnan(g), np.where(exact, ~cr.differs(g, w), free | (np.abs(g.astype(F64) - w.astype(F64)) <= tol)))
+                assert ok.all(), (what, "pole rows", int((~ok).sum()), g[~ok][:3], w[~ok][:3], tol[~ok][:3])
+                n_cap += int((~free).sum())
+    assert n_cap > 1000

@@ -9,7 +9,11 @@ anything on a GPU is held to it:
   * the inputs of tests/test_contract_gpu.py can tell the contract from five deliberately wrong recipes: the shares of differing
     outputs are printed and each must reach 1 %.  The patterns here are the from_weights pattern of the GPU test itself, the saved
     patterns of its small Stores and fixed patterns that need no Store; the GPU test repeats the same check, reference against reference,
-    on the patterns of all its Stores."""
+    on the patterns of all its Stores;
+  * the restatements of the transpose, the rotation and the Grid -> Grid wind chain equal independent numpy statements of the same
+    sentences (a loop of cr.fma_vec over a stable sort by source; plain float64 numpy, which neither fuses nor reorders), the transpose
+    lies within _transpose_ref.transpose_ref's bound of the long-double sum, its inputs tell a reversed segment and a separate multiply
+    and add from the contract, and the special grid values and mass winds reach every field while 90 % of the outputs stay finite."""
 import math
 from fractions import Fraction as F
 
@@ -309,3 +313,172 @@ def test_pole_cap_rows_with_one_huge_value_are_held():
     pts, want, bound, must_nan, free = cr.pole_caps(pat, x, 2, 1, False, np.float64, True, 1.0, 0.0)
     assert free.tolist() == [[[False, False], [False, True]]] and not must_nan.any()
     assert np.isfinite(bound[0, 0, 0]) and 1e305 < want[0, 0, 0] < 1e306 and np.isfinite(bound[0, 1, 0])
+
+
+# ---- the transpose, the rotation and the Grid -> Grid wind chain ---------------------------------------------------------------------
+def _transpose_patterns():
+    (_, _, _), fw = cr.from_weights_case()
+    (_, _, _), syn = cr.synthetic_transpose_case()
+    return [("saved Store pattern: " + k, v) for k, v in cr.golden_patterns().items()] + [("from_weights CSR", fw), ("synthetic segments", syn)]
+
+
+class _AsHandle:
+    """what _transpose_ref.transpose_ref reads of a RouteHandle, from a Pattern (no pole caps: the saved patterns carry none)"""
+
+    def __init__(self, pat):
+        self.pat, self.n_src, self.n_dst, self.nnz_per_row = pat, pat.n_src, pat.n_dst, pat.nnz
+
+    def weights(self):
+        return self.pat.weights()
+
+    def csr(self):
+        return self.pat.csr()
+
+    def pole(self):
+        return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0), 0
+
+    def to_esmf_weights(self):
+        pt = cr.transposed(self.pat)
+        col = np.repeat(np.arange(pt.n_dst), np.diff(pt.rowptr))
+        return pt.col + 1, col + 1, pt.val
+
+
+def _transpose_by_numpy(pat, g, nlev, nfields):
+    """acc[c] = fma(w_j, g[row_j], acc[c]) entry by entry with cr.fma_vec, the segments taken from a stable sort by source"""
+    pt = cr.transposed(pat)
+    lens = np.diff(pt.rowptr)
+    acc = np.zeros((nfields, nlev, pat.n_src))
+    g = np.asarray(g, np.float64).reshape(nfields, nlev, pat.n_dst)
+    for j in range(int(lens.max())):
+        sel = np.nonzero(lens > j)[0]
+        e = pt.rowptr[sel] + j
+        acc[:, :, sel] = cr.fma_vec(pt.val[e][None, None, :], g[:, :, pt.col[e]], acc[:, :, sel])
+    return acc
+
+
+def test_the_synthetic_handle_holds_the_listed_segments():
+    (row, col, S), pat = cr.synthetic_transpose_case()
+    lens = cr.segment_lengths(pat)
+    assert set(cr.SYN_LENGTHS) <= set(lens.tolist()) and lens.max() == 300 and (0, 16, 17, 64, 65) == tuple(n for n in (0, 16, 17, 64, 65) if n in lens)
+    assert pat.n_src == 41 and pat.n_src % 64 and 380 <= pat.n_dst <= 420 and pat.nnz == 0
+    pairs = np.stack([row, col], axis=1)
+    uniq, count = np.unique(pairs, axis=0, return_counts=True)
+    assert count.max() >= 3 and (count > 1).sum() > 10, "duplicate (row, col) pairs"
+    assert pat.rowptr[1] - pat.rowptr[0] == 1, "destination point 0 holds one entry"
+    inside = np.setdiff1d(np.arange(pat.col.size - 1), pat.rowptr[1:-1] - 1)
+    assert (np.diff(pat.col)[inside] < 0).any() and (np.diff(pat.col)[inside] > 0).any(), "rows are stored in no particular column order"
+
+
+@pytest.mark.parametrize("what,pat", _transpose_patterns(), ids=lambda v: v if isinstance(v, str) else "")
+def test_transpose_restatement(what, pat):
+    from _transpose_ref import assert_f32_close, assert_f64_close, transpose_ref
+    nlev, nf = 3, 2
+    g = cr.ordinary(pat.n_dst, nlev, nf) - 250.0                 # both signs: cancellation inside a segment
+    by_numpy = _transpose_by_numpy(pat, g, nlev, nf)
+    got, cap = cr.transpose(pat, g, nlev, nf)
+    assert cr.same(got, by_numpy) and not cap.any()
+    assert cr.same(got, cr.apply(cr.transposed(pat), g, nlev, nf, epilogue=False)), "the CSR chain over the transposed pattern"
+    assert (got[:, :, cr.segment_lengths(pat) == 0] == 0.0).all() and not np.signbit(got[:, :, cr.segment_lengths(pat) == 0]).any()
+    assert cr.same(cr.transpose(pat, g, nlev, nf, dst_dtype=np.float32)[0], by_numpy.astype(np.float32))
+    assert cr.same(cr.transpose(pat, g, nlev, nf, dst_lev_fast=True)[0], by_numpy.transpose(0, 2, 1))
+    g32 = cr.to_f32(g)
+    assert cr.same(cr.transpose(pat, g32, nlev, nf)[0], _transpose_by_numpy(pat, g32, nlev, nf))
+    ld = pat.n_dst + 5                                            # pitched planes, NaN in the pad
+    buf = np.full((nf * nlev, ld), np.nan)
+    buf[:, :pat.n_dst] = g.reshape(nf * nlev, pat.n_dst)
+    assert cr.same(cr.transpose(pat, buf, nlev, nf, g_level_stride=ld)[0], by_numpy)
+    rh = _AsHandle(pat)
+    for f in range(nf):
+        want, bound = transpose_ref(rh, g[f])
+        assert_f64_close(got[f], want, bound, what)
+        assert_f32_close(cr.transpose(pat, g, nlev, nf, dst_dtype=np.float32)[0][f], want, bound, what)
+    if cr.segment_lengths(pat).max() >= 3:
+        assert not cr.same(cr.transpose(pat, g, nlev, nf, variant=cr.REVERSED)[0], got)
+
+
+def test_transpose_cap_rows_and_nearest_weights():
+    pat = cr.golden_patterns()["pole 4"]
+    pat.pole = (np.array([5, 9, 2600], np.int32), np.array([0, 0, pat.n_src - 72], np.int32), np.array([0.25, 0.0, 0.5]), 72)
+    _, cap = cr.transpose(pat, cr.ordinary(pat.n_dst, 1, 1))
+    assert cap.sum() == 144 and cap[:72].all() and cap[-72:].all()
+    pat.pole = (np.array([9], np.int32), np.array([0], np.int32), np.array([0.0]), 72)
+    assert not cr.transpose(pat, cr.ordinary(pat.n_dst, 1, 1))[1].any(), "a cap of weight zero adds nothing"
+    # a nearest handle's weight is 1.0 whatever its stored weight array holds
+    p1 = cr.Pattern(3, 4, 1, idx=[[2], [0], [-1], [2]], w=[[0.5], [0.5], [0.0], [0.5]])
+    got, _ = cr.transpose(p1, np.array([1.0, 2.0, 4.0, 8.0]))
+    assert got.reshape(-1).tolist() == [2.0, 0.0, 9.0]
+
+
+def test_transpose_inputs_can_tell_the_difference():
+    """on the grid values test_contract_adjoint_gpu.py uses (cr.ordinary over the handle's n_dst, two fields, 17 levels): each wrong
+    recipe that can change a source of the pattern changes at least 1 % of the outputs it can change"""
+    listed = 0
+    for what, pat in _transpose_patterns():
+        shares = cr.transpose_shares(pat, cr.ordinary(pat.n_dst, 17, 2), 17, 2)
+        _report(what + " (transpose)", shares)
+        listed += len(shares)
+    (_, _, _), syn = cr.synthetic_transpose_case()
+    assert set(cr.transpose_shares(syn, cr.ordinary(syn.n_dst, 17, 2), 17, 2)) == {"segment reversed", "separate multiply and add"} and listed >= 8
+
+
+def test_transpose_special_grid_values_stay_informative():
+    for what, pat in _transpose_patterns():
+        for nlev in (1, 2, 17, 65):
+            x, where, pt = cr.special_g(pat, nlev, 2)
+            assert np.isnan(x[:, :, 0]).all(), "a NaN at destination point 0 of every plane"
+            for s in (x, cr.to_f32(x)):
+                fin = cr.special_is_informative(pt, s, where, nlev, 2)
+                reach = {name: int(np.isin(np.nonzero(m.reshape(-1, pt.n_src).any(axis=0))[0], pt.used).sum()) for name, m in where.items()}
+                print("%-34s %2d levels %-8s finite %6.2f %%  points read per kind: %s" % (what, nlev, s.dtype, 100.0 * fin, sorted(reach.values())))
+
+
+def test_rotation_is_plain_float64():
+    rng = np.random.default_rng(6)
+    for npts, nlev in ((1, 1), (257, 3), (1000, 65)):
+        phi = rng.uniform(0.0, 2.0 * np.pi, npts)
+        ca, sa = np.cos(phi), np.sin(phi)
+        ca[::97], ca[5::101] = 0.0, -0.0
+        u, v, where = cr.mass_winds(npts, 1, nlev, "special")
+        gu, gv = cr.rotate(ca, sa, u, v)
+        with np.errstate(all="ignore"):
+            tana = sa / ca
+            den = ca + sa * tana
+            un = (u + v * tana) / den
+            vn = (v - un * sa) / ca
+        assert cr.same(gu, un) and cr.same(gv, vn) and (npts == 1 or len(where) == len(cr.SPECIALS))
+        assert npts == 1 or (np.isfinite(gu).mean() > 0.9 and not np.isfinite(gu[:, ca == 0.0]).all())
+
+
+def test_wind_chain_restatement():
+    """cr_wind_destagger is cr_rotate, then the 4-slot chain, then the store of each result type -- on 4-slot patterns that need no Store"""
+    nx, ny, nlev = 19, 11, 3
+    n = nx * ny
+    p1, p2 = cr.synthetic_fixed(4, n, (nx + 1) * ny), cr.synthetic_fixed(4, n, nx * (ny + 1), seed=9)
+    rng = np.random.default_rng(12)
+    phi = rng.uniform(-0.6, 0.6, n)
+    ca, sa = np.cos(phi), np.sin(phi)
+    ca[7], ca[100] = 0.0, -0.0
+    for kind in ("ordinary", "special"):
+        um, vm, where = cr.mass_winds(nx, ny, nlev, kind)
+        for rot in (True, False):
+            ru, rv = cr.rotate(ca, sa, um, vm) if rot else (um, vm)
+            for dst_type in (0, 1, 2, 3):
+                U, V, ku, kv = cr.wind_destagger(p1, p2, ca if rot else None, sa if rot else None, um, vm, nlev, dst_type, keep_mass=True)
+                dt = np.float32 if dst_type & 1 else np.float64
+                for got, pat, src in ((U, p1, ru), (V, p2, rv)):
+                    want = cr.apply(pat, src, nlev, 1, dst_dtype=dt, epilogue=dst_type != 0)[0]
+                    assert cr.same(cr.swap(got) if dst_type & 2 else got, want), (kind, rot, dst_type)
+                    assert (cr.bits(got[:, pat.unmapped]) == 0).all(), "an unmapped point is +0.0, in either byte order"
+                assert (ku is None) == (not rot) and (not rot or (cr.same(ku, ru) and cr.same(kv, rv)))
+            if kind == "special":
+                U, V, _, _ = cr.wind_destagger(p1, p2, ca if rot else None, sa if rot else None, um, vm, nlev)
+                print("special mass winds, %s: finite %.2f %%" % ("rotated" if rot else "unrotated", 100.0 * cr.winds_are_informative(p1, p2, rot, where, U, V)))
+    um, vm, _ = cr.mass_winds(nx, ny, nlev, "ordinary")
+    U, V, _, _ = cr.wind_destagger(p1, None, None, None, um, None, nlev, 1)
+    assert V is None and cr.same(U, cr.apply(p1, um, nlev, 1, dst_dtype=np.float32)[0])
+    U, V, _, _ = cr.wind_destagger(None, p2, None, None, None, vm, nlev, 0, dst_level_stride=p2.n_dst + 7)
+    assert U is None and cr.same(V[:, :p2.n_dst], cr.apply(p2, vm, nlev, 1, epilogue=False)[0]) and np.isnan(V[:, p2.n_dst:]).all()
+    # the float64 entry keeps a -0.0 sum, a typed result stores fma(-0.0, 1, 0) = +0.0
+    one = cr.Pattern(4, 1, 4, idx=[[0, 1, 2, 3]], w=[[-1.0, 0.0, 0.0, 0.0]])
+    z = np.zeros((1, 4))
+    assert np.signbit(cr.wind_destagger(one, None, None, None, z, None, 1, 0)[0][0, 0]) == np.signbit(cr.apply(one, z, epilogue=False)[0, 0, 0])
