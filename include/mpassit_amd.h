@@ -615,6 +615,47 @@ int mpg_wind_destagger_pitched_dev(mpg_handle rh_edge1, mpg_handle rh_edge2, con
 int mpg_wind_destagger(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *cosa_host, const double *sina_host,
                        const double *umass_host, const double *vmass_host, int nlev, void *u_host, void *v_host, int dst_type,
                        double *umass_rot_host, double *vmass_rot_host);
+/* The ADJOINT of the wind chain, for a loss on the target grid's U and V whose gradient has to reach the mass-point winds (and from
+ * there the mesh, through mpg_regrid_transpose_dev): a three-call chain -- mpg_regrid_transpose_dev on each handle, then the rotation's
+ * adjoint below -- and a fused call that matches that chain bit for bit.
+ * mpg_rotate_winds_transpose_dev: the adjoint of mpg_rotate_winds_dev, in place on the gradients gu, gv [nlev][npts] float64 with
+ * cosa / sina [npts].  Values, a contract by identity: the reverse mode of interp.F90:737-748 as stated above, per point
+ *   tana = sa / ca;  den = ca + sa * tana                       and per level, from the incoming gun, gvn (the gradients of un, vn)
+ *   a = gvn / ca;  t = a * sa;  b = gun - t;  guo = b / den;  p = guo * tana;  gvo = a + p
+ * each operation rounded once, nothing contracted or reordered; ca == +-0.0 and non-finite inputs give what IEEE 754 gives.
+ * (Algebraically guo = gun ca - gvn sa, gvo = gun sa + gvn ca.)  Not an adjoint with respect to the angles. */
+int mpg_rotate_winds_transpose_dev(int64_t npts, int nlev, const double *cosa_dev, const double *sina_dev, double *gu_dev, double *gv_dev,
+                                   void *hip_stream);
+/* The adjoint of mpg_wind_destagger_dev in ONE pass: the gradients of U and V back to the gradients of the mass-point winds.
+ *   rh_edge1, rh_edge2   the CENTER -> EDGE1 / CENTER -> EDGE2 pair of one grid, under the same test as mpg_wind_destagger_dev; anything
+ *                        else -> MPG_ERR_UNSUPPORTED.  Either may be NULL without a rotation (that component is not produced)
+ *   cosa_dev, sina_dev   [ny][nx] as for the forward, or both NULL: no rotation
+ *   gu_dev, gv_dev       [nlev][ny][nx+1], [nlev][ny+1][nx], both of src_type (MPG_TYPE_F64 or MPG_TYPE_F32), planes src_level_stride
+ *                        elements apart: 0 = dense, else ONE stride for both, at least the larger plane.  A pitched result of
+ *                        mpg_wind_destagger_pitched_dev can be fed back as it is, its pad is never read
+ *   gumass_rot_dev, gvmass_rot_dev   optional (NULL): the gradients of the forward's umass_rot / vmass_rot results, [nlev][ny][nx]
+ *                        float64 (rotation only)
+ *   gumass_dev, gvmass_dev   [nlev][ny][nx] float64, dense, fully overwritten
+ * Values, per (mass point c, level k):
+ *   s1, s2    exactly the sums of the mpg_regrid_transpose_dev contract on rh_edge1 / rh_edge2: ascending (destination point, slot)
+ *             order, an fma chain from +0.0, +0.0 for a source no entry references.  Unmapped U and V points have no entries and are
+ *             never read
+ *   gun = s1 + gumass_rot, gvn = s2 + gvmass_rot   one add; no add when the pointer is NULL
+ *   with rotation (guo, gvo) come from (gun, gvn) by the expressions of mpg_rotate_winds_transpose_dev; without, the components are
+ *   independent, as in the forward: gumass = s1 iff rh_edge1 is given, gvmass = s2 iff rh_edge2 is given, and for handles with pole
+ *   caps the pole term of the transpose contract is added last.
+ * MPG_ERR_INVALID_ARG: both handles NULL; cosa without sina or the reverse; a rotation without both handles; gumass_rot_dev /
+ * gvmass_rot_dev without a rotation; nlev < 1; a stride below the larger plane; an output pointer equal to an input pointer; a NULL
+ * array that is needed.  MPG_ERR_UNSUPPORTED: MPG_TYPE_BE; a rotation together with pole caps, as in the forward; a level plane of
+ * 4 GiB or more.
+ * Bit contract: the result equals two mpg_regrid_transpose_dev calls into float64, then the optional adds, then
+ * mpg_rotate_winds_transpose_dev.  The same bits across calls and across float32 / float64 inputs that hold the same values.  No
+ * floating-point atomics.  Stream as mpg_regrid_transpose_dev: the first call on a handle builds its transposed index (allocates and
+ * synchronises); every later call only enqueues and can be captured in a hipGraph. */
+int mpg_wind_destagger_transpose_dev(mpg_handle rh_edge1, mpg_handle rh_edge2, const double *cosa_dev, const double *sina_dev,
+                                     const void *gu_dev, const void *gv_dev, int src_type, int64_t src_level_stride, int nlev,
+                                     const double *gumass_rot_dev, const double *gvmass_rot_dev, double *gumass_dev, double *gvmass_dev,
+                                     void *hip_stream);
 /* The wind chain turned round: U on one stagger and V on another -- grid-relative on a Lambert grid -- onto the points of a mesh as
  * earth-relative winds (uReconstructZonal / uReconstructMeridional), in ONE pass: the two Regrids, the rotation and the cast, without
  * float64 intermediates.  The inverse of interp.F90:737-748, which is algebraically u_g = u_e ca + v_e sa, v_g = v_e ca - u_e sa.

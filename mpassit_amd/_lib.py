@@ -34,6 +34,7 @@ SYMBOLS = [
     "mpg_sphere_frames_dev", "mpg_wind_vector_weights_dev", "mpg_wind_vector_dev",
     "mpg_reconstruct_store", "mpg_reconstruct_weights_dev", "mpg_wind_reconstruct_dev",
     "mpg_handle_compose", "mpg_compose_weights_dev",
+    "mpg_rotate_winds_transpose_dev", "mpg_wind_destagger_transpose_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -299,6 +300,29 @@ def wind_vector_dev(*args):
     if "vector" not in _to_mesh_fns:
         _to_mesh_fns["vector"] = _WIND_VECTOR_PROTO(("mpg_wind_vector_dev", load()))
     return _to_mesh_fns["vector"](*args)
+
+
+# The adjoint of the wind chain, bound the same way.
+#   mpg_rotate_winds_transpose_dev(npts, nlev, cosa_dev, sina_dev, gu_dev, gv_dev, hip_stream)
+#   mpg_wind_destagger_transpose_dev(rh_edge1, rh_edge2, cosa_dev, sina_dev, gu_dev, gv_dev, src_type, src_level_stride, nlev,
+#                                    gumass_rot_dev, gvmass_rot_dev, gumass_dev, gvmass_dev, hip_stream)
+_ROTATE_WINDS_TRANSPOSE_PROTO = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_WIND_DESTAGGER_TRANSPOSE_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def rotate_winds_transpose_dev(*args):
+    """The typed binding of mpg_rotate_winds_transpose_dev; returns the call's status code."""
+    if "rotate_t" not in _to_mesh_fns:
+        _to_mesh_fns["rotate_t"] = _ROTATE_WINDS_TRANSPOSE_PROTO(("mpg_rotate_winds_transpose_dev", load()))
+    return _to_mesh_fns["rotate_t"](*args)
+
+
+def wind_destagger_transpose_dev(*args):
+    """The typed binding of mpg_wind_destagger_transpose_dev; returns the call's status code."""
+    if "destagger_t" not in _to_mesh_fns:
+        _to_mesh_fns["destagger_t"] = _WIND_DESTAGGER_TRANSPOSE_PROTO(("mpg_wind_destagger_transpose_dev", load()))
+    return _to_mesh_fns["destagger_t"](*args)
 
 
 # Winds from edge-normal u, bound the same way.

@@ -45,6 +45,30 @@ __global__ __launch_bounds__(256) void k_rotate(int64_t npts, int nlev, const do
   }
 }
 
+// The adjoint of k_rotate: the reverse mode of interp.F90:737-748 as the header states the forward, in place on the incoming gradients of
+// (un, vn); evaluated exactly as written (no FMA), as the forward is
+__global__ __launch_bounds__(256) void k_rotate_t(int64_t npts, int nlev, const double *__restrict__ cosa,
+                                                  const double *__restrict__ sina, double *__restrict__ gu, double *__restrict__ gv) {
+#pragma clang fp contract(off)
+  int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= npts) return;
+  double ca = cosa[p], sa = sina[p];
+  double tana = sa / ca;
+  double den = ca + sa * tana;
+  for (int k = 0; k < nlev; ++k) {
+    int64_t q = (int64_t)k * npts + p;
+    double gun = gu[q], gvn = gv[q];
+    double a = gvn / ca;
+    double t = a * sa;
+    double b = gun - t;
+    double guo = b / den;
+    double pp = guo * tana;
+    double gvo = a + pp;
+    gu[q] = guo;
+    gv[q] = gvo;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_pack(const double *__restrict__ src, int64_t nsrc, int nlev,
                                               const int32_t *__restrict__ ids, int64_t nids, double *__restrict__ dst) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -147,6 +171,13 @@ int mpg_zero_planes(void *dst, size_t esz, int64_t P, int64_t nplanes, int64_t l
 int mpg_k_rotate(int64_t npts, int nlev, const double *cosa, const double *sina, double *u, double *v, hipStream_t s) {
   if (npts == 0 || nlev == 0) return MPG_SUCCESS;
   k_rotate<<<(unsigned)((npts + 255) / 256), 256, 0, s>>>(npts, nlev, cosa, sina, u, v);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
+int mpg_k_rotate_transpose(int64_t npts, int nlev, const double *cosa, const double *sina, double *gu, double *gv, hipStream_t s) {
+  if (npts == 0 || nlev == 0) return MPG_SUCCESS;
+  k_rotate_t<<<(unsigned)((npts + 255) / 256), 256, 0, s>>>(npts, nlev, cosa, sina, gu, gv);
   MPG_HIP(hipGetLastError());
   return MPG_SUCCESS;
 }

@@ -28,8 +28,8 @@
 #include <vector>
 
 #include "apply_mesh.h"
+#include "transpose_seg.h"   // TR_SHORT: the longest segment served by one lane (registers); longer ones go to k_tr_long
 
-#define TR_SHORT 16   // longest segment served by one lane (registers); longer ones go to k_tr_long
 #define TR_LF_CELLS 64
 #define TR_LF_LEVS 64
 
@@ -211,64 +211,7 @@ int mpg_k_transpose_build(mpg_handle_s *h, hipStream_t s) {
 }
 
 // ---- apply ------------------------------------------------------------------------------------------------------------
-// sum over one segment held in registers, ascending order; sf = the level's source plane.  nmax: the longest segment in the wave
-// (uniform).  Slots past a lane's own n load a valid row (tr_load_seg fills them with row 0) and are dropped by a select, so the loads
-// carry no branches and issue back to back; most handles (C4 bilinear: 4 at most) take the 4-slot form.
-template <typename TS>
-__device__ __forceinline__ double tr_seg_regs(const int32_t (&r)[TR_SHORT], const double (&w)[TR_SHORT], int n, int nmax, const TS *__restrict__ sf) {
-  double acc = 0.0;
-  if (nmax <= 4) {
-    double v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (double)sf[r[j]];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = j < n ? fma(w[j], v[j], acc) : acc;
-    return acc;
-  }
-#pragma unroll
-  for (int j = 0; j < TR_SHORT; ++j)
-    if (j < nmax) {
-      const double v = (double)sf[r[j]];
-      acc = j < n ? fma(w[j], v, acc) : acc;
-    }
-  return acc;
-}
-// the same sum read from memory (any length)
-template <typename TS>
-__device__ __forceinline__ double tr_seg_mem(const int32_t *__restrict__ rows, const double *__restrict__ wts, int32_t b, int32_t e,
-                                             const TS *__restrict__ sf) {
-  double acc = 0.0;
-  for (int32_t j = b; j < e; ++j) acc = fma(wts[j], (double)sf[rows[j]], acc);
-  return acc;
-}
-
-// one lane per source; sources with a segment longer than TR_SHORT get 0 here (k_tr_long / k_tr_pole overwrite them later)
-template <typename TS>
-__device__ __forceinline__ int tr_load_seg(const int32_t *__restrict__ ptr, const int32_t *__restrict__ rows, const double *__restrict__ wts,
-                                           int64_t c, bool act, int32_t (&r)[TR_SHORT], double (&w)[TR_SHORT]) {
-  int n = 0;
-  int32_t b = 0;
-  if (act) {
-    b = ptr[c];
-    n = ptr[c + 1] - b;
-    if (n > TR_SHORT) n = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < TR_SHORT; ++j) {
-    r[j] = 0;
-    w[j] = 0.0;
-    if (j < n) {
-      r[j] = rows[b + j];
-      w[j] = wts[b + j];
-    }
-  }
-  return n;
-}
-__device__ __forceinline__ int tr_wave_max(int n) {
-  for (int o = 32; o > 0; o >>= 1) n = max(n, __shfl_xor(n, o));
-  return n;
-}
-
+// the segment sum itself -- tr_load_seg, tr_seg_regs, tr_seg_mem -- is transpose_seg.h: one text for this file and k_wind_transpose.hip
 // cell-fast: out [f][lev][cell]; 256 consecutive sources per workgroup, every level
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void k_tr_short_cf(const int32_t *__restrict__ ptr, const int32_t *__restrict__ rows, const double *__restrict__ wts,
@@ -416,6 +359,25 @@ int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, 
   return mpg_dispatch_types(src_type, dst_type, [&](auto ts, auto td) {   // (apply_mesh.h)
     return launch_tr<decltype(ts), decltype(td)>(h, src, ld, nlev, nfields, dst, levf, s);
   });
+}
+
+// The pole term alone, for a caller that has computed the segment sums itself (k_wind_transpose.hip): k_tr_pole rewrites the sources of
+// the two CENTER rows of dst [nlev][n_src] float64 as segment sum + term / row_len -- the launch launch_tr ends with, the same bits.
+// The handle's transposed index must be built.
+int mpg_k_transpose_pole(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, double *dst, hipStream_t s) {
+  if (!h->n_pole || nlev == 0) return MPG_SUCCESS;
+  if (h->kind != MPG_KIND_FIXED || h->pole_len <= 0 || h->pole_len > h->n_src || !h->tr_built) {
+    mpg_set_error("mpg_k_transpose_pole: pole terms on a handle that is not a Grid -> Grid bilinear one with a transposed index");
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (src_type & MPG_TYPE_F32)
+    k_tr_pole<float, double, false><<<(unsigned)nlev, 256, 0, s>>>(h->tr_ptr.p, h->tr_row.p, h->tr_w.p, h->pole_dst.p, h->pole_src0.p, h->pole_w.p,
+                                                                  (int)h->n_pole, h->pole_len, (const float *)src, dst, h->n_src, ld, nlev);
+  else
+    k_tr_pole<double, double, false><<<(unsigned)nlev, 256, 0, s>>>(h->tr_ptr.p, h->tr_row.p, h->tr_w.p, h->pole_dst.p, h->pole_src0.p, h->pole_w.p,
+                                                                   (int)h->n_pole, h->pole_len, (const double *)src, dst, h->n_src, ld, nlev);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

@@ -299,11 +299,9 @@ static int launch_wind(const WindArgs &a, bool rot, unsigned nwg, hipStream_t s)
   return MPG_SUCCESS;
 }
 
-// h1 / h2: the CENTER -> EDGE1 / CENTER -> EDGE2 handles of ONE grid (either may be NULL: that component is not
-// produced); cosa / sina NULL: no rotation.  -> MPG_ERR_UNSUPPORTED when the handles are not such a pair (the caller
-// keeps the three-call chain).
-int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const double *um, const double *vm, int nlev,
-                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s, int64_t ld) {
+// The pair test of the chain and of its adjoint (k_wind_transpose.hip): h1 / h2 are the CENTER -> EDGE1 / CENTER -> EDGE2 handles of ONE grid
+// (either may be NULL, not both), as stored (not re-indexed), and a level plane stays within 32-bit byte offsets.
+int mpg_wind_pair_dims(const mpg_handle_s *h1, const mpg_handle_s *h2, int *nx_out, int *ny_out) {
   int nx, ny;
   if (h2) {
     nx = h2->nx_dst;
@@ -313,7 +311,7 @@ int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa,
     ny = h1->ny_dst;
   }
   const int64_t NP = (int64_t)nx * ny;
-  for (mpg_handle_s *h : {h1, h2}) {
+  for (const mpg_handle_s *h : {h1, h2}) {
     if (!h) continue;
     const bool e1 = h == h1;
     if (h->kind != MPG_KIND_FIXED || h->nnz_per_row != 4 || h->localized || h->n_src != NP || nx < 1 || ny < 1 || h->nx_dst != nx + (e1 ? 1 : 0) ||
@@ -321,6 +319,19 @@ int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa,
       return MPG_ERR_UNSUPPORTED;
   }
   if ((int64_t)(nx + 1) * (ny + 1) * 8 >= 0xFFFFFFFFLL) return MPG_ERR_UNSUPPORTED;   // 32-bit byte offsets inside a level plane
+  *nx_out = nx;
+  *ny_out = ny;
+  return MPG_SUCCESS;
+}
+
+// h1 / h2: the CENTER -> EDGE1 / CENTER -> EDGE2 handles of ONE grid (either may be NULL: that component is not
+// produced); cosa / sina NULL: no rotation.  -> MPG_ERR_UNSUPPORTED when the handles are not such a pair (the caller
+// keeps the three-call chain).
+int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const double *um, const double *vm, int nlev,
+                         void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s, int64_t ld) {
+  int nx, ny;
+  if (int rc = mpg_wind_pair_dims(h1, h2, &nx, &ny)) return rc;
+  const int64_t NP = (int64_t)nx * ny;
   const bool rot = cosa != nullptr;
   const int64_t n_pole = (h1 ? h1->n_pole : 0) + (h2 ? h2->n_pole : 0);
   if (rot && n_pole) return MPG_ERR_UNSUPPORTED;   // (a rotated field under pole caps: no projection of the reference asks for it)

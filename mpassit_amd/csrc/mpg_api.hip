@@ -128,7 +128,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1709,6 +1709,54 @@ int mpg_wind_destagger_pitched_dev(mpg_handle h1, mpg_handle h2, const double *c
   }
   rc = mpg_k_wind_destagger(h1, h2, cosa_dev, sina_dev, umass_dev, vmass_dev, nlev, u_dev, v_dev, dst_type, umass_rot_dev, vmass_rot_dev,
                             (hipStream_t)hip_stream, dst_level_stride);
+  if (rc == MPG_ERR_UNSUPPORTED) mpg_set_error("mpg_wind_destagger: the handles are not the CENTER -> EDGE1 / EDGE2 pair of one grid");
+  return rc;
+}
+
+// ---- the adjoint of the wind chain: the rotation's, and the fused call (k_wind_transpose.hip) -----------------------------------------------
+int mpg_rotate_winds_transpose_dev(int64_t npts, int nlev, const double *cosa_dev, const double *sina_dev, double *gu_dev, double *gv_dev,
+                                   void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(cosa_dev && sina_dev && gu_dev && gv_dev, "mpg_rotate_winds_transpose: NULL argument");
+  MPG_ARG(npts >= 0 && nlev >= 1, "mpg_rotate_winds_transpose: bad sizes");
+  return mpg_k_rotate_transpose(npts, nlev, cosa_dev, sina_dev, gu_dev, gv_dev, (hipStream_t)hip_stream);
+}
+
+int mpg_wind_destagger_transpose_dev(mpg_handle h1, mpg_handle h2, const double *cosa_dev, const double *sina_dev, const void *gu_dev,
+                                     const void *gv_dev, int src_type, int64_t src_level_stride, int nlev, const double *gumass_rot_dev,
+                                     const double *gvmass_rot_dev, double *gumass_dev, double *gvmass_dev, void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h1 || h2, "mpg_wind_destagger_transpose: no handle");
+  MPG_ARG((cosa_dev == nullptr) == (sina_dev == nullptr), "mpg_wind_destagger_transpose: cosa and sina come together");
+  const bool rot = cosa_dev != nullptr;
+  MPG_ARG(!rot || (h1 && h2), "mpg_wind_destagger_transpose: the rotation needs both components (interp.F90:291)");
+  MPG_ARG(rot || (!gumass_rot_dev && !gvmass_rot_dev), "mpg_wind_destagger_transpose: a gradient of the rotated mass winds without a rotation");
+  MPG_ARG(nlev >= 1, "mpg_wind_destagger_transpose: nlev must be >= 1");
+  MPG_ARG(src_type >= 0 && src_type <= 3, "mpg_wind_destagger_transpose: src_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if (src_type & MPG_TYPE_BE) {
+    mpg_set_error("mpg_wind_destagger_transpose: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  MPG_ARG((!h1 || gu_dev) && (!h2 || gv_dev), "mpg_wind_destagger_transpose: NULL gradient of U / V");
+  MPG_ARG((!h1 || gumass_dev) && (!h2 || gvmass_dev), "mpg_wind_destagger_transpose: NULL destination");
+  for (const void *o : {(const void *)(h1 ? gumass_dev : nullptr), (const void *)(h2 ? gvmass_dev : nullptr)}) {
+    if (!o) continue;
+    MPG_ARG(o != gu_dev && o != gv_dev && o != (const void *)gumass_rot_dev && o != (const void *)gvmass_rot_dev && o != (const void *)cosa_dev &&
+                o != (const void *)sina_dev,
+            "mpg_wind_destagger_transpose: a result cannot replace an input (neighbouring points read it)");
+  }
+  MPG_ARG(!(h1 && h2) || (const void *)gumass_dev != (const void *)gvmass_dev, "mpg_wind_destagger_transpose: the two results are one array");
+  // one stride for gU [ny][nx+1] and gV [ny+1][nx]: at least the plane of each component given; 0: each dense
+  const int64_t p1 = h1 ? h1->n_dst : 0, p2 = h2 ? h2->n_dst : 0;
+  int64_t ldu = p1, ldv = p2;
+  if (src_level_stride != 0) {
+    int64_t ld;
+    int rc = dst_stride("mpg_wind_destagger_transpose: source", std::max(p1, p2), nlev, (src_type & MPG_TYPE_F32) ? 4 : 8, src_level_stride, &ld);
+    if (rc) return rc;
+    ldu = ldv = ld;
+  }
+  const int rc = mpg_k_wind_destagger_transpose(h1, h2, cosa_dev, sina_dev, gu_dev, gv_dev, src_type, ldu, ldv, nlev, gumass_rot_dev, gvmass_rot_dev,
+                                                gumass_dev, gvmass_dev, (hipStream_t)hip_stream);
   if (rc == MPG_ERR_UNSUPPORTED) mpg_set_error("mpg_wind_destagger: the handles are not the CENTER -> EDGE1 / EDGE2 pair of one grid");
   return rc;
 }

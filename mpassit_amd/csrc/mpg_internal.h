@@ -466,6 +466,8 @@ int mpg_k_pole_fix(mpg_handle_s *h, const void *src, int src_type, int layout, i
 int mpg_k_transpose_build(mpg_handle_s *h, hipStream_t s);
 int mpg_k_transpose(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, int nfields, void *dst, int dst_type, int layout,
                     hipStream_t s);
+// the pole term of the transpose alone, over segment sums the caller has stored: dst [nlev][n_src] float64 (index built)
+int mpg_k_transpose_pole(mpg_handle_s *h, const void *src, int src_type, int64_t ld, int nlev, double *dst, hipStream_t s);
 // k_apply_masked.hip: the masked Regrid (include/mpassit_amd.h mpg_regrid_masked_dev; arguments checked by the API entry point); ld as above
 int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type, int64_t ld,
                        const mpg_mask_opts *opts, hipStream_t s);
@@ -552,6 +554,14 @@ int mpg_k_post_ptop_parts(const double *src, int nlev, int64_t P, double *vmax_h
 int mpg_k_rotate(int64_t npts, int nlev, const double *cosa, const double *sina, double *u, double *v, hipStream_t s);
 int mpg_k_wind_destagger(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const double *um, const double *vm, int nlev,
                          void *u, void *v, int dst_type, double *um_rot, double *vm_rot, hipStream_t s, int64_t ld = 0);   // k_wind.hip; ld: U's and V's (0: each dense)
+// the test both wind-chain kernels put their handles to: the CENTER -> EDGE1 / EDGE2 pair of one grid (either may be NULL), the level planes within
+// 32-bit byte offsets -> MPG_ERR_UNSUPPORTED otherwise; nx, ny: the CENTER stagger's sizes
+int mpg_wind_pair_dims(const mpg_handle_s *h1, const mpg_handle_s *h2, int *nx, int *ny);
+int mpg_k_rotate_transpose(int64_t npts, int nlev, const double *cosa, const double *sina, double *gu, double *gv, hipStream_t s);
+// k_wind_transpose.hip: the adjoint of the chain; gu / gv of src_type, planes ldu / ldv elements apart; gur / gvr optional (rotation only)
+int mpg_k_wind_destagger_transpose(mpg_handle_s *h1, mpg_handle_s *h2, const double *cosa, const double *sina, const void *gu, const void *gv,
+                                   int src_type, int64_t ldu, int64_t ldv, int nlev, const double *gur, const double *gvr, double *gum, double *gvm,
+                                   hipStream_t s);
 int mpg_k_pack(const double *src, int64_t n_src, int nlev, const int32_t *ids, int64_t n_ids, double *dst, hipStream_t s);
 int mpg_k_tune(const char *key, int value);
 int mpg_store_boxes();         // "store_boxes" knob: 1 (default) index-space candidate boxes on projection-built grids, 0 pyramid walk only

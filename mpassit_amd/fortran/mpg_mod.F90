@@ -401,6 +401,27 @@ module mpg
       integer(c_int), value :: nlev, dst_type
       integer(c_int) :: rc
     end function mpg_wind_destagger
+    !> the adjoint of mpg_rotate_winds_dev, in place on the gradients gu_dev, gv_dev [nlev][npts] (include/mpassit_amd.h)
+    function mpg_rotate_winds_transpose_dev(npts, nlev, cosa_dev, sina_dev, gu_dev, gv_dev, hip_stream) &
+      bind(C, name="mpg_rotate_winds_transpose_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: npts
+      integer(c_int), value :: nlev
+      type(c_ptr), value :: cosa_dev, sina_dev, gu_dev, gv_dev, hip_stream
+      integer(c_int) :: rc
+    end function mpg_rotate_winds_transpose_dev
+    !> the adjoint of mpg_wind_destagger_dev in one pass: the gradients of U and V back to the gradients of the mass-point winds
+    !! (float64, dense); gumass_rot_dev / gvmass_rot_dev optional (c_null_ptr); include/mpassit_amd.h
+    function mpg_wind_destagger_transpose_dev(rh_edge1, rh_edge2, cosa_dev, sina_dev, gu_dev, gv_dev, src_type, src_level_stride, nlev, &
+                                              gumass_rot_dev, gvmass_rot_dev, gumass_dev, gvmass_dev, hip_stream) &
+      bind(C, name="mpg_wind_destagger_transpose_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: rh_edge1, rh_edge2, cosa_dev, sina_dev, gu_dev, gv_dev
+      type(c_ptr), value :: gumass_rot_dev, gvmass_rot_dev, gumass_dev, gvmass_dev, hip_stream
+      integer(c_int), value :: src_type, nlev
+      integer(c_int64_t), value :: src_level_stride
+      integer(c_int) :: rc
+    end function mpg_wind_destagger_transpose_dev
     !> the wind chain turned round: U / V on two staggers onto mesh points as earth-relative winds in one pass, the inverse of
     !! interp.F90:737-748 (cosa_dev / sina_dev at the MESH points, both c_null_ptr: no rotation; include/mpassit_amd.h)
     function mpg_wind_to_mesh_dev(rh_u, rh_v, cosa_dev, sina_dev, u_dev, v_dev, src_type, u_level_stride, v_level_stride, nlev, ue_dev, &

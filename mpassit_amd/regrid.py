@@ -27,7 +27,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
            "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
-           "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights"]
+           "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights",
+           "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd"]
 
 
 def _f64(a):
@@ -1069,6 +1070,126 @@ def wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, d
                                                   C.c_int(int(out_dtype == torch.float32) | (2 if dst_be else 0)), p(ur), p(vr), C.c_int64(ld),
                                                   _stream_ptr()))
     return u, v, ur, vr
+
+
+def rotate_winds_cgrid_transpose(cosa, sina, gu, gv):
+    """mpg_rotate_winds_transpose_dev: the adjoint of rotate_winds_cgrid, in place on the gradients gu, gv -- contiguous float64 CUDA
+    tensors [nlev][ny][nx] (or [ny][nx]); cosa / sina [ny][nx] float64 CUDA tensors, reused over the levels.  The same bits as
+    target_grid.rotate_winds_transpose_at.  Returns (gu, gv)."""
+    import torch
+    for t in (cosa, sina, gu, gv):
+        if not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64):
+            raise ValueError("rotate_winds_cgrid_transpose needs contiguous float64 CUDA tensors (the gradients are rotated in place)")
+    npts = cosa.numel()
+    if sina.numel() != npts or npts == 0 or gu.numel() % npts or gu.numel() == 0 or gv.numel() != gu.numel():
+        raise ValueError("rotate_winds_cgrid_transpose: gu and gv must hold the same whole number of [ny][nx] planes as cosa / sina have points")
+    nlev = gu.numel() // npts
+    check(L.rotate_winds_transpose_dev(C.c_int64(npts), C.c_int(nlev), C.c_void_p(cosa.data_ptr()), C.c_void_p(sina.data_ptr()),
+                                       C.c_void_p(gu.data_ptr()), C.c_void_p(gv.data_ptr()), _stream_ptr()))
+    return gu, gv
+
+
+def wind_destagger_transpose(rh_u, rh_v, cosa, sina, gu, gv, nlev, g_umass_rot=None, g_vmass_rot=None, outs=None):
+    """mpg_wind_destagger_transpose_dev: the adjoint of wind_destagger in one pass -- the gradients gu [nlev][ny][nx+1] and gv
+    [nlev][ny+1][nx] of U and V (float32 or float64 CUDA tensors of ONE dtype, dense or plane-pitched with one level stride for both, as
+    wind_destagger's outs) back to the gradients (g_umass, g_vmass) of the mass-point winds, float64 [nlev][ny][nx]; an entry is None
+    for a component that is not produced (its handle is None).  cosa / sina None: no rotation, and either handle may be None.
+    g_umass_rot / g_vmass_rot: the gradients of wind_destagger's keep_mass results (float64, rotation only), added before the rotation's
+    adjoint.  Bit-identical to rh_u.regrid_transpose(gu) and rh_v.regrid_transpose(gv) into float64, the adds, and
+    rotate_winds_cgrid_transpose.  outs=(g_umass, g_vmass): contiguous float64 CUDA tensors to write into."""
+    import torch
+    if (cosa is None) != (sina is None):
+        raise ValueError("wind_destagger_transpose: cosa and sina come together")
+    if rh_u is None and rh_v is None:
+        raise ValueError("wind_destagger_transpose: no handle")
+    rot = cosa is not None
+    nx, ny = (rh_v.nx_dst, rh_v.ny_dst - 1) if rh_v is not None else (rh_u.nx_dst - 1, rh_u.ny_dst)
+    pitched, dense, dts = set(), [], set()
+    for t, rh in ((gu, rh_u), (gv, rh_v)):
+        if rh is None:
+            continue
+        if not (_is_torch(t) and t.is_cuda and t.dtype in (torch.float32, torch.float64)):
+            raise ValueError("wind_destagger_transpose needs float32/float64 CUDA tensors")
+        dts.add(t.dtype)
+        if t.is_contiguous():
+            if t.numel() != nlev * rh.n_dst:
+                raise ValueError("wind_destagger_transpose: a gradient has %d elements, its handle expects %d" % (t.numel(), nlev * rh.n_dst))
+            dense.append(rh.n_dst)
+        else:
+            if t.dim() != 3:
+                raise ValueError("wind_destagger_transpose: a strided gradient must be (nlev, ny, nx) with plane-pitched levels")
+            pitched.add(_level_stride(t, (nlev,), rh.ny_dst, rh.nx_dst, "wind_destagger_transpose"))
+    if len(dts) > 1:
+        raise ValueError("wind_destagger_transpose: gu and gv must have one dtype")
+    # one stride for both: a contiguous tensor beside a pitched one has the stride of its own plane
+    if len(pitched) > 1 or (pitched and nlev > 1 and any(n != max(pitched) for n in dense)):
+        raise ValueError("wind_destagger_transpose: gu and gv must share one level stride (or both be dense)")
+    ld = pitched.pop() if pitched else 0
+    for t in (cosa, sina, g_umass_rot, g_vmass_rot):
+        if t is None:
+            continue
+        if not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64):
+            raise ValueError("wind_destagger_transpose: the angles and the mass-wind gradients must be contiguous float64 CUDA tensors")
+    if rot and (cosa.numel() != nx * ny or sina.numel() != nx * ny):
+        raise ValueError("wind_destagger_transpose: cosa / sina must have %d points" % (nx * ny))
+    for t in (g_umass_rot, g_vmass_rot):
+        if t is not None and t.numel() != nlev * nx * ny:
+            raise ValueError("wind_destagger_transpose: a mass-wind gradient must have %d elements" % (nlev * nx * ny))
+    ref = gu if rh_u is not None else gv
+    og, ov = outs if outs is not None else (None, None)
+    if og is None and rh_u is not None:
+        og = torch.empty((nlev, ny, nx), dtype=torch.float64, device=ref.device)
+    if ov is None and rh_v is not None:
+        ov = torch.empty((nlev, ny, nx), dtype=torch.float64, device=ref.device)
+    for t, rh in ((og, rh_u), (ov, rh_v)):
+        if rh is not None and not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == nlev * nx * ny):
+            raise ValueError("wind_destagger_transpose: outs must be contiguous float64 CUDA tensors of %d elements" % (nlev * nx * ny))
+
+    def p(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    check(L.wind_destagger_transpose_dev(rh_u._h if rh_u is not None else None, rh_v._h if rh_v is not None else None, p(cosa), p(sina),
+                                         p(gu) if rh_u is not None else None, p(gv) if rh_v is not None else None,
+                                         C.c_int(int(dts.pop() == torch.float32)), C.c_int64(ld), C.c_int(nlev), p(g_umass_rot), p(g_vmass_rot),
+                                         p(og) if rh_u is not None else None, p(ov) if rh_v is not None else None, _stream_ptr()))
+    return (og if rh_u is not None else None), (ov if rh_v is not None else None)
+
+
+if _torch is not None:
+    class WindDestaggerFunction(_torch.autograd.Function):
+        """wind_destagger with a gradient: forward is wind_destagger, backward ONE wind_destagger_transpose call.  Returns the tensors
+        among (U, V, UMASS', VMASS') only; use wind_destagger_autograd()."""
+
+        @staticmethod
+        def forward(ctx, umass, vmass, rh_u, rh_v, cosa, sina, nlev, out_dtype, keep_mass):
+            ctx.rh_u, ctx.rh_v, ctx.cosa, ctx.sina, ctx.nlev = rh_u, rh_v, cosa, sina, nlev
+            ctx.given = (umass is not None, vmass is not None)
+            res = wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=out_dtype, keep_mass=keep_mass)
+            ctx.which = tuple(i for i, r in enumerate(res) if r is not None)
+            return tuple(res[i] for i in ctx.which)
+
+        @staticmethod
+        def backward(ctx, *grads):
+            g = dict(zip(ctx.which, grads))
+
+            def c(t):
+                return t.contiguous() if t is not None else None
+            gum, gvm = wind_destagger_transpose(ctx.rh_u, ctx.rh_v, ctx.cosa, ctx.sina, c(g.get(0)), c(g.get(1)), ctx.nlev,
+                                                g_umass_rot=c(g.get(2)), g_vmass_rot=c(g.get(3)))
+            return (gum if ctx.given[0] else None, gvm if ctx.given[1] else None) + (None,) * 7
+
+
+def wind_destagger_autograd(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=None, keep_mass=False):
+    """wind_destagger(rh_u, rh_v, cosa, sina, umass, vmass, nlev, out_dtype=out_dtype, keep_mass=keep_mass) on float64 CUDA tensors as a
+    differentiable torch op: the same bits and the same 4-tuple (U, V, UMASS', VMASS').  The backward is one wind_destagger_transpose
+    call on the incoming gradients (float32 or float64, as out_dtype) -- with keep_mass the gradients of the rotated mass winds go in as
+    g_umass_rot / g_vmass_rot -- and the gradients with respect to umass and vmass are always float64; None for an input that was not
+    given.  The angles are constants."""
+    res = WindDestaggerFunction.apply(umass, vmass, rh_u, rh_v, cosa, sina, nlev, out_dtype, keep_mass)
+    out = [None, None, None, None]
+    slots = [i for i, have in enumerate((rh_u is not None, rh_v is not None, keep_mass and cosa is not None, keep_mass and cosa is not None)) if have]
+    for i, r in zip(slots, res):
+        out[i] = r
+    return tuple(out)
 
 
 def _wind_source(t, rh, nlev, who):

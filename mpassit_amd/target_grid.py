@@ -273,6 +273,24 @@ def rotang_at(proj, lon_deg):
     return np.cos(alpha), np.sin(alpha)
 
 
+def rotate_winds_transpose_at(cosa, sina, gu, gv):
+    """The host mirror of mpg_rotate_winds_transpose_dev: the adjoint of rotate_winds_cgrid (interp.F90:737-748) on the gradients gu, gv
+    ([nlev][ny][nx] or [ny][nx], float64) with cosa / sina [ny][nx] reused over the levels.  The same float64 operations in the same
+    order as the kernel, each rounded once (numpy contracts nothing): the same bits.  Returns new arrays (guo, gvo)."""
+    ca, sa = np.asarray(cosa, dtype=np.float64), np.asarray(sina, dtype=np.float64)
+    gun, gvn = np.asarray(gu, dtype=np.float64), np.asarray(gv, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        tana = sa / ca
+        den = ca + sa * tana
+        a = gvn / ca
+        t = a * sa
+        b = gun - t
+        guo = b / den
+        p = guo * tana
+        gvo = a + p
+    return guo, gvo
+
+
 def edge_rotang_at(proj, lon_deg, angle_edge):
     """(cn, sn) = cos / sin of phi = angle_edge - alpha at mesh edges: alpha as rotang_at at the edges' longitudes (degrees), angle_edge
     the MPAS angleEdge (radians) -- the rotation to earth-relative winds and the projection onto the edge normal as ONE rotation.  The
