@@ -545,6 +545,45 @@ typedef struct mpg_mask_opts {
 } mpg_mask_opts;
 int mpg_regrid_masked_dev(mpg_handle rh, const void *src_dev, int src_type, int src_layout, int nlev, int nfields,
                           void *dst_dev, int dst_type, int64_t dst_level_stride, const mpg_mask_opts *opts, void *hip_stream);
+/* The adjoint of the masked Regrid: the gradient of a loss with respect to the source of mpg_regrid_masked_dev, from its gradient with
+ * respect to the result.  The forward is linear in the valid source values and Wv depends only on WHICH sources are missing, so the
+ * adjoint is exact.  mpg_regrid_transpose_dev of the incoming gradient is not it: that ignores Wt / Wv, sends gradient into sources
+ * that never entered the forward, and lets a NaN in the gradient of an undefined output spread to every source the output touches.
+ *   g_dev     the gradient of the masked Regrid's result, [nfields][nlev][plane of n_dst], MPG_TYPE_F64 or MPG_TYPE_F32; planes
+ *             g_level_stride elements apart (0 = dense, below n_dst -> MPG_ERR_INVALID_ARG).  The pad is never read: a pitched
+ *             result buffer can be fed back as it is.
+ *   src_dev   the source the forward call read, in src_layout ([lev][cell] or [cell][lev]), nfields slabs.  It is read only to decide
+ *             validity: its values never enter a product.
+ *   dst_dev   the gradient with respect to src: nfields slabs of nlev * n_src in the same src_layout, fully overwritten.
+ *   opts      the forward's mpg_mask_opts: flags, missing_value, src_mask_dev, min_valid_frac and scale are used; fill_value and
+ *             offset are ignored (they have no derivative).
+ *   work_dev  a caller-owned float64 workspace of nfields * nlev * n_dst elements, dense.  It holds the scaled gradient h below and is
+ *             fully overwritten; its contents on return are part of the contract.  It must not be NULL and must not alias g_dev,
+ *             src_dev or dst_dev (MPG_ERR_INVALID_ARG).
+ * MPG_TYPE_F64 or MPG_TYPE_F32 on each of g, src and dst independently; arithmetic is float64, with one rounding at the store.
+ * Contract by identity, no tolerance; nothing is contracted.  valid(q), Wt, Wv and defined are, word for word, those of the
+ * mpg_regrid_masked_dev contract above: same order, same expressions; the decision Wv > 0 && Wv >= min_valid_frac * Wt is bit-exact.
+ *   h[k][p]    = defined(p, k) ? ((double)g[k][p] * scale) * (Wt / Wv) : +0.0 -- two separately rounded products; a select, never a
+ *                product with 0: a NaN or Inf in g at an undefined or unmapped point reaches no source
+ *   acc        = fma(w_j, h[k][row_j], acc) from +0.0 over the stored entries j that reference source c, in ascending (destination
+ *                point, slot) order -- exactly the chain of mpg_regrid_transpose_dev (nearest neighbour: w_j = 1.0)
+ *   ok(c, k)   = src_mask[c] == 0 and src(c, k) not missing under flags
+ *   dst[c][k]  = ok(c, k) ? (dst type) acc : +0.0 -- a select; a source no entry references gets +0.0
+ * Identity with the unmasked transpose: with nothing missing, scale == 1 and every point mapped, Wt / Wv == 1.0, h equals (double)g
+ * bit for bit and the result equals mpg_regrid_transpose_dev into the same type and layout bit for bit.
+ * Derivative: the result is the derivative of the forward with respect to every valid source element, and exactly +0.0 at every
+ * invalid one.  It is the adjoint of the linear part, scale included; it is not an inverse.
+ * No floating-point atomics: the same bits across calls, across nfields batching, for the two layouts and across float32 / float64
+ * inputs that hold the same values.
+ * Refused as mpg_regrid_masked_dev refuses: MPG_ERR_UNSUPPORTED for MPG_TYPE_BE on any side and for handles with pole caps;
+ * MPG_ERR_INVALID_ARG for a NULL rh, opts, g_dev, src_dev, dst_dev or work_dev, a bad layout, nlev or nfields < 1, min_valid_frac
+ * outside [0, 1] or NaN, MPG_MISSING_VALUE with a NaN missing_value, unknown flag bits, a stride below n_dst and an aliased workspace.
+ * A refused call writes nothing.
+ * Stream as mpg_regrid_transpose_dev: the first call on a handle builds its transposed index, which allocates and synchronises;
+ * later calls only enqueue and can be captured in a hipGraph. */
+int mpg_regrid_masked_transpose_dev(mpg_handle rh, const void *g_dev, int g_type, int64_t g_level_stride, const void *src_dev, int src_type,
+                                    int src_layout, int nlev, int nfields, void *dst_dev, int dst_type, const mpg_mask_opts *opts,
+                                    double *work_dev, void *hip_stream);
 /* ESMF_FieldBundleRegrid as interp.F90:240-254 issues it: ONE Regrid over every field of a bundle whose fields are SEPARATE
  * arrays (an ESMF bundle holds independent fields; here: nfields device pointers on either side, host arrays of pointers).
  * All fields share the handle, the layout, nlev and the element types; offsets (nfields values, or NULL for 0) is the

@@ -35,6 +35,7 @@ SYMBOLS = [
     "mpg_reconstruct_store", "mpg_reconstruct_weights_dev", "mpg_wind_reconstruct_dev",
     "mpg_handle_compose", "mpg_compose_weights_dev",
     "mpg_rotate_winds_transpose_dev", "mpg_wind_destagger_transpose_dev",
+    "mpg_regrid_masked_transpose_dev",
 ]
 
 MPG_SUCCESS = 0
@@ -71,6 +72,22 @@ def regrid_masked_dev(*args):
     if _masked_fn is None:
         _masked_fn = _MASKED_PROTO(("mpg_regrid_masked_dev", load()))
     return _masked_fn(*args)
+
+
+# Its adjoint, bound the same way:
+#   mpg_regrid_masked_transpose_dev(rh, g_dev, g_type, g_level_stride, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type,
+#                                   opts, work_dev, hip_stream)
+_REGRID_MASKED_TRANSPOSE_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int, C.POINTER(MaskOpts), C.c_void_p, C.c_void_p)
+_masked_transpose_fn = None
+
+
+def regrid_masked_transpose_dev(*args):
+    """The typed binding of mpg_regrid_masked_transpose_dev; returns the call's status code."""
+    global _masked_transpose_fn
+    if _masked_transpose_fn is None:
+        _masked_transpose_fn = _REGRID_MASKED_TRANSPOSE_PROTO(("mpg_regrid_masked_transpose_dev", load()))
+    return _masked_transpose_fn(*args)
 
 
 # The Grid -> Mesh calls with their argument types, bound like the masked Regrid above.

@@ -19,16 +19,7 @@
 //                 chunk of 64 levels (bounded whatever nlev is), stores with lanes = points
 //   k_masked_csr  CSR (conservative, mpg_handle_from_weights), both layouts: one thread per point, two levels per pass over the row
 #include "apply_mesh.h"
-
-struct MaskPar {            // by value in the kernels' argument block
-  const uint8_t *mask;      // [n_src] non-zero = never use, or nullptr
-  double missing, frac, fill, scale, offset;
-  int use_nan, use_val;
-};
-
-__device__ __forceinline__ bool mk_missing(double x, const MaskPar &m) {
-  return (m.use_nan && __builtin_isnan(x)) || (m.use_val && x == m.missing);
-}
+#include "masked_par.h"   // MaskPar, mk_missing: shared with the adjoint (k_transpose_masked.hip)
 
 // defined ? epilogue(N * Wt / Wv) : fill -- one select; Wv == Wt gives the quotient 1.0 exactly
 __device__ __forceinline__ double mk_resolve(double N, double Wt, double Wv, const MaskPar &m) {

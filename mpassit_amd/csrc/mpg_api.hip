@@ -128,7 +128,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1604,6 +1604,48 @@ int mpg_regrid_masked_dev(mpg_handle h, const void *src_dev, int src_type, int s
   int rc = dst_stride("mpg_regrid_masked", h->n_dst, (int64_t)nlev * nfields, (dst_type & MPG_TYPE_F32) ? 4 : 8, dst_level_stride, &ld);
   if (rc) return rc;
   return mpg_k_apply_masked(h, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, ld, opts, (hipStream_t)hip_stream);
+}
+
+// ---- its adjoint: the scaled gradient h into the caller's workspace, then the transposed gather with the select (k_transpose_masked.hip) ----
+int mpg_regrid_masked_transpose_dev(mpg_handle h, const void *g_dev, int g_type, int64_t g_level_stride, const void *src_dev, int src_type,
+                                    int src_layout, int nlev, int nfields, void *dst_dev, int dst_type, const mpg_mask_opts *opts, double *work_dev,
+                                    void *hip_stream) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h, "mpg_regrid_masked_transpose: NULL handle");
+  MPG_ARG(opts, "mpg_regrid_masked_transpose: NULL options");
+  MPG_ARG(g_dev && src_dev && dst_dev && work_dev, "mpg_regrid_masked_transpose: NULL argument");
+  MPG_ARG(nlev >= 1 && nfields >= 1, "mpg_regrid_masked_transpose: nlev and nfields must be >= 1");
+  MPG_ARG(src_layout == MPG_LAYOUT_CELL_FAST || src_layout == MPG_LAYOUT_LEV_FAST, "mpg_regrid_masked_transpose: bad src_layout");
+  MPG_ARG(g_type >= 0 && g_type <= 3 && src_type >= 0 && src_type <= 3 && dst_type >= 0 && dst_type <= 3,
+          "mpg_regrid_masked_transpose: g_type / src_type / dst_type must be MPG_TYPE_F64 or MPG_TYPE_F32");
+  if ((g_type | src_type | dst_type) & MPG_TYPE_BE) {
+    mpg_set_error("mpg_regrid_masked_transpose: big-endian values (MPG_TYPE_BE) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (h->n_pole > 0) {
+    mpg_set_error("mpg_regrid_masked_transpose: handles with pole-cap terms (periodic Grid -> Grid) are not supported");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  MPG_ARG((opts->flags & ~(MPG_MISSING_NAN | MPG_MISSING_VALUE)) == 0, "mpg_regrid_masked_transpose: unknown flag bits");
+  MPG_ARG(opts->min_valid_frac >= 0.0 && opts->min_valid_frac <= 1.0, "mpg_regrid_masked_transpose: min_valid_frac must lie in [0, 1]");   // (false for NaN)
+  MPG_ARG(!(opts->flags & MPG_MISSING_VALUE) || opts->missing_value == opts->missing_value, "mpg_regrid_masked_transpose: MPG_MISSING_VALUE with a NaN missing_value (use MPG_MISSING_NAN)");
+  const int64_t nplanes = (int64_t)nlev * nfields;
+  const int gsz = (g_type & MPG_TYPE_F32) ? 4 : 8;
+  int64_t ld;   // the gradient's level stride, checked as a destination stride is
+  int rc = dst_stride("mpg_regrid_masked_transpose: gradient", h->n_dst, nplanes, gsz, g_level_stride, &ld);
+  if (rc) return rc;
+  MPG_ARG(h->n_dst == 0 || nplanes <= (INT64_MAX / 8) / h->n_dst, "mpg_regrid_masked_transpose: the workspace cannot be addressed");
+  MPG_ARG(h->n_src == 0 || nplanes <= (INT64_MAX / 8) / h->n_src, "mpg_regrid_masked_transpose: the source cannot be addressed");
+  // the workspace is written while g and src are read and before dst is: it may overlap none of them
+  auto overlaps = [&](const void *p, int64_t bytes) {
+    const uintptr_t a = (uintptr_t)work_dev, b = a + (uintptr_t)(nplanes * h->n_dst * 8), c = (uintptr_t)p, d = c + (uintptr_t)bytes;
+    return p == (const void *)work_dev || (a < d && c < b);
+  };
+  MPG_ARG(!overlaps(g_dev, ((nplanes - 1) * ld + h->n_dst) * gsz) && !overlaps(src_dev, nplanes * h->n_src * ((src_type & MPG_TYPE_F32) ? 4 : 8)) &&
+              !overlaps(dst_dev, nplanes * h->n_src * ((dst_type & MPG_TYPE_F32) ? 4 : 8)),
+          "mpg_regrid_masked_transpose: work_dev must not alias g_dev, src_dev or dst_dev");
+  return mpg_k_transpose_masked(h, g_dev, g_type, ld, src_dev, src_type, src_layout, nlev, nfields, dst_dev, dst_type, opts, work_dev,
+                                (hipStream_t)hip_stream);
 }
 
 int mpg_handle_transpose_stats(mpg_handle h, int64_t *n_referenced, int64_t *max_per_source) {

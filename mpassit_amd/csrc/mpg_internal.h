@@ -471,6 +471,10 @@ int mpg_k_transpose_pole(mpg_handle_s *h, const void *src, int src_type, int64_t
 // k_apply_masked.hip: the masked Regrid (include/mpassit_amd.h mpg_regrid_masked_dev; arguments checked by the API entry point); ld as above
 int mpg_k_apply_masked(mpg_handle_s *h, const void *src, int src_type, int layout, int nlev, int nfields, void *dst, int dst_type, int64_t ld,
                        const mpg_mask_opts *opts, hipStream_t s);
+// k_transpose_masked.hip: its adjoint (include/mpassit_amd.h mpg_regrid_masked_transpose_dev; arguments checked by the API entry point);
+// ldg: the level stride of g in elements; work: [nfields][nlev][n_dst] float64, dense.  Builds the handle's transposed index if needed.
+int mpg_k_transpose_masked(mpg_handle_s *h, const void *g, int g_type, int64_t ldg, const void *src, int src_type, int layout, int nlev, int nfields,
+                           void *dst, int dst_type, const mpg_mask_opts *opts, double *work, hipStream_t s);
 // k_store_to_mesh.hip: Grid -> Mesh Store (bilinear: 4 slots, nearest: 1) of the grid's `stagger` points onto the mesh's cells / vertices
 int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s);
 // k_store_periodic_to_mesh.hip: bilinear Store of a grid periodic in i (CENTER points, the i-wrap and the pole caps) onto the mesh's cells /

@@ -343,6 +343,16 @@ module mpg
       type(mpg_mask_opts), intent(in) :: opts
       integer(c_int) :: rc
     end function mpg_regrid_masked_dev
+    ! its adjoint: the gradient with respect to the source from the gradient with respect to the result (work_dev: float64 workspace)
+    function mpg_regrid_masked_transpose_dev(rh, g_dev, g_type, g_level_stride, src_dev, src_type, src_layout, nlev, nfields, dst_dev, &
+                                             dst_type, opts, work_dev, hip_stream) bind(C, name="mpg_regrid_masked_transpose_dev") result(rc)
+      import :: c_int, c_int64_t, c_ptr, mpg_mask_opts
+      type(c_ptr), value :: rh, g_dev, src_dev, dst_dev, work_dev, hip_stream
+      integer(c_int), value :: g_type, src_type, src_layout, nlev, nfields, dst_type
+      integer(c_int64_t), value :: g_level_stride
+      type(mpg_mask_opts), intent(in) :: opts
+      integer(c_int) :: rc
+    end function mpg_regrid_masked_transpose_dev
     function mpg_regrid_bundle_typed_pitched_dev(rh, nfields, src, src_f32, src_layout, nlev, dst, dst_f32, scale, offsets, &
                                                  dst_level_stride, stream) bind(C, name="mpg_regrid_bundle_typed_pitched_dev") result(rc)
       import :: c_int, c_int64_t, c_double, c_ptr

@@ -28,7 +28,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
            "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights",
-           "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd"]
+           "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd",
+           "regrid_masked_autograd"]
 
 
 def _f64(a):
@@ -98,6 +99,36 @@ def _level_stride(out, lead, ny, nx, who):
     if ld < ny * nx:
         raise ValueError("%s: out's level stride %d is below the plane size %d" % (who, ld, ny * nx))
     return ld
+
+
+def _parse_missing(who, src, missing, src_mask, n_src):
+    """(flags, missing_value, mask pointer or None) of mpg_mask_opts from regrid_masked's `missing` ("nan", a number, a tuple of both, or
+    None) and `src_mask` (bool / uint8 CUDA tensor of n_src).  With a float32 `src` the number is rounded to float32 first, so that a
+    file's sentinel compares equal.  One text for the masked Regrid and its adjoint: both must take the same sources for missing."""
+    import torch
+    flags, mv = 0, 0.0
+    for item in (missing if isinstance(missing, (tuple, list)) else (missing,)):
+        if item is None:
+            continue
+        if isinstance(item, str):
+            if item.lower() != "nan":
+                raise ValueError("%s: missing must be \"nan\", a number, a tuple of both, or None" % who)
+            flags |= L.MISSING_NAN
+        elif np.isnan(float(item)):
+            flags |= L.MISSING_NAN
+        else:
+            if flags & L.MISSING_VALUE:
+                raise ValueError("%s: one numeric missing value at most" % who)
+            flags |= L.MISSING_VALUE
+            mv = float(np.float32(item)) if src.dtype == torch.float32 else float(item)
+    mask_ptr = None
+    if src_mask is not None:
+        if not (_is_torch(src_mask) and src_mask.is_cuda and src_mask.is_contiguous() and src_mask.dtype in (torch.bool, torch.uint8)):
+            raise ValueError("%s: src_mask must be a contiguous bool/uint8 CUDA tensor" % who)
+        if src_mask.numel() != n_src:
+            raise ValueError("src_mask has %d elements, handle expects %d" % (src_mask.numel(), n_src))
+        mask_ptr = src_mask.data_ptr()
+    return flags, mv, mask_ptr
 
 
 class Mesh:
@@ -623,28 +654,7 @@ class RouteHandle:
             raise ValueError("regrid_masked needs a contiguous float32/float64 CUDA tensor")
         if src.numel() != nfields * nlev * self.n_src:
             raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
-        flags, mv = 0, 0.0
-        for item in (missing if isinstance(missing, (tuple, list)) else (missing,)):
-            if item is None:
-                continue
-            if isinstance(item, str):
-                if item.lower() != "nan":
-                    raise ValueError("regrid_masked: missing must be \"nan\", a number, a tuple of both, or None")
-                flags |= L.MISSING_NAN
-            elif np.isnan(float(item)):
-                flags |= L.MISSING_NAN
-            else:
-                if flags & L.MISSING_VALUE:
-                    raise ValueError("regrid_masked: one numeric missing value at most")
-                flags |= L.MISSING_VALUE
-                mv = float(np.float32(item)) if src.dtype == torch.float32 else float(item)
-        mask_ptr = None
-        if src_mask is not None:
-            if not (_is_torch(src_mask) and src_mask.is_cuda and src_mask.is_contiguous() and src_mask.dtype in (torch.bool, torch.uint8)):
-                raise ValueError("regrid_masked: src_mask must be a contiguous bool/uint8 CUDA tensor")
-            if src_mask.numel() != self.n_src:
-                raise ValueError("src_mask has %d elements, handle expects %d" % (src_mask.numel(), self.n_src))
-            mask_ptr = src_mask.data_ptr()
+        flags, mv, mask_ptr = _parse_missing("regrid_masked", src, missing, src_mask, self.n_src)
         out_dtype = out_dtype or src.dtype
         if out is None:
             out = torch.empty((nfields, nlev, self.ny_dst, self.nx_dst), dtype=out_dtype, device=src.device)
@@ -657,6 +667,54 @@ class RouteHandle:
         _account_regrid(self, nlev, nfields, src.element_size(), out.element_size())
         check(L.regrid_masked_dev(self._h, src.data_ptr(), int(src.dtype == torch.float32), int(layout), int(nlev), int(nfields),
                                   out.data_ptr(), int(out.dtype == torch.float32), ld, C.byref(opts), torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def regrid_masked_transpose(self, grad, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, missing="nan", src_mask=None, min_valid_frac=0.5,
+                                scale=1.0, out_dtype=None, out=None, work=None):
+        """mpg_regrid_masked_transpose_dev: the adjoint of regrid_masked -- the gradient with respect to `src` from `grad`, the gradient
+        with respect to regrid_masked's result.  `src`, `layout`, `missing`, `src_mask`, `min_valid_frac` and `scale` are the forward
+        call's (missing is parsed as regrid_masked parses it); `src` is read only to decide which elements are valid.  The gradient
+        at a missing or statically masked source is exactly 0 (never NaN), and `grad` at filled outputs -- undefined and unmapped points
+        -- is ignored, NaN included.  With nothing missing and scale 1 the result equals regrid_transpose(grad) bit for bit on a
+        handle that maps every point.
+        grad: [nfields][nlev][ny_dst][nx_dst] float32 / float64 CUDA tensor, contiguous or a plane-pitched view as empty_pitched makes.
+        work: float64 CUDA workspace of nfields * nlev * n_dst elements (allocated when None); on return it holds the scaled gradient
+        grad * scale * Wt / Wv, 0 at filled outputs.  Returns nfields slabs of nlev * n_src values of out_dtype (default: src's) in
+        `layout`: (nfields, nlev, n_src) for LAYOUT_CELL_FAST, (nfields, n_src, nlev) for LAYOUT_LEV_FAST."""
+        import torch
+        who = "regrid_masked_transpose"
+        if not (_is_torch(src) and src.is_cuda and src.is_contiguous() and src.dtype in (torch.float32, torch.float64)):
+            raise ValueError(who + " needs a contiguous float32/float64 CUDA tensor as src")
+        if src.numel() != nfields * nlev * self.n_src:
+            raise ValueError("source has %d elements, handle expects %d" % (src.numel(), nfields * nlev * self.n_src))
+        if not (_is_torch(grad) and grad.is_cuda and grad.dtype in (torch.float32, torch.float64)):
+            raise ValueError(who + " needs a float32/float64 CUDA tensor as grad")
+        if grad.is_contiguous():
+            if grad.numel() != nfields * nlev * self.n_dst:
+                raise ValueError("grad has %d elements, handle expects %d" % (grad.numel(), nfields * nlev * self.n_dst))
+            ld = 0
+        else:
+            lead = (nfields, nlev) if grad.dim() == 4 else (nlev,)
+            if grad.dim() not in (3, 4) or (grad.dim() == 3 and nfields != 1):
+                raise ValueError(who + ": a strided grad must be (nfields, nlev, ny, nx) or (nlev, ny, nx) with plane-pitched levels")
+            ld = _level_stride(grad, lead, self.ny_dst, self.nx_dst, who)
+        flags, mv, mask_ptr = _parse_missing(who, src, missing, src_mask, self.n_src)
+        out_dtype = out_dtype or src.dtype
+        if isinstance(out_dtype, np.dtype) or out_dtype in (np.float32, np.float64):
+            out_dtype = torch.float32 if np.dtype(out_dtype) == np.float32 else torch.float64
+        shape = (nfields, nlev, self.n_src) if layout == LAYOUT_CELL_FAST else (nfields, self.n_src, nlev)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=src.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64) and out.numel() == nfields * nlev * self.n_src):
+            raise ValueError(who + ": out must be a contiguous float32/float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_src))
+        if work is None:
+            work = torch.empty((nfields, nlev, self.n_dst), dtype=torch.float64, device=src.device)
+        elif not (_is_torch(work) and work.is_cuda and work.is_contiguous() and work.dtype == torch.float64 and work.numel() == nfields * nlev * self.n_dst):
+            raise ValueError(who + ": work must be a contiguous float64 CUDA tensor of %d elements" % (nfields * nlev * self.n_dst))
+        opts = L.MaskOpts(flags, mv, mask_ptr, float(min_valid_frac), 0.0, float(scale), 0.0)
+        check(L.regrid_masked_transpose_dev(self._h, grad.data_ptr(), int(grad.dtype == torch.float32), ld, src.data_ptr(),
+                                            int(src.dtype == torch.float32), int(layout), int(nlev), int(nfields), out.data_ptr(),
+                                            int(out.dtype == torch.float32), C.byref(opts), work.data_ptr(), torch.cuda.current_stream().cuda_stream))
         return out
 
     @classmethod
@@ -788,6 +846,40 @@ def regrid_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST):
     """rh.regrid_typed(src) (float32 or float64 CUDA tensor, scale 1, offset 0) as a differentiable torch op: the gradient with
     respect to src is rh.regrid_transpose of the incoming gradient, in src's layout and dtype."""
     return RegridFunction.apply(src, rh, nlev, nfields, layout)
+
+
+if _torch is not None:
+    class RegridMaskedFunction(_torch.autograd.Function):
+        """regrid_masked with a gradient: forward is regrid_masked (scale 1, offset 0) in src's dtype, backward is
+        regrid_masked_transpose of the same handle, source and options into src's layout and dtype.  Use regrid_masked_autograd()."""
+
+        @staticmethod
+        def forward(ctx, src, rh, nlev, nfields, layout, missing, src_mask, min_valid_frac, fill_value):
+            ctx.rh, ctx.nlev, ctx.nfields, ctx.layout = rh, nlev, nfields, layout
+            ctx.missing, ctx.src_mask, ctx.min_valid_frac = missing, src_mask, min_valid_frac
+            ctx.src_shape = src.shape
+            data = src.detach().contiguous()
+            ctx.save_for_backward(data)         # read again only to decide which elements were valid
+            return rh.regrid_masked(data, nlev=nlev, nfields=nfields, layout=layout, missing=missing, src_mask=src_mask,
+                                    min_valid_frac=min_valid_frac, fill_value=fill_value, out_dtype=src.dtype)
+
+        @staticmethod
+        def backward(ctx, grad):
+            data, = ctx.saved_tensors
+            g = ctx.rh.regrid_masked_transpose(grad.contiguous(), data, nlev=ctx.nlev, nfields=ctx.nfields, layout=ctx.layout, missing=ctx.missing,
+                                               src_mask=ctx.src_mask, min_valid_frac=ctx.min_valid_frac, out_dtype=data.dtype)
+            return (g.reshape(ctx.src_shape),) + (None,) * 8
+
+
+def regrid_masked_autograd(rh, src, nlev=1, nfields=1, layout=LAYOUT_CELL_FAST, missing="nan", src_mask=None, min_valid_frac=0.5,
+                           fill_value=float("nan")):
+    """rh.regrid_masked(src) (float32 or float64 CUDA tensor, scale 1, offset 0) as a differentiable torch op; `layout`, `missing`,
+    `src_mask`, `min_valid_frac` and `fill_value` as regrid_masked takes them.  The gradient with respect to src is
+    rh.regrid_masked_transpose of the incoming gradient, in src's layout and dtype: the exact derivative at every valid source element.
+    The gradient at a missing or statically masked source is 0, not NaN (such an element never entered the result), and the incoming
+    gradient at filled outputs -- undefined and unmapped points, whose value is the constant fill_value -- is ignored, a NaN there
+    included.  The first backward on a handle builds its transposed index."""
+    return RegridMaskedFunction.apply(src, rh, nlev, nfields, layout, missing, src_mask, min_valid_frac, fill_value)
 
 
 if _torch is not None:
