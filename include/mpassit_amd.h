@@ -965,6 +965,59 @@ int mpg_handle_compose(mpg_handle outer, mpg_handle inner, mpg_handle *out);
 int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle inner, int nplanes, const double *inner_m_dev,
                             double *m_dev, void *hip_stream);
 
+/* ---- extrapolation: the unmapped rows of a handle filled from the nearest source points ---------------------------------------------------
+ * Every Store maps a destination point only where the source geometry covers it; elsewhere the handle holds idx = -1 or an empty row and
+ * every Regrid writes +0.0: the outermost U columns and V rows of the destagger handles, the grid points outside a limited-area mesh, the
+ * rim of a mesh under a regional analysis, the cap points of MPG_POLEMETHOD_NONE.  mpg_handle_extrapolate is ESMF_FieldRegridStore's
+ * extrapMethod (with extrapNumSrcPnts and extrapDistExponent) as a call of its own: it returns an ordinary handle whose unmapped rows are
+ * filled, which every consumer takes; a host that extrapolates its Stores once pays nothing per Regrid.
+ *
+ * Point sets (mpg_points): exactly one of mesh / grid is non-NULL.  Sources: a mesh's cells (MPG_MESHLOC_ELEMENT, searched through the
+ *   mesh's site BVH built whole) or any stagger of any grid (searched through that stagger's point pyramid).  Destinations: any stagger of
+ *   a grid, or a mesh's cells, vertices or edges.  One entry point serves Mesh -> Grid, Mesh -> Mesh, Grid -> Mesh and Grid -> Grid.
+ * Unmapped row: of a fixed handle, slot 0's index < 0; of a CSR handle, an empty row.  Every other row is copied verbatim.
+ * Neighbours of an unmapped destination point p: the candidates are all source points; d2(p, c) is dist2_nofma of the stored unit
+ *   vectors, ((dx*dx + dy*dy) + dz*dz) in float64 without contraction (mpg_mesh_get_xyz / mpg_grid_get_xyz export their bits).  The row takes
+ *   the K = min(N, n_src) smallest candidates in lexicographic (d2, id) order, N = 1 for MPG_EXTRAPMETHOD_NEAREST_STOD; id is the handle's
+ *   source index: the cell id, or j * snx + i.  Ties go to the lower id, at every rank including the last.
+ * MPG_EXTRAPMETHOD_NEAREST_STOD: one entry (c0, 1.0).
+ * MPG_EXTRAPMETHOD_NEAREST_IDAVG: if d2_0 == 0.0, one entry (c0, 1.0).  Otherwise, for i = 0 .. K - 1 in that order: r_i = d2_0 / d2_i,
+ *   t_i = r_i when e == 2.0, else pow(r_i, 0.5 * e); S = ((t_0 + t_1) + ...) from left to right; w_i = t_i / S.  Every operation is rounded
+ *   on its own (fp contract(off)).  This is ESMF's (1/d^e) / sum(1/d^e) with the nearest distance divided out: nothing overflows, and a
+ *   far neighbour may underflow to weight 0.  The entries are stored in ascending (d2, id) order, which is the Regrid's summation order.
+ *   A contract by identity with the numpy mirror target_grid.extrapolate_rows for e == 2.0; for other exponents up to the device pow.
+ * Output: a new handle with the input's n_src, n_dst, nx_dst, ny_dst and method.  It is not cached and owns its arrays: pair it with
+ *   mpg_handle_release; rh may be released right after the call.  It carries no dst_frac.  mpg_handle_store_ms is the GPU time of the call;
+ *   mpg_handle_store_stats [1] is the number of rows filled, [2] is K.
+ *   Fixed output: a fixed input of S slots stays fixed when every new row fits: STOD always, IDAVG when N <= S.  A new row puts its
+ *   entries in slots 0 .. k - 1; every remaining slot repeats entry 0's id with weight +0.0.  A nearest handle without a weight array
+ *   stays without one.  (This keeps a filled bilinear Mesh -> Grid handle on the staged kernels.)
+ *   CSR output: otherwise.  A mapped row of a fixed input becomes its S slots in slot order with their weights (a slot without an index is
+ *   dropped; a nearest handle has weight 1.0); a mapped row of a CSR input is its entries in stored order.  The longest row is recorded.
+ *   Nothing unmapped is success: a copy of the pattern.  A source set without points fills nothing.
+ * Determinism: the same bytes from run to run; no floating-point atomics.
+ * Blocking: the call allocates, reads the count of unmapped rows back, and drains the Store worker first (it may build a grid's pyramid
+ *   or a mesh's BVH).  It orders itself after whatever produced rh, as mpg_handle_get_csr does.
+ * Refusals, each with a message that names mpg_handle_extrapolate and the way out.  MPG_ERR_INVALID_ARG: a NULL argument; both or neither
+ *   of mesh / grid set in a point set; an unknown method; N outside 1..MPG_EXTRAP_MAX_PNTS; e not finite or <= 0; rh's n_src differs from
+ *   the source set's size (both numbers are printed; a node-located handle fails here); rh's n_dst, nx_dst or ny_dst differ from the
+ *   destination set (both are printed); a source mesh location other than ELEMENT; a destination MPG_MESHLOC_EDGE on a mesh without edges;
+ *   a stagger without coordinates.  MPG_ERR_UNSUPPORTED: a handle with pole terms (mpg_handle_pole_count > 0); a localized or rebased
+ *   handle; a source mesh that carries a source window.  MPG_ERR_OVERFLOW: a CSR output of more than 2^31 - 2 entries.  A failed
+ *   allocation returns its error and leaks nothing. */
+enum { MPG_EXTRAPMETHOD_NEAREST_STOD = 1, MPG_EXTRAPMETHOD_NEAREST_IDAVG = 2 };
+#define MPG_EXTRAP_MAX_PNTS 8
+typedef struct mpg_points {      /* a point set: exactly one of mesh / grid is non-NULL */
+  mpg_mesh mesh; int meshloc;    /* MPG_MESHLOC_* */
+  mpg_grid grid; int staggerloc; /* MPG_STAGGERLOC_* */
+} mpg_points;
+typedef struct mpg_extrap_opts {
+  int method;            /* MPG_EXTRAPMETHOD_* */
+  int num_src_pnts;      /* IDAVG: N in 1..MPG_EXTRAP_MAX_PNTS (ESMF's default 8); ignored for STOD */
+  double dist_exponent;  /* IDAVG: e, finite and > 0 (ESMF's default 2.0); ignored for STOD */
+} mpg_extrap_opts;
+int mpg_handle_extrapolate(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts, mpg_handle *out);
+
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the
@@ -1053,6 +1106,10 @@ int mpg_handle_pole_count(mpg_handle rh, int64_t *n_points, int *row_len);
 int mpg_handle_get_pole(mpg_handle rh, int32_t *dst_id_host, int32_t *src_row_start_host, double *w_pole_host);
 /* dual (Delaunay) triangles of a mesh: tri_host [nVertices][3], 0-based cell ids or -1 */
 int mpg_mesh_get_triangles(mpg_mesh mesh, int32_t *tri_host);
+/* the stored unit vectors of a point set, xyz_host [3][n] (x, y, z planes): the bits every search of this library uses (its sin and cos
+ * are not the host's).  mesh: n of MPG_MESHLOC_ELEMENT / NODE / EDGE; grid: n = snx * sny of the stagger, j * snx + i */
+int mpg_mesh_get_xyz(mpg_mesh mesh, int meshloc, double *xyz_host);     /* [3][n]: the stored unit vectors */
+int mpg_grid_get_xyz(mpg_grid grid, int staggerloc, double *xyz_host);  /* [3][snx*sny] */
 
 /* Multi-GPU (ESMF's per-Regrid source exchange): sorted unique source ids the handle
  * references.  Call with ids_host == NULL to get the count.  mpg_handle_localize rewrites the handle's

@@ -36,6 +36,7 @@ SYMBOLS = [
     "mpg_handle_compose", "mpg_compose_weights_dev",
     "mpg_rotate_winds_transpose_dev", "mpg_wind_destagger_transpose_dev",
     "mpg_regrid_masked_transpose_dev",
+    "mpg_handle_extrapolate", "mpg_mesh_get_xyz", "mpg_grid_get_xyz",
 ]
 
 MPG_SUCCESS = 0
@@ -51,6 +52,9 @@ MPG_NORM_DSTAREA, MPG_NORM_FRACAREA = 0, 1
 NORM_DSTAREA, NORM_FRACAREA = MPG_NORM_DSTAREA, MPG_NORM_FRACAREA
 MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG = 0, 1
 POLEMETHOD_NONE, POLEMETHOD_ALLAVG = MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG
+MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG = 1, 2
+EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG = MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG
+EXTRAP_MAX_PNTS = 8
 
 
 class MaskOpts(C.Structure):
@@ -393,6 +397,46 @@ def compose_weights_dev(*args):
     if "compose_weights" not in _to_mesh_fns:
         _to_mesh_fns["compose_weights"] = _COMPOSE_WEIGHTS_PROTO(("mpg_compose_weights_dev", load()))
     return _to_mesh_fns["compose_weights"](*args)
+
+
+# Extrapolation, bound the same way.
+#   mpg_handle_extrapolate(rh, src, dst, opts, out)
+#   mpg_mesh_get_xyz(mesh, meshloc, xyz_host)
+#   mpg_grid_get_xyz(grid, staggerloc, xyz_host)
+class Points(C.Structure):
+    """mpg_points of include/mpassit_amd.h: exactly one of mesh / grid is set."""
+    _fields_ = [("mesh", C.c_void_p), ("meshloc", C.c_int), ("grid", C.c_void_p), ("staggerloc", C.c_int)]
+
+
+class ExtrapOpts(C.Structure):
+    """mpg_extrap_opts of include/mpassit_amd.h."""
+    _fields_ = [("method", C.c_int), ("num_src_pnts", C.c_int), ("dist_exponent", C.c_double)]
+
+
+_HANDLE_EXTRAPOLATE_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Points), C.POINTER(Points), C.POINTER(ExtrapOpts), C.c_void_p)
+_MESH_GET_XYZ_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p)
+_GRID_GET_XYZ_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p)
+
+
+def handle_extrapolate(*args):
+    """The typed binding of mpg_handle_extrapolate; returns the call's status code."""
+    if "handle_extrapolate" not in _to_mesh_fns:
+        _to_mesh_fns["handle_extrapolate"] = _HANDLE_EXTRAPOLATE_PROTO(("mpg_handle_extrapolate", load()))
+    return _to_mesh_fns["handle_extrapolate"](*args)
+
+
+def mesh_get_xyz(*args):
+    """The typed binding of mpg_mesh_get_xyz; returns the call's status code."""
+    if "mesh_get_xyz" not in _to_mesh_fns:
+        _to_mesh_fns["mesh_get_xyz"] = _MESH_GET_XYZ_PROTO(("mpg_mesh_get_xyz", load()))
+    return _to_mesh_fns["mesh_get_xyz"](*args)
+
+
+def grid_get_xyz(*args):
+    """The typed binding of mpg_grid_get_xyz; returns the call's status code."""
+    if "grid_get_xyz" not in _to_mesh_fns:
+        _to_mesh_fns["grid_get_xyz"] = _GRID_GET_XYZ_PROTO(("mpg_grid_get_xyz", load()))
+    return _to_mesh_fns["grid_get_xyz"](*args)
 
 
 _lib = None

@@ -7,6 +7,7 @@
 #include <string.h>
 #include <time.h>
 
+#include <cmath>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -128,7 +129,7 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -452,7 +453,38 @@ int mpg_mesh_get_triangles(mpg_mesh m, int32_t *tri_host) {
   return MPG_SUCCESS;
 }
 
+// the stored unit vectors of a point set, [3][n] on the host: the bits every search of this library uses
+static int get_xyz(const char *who, const PointSet &pts, int64_t n, double *xyz_host) {
+  if (pts.n != n || n == 0) {
+    if (n == 0) return MPG_SUCCESS;
+    mpg_set_error("%s: the location has no coordinates", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  MPG_HIP(hipMemcpy(xyz_host, pts.x.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+  MPG_HIP(hipMemcpy(xyz_host + n, pts.y.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+  MPG_HIP(hipMemcpy(xyz_host + 2 * n, pts.z.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return MPG_SUCCESS;
+}
+
+int mpg_mesh_get_xyz(mpg_mesh m, int meshloc, double *xyz_host) {
+  MPG_CHECK_INIT();
+  MPG_ARG(m && xyz_host, "mpg_mesh_get_xyz: NULL argument");
+  MPG_ARG(meshloc == MPG_MESHLOC_ELEMENT || meshloc == MPG_MESHLOC_NODE || meshloc == MPG_MESHLOC_EDGE, "mpg_mesh_get_xyz: bad mesh location");
+  MPG_ARG(meshloc != MPG_MESHLOC_NODE || m->vwn == m->nVertices,
+          "mpg_mesh_get_xyz: the vertices of a mesh cut to a grid (mpg_mesh_create_window) are not all resident");
+  const PointSet &pts = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
+  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+  return get_xyz("mpg_mesh_get_xyz", pts, n, xyz_host);
+}
+
 // ---- grid -----------------------------------------------------------------------------------------
+int mpg_grid_get_xyz(mpg_grid g, int staggerloc, double *xyz_host) {
+  MPG_CHECK_INIT();
+  MPG_ARG(g && xyz_host, "mpg_grid_get_xyz: NULL argument");
+  MPG_ARG(staggerloc >= 0 && staggerloc < 4, "mpg_grid_get_xyz: bad stagger location");
+  return get_xyz("mpg_grid_get_xyz", g->pts[staggerloc], (int64_t)g->snx[staggerloc] * g->sny[staggerloc], xyz_host);
+}
+
 int mpg_grid_create(int nx, int ny, int periodic_i, const double *lon_center, const double *lat_center, const double *lon_corner,
                     const double *lat_corner, const double *lon_edge1, const double *lat_edge1, const double *lon_edge2,
                     const double *lat_edge2, mpg_grid *out) {
@@ -1577,6 +1609,139 @@ int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle in
     return MPG_SUCCESS;
   }
   return mpg_k_compose_values(composed, outer, inner, nplanes, inner_m_dev, m_dev, (hipStream_t)hip_stream);
+}
+
+// ---- extrapolation: the unmapped rows of a handle filled from the nearest source points (k_extrapolate.hip) ---------------------------------
+// a point set of the call: how many points, their row shape as a handle records it, and where they are
+static int ex_points(const char *role, const mpg_points *p, bool source, int64_t *n, int *nx, int *ny, const PointSet **pts) {
+  if ((p->mesh != nullptr) == (p->grid != nullptr)) {
+    mpg_set_error("mpg_handle_extrapolate: exactly one of mesh / grid must be set in the %s point set (%s are)", role, p->mesh ? "both" : "neither");
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (p->mesh) {
+    mpg_mesh_s *m = p->mesh;
+    const int loc = p->meshloc;
+    if (source && loc != MPG_MESHLOC_ELEMENT) {
+      mpg_set_error("mpg_handle_extrapolate: a source mesh is searched through its cells only (MPG_MESHLOC_ELEMENT, not location %d): "
+                    "node-located sources are not served", loc);
+      return MPG_ERR_INVALID_ARG;
+    }
+    if (loc != MPG_MESHLOC_ELEMENT && loc != MPG_MESHLOC_NODE && loc != MPG_MESHLOC_EDGE) {
+      mpg_set_error("mpg_handle_extrapolate: bad mesh location %d in the %s point set", loc, role);
+      return MPG_ERR_INVALID_ARG;
+    }
+    if (loc == MPG_MESHLOC_EDGE && m->edge.n == 0) {
+      mpg_set_error("mpg_handle_extrapolate: the %s mesh has no edges: call mpg_mesh_set_edges first", role);
+      return MPG_ERR_INVALID_ARG;
+    }
+    if (loc == MPG_MESHLOC_NODE && m->vwn != m->nVertices) {
+      mpg_set_error("mpg_handle_extrapolate: the vertices of a mesh cut to a grid (mpg_mesh_create_window) are not all resident: use the whole mesh");
+      return MPG_ERR_UNSUPPORTED;
+    }
+    *pts = loc == MPG_MESHLOC_EDGE ? &m->edge : loc == MPG_MESHLOC_ELEMENT ? &m->cell : &m->vert;
+    *n = loc == MPG_MESHLOC_EDGE ? m->edge.n : loc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+    *nx = (int)*n;
+    *ny = 1;
+    return MPG_SUCCESS;
+  }
+  mpg_grid_s *g = p->grid;
+  const int st = p->staggerloc;
+  if (st < 0 || st >= 4) {
+    mpg_set_error("mpg_handle_extrapolate: bad stagger location %d in the %s point set", st, role);
+    return MPG_ERR_INVALID_ARG;
+  }
+  *nx = g->snx[st];
+  *ny = g->sny[st];
+  *n = (int64_t)*nx * *ny;
+  *pts = &g->pts[st];
+  if (g->pts[st].n != *n) {
+    mpg_set_error("mpg_handle_extrapolate: stagger %d of the %s grid has no coordinates: create the grid with them", st, role);
+    return MPG_ERR_INVALID_ARG;
+  }
+  return MPG_SUCCESS;
+}
+
+int mpg_handle_extrapolate(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(rh && src && dst && opts && out, "mpg_handle_extrapolate: NULL argument (rh, src, dst, opts and out are all mandatory)");
+  MPG_ARG(opts->method == MPG_EXTRAPMETHOD_NEAREST_STOD || opts->method == MPG_EXTRAPMETHOD_NEAREST_IDAVG,
+          "mpg_handle_extrapolate: unknown method: MPG_EXTRAPMETHOD_NEAREST_STOD or MPG_EXTRAPMETHOD_NEAREST_IDAVG");
+  const bool idavg = opts->method == MPG_EXTRAPMETHOD_NEAREST_IDAVG;
+  if (idavg && (opts->num_src_pnts < 1 || opts->num_src_pnts > MPG_EXTRAP_MAX_PNTS)) {
+    mpg_set_error("mpg_handle_extrapolate: num_src_pnts = %d is outside 1..%d (MPG_EXTRAP_MAX_PNTS)", opts->num_src_pnts, MPG_EXTRAP_MAX_PNTS);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (idavg && !(std::isfinite(opts->dist_exponent) && opts->dist_exponent > 0.0)) {
+    mpg_set_error("mpg_handle_extrapolate: dist_exponent = %g must be finite and > 0 (ESMF's default is 2.0)", opts->dist_exponent);
+    return MPG_ERR_INVALID_ARG;
+  }
+  int rc;
+  int64_t ns = 0, nd = 0;
+  int sx = 0, sy = 0, dx = 0, dy = 0;
+  const PointSet *sp = nullptr, *dp = nullptr;
+  if ((rc = ex_points("source", src, true, &ns, &sx, &sy, &sp)) || (rc = ex_points("destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
+  if (rh->n_pole > 0) {
+    mpg_set_error("mpg_handle_extrapolate: the handle has pole terms (mpg_handle_pole_count > 0), which an extrapolated copy cannot carry: "
+                  "store with MPG_POLEMETHOD_NONE, or fill from a non-periodic handle");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->localized) {
+    mpg_set_error("mpg_handle_extrapolate: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no "
+                  "longer source ids -- extrapolate first, re-index the result");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (mpg_handle_is_windowed(rh) || (src->mesh && src->mesh->win_count[MPG_MESHLOC_ELEMENT] >= 0)) {
+    mpg_set_error("mpg_handle_extrapolate: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
+                  "window-relative -- reset the window to the whole mesh first");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_src != ns) {
+    mpg_set_error("mpg_handle_extrapolate: the handle has n_src = %lld, the source point set has %lld points (a node-located handle has "
+                  "no source set here)", (long long)rh->n_src, (long long)ns);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (rh->n_dst != nd || rh->nx_dst != dx || rh->ny_dst != dy) {
+    mpg_set_error("mpg_handle_extrapolate: the handle has n_dst = %lld (%d x %d), the destination point set has %lld points (%d x %d)",
+                  (long long)rh->n_dst, rh->nx_dst, rh->ny_dst, (long long)nd, dx, dy);
+    return MPG_ERR_INVALID_ARG;
+  }
+  // The search builds the source's tree (a grid's point pyramid, a mesh's site BVH): a begun Store may be building the same one on the worker.
+  store_worker_drain();
+  // rh is finished: a Store waits for its build before it hands its handle out.  The build runs on the set-up stream, as
+  // mpg_handle_get_csr's copies follow whatever produced the handle.
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = rh->method;
+  h->n_src = rh->n_src;
+  h->n_dst = rh->n_dst;
+  h->nx_dst = rh->nx_dst;
+  h->ny_dst = rh->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("mpg_handle_extrapolate: hipEventCreate failed");
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_extrapolate(rh, src->mesh, src->grid, src->staggerloc, *dp, opts->method, opts->num_src_pnts, opts->dist_exponent, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("mpg_handle_extrapolate: %s", hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
 }
 
 // ---- masked Regrid: missing sources skipped, the valid ones renormalised, fill elsewhere (k_apply_masked.hip) --------------

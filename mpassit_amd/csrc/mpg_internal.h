@@ -511,6 +511,11 @@ int mpg_k_wind_reconstruct(mpg_handle_s *h, const double *m, int nout, const voi
 int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t s);
 int mpg_k_compose_values(mpg_handle_s *c, mpg_handle_s *a, mpg_handle_s *b, int nplanes, const double *bm, double *m, hipStream_t s);
 void mpg_set_compose_block_rows(int v);     // "compose_block_rows" knob (k_compose.hip)
+// k_extrapolate.hip: `out` (shape and method set by the caller, arrays empty) <- `in` with its unmapped rows filled from the nearest source
+// points: the cells of src_mesh (its site BVH, built whole) or the `src_stagger` points of src_grid (their point pyramid), exactly one set;
+// dst: the in->n_dst destination points.  Arguments checked by the API entry point; blocking: it allocates and reads counts back
+int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_grid, int src_stagger, const PointSet &dst, int method, int npnts,
+                      double e, mpg_handle_s *out, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

@@ -45,6 +45,20 @@ module mpg
     real(c_double) :: fill_value       !< what undefined points (unmapped ones included) get
     real(c_double) :: scale, offset    !< the writer's epilogue, defined points only
   end type mpg_mask_opts
+  !> mpg_handle_extrapolate (include/mpassit_amd.h): a point set -- exactly one of mesh / grid is not c_null_ptr -- and the options
+  integer(c_int), parameter :: MPG_EXTRAPMETHOD_NEAREST_STOD = 1, MPG_EXTRAPMETHOD_NEAREST_IDAVG = 2
+  integer(c_int), parameter :: MPG_EXTRAP_MAX_PNTS = 8
+  type, bind(C) :: mpg_points
+    type(c_ptr) :: mesh
+    integer(c_int) :: meshloc          !< MPG_MESHLOC_*
+    type(c_ptr) :: grid
+    integer(c_int) :: staggerloc       !< MPG_STAGGERLOC_*
+  end type mpg_points
+  type, bind(C) :: mpg_extrap_opts
+    integer(c_int) :: method           !< MPG_EXTRAPMETHOD_*
+    integer(c_int) :: num_src_pnts     !< IDAVG: 1 .. MPG_EXTRAP_MAX_PNTS (ESMF's default 8)
+    real(c_double) :: dist_exponent    !< IDAVG: finite and > 0 (ESMF's default 2.0)
+  end type mpg_extrap_opts
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -557,6 +571,28 @@ module mpg
       integer(c_int), value :: nplanes
       integer(c_int) :: rc
     end function mpg_compose_weights_dev
+    !> extrapolation: the unmapped rows of rh filled from the nearest source points, as a new handle (mpg_handle_release it); and the
+    !> stored unit vectors [3][n] of a mesh location / a grid stagger, the bits the searches use
+    function mpg_handle_extrapolate(rh, src, dst, opts, out) bind(C, name="mpg_handle_extrapolate") result(rc)
+      import :: c_int, c_ptr, mpg_points, mpg_extrap_opts
+      type(c_ptr), value :: rh
+      type(mpg_points), intent(in) :: src, dst
+      type(mpg_extrap_opts), intent(in) :: opts
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_extrapolate
+    function mpg_mesh_get_xyz(mesh, meshloc, xyz_host) bind(C, name="mpg_mesh_get_xyz") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: mesh, xyz_host
+      integer(c_int), value :: meshloc
+      integer(c_int) :: rc
+    end function mpg_mesh_get_xyz
+    function mpg_grid_get_xyz(grid, staggerloc, xyz_host) bind(C, name="mpg_grid_get_xyz") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: grid, xyz_host
+      integer(c_int), value :: staggerloc
+      integer(c_int) :: rc
+    end function mpg_grid_get_xyz
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

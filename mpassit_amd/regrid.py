@@ -16,7 +16,8 @@ import numpy as np
 from . import _lib as L
 from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, MESHLOC_EDGE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
-                   NORM_DSTAREA, NORM_FRACAREA, POLEMETHOD_NONE, POLEMETHOD_ALLAVG, check)
+                   NORM_DSTAREA, NORM_FRACAREA, POLEMETHOD_NONE, POLEMETHOD_ALLAVG, EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG,
+                   EXTRAP_MAX_PNTS, check)
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
            "regrid_store_to_mesh", "regrid_to_mesh_autograd", "regrid_store_conserve_to_mesh", "regrid_csr_to_mesh_autograd", "NORM_DSTAREA",
@@ -29,7 +30,7 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
            "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights",
            "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd",
-           "regrid_masked_autograd"]
+           "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS"]
 
 
 def _f64(a):
@@ -192,6 +193,13 @@ class Mesh:
         check(L.load().mpg_mesh_get_triangles(self._h, _ptr(tri)))
         return tri
 
+    def xyz(self, meshloc=MESHLOC_ELEMENT):
+        """mpg_mesh_get_xyz: the stored unit vectors of the cells, vertices or edges, [3][n] float64 -- the bits the searches use."""
+        n = {MESHLOC_ELEMENT: self.nCells, MESHLOC_NODE: self.nVertices, MESHLOC_EDGE: self.nEdges}[meshloc]
+        xyz = np.empty((3, n))
+        check(L.mesh_get_xyz(self._h, int(meshloc), _ptr(xyz)))
+        return xyz
+
     def destroy(self):
         if self._h:
             check(L.load().mpg_mesh_destroy(self._h))
@@ -292,6 +300,14 @@ class Grid:
         mf = np.empty(self.stagger_shape(staggerloc))
         check(L.load().mpg_grid_get_mapfac(self._h, C.c_int(staggerloc), _ptr(mf)))
         return mf
+
+    def xyz(self, staggerloc=STAGGERLOC_CENTER):
+        """mpg_grid_get_xyz: the stored unit vectors of a stagger's points, [3][snx * sny] float64 (point j * snx + i) -- the bits the
+        searches use."""
+        ny, nx = self.stagger_shape(staggerloc)
+        xyz = np.empty((3, ny * nx))
+        check(L.grid_get_xyz(self._h, int(staggerloc), _ptr(xyz)))
+        return xyz
 
     def stagger_shape(self, staggerloc):
         return {STAGGERLOC_CENTER: (self.ny, self.nx), STAGGERLOC_EDGE1: (self.ny, self.nx + 1),
@@ -1846,3 +1862,27 @@ def compose_weights(composed, outer, inner, m_inner):
     check(L.compose_weights_dev(composed._h, outer._h, inner._h, int(m_inner.shape[0]), m_inner.data_ptr(), m.data_ptr(),
                                 torch.cuda.current_stream().cuda_stream))
     return m
+
+
+# ---- extrapolation: the unmapped rows of a handle filled from the nearest source points -----------------------------------------------------
+def _points(obj, loc, who):
+    if isinstance(obj, Mesh):
+        return L.Points(mesh=obj._h, meshloc=int(MESHLOC_ELEMENT if loc is None else loc), grid=None, staggerloc=0)
+    if isinstance(obj, Grid):
+        return L.Points(mesh=None, meshloc=0, grid=obj._h, staggerloc=int(STAGGERLOC_CENTER if loc is None else loc))
+    raise ValueError("extrapolate: %s must be a Mesh or a Grid" % who)
+
+
+def extrapolate(rh, src, dst, method=EXTRAPMETHOD_NEAREST_STOD, num_src_pnts=8, dist_exponent=2.0, src_loc=None, dst_loc=None):
+    """mpg_handle_extrapolate (ESMF's extrapMethod / extrapNumSrcPnts / extrapDistExponent): a new RouteHandle of rh's shape whose unmapped
+    rows -- idx -1 in slot 0, or an empty CSR row -- are filled from the nearest points of `src`, every other row copied.  src / dst: the
+    Mesh or Grid objects rh was stored on; src_loc / dst_loc: a mesh location or a stagger (default MESHLOC_ELEMENT / STAGGERLOC_CENTER;
+    a source mesh is searched through its cells only).  EXTRAPMETHOD_NEAREST_STOD: the nearest source with weight 1.
+    EXTRAPMETHOD_NEAREST_IDAVG: the num_src_pnts (1..EXTRAP_MAX_PNTS) nearest, weighted by distance ** -dist_exponent and normalised.  A
+    fixed rh stays fixed when the new rows fit its slots (STOD; IDAVG with num_src_pnts <= nnz_per_row), otherwise the result is CSR.  The
+    bits of target_grid.extrapolate_rows fed with src.xyz() / dst.xyz().  Not cached: release() it; rh may be released."""
+    ps, pd = _points(src, src_loc, "src"), _points(dst, dst_loc, "dst")
+    opts = L.ExtrapOpts(method=int(method), num_src_pnts=int(num_src_pnts), dist_exponent=float(dist_exponent))
+    h = C.c_void_p()
+    check(L.handle_extrapolate(rh._h if rh is not None else None, C.byref(ps), C.byref(pd), C.byref(opts), C.byref(h)))
+    return RouteHandle(h)

@@ -396,6 +396,73 @@ def fixed_to_csr(idx, w=None):
     return rowptr, idx[keep].astype(np.int32), np.ascontiguousarray(val[keep])
 
 
+EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG = 1, 2
+
+
+def extrapolate_neighbours(src_xyz, dst_xyz, rows, K):
+    """The K nearest sources of the destination points `rows` by brute force -> (ids [n][K] int32, d2 [n][K]): per point a lexsort on
+    (d2, id) with d2 = (dx*dx + dy*dy) + dz*dz in float64, dist2_nofma's expression; ties go to the lower id at every rank.  (The sort
+    runs over the sources at or below the point's K-th smallest d2: every tie at the last rank is among them.)"""
+    src_xyz, dst_xyz = np.asarray(src_xyz, np.float64), np.asarray(dst_xyz, np.float64)
+    rows = np.asarray(rows, np.int64)
+    n_src = src_xyz.shape[1]
+    K = min(int(K), n_src)
+    ids, d2k = np.full((rows.size, K), -1, np.int32), np.zeros((rows.size, K))
+    if rows.size == 0 or K == 0:
+        return ids, d2k
+    step = max(1, (1 << 22) // n_src)
+    for a in range(0, rows.size, step):
+        p = dst_xyz[:, rows[a:a + step]]
+        dx, dy, dz = (p[k][:, None] - src_xyz[k][None, :] for k in range(3))
+        d2 = (dx * dx + dy * dy) + dz * dz
+        kth = np.partition(d2, K - 1, axis=1)[:, K - 1]
+        for u in range(d2.shape[0]):
+            cand = np.flatnonzero(d2[u] <= kth[u])
+            order = cand[np.lexsort((cand, d2[u][cand]))[:K]]
+            ids[a + u] = order
+            d2k[a + u] = d2[u][order]
+    return ids, d2k
+
+
+def extrapolate_weights(d2k, method=EXTRAPMETHOD_NEAREST_STOD, dist_exponent=2.0):
+    """The value rule of mpg_handle_extrapolate for rows of K ascending squared distances d2k [n][K] -> (rowlen [n] int32, w [n][K] with
+    0.0 behind a row's end).  STOD, K == 1 or d2_0 == 0: one entry of weight 1; else r_i = d2_0 / d2_i, t_i = r_i (e == 2) or
+    r_i ** (e / 2), S = ((t_0 + t_1) + ...) from left to right, w_i = t_i / S, every operation rounded on its own."""
+    d2k = np.asarray(d2k, np.float64)
+    n, K = d2k.shape
+    rowlen, w = np.zeros(n, np.int32), np.zeros((n, K))
+    if n == 0 or K == 0:
+        return rowlen, w
+    one = np.full(n, method != EXTRAPMETHOD_NEAREST_IDAVG) | (d2k[:, 0] == 0.0) | (K == 1)
+    rowlen[:] = np.where(one, 1, K)
+    w[:, 0] = 1.0
+    many = np.flatnonzero(~one)
+    if many.size:
+        r = d2k[many, :1] / d2k[many]
+        t = r if dist_exponent == 2.0 else np.power(r, 0.5 * dist_exponent)
+        S = t[:, 0].copy()
+        for i in range(1, K):
+            S = S + t[:, i]
+        w[many] = t / S[:, None]
+    return rowlen, w
+
+
+def extrapolate_rows(src_xyz, dst_xyz, unmapped, method=EXTRAPMETHOD_NEAREST_STOD, num_src_pnts=8, dist_exponent=2.0):
+    """The numpy mirror of mpg_handle_extrapolate's new rows, by brute force.  src_xyz [3][n_src], dst_xyz [3][n_dst]: the library's stored
+    unit vectors (Mesh.xyz / Grid.xyz); unmapped: the rows to fill (a bool mask of n_dst, or row numbers).  Per row, in ascending row order:
+    the K = min(N, n_src) nearest sources by a lexsort on (d2, id), d2 = (dx*dx + dy*dy) + dz*dz in float64 (dist2_nofma's expression),
+    N = 1 for STOD (extrapolate_neighbours); the weights of extrapolate_weights.
+    -> (rowlen [nu] int32, ids [nu][K] int32 with -1 behind a row's end, w [nu][K] with 0.0 there)."""
+    unmapped = np.asarray(unmapped)
+    rows = np.flatnonzero(unmapped) if unmapped.dtype == bool else np.sort(unmapped.astype(np.int64))
+    if method not in (EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG):
+        raise ValueError("extrapolate_rows: unknown method")
+    ids, d2k = extrapolate_neighbours(src_xyz, dst_xyz, rows, int(num_src_pnts) if method == EXTRAPMETHOD_NEAREST_IDAVG else 1)
+    rowlen, w = extrapolate_weights(d2k, method, dist_exponent)
+    ids[np.arange(ids.shape[1])[None, :] >= rowlen[:, None]] = -1
+    return rowlen, ids, w
+
+
 _COMPOSE_VECTOR_PASSES = 64   # terms of an entry of C summed by vectorised passes; what lies behind them is summed by a plain loop
 
 
