@@ -505,8 +505,8 @@ int mpg_handle_transpose_stats(mpg_handle rh, int64_t *n_referenced, int64_t *ma
 /* GPU time (ms) of the last transposed index build of this handle; 0 while none is built */
 int mpg_handle_transpose_build_ms(mpg_handle rh, float *ms);
 /* Masked Regrid: missing sources are skipped, the valid ones stand in for them above a threshold, everything else is filled.
- * What ESMF calls dynamic masking (dynamicSrcMaskValue) and xESMF skipna / na_thres -- NOT ESMF's Store-time srcMaskValues: the
- * weights are those of the unmasked Store of this handle, only their use changes per call.
+ * What ESMF calls dynamic masking (dynamicSrcMaskValue) and xESMF skipna / na_thres -- NOT ESMF's Store-time srcMaskValues (mpg_handle_mask and
+ * mpg_handle_extrapolate_masked are those): the weights are those of the unmasked Store of this handle, only their use changes per call.
  * For a destination point p and level k take the stored entries q in stored order (slot order of a fixed-nnz handle, CSR order of
  * a conservative or a from-weights handle, duplicates included).  All arithmetic is float64.
  *   valid(q)   idx_q >= 0, its source is not statically masked (src_mask_dev), and its value at level k is not missing under
@@ -1017,6 +1017,72 @@ typedef struct mpg_extrap_opts {
   double dist_exponent;  /* IDAVG: e, finite and > 0 (ESMF's default 2.0); ignored for STOD */
 } mpg_extrap_opts;
 int mpg_handle_extrapolate(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts, mpg_handle *out);
+
+/* ---- Store-time masks: ESMF_FieldRegridStore's srcMaskValues / dstMaskValues as two handle-to-handle calls ---------------------------------
+ * Land values must not be made from water cells: a land point of the target takes the nearest LAND cell, a conservative mean is taken over
+ * the land part of a cell.  Masks that do not change from call to call belong into the handle: mpg_handle_mask removes masked sources and
+ * destinations from a finished handle's pattern, mpg_handle_extrapolate_masked refills rows from the UNMASKED sources alone.  Both return
+ * an ordinary handle which every consumer takes, so every Store and every Regrid is served at once and a host that masks its Stores once
+ * pays nothing per Regrid.  (mpg_regrid_masked_dev is the other thing: masks that change per call, renormalised per call on the weights of
+ * the unmasked Store, never a search for the next valid neighbour.)  Masks are device bytes, non-zero = masked.
+ *
+ * mpg_handle_mask(rh, opts, out): static masks on a handle's pattern.  It needs no geometry.
+ *   src_mask_dev [n_src] in the handle's source index space, dst_mask_dev [n_dst]; either may be NULL (no mask on that side); both NULL is
+ *   success: a copy of the pattern.
+ *   Destination mask: a masked destination row becomes unmapped, under either rule.
+ *   MPG_MASKRULE_ROW (ESMF's rule for bilinear and nearest: a source cell with a masked corner is masked): a row with at least one stored
+ *     entry (index >= 0, whatever its weight, a weight of 0.0 included) that references a masked source becomes unmapped; every other row is
+ *     copied verbatim.  Fixed and CSR handles are served.  The cap rows of a periodic Grid -> Mesh CSR handle (MPG_POLEMETHOD_NONE's or
+ *     ALLAVG's rows of nx entries) are rows like any other: one masked point of the end row unmaps them.  A fixed input stays fixed with the
+ *     same slot count, a nearest handle stays without a weight array, and an unmapped row is written as the Stores write one: every slot's
+ *     index -1, every weight +0.0.  A CSR input stays CSR: unmapped rows are empty.
+ *   MPG_MASKRULE_ENTRY (ESMF's rule for conservative: masked source cells do not take part), CSR handles only: the entries of masked
+ *     sources are removed, the kept entries stay in stored order.  Wk = ((0.0 + v_0) + v_1) + ... over the kept values from left to right,
+ *     each add rounded on its own (fp contract(off)).  MPG_NORM_DSTAREA: the values are unchanged and frac' = Wk.  MPG_NORM_FRACAREA:
+ *     w' = w / Wk and frac' = frac * Wk.  norm_type is the one the Store was called with.  A row with nothing kept, or with Wk <= 0 (or
+ *     NaN), is empty and frac' = +0.0.  A row with no masked entry is copied verbatim, its dst_frac included, bit for bit.  A
+ *     destination-masked row is empty with frac' = +0.0.  An input without dst_frac gives an output without one (frac reads as 0.0 in the
+ *     rule and frac' is dropped); under MPG_MASKRULE_ROW a dst_frac is carried, +0.0 on the rows the call unmaps.
+ *   MPG_MASKRULE_AUTO: ROW for handles whose method is MPG_REGRIDMETHOD_BILINEAR or MPG_REGRIDMETHOD_NEAREST_STOD, ENTRY for
+ *     MPG_REGRIDMETHOD_CONSERVE.  Where the handle records no method (from weights, composed, reconstruct): MPG_ERR_INVALID_ARG, the message
+ *     asks for an explicit rule.
+ *   Output: a new handle with the input's n_src, n_dst, nx_dst, ny_dst, method and kind.  It is not cached and owns its arrays: pair it
+ *     with mpg_handle_release; rh may be released right after the call.  A CSR output records its longest row.  mpg_handle_store_ms is the
+ *     GPU time of the call.  mpg_handle_store_stats: [1] = mapped rows (a stored entry) the source rule unmapped, [2] = mapped rows the
+ *     destination mask unmapped (a row under both counts here), [3] = stored entries removed (the input's minus the output's).
+ *     A contract by identity with the numpy mirror target_grid.mask_rows.  The same bytes from run to run; no floating-point atomics.
+ *   Blocking: the call allocates, reads its counts back and drains the Store worker first.  It orders itself after whatever produced rh, as
+ *     mpg_handle_get_csr does.
+ *   Refusals, each with a message that names mpg_handle_mask and the way out.  MPG_ERR_INVALID_ARG: a NULL rh, opts or out; an unknown rule;
+ *     under ENTRY an unknown norm_type; AUTO on a handle without a method.  MPG_ERR_UNSUPPORTED: a handle with pole terms
+ *     (mpg_handle_pole_count > 0); a localized or rebased handle; a handle whose mesh carries a source window; ENTRY on a fixed handle
+ *     (mpg_handle_get_weights -> mpg_handle_from_weights makes a CSR handle of it).  The output never has more entries than the input:
+ *     there is no overflow refusal.  A failed allocation returns its error and leaks nothing.
+ *
+ * mpg_handle_extrapolate_masked(rh, src, dst, opts, src_mask_dev, dst_skip_dev, out): the contract of mpg_handle_extrapolate above, word
+ *   for word, with two changes.  First, the candidates are the sources c with src_mask[c] == 0, and K = min(N, number of unmasked
+ *   sources).  Second, an unmapped row with dst_skip[p] != 0 is left unmapped.  The (d2, id) order is the same: ties go to the lower
+ *   UNMASKED id at every rank; knn_weights and the fixed-or-CSR output rule are the same.  Either pointer may be NULL; with both NULL the
+ *   output bytes equal mpg_handle_extrapolate's.  With every source masked nothing is filled: that is success.
+ *   mpg_handle_store_stats: [1] = rows filled, [2] = K, [3] = unmasked sources.  A contract by identity with the numpy mirror
+ *   target_grid.extrapolate_rows_masked (for e == 2.0; for other exponents up to the device pow).
+ *   The search never enters a subtree that holds no unmasked source: per call one `alive` byte per tree node is built bottom-up (a leaf
+ *   is alive if it holds an unmasked item, a parent if a child is) and the walk sees a dead node as absent; without that a query would walk
+ *   the whole tree while fewer than K unmasked sources have been met.  The boxes stay valid lower bounds, so the result is exact.
+ *   Refusals: those of mpg_handle_extrapolate, each message under the name mpg_handle_extrapolate_masked.
+ *
+ * ESMF's masked Store is the composition mask, then extrapolate_masked: regrid.store_masks (Python), INTEGRATION.md.
+ * Not served: handles with pole terms, localized or windowed handles, node-located sources, creep fills. */
+enum { MPG_MASKRULE_AUTO = 0, MPG_MASKRULE_ROW = 1, MPG_MASKRULE_ENTRY = 2 };
+typedef struct mpg_store_mask_opts {
+  const uint8_t *src_mask_dev;  /* [n_src] device bytes in the handle's index space, non-zero = masked; NULL = none */
+  const uint8_t *dst_mask_dev;  /* [n_dst] device bytes, non-zero = masked; NULL = none */
+  int rule;                     /* MPG_MASKRULE_* */
+  int norm_type;                /* ENTRY rule only: MPG_NORM_DSTAREA / MPG_NORM_FRACAREA, the one the Store was called with */
+} mpg_store_mask_opts;
+int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *out);
+int mpg_handle_extrapolate_masked(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts,
+                                  const uint8_t *src_mask_dev, const uint8_t *dst_skip_dev, mpg_handle *out);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

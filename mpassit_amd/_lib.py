@@ -37,6 +37,7 @@ SYMBOLS = [
     "mpg_rotate_winds_transpose_dev", "mpg_wind_destagger_transpose_dev",
     "mpg_regrid_masked_transpose_dev",
     "mpg_handle_extrapolate", "mpg_mesh_get_xyz", "mpg_grid_get_xyz",
+    "mpg_handle_mask", "mpg_handle_extrapolate_masked",
 ]
 
 MPG_SUCCESS = 0
@@ -55,6 +56,8 @@ POLEMETHOD_NONE, POLEMETHOD_ALLAVG = MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG
 MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG = 1, 2
 EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG = MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG
 EXTRAP_MAX_PNTS = 8
+MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY = 0, 1, 2
+MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY = MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY
 
 
 class MaskOpts(C.Structure):
@@ -437,6 +440,33 @@ def grid_get_xyz(*args):
     if "grid_get_xyz" not in _to_mesh_fns:
         _to_mesh_fns["grid_get_xyz"] = _GRID_GET_XYZ_PROTO(("mpg_grid_get_xyz", load()))
     return _to_mesh_fns["grid_get_xyz"](*args)
+
+
+# Store-time masks, bound the same way.
+#   mpg_handle_mask(rh, opts, out)
+#   mpg_handle_extrapolate_masked(rh, src, dst, opts, src_mask_dev, dst_skip_dev, out)
+class StoreMaskOpts(C.Structure):
+    """mpg_store_mask_opts of include/mpassit_amd.h: device byte masks (0 / None = none), the rule and the Store's norm type."""
+    _fields_ = [("src_mask_dev", C.c_void_p), ("dst_mask_dev", C.c_void_p), ("rule", C.c_int), ("norm_type", C.c_int)]
+
+
+_HANDLE_MASK_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(StoreMaskOpts), C.c_void_p)
+_HANDLE_EXTRAPOLATE_MASKED_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Points), C.POINTER(Points), C.POINTER(ExtrapOpts), C.c_void_p,
+                                               C.c_void_p, C.c_void_p)
+
+
+def handle_mask(*args):
+    """The typed binding of mpg_handle_mask; returns the call's status code."""
+    if "handle_mask" not in _to_mesh_fns:
+        _to_mesh_fns["handle_mask"] = _HANDLE_MASK_PROTO(("mpg_handle_mask", load()))
+    return _to_mesh_fns["handle_mask"](*args)
+
+
+def handle_extrapolate_masked(*args):
+    """The typed binding of mpg_handle_extrapolate_masked; returns the call's status code."""
+    if "handle_extrapolate_masked" not in _to_mesh_fns:
+        _to_mesh_fns["handle_extrapolate_masked"] = _HANDLE_EXTRAPOLATE_MASKED_PROTO(("mpg_handle_extrapolate_masked", load()))
+    return _to_mesh_fns["handle_extrapolate_masked"](*args)
 
 
 _lib = None

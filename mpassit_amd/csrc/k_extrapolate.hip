@@ -14,8 +14,14 @@
 //                          copied (a fixed row: its slots in slot order, a nearest handle's weight 1.0), new rows written in ascending
 //                          (d2, id) order, which is the Regrid's summation order; the longest row is recorded (an integer maximum)
 // The weights are knn_weights (knn.h): one text for device and host.  No floating-point atomics: the same bytes from run to run.
+//
+// mpg_handle_extrapolate_masked runs the same passes with two changes.  k_ex_flag_skip leaves the rows of dst_skip out of the list.  With a
+// source mask, K = min(N, unmasked sources) (k_ex_unmasked, summed), one `alive` byte per tree node is built bottom-up (k_ex_alive_leaf,
+// then k_ex_alive_up per level: knn_mask.h says why) and k_ex_knn_masked<Src, KCAP> walks the AliveTree: it never enters a subtree without
+// an unmasked source, and its leaf bodies test mask[id] before they compute a distance.  Without a mask the unmasked kernels run as they are.
 #include "geom.h"
 #include "knn.h"
+#include "knn_mask.h"
 #include "mpg_internal.h"
 
 #define EX_MAX_SLOTS 4   // slots per row of a fixed handle (3, 4 or 1)
@@ -49,6 +55,22 @@ struct ExMeshSrc {
     const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
     for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) f(dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]), b.sid[i]);
   }
+  // ... every UNMASKED item: the mask is read first, a masked item costs no distance
+  template <class F>
+  __device__ __forceinline__ void leaf_masked(int node, double X, double Y, double Z, const uint8_t *__restrict__ mask, F f) const {
+    const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
+    for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) {
+      const int32_t c = b.sid[i];
+      if (mask[c]) continue;
+      f(dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]), c);
+    }
+  }
+  __device__ __forceinline__ bool leaf_alive(int node, const uint8_t *__restrict__ mask) const {
+    const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
+    bool a = false;
+    for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) a |= mask[b.sid[i]] == 0;
+    return a;
+  }
 };
 struct ExGridSrc {
   typedef PyrTree Tree;
@@ -66,6 +88,25 @@ struct ExGridSrc {
         f(dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]), c);
       }
   }
+  template <class F>
+  __device__ __forceinline__ void leaf_masked(int node, double X, double Y, double Z, const uint8_t *__restrict__ mask, F f) const {
+    const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
+    const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
+    for (int j = bj * MPG_PYR_B0; j < j1; ++j)
+      for (int i = bi * MPG_PYR_B0; i < i1; ++i) {
+        const int c = j * snx + i;
+        if (mask[c]) continue;
+        f(dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]), c);
+      }
+  }
+  __device__ __forceinline__ bool leaf_alive(int node, const uint8_t *__restrict__ mask) const {
+    const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
+    const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
+    bool a = false;
+    for (int j = bj * MPG_PYR_B0; j < j1; ++j)
+      for (int i = bi * MPG_PYR_B0; i < i1; ++i) a |= mask[j * snx + i] == 0;
+    return a;
+  }
 };
 
 static inline unsigned ex_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -77,6 +118,33 @@ __global__ __launch_bounds__(256) void k_ex_flag(ExIn in, int32_t *__restrict__ 
   int f = 0;
   if (i < in.n) f = in.rowptr ? in.rowptr[i + 1] == in.rowptr[i] : in.col[i] < 0;
   flag[i] = f;
+}
+
+// ... the same with the rows of `skip` left out (mpg_handle_extrapolate_masked's dst_skip): they stay unmapped
+__global__ __launch_bounds__(256) void k_ex_flag_skip(ExIn in, const uint8_t *__restrict__ skip, int32_t *__restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i > in.n) return;
+  int f = 0;
+  if (i < in.n && !skip[i]) f = in.rowptr ? in.rowptr[i + 1] == in.rowptr[i] : in.col[i] < 0;
+  flag[i] = f;
+}
+
+// u[c] = 1 for an unmasked source (summed: the candidates' count)
+__global__ __launch_bounds__(256) void k_ex_unmasked(int64_t n, const uint8_t *__restrict__ mask, int32_t *__restrict__ u) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c < n) u[c] = mask[c] == 0;
+}
+
+// the alive bytes of knn_mask.h, one kernel per level: the leaves from the mask, every upper level from the one below
+template <class Src>
+__global__ __launch_bounds__(256) void k_ex_alive_leaf(Src src, int64_t leaves, const uint8_t *__restrict__ mask, uint8_t *__restrict__ alive) {
+  const int64_t node = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (node < leaves) alive[src.tree().v.off[0] + node] = src.leaf_alive((int)node, mask);
+}
+template <class Src>
+__global__ __launch_bounds__(256) void k_ex_alive_up(Src src, int lev, int64_t nodes, uint8_t *alive) {
+  const int64_t node = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (node < nodes) alive[src.tree().v.off[lev] + node] = alive_parent(src.tree(), lev, (int)node, alive);
 }
 
 __global__ __launch_bounds__(256) void k_ex_compact(int64_t n, const int32_t *__restrict__ flag, const int32_t *__restrict__ pos,
@@ -102,6 +170,29 @@ __global__ __launch_bounds__(256) void k_ex_knn(int64_t nu, const int32_t *__res
     d2[(int64_t)k * nu + u] = best.d2[k];
   }
   cnt[u] = (!idavg || best.d2[0] == 0.0) ? min(best.n, 1) : min(best.n, kmax);   // (KCAP >= N: the list may hold more than the row takes)
+}
+
+// the same search over the unmasked sources alone, through the alive bytes (the caller launches it only when a source is unmasked; a
+// dead root would be no search at all: knn_search_masked)
+template <class Src, int KCAP>
+__global__ __launch_bounds__(256) void k_ex_knn_masked(int64_t nu, const int32_t *__restrict__ list, const double *__restrict__ px,
+                                                       const double *__restrict__ py, const double *__restrict__ pz, Src src,
+                                                       const uint8_t *__restrict__ mask, const uint8_t *__restrict__ alive, int idavg, int kmax,
+                                                       int32_t *__restrict__ ids, double *__restrict__ d2, int32_t *__restrict__ cnt) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nu) return;
+  const int64_t p = list[u];
+  const double X = px[p], Y = py[p], Z = pz[p];
+  KBest<KCAP> best;
+  knn_search_masked(
+      src.tree(), alive, [&](const double *bx) { return boxdist2_nofma(X, Y, Z, bx); },
+      [&](int node, auto f) { src.leaf_masked(node, X, Y, Z, mask, f); }, best);
+#pragma unroll
+  for (int k = 0; k < KCAP; ++k) {
+    ids[(int64_t)k * nu + u] = best.id[k];
+    d2[(int64_t)k * nu + u] = best.d2[k];
+  }
+  cnt[u] = (!idavg || best.d2[0] == 0.0) ? min(best.n, 1) : min(best.n, kmax);
 }
 
 // the entries of listed row u: ids, weights, count
@@ -207,20 +298,39 @@ static void ex_launch_knn(int kcap, int64_t nu, const int32_t *list, const Point
   else k_ex_knn<Src, 8><<<nb, 256, 0, s>>>(nu, list, dst.x.p, dst.y.p, dst.z.p, src, idavg, kmax, ids, d2, cnt);
 }
 
+template <class Src>
+static void ex_launch_knn_masked(int kcap, int64_t nu, const int32_t *list, const PointSet &dst, const Src &src, const uint8_t *mask,
+                                 const uint8_t *alive, int idavg, int kmax, int32_t *ids, double *d2, int32_t *cnt, hipStream_t s) {
+  const unsigned nb = ex_grid(nu);
+  if (kcap == 1) k_ex_knn_masked<Src, 1><<<nb, 256, 0, s>>>(nu, list, dst.x.p, dst.y.p, dst.z.p, src, mask, alive, idavg, kmax, ids, d2, cnt);
+  else if (kcap == 2) k_ex_knn_masked<Src, 2><<<nb, 256, 0, s>>>(nu, list, dst.x.p, dst.y.p, dst.z.p, src, mask, alive, idavg, kmax, ids, d2, cnt);
+  else if (kcap == 4) k_ex_knn_masked<Src, 4><<<nb, 256, 0, s>>>(nu, list, dst.x.p, dst.y.p, dst.z.p, src, mask, alive, idavg, kmax, ids, d2, cnt);
+  else k_ex_knn_masked<Src, 8><<<nb, 256, 0, s>>>(nu, list, dst.x.p, dst.y.p, dst.z.p, src, mask, alive, idavg, kmax, ids, d2, cnt);
+}
+
+// the alive bytes of the source's tree under `mask`, bottom-up: one launch per level (nlev and the level sizes are the host's own copy)
+template <class Src>
+static int ex_alive_build(const Src &src, int nlev, const int64_t *level_nodes, const uint8_t *mask, uint8_t *alive, hipStream_t s) {
+  k_ex_alive_leaf<Src><<<ex_grid(level_nodes[0]), 256, 0, s>>>(src, level_nodes[0], mask, alive);
+  for (int lev = 1; lev < nlev; ++lev) k_ex_alive_up<Src><<<ex_grid(level_nodes[lev]), 256, 0, s>>>(src, lev, level_nodes[lev], alive);
+  MPG_HIP(hipGetLastError());
+  return MPG_SUCCESS;
+}
+
 // in: the handle to fill.  Exactly one of src_mesh (its cells) / src_grid (its `src_stagger` points, which exist) is set; dst: the
 // destination points, in.n_dst of them.  out: shape and method set by the caller, arrays empty.  Blocking.
+// src_mask [n_src] / dst_skip [n_dst]: device bytes or nullptr (mpg_handle_extrapolate_masked); who: the entry point the messages name.
 int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_grid, int src_stagger, const PointSet &dst, int method, int npnts,
-                      double e, mpg_handle_s *out, hipStream_t s) {
+                      double e, mpg_handle_s *out, hipStream_t s, const uint8_t *src_mask, const uint8_t *dst_skip, const char *who) {
   int rc;
   const int64_t n = in->n_dst, n_src = in->n_src;
   const int idavg = method == MPG_EXTRAPMETHOD_NEAREST_IDAVG;
   const int N = idavg ? npnts : 1;
-  const int K = (int)(n_src < N ? n_src : N);
   const int kcap = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : 8;
   const ExIn I = ex_in(in);
   const bool fixed_out = in->kind == MPG_KIND_FIXED && N <= in->nnz_per_row;
   if (in->kind == MPG_KIND_FIXED && in->nnz_per_row > EX_MAX_SLOTS) {
-    mpg_set_error("mpg_handle_extrapolate: a fixed handle of %d slots per row is not served (%d at most)", in->nnz_per_row, EX_MAX_SLOTS);
+    mpg_set_error("%s: a fixed handle of %d slots per row is not served (%d at most)", who, in->nnz_per_row, EX_MAX_SLOTS);
     return MPG_ERR_UNSUPPORTED;
   }
   // the search structure first: a tree that cannot be built refuses the call before anything else is allocated
@@ -234,34 +344,68 @@ int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_gr
     Pyramid &pyr = src_grid->pyr[src_stagger];
     const PointSet &sp = src_grid->pts[src_stagger];
     if (!pyr.built && (rc = mpg_k_build_pyramid(sp, src_grid->snx[src_stagger], src_grid->sny[src_stagger], pyr, s))) return rc;
-    if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], "mpg_handle_extrapolate"))) return rc;
+    if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], who))) return rc;
     gs.pyr = mpg_pyr_view(pyr);
     gs.snx = src_grid->snx[src_stagger]; gs.sny = src_grid->sny[src_stagger];
     gs.sx = sp.x.p; gs.sy = sp.y.p; gs.sz = sp.z.p;
   }
+  // the candidates: every source, or the unmasked ones (counted, read back with the rows below)
+  TmpBuf<long long> nlive;
+  if (src_mask && n_src > 0) {
+    TmpBuf<int32_t> u;
+    if ((rc = u.alloc((size_t)n_src, s)) || (rc = nlive.alloc(1, s))) return rc;
+    k_ex_unmasked<<<ex_grid(n_src), 256, 0, s>>>(n_src, src_mask, u.p);
+    MPG_HIP(hipGetLastError());
+    if ((rc = mpg_sum_i32_i64(u.p, n_src, nlive.p, s))) return rc;
+  }
   // pass 1
   TmpBuf<int32_t> flag, pos, list, ids, cnt;
   TmpBuf<double> d2;
+  TmpBuf<uint8_t> alive;
   if ((rc = flag.alloc((size_t)n + 1, s)) || (rc = pos.alloc((size_t)n + 1, s))) return rc;
-  k_ex_flag<<<ex_grid(n + 1), 256, 0, s>>>(I, flag.p);
+  if (dst_skip) k_ex_flag_skip<<<ex_grid(n + 1), 256, 0, s>>>(I, dst_skip, flag.p);
+  else k_ex_flag<<<ex_grid(n + 1), 256, 0, s>>>(I, flag.p);
   MPG_HIP(hipGetLastError());
   if ((rc = mpg_scan_excl_i32(flag.p, pos.p, n + 1, s))) return rc;
   int32_t nu32 = 0;
+  long long live = n_src;
   MPG_HIP(hipMemcpyAsync(&nu32, pos.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (nlive.p) MPG_HIP(hipMemcpyAsync(&live, nlive.p, sizeof(long long), hipMemcpyDeviceToHost, s));
   MPG_HIP(hipStreamSynchronize(s));
-  const int64_t nu = K > 0 ? nu32 : 0;   // without a source point nothing can be filled
+  const int K = (int)(live < N ? live : N);
+  const int64_t nu = K > 0 ? nu32 : 0;   // without a candidate nothing can be filled, and no tree is walked: its root would be dead
   // pass 2
   if (nu > 0) {
     if ((rc = list.alloc((size_t)nu, s)) || (rc = ids.alloc((size_t)kcap * nu, s)) || (rc = d2.alloc((size_t)kcap * nu, s)) ||
         (rc = cnt.alloc((size_t)nu, s)))
       return rc;
     k_ex_compact<<<ex_grid(n), 256, 0, s>>>(n, flag.p, pos.p, list.p);
-    if (src_mesh) ex_launch_knn(kcap, nu, list.p, dst, ms, idavg, K, ids.p, d2.p, cnt.p, s);
+    if (src_mask) {
+      // the alive bytes of this call's mask, then the walk that never enters a dead subtree
+      int64_t level_nodes[MPG_PYR_MAXLEV > MPG_BVH_MAXLEV ? MPG_PYR_MAXLEV : MPG_BVH_MAXLEV];
+      int nlev;
+      int64_t total;
+      if (src_mesh) {
+        nlev = ms.b.nlev;
+        for (int l = 0; l < nlev; ++l) level_nodes[l] = ms.b.nnodes[l];
+        total = ms.b.off[nlev];
+      } else {
+        nlev = gs.pyr.nlev;
+        for (int l = 0; l < nlev; ++l) level_nodes[l] = (int64_t)gs.pyr.nx[l] * gs.pyr.ny[l];
+        total = gs.pyr.off[nlev];
+      }
+      if ((rc = alive.alloc((size_t)total, s))) return rc;
+      if ((rc = src_mesh ? ex_alive_build(ms, nlev, level_nodes, src_mask, alive.p, s) : ex_alive_build(gs, nlev, level_nodes, src_mask, alive.p, s)))
+        return rc;
+      if (src_mesh) ex_launch_knn_masked(kcap, nu, list.p, dst, ms, src_mask, alive.p, idavg, K, ids.p, d2.p, cnt.p, s);
+      else ex_launch_knn_masked(kcap, nu, list.p, dst, gs, src_mask, alive.p, idavg, K, ids.p, d2.p, cnt.p, s);
+    } else if (src_mesh) ex_launch_knn(kcap, nu, list.p, dst, ms, idavg, K, ids.p, d2.p, cnt.p, s);
     else ex_launch_knn(kcap, nu, list.p, dst, gs, idavg, K, ids.p, d2.p, cnt.p, s);
     MPG_HIP(hipGetLastError());
   }
   out->store_stats[1] = nu;
   out->store_stats[2] = K;
+  if (src_mask || dst_skip) out->store_stats[3] = live;   // (the masked call's statistic: its entry point sets it when both are nullptr)
   // pass 3
   if (fixed_out) {
     const int nz = in->nnz_per_row;
@@ -298,8 +442,8 @@ int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_gr
   MPG_HIP(hipMemcpyAsync(&nnz, total.p, sizeof(long long), hipMemcpyDeviceToHost, s));
   MPG_HIP(hipStreamSynchronize(s));
   if (!knn_nnz_fits(nnz)) {
-    mpg_set_error("mpg_handle_extrapolate: the CSR output would have %lld entries, more than 2^31 - 2 (rowptr is int32): lower num_src_pnts, or "
-                  "extrapolate the parts of the destination separately", nnz);
+    mpg_set_error("%s: the CSR output would have %lld entries, more than 2^31 - 2 (rowptr is int32): lower num_src_pnts, or "
+                  "extrapolate the parts of the destination separately", who, nnz);
     return MPG_ERR_OVERFLOW;
   }
   if ((rc = mpg_scan_excl_i32(len.p, out->rowptr.p, n + 1, s))) return rc;

@@ -129,7 +129,8 @@ void mpg_pool_release() {
   X(k_apply) X(k_apply_lfu) X(k_apply_typed) X(k_wind) X(k_pole) X(k_post) X(k_halo) X(mpg_comm) X(k_mesh_window) X(k_prims) X(k_sort) \
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
-  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate)
+  X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
+  X(k_handle_mask)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1613,29 +1614,29 @@ int mpg_compose_weights_dev(mpg_handle composed, mpg_handle outer, mpg_handle in
 
 // ---- extrapolation: the unmapped rows of a handle filled from the nearest source points (k_extrapolate.hip) ---------------------------------
 // a point set of the call: how many points, their row shape as a handle records it, and where they are
-static int ex_points(const char *role, const mpg_points *p, bool source, int64_t *n, int *nx, int *ny, const PointSet **pts) {
+static int ex_points(const char *who, const char *role, const mpg_points *p, bool source, int64_t *n, int *nx, int *ny, const PointSet **pts) {
   if ((p->mesh != nullptr) == (p->grid != nullptr)) {
-    mpg_set_error("mpg_handle_extrapolate: exactly one of mesh / grid must be set in the %s point set (%s are)", role, p->mesh ? "both" : "neither");
+    mpg_set_error("%s: exactly one of mesh / grid must be set in the %s point set (%s are)", who, role, p->mesh ? "both" : "neither");
     return MPG_ERR_INVALID_ARG;
   }
   if (p->mesh) {
     mpg_mesh_s *m = p->mesh;
     const int loc = p->meshloc;
     if (source && loc != MPG_MESHLOC_ELEMENT) {
-      mpg_set_error("mpg_handle_extrapolate: a source mesh is searched through its cells only (MPG_MESHLOC_ELEMENT, not location %d): "
-                    "node-located sources are not served", loc);
+      mpg_set_error("%s: a source mesh is searched through its cells only (MPG_MESHLOC_ELEMENT, not location %d): "
+                    "node-located sources are not served", who, loc);
       return MPG_ERR_INVALID_ARG;
     }
     if (loc != MPG_MESHLOC_ELEMENT && loc != MPG_MESHLOC_NODE && loc != MPG_MESHLOC_EDGE) {
-      mpg_set_error("mpg_handle_extrapolate: bad mesh location %d in the %s point set", loc, role);
+      mpg_set_error("%s: bad mesh location %d in the %s point set", who, loc, role);
       return MPG_ERR_INVALID_ARG;
     }
     if (loc == MPG_MESHLOC_EDGE && m->edge.n == 0) {
-      mpg_set_error("mpg_handle_extrapolate: the %s mesh has no edges: call mpg_mesh_set_edges first", role);
+      mpg_set_error("%s: the %s mesh has no edges: call mpg_mesh_set_edges first", who, role);
       return MPG_ERR_INVALID_ARG;
     }
     if (loc == MPG_MESHLOC_NODE && m->vwn != m->nVertices) {
-      mpg_set_error("mpg_handle_extrapolate: the vertices of a mesh cut to a grid (mpg_mesh_create_window) are not all resident: use the whole mesh");
+      mpg_set_error("%s: the vertices of a mesh cut to a grid (mpg_mesh_create_window) are not all resident: use the whole mesh", who);
       return MPG_ERR_UNSUPPORTED;
     }
     *pts = loc == MPG_MESHLOC_EDGE ? &m->edge : loc == MPG_MESHLOC_ELEMENT ? &m->cell : &m->vert;
@@ -1647,7 +1648,7 @@ static int ex_points(const char *role, const mpg_points *p, bool source, int64_t
   mpg_grid_s *g = p->grid;
   const int st = p->staggerloc;
   if (st < 0 || st >= 4) {
-    mpg_set_error("mpg_handle_extrapolate: bad stagger location %d in the %s point set", st, role);
+    mpg_set_error("%s: bad stagger location %d in the %s point set", who, st, role);
     return MPG_ERR_INVALID_ARG;
   }
   *nx = g->snx[st];
@@ -1655,53 +1656,75 @@ static int ex_points(const char *role, const mpg_points *p, bool source, int64_t
   *n = (int64_t)*nx * *ny;
   *pts = &g->pts[st];
   if (g->pts[st].n != *n) {
-    mpg_set_error("mpg_handle_extrapolate: stagger %d of the %s grid has no coordinates: create the grid with them", st, role);
+    mpg_set_error("%s: stagger %d of the %s grid has no coordinates: create the grid with them", who, st, role);
     return MPG_ERR_INVALID_ARG;
   }
   return MPG_SUCCESS;
 }
 
+// the one body of the two entry points (below them); who: the name the messages carry
+static int ex_extrapolate(const char *who, mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts,
+                          const uint8_t *src_mask_dev, const uint8_t *dst_skip_dev, mpg_handle *out);
+
 int mpg_handle_extrapolate(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts, mpg_handle *out) {
+  return ex_extrapolate("mpg_handle_extrapolate", rh, src, dst, opts, nullptr, nullptr, out);
+}
+
+// ---- Store-time masks: the same fill from the UNMASKED sources only, destination rows that stay unmapped (k_extrapolate.hip, knn_mask.h)
+int mpg_handle_extrapolate_masked(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts,
+                                  const uint8_t *src_mask_dev, const uint8_t *dst_skip_dev, mpg_handle *out) {
+  const int rc = ex_extrapolate("mpg_handle_extrapolate_masked", rh, src, dst, opts, src_mask_dev, dst_skip_dev, out);
+  if (!rc && !src_mask_dev && !dst_skip_dev) (*out)->store_stats[3] = rh->n_src;   // [3] = the unmasked sources: all of them
+  return rc;
+}
+
+static int ex_extrapolate(const char *who, mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts,
+                          const uint8_t *src_mask_dev, const uint8_t *dst_skip_dev, mpg_handle *out) {
   MPG_CHECK_INIT();
-  MPG_ARG(rh && src && dst && opts && out, "mpg_handle_extrapolate: NULL argument (rh, src, dst, opts and out are all mandatory)");
-  MPG_ARG(opts->method == MPG_EXTRAPMETHOD_NEAREST_STOD || opts->method == MPG_EXTRAPMETHOD_NEAREST_IDAVG,
-          "mpg_handle_extrapolate: unknown method: MPG_EXTRAPMETHOD_NEAREST_STOD or MPG_EXTRAPMETHOD_NEAREST_IDAVG");
+  if (!(rh && src && dst && opts && out)) {
+    mpg_set_error("%s: NULL argument (rh, src, dst, opts and out are all mandatory)", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (opts->method != MPG_EXTRAPMETHOD_NEAREST_STOD && opts->method != MPG_EXTRAPMETHOD_NEAREST_IDAVG) {
+    mpg_set_error("%s: unknown method: MPG_EXTRAPMETHOD_NEAREST_STOD or MPG_EXTRAPMETHOD_NEAREST_IDAVG", who);
+    return MPG_ERR_INVALID_ARG;
+  }
   const bool idavg = opts->method == MPG_EXTRAPMETHOD_NEAREST_IDAVG;
   if (idavg && (opts->num_src_pnts < 1 || opts->num_src_pnts > MPG_EXTRAP_MAX_PNTS)) {
-    mpg_set_error("mpg_handle_extrapolate: num_src_pnts = %d is outside 1..%d (MPG_EXTRAP_MAX_PNTS)", opts->num_src_pnts, MPG_EXTRAP_MAX_PNTS);
+    mpg_set_error("%s: num_src_pnts = %d is outside 1..%d (MPG_EXTRAP_MAX_PNTS)", who, opts->num_src_pnts, MPG_EXTRAP_MAX_PNTS);
     return MPG_ERR_INVALID_ARG;
   }
   if (idavg && !(std::isfinite(opts->dist_exponent) && opts->dist_exponent > 0.0)) {
-    mpg_set_error("mpg_handle_extrapolate: dist_exponent = %g must be finite and > 0 (ESMF's default is 2.0)", opts->dist_exponent);
+    mpg_set_error("%s: dist_exponent = %g must be finite and > 0 (ESMF's default is 2.0)", who, opts->dist_exponent);
     return MPG_ERR_INVALID_ARG;
   }
   int rc;
   int64_t ns = 0, nd = 0;
   int sx = 0, sy = 0, dx = 0, dy = 0;
   const PointSet *sp = nullptr, *dp = nullptr;
-  if ((rc = ex_points("source", src, true, &ns, &sx, &sy, &sp)) || (rc = ex_points("destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
+  if ((rc = ex_points(who, "source", src, true, &ns, &sx, &sy, &sp)) || (rc = ex_points(who, "destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
   if (rh->n_pole > 0) {
-    mpg_set_error("mpg_handle_extrapolate: the handle has pole terms (mpg_handle_pole_count > 0), which an extrapolated copy cannot carry: "
-                  "store with MPG_POLEMETHOD_NONE, or fill from a non-periodic handle");
+    mpg_set_error("%s: the handle has pole terms (mpg_handle_pole_count > 0), which an extrapolated copy cannot carry: "
+                  "store with MPG_POLEMETHOD_NONE, or fill from a non-periodic handle", who);
     return MPG_ERR_UNSUPPORTED;
   }
   if (rh->localized) {
-    mpg_set_error("mpg_handle_extrapolate: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no "
-                  "longer source ids -- extrapolate first, re-index the result");
+    mpg_set_error("%s: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no "
+                  "longer source ids -- extrapolate first, re-index the result", who);
     return MPG_ERR_UNSUPPORTED;
   }
   if (mpg_handle_is_windowed(rh) || (src->mesh && src->mesh->win_count[MPG_MESHLOC_ELEMENT] >= 0)) {
-    mpg_set_error("mpg_handle_extrapolate: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
-                  "window-relative -- reset the window to the whole mesh first");
+    mpg_set_error("%s: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
+                  "window-relative -- reset the window to the whole mesh first", who);
     return MPG_ERR_UNSUPPORTED;
   }
   if (rh->n_src != ns) {
-    mpg_set_error("mpg_handle_extrapolate: the handle has n_src = %lld, the source point set has %lld points (a node-located handle has "
-                  "no source set here)", (long long)rh->n_src, (long long)ns);
+    mpg_set_error("%s: the handle has n_src = %lld, the source point set has %lld points (a node-located handle has "
+                  "no source set here)", who, (long long)rh->n_src, (long long)ns);
     return MPG_ERR_INVALID_ARG;
   }
   if (rh->n_dst != nd || rh->nx_dst != dx || rh->ny_dst != dy) {
-    mpg_set_error("mpg_handle_extrapolate: the handle has n_dst = %lld (%d x %d), the destination point set has %lld points (%d x %d)",
+    mpg_set_error("%s: the handle has n_dst = %lld (%d x %d), the destination point set has %lld points (%d x %d)", who,
                   (long long)rh->n_dst, rh->nx_dst, rh->ny_dst, (long long)nd, dx, dy);
     return MPG_ERR_INVALID_ARG;
   }
@@ -1718,18 +1741,95 @@ int mpg_handle_extrapolate(mpg_handle rh, const mpg_points *src, const mpg_point
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
     if (e0) (void)hipEventDestroy(e0);
-    mpg_set_error("mpg_handle_extrapolate: hipEventCreate failed");
+    mpg_set_error("%s: hipEventCreate failed", who);
     handle_free(h);
     return MPG_ERR_HIP;
   }
   (void)hipEventRecord(e0, g_stream);
-  rc = mpg_k_extrapolate(rh, src->mesh, src->grid, src->staggerloc, *dp, opts->method, opts->num_src_pnts, opts->dist_exponent, h, g_stream);
+  rc = mpg_k_extrapolate(rh, src->mesh, src->grid, src->staggerloc, *dp, opts->method, opts->num_src_pnts, opts->dist_exponent, h, g_stream,
+                         src_mask_dev, dst_skip_dev, who);
   if (!rc) {
     hipError_t he = hipEventRecord(e1, g_stream);
     if (he == hipSuccess) he = hipEventSynchronize(e1);
     if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
     if (he != hipSuccess) {
-      mpg_set_error("mpg_handle_extrapolate: %s", hipGetErrorString(he));
+      mpg_set_error("%s: %s", who, hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+// ---- Store-time masks on a handle's pattern (k_handle_mask.hip): no geometry, every Store and every consumer served at once ----------------
+int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(rh && opts && out, "mpg_handle_mask: NULL argument (rh, opts and out are all mandatory)");
+  MPG_ARG(opts->rule == MPG_MASKRULE_AUTO || opts->rule == MPG_MASKRULE_ROW || opts->rule == MPG_MASKRULE_ENTRY,
+          "mpg_handle_mask: unknown rule: MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW or MPG_MASKRULE_ENTRY");
+  int rule = opts->rule;
+  if (rule == MPG_MASKRULE_AUTO) {
+    if (rh->method == MPG_REGRIDMETHOD_BILINEAR || rh->method == MPG_REGRIDMETHOD_NEAREST_STOD) rule = MPG_MASKRULE_ROW;
+    else if (rh->method == MPG_REGRIDMETHOD_CONSERVE) rule = MPG_MASKRULE_ENTRY;
+    else {
+      mpg_set_error("mpg_handle_mask: MPG_MASKRULE_AUTO follows the handle's regrid method, and this handle records none (from weights, "
+                    "composed, reconstruct): pass MPG_MASKRULE_ROW or MPG_MASKRULE_ENTRY");
+      return MPG_ERR_INVALID_ARG;
+    }
+  }
+  const bool entry = rule == MPG_MASKRULE_ENTRY;
+  if (entry) MPG_ARG(opts->norm_type == MPG_NORM_DSTAREA || opts->norm_type == MPG_NORM_FRACAREA,
+                     "mpg_handle_mask: unknown norm_type: MPG_NORM_DSTAREA or MPG_NORM_FRACAREA, the one the Store was called with");
+  if (rh->n_pole > 0) {
+    mpg_set_error("mpg_handle_mask: the handle has pole terms (mpg_handle_pole_count > 0), which a masked copy cannot carry: store with "
+                  "MPG_POLEMETHOD_NONE");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->localized) {
+    mpg_set_error("mpg_handle_mask: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no longer "
+                  "source ids -- mask first, re-index the result");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (mpg_handle_is_windowed(rh)) {
+    mpg_set_error("mpg_handle_mask: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
+                  "window-relative -- reset the window to the whole mesh first");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (entry && rh->kind != MPG_KIND_CSR) {
+    mpg_set_error("mpg_handle_mask: MPG_MASKRULE_ENTRY removes entries, which the slots of a fixed handle cannot express: "
+                  "mpg_handle_get_weights, then mpg_handle_from_weights, makes a CSR handle of it (or use MPG_MASKRULE_ROW)");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  // rh is finished (a Store waits for its build before it hands its handle out); a begun Store may still allocate on the worker
+  store_worker_drain();
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = rh->method;
+  h->n_src = rh->n_src;
+  h->n_dst = rh->n_dst;
+  h->nx_dst = rh->nx_dst;
+  h->ny_dst = rh->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("mpg_handle_mask: hipEventCreate failed");
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  int rc = mpg_k_handle_mask(rh, opts->src_mask_dev, opts->dst_mask_dev, entry, opts->norm_type, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("mpg_handle_mask: %s", hipGetErrorString(he));
       rc = MPG_ERR_HIP;
     }
   }

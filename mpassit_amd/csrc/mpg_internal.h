@@ -513,9 +513,16 @@ int mpg_k_compose_values(mpg_handle_s *c, mpg_handle_s *a, mpg_handle_s *b, int 
 void mpg_set_compose_block_rows(int v);     // "compose_block_rows" knob (k_compose.hip)
 // k_extrapolate.hip: `out` (shape and method set by the caller, arrays empty) <- `in` with its unmapped rows filled from the nearest source
 // points: the cells of src_mesh (its site BVH, built whole) or the `src_stagger` points of src_grid (their point pyramid), exactly one set;
-// dst: the in->n_dst destination points.  Arguments checked by the API entry point; blocking: it allocates and reads counts back
+// dst: the in->n_dst destination points.  Arguments checked by the API entry point; blocking: it allocates and reads counts back.
+// src_mask [n_src] / dst_skip [n_dst] (device bytes, non-zero = masked / skipped, either may be nullptr): mpg_handle_extrapolate_masked's
+// candidate restriction and the rows it leaves unmapped; who: the entry point the messages name
 int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_grid, int src_stagger, const PointSet &dst, int method, int npnts,
-                      double e, mpg_handle_s *out, hipStream_t s);
+                      double e, mpg_handle_s *out, hipStream_t s, const uint8_t *src_mask = nullptr, const uint8_t *dst_skip = nullptr,
+                      const char *who = "mpg_handle_extrapolate");
+// k_handle_mask.hip: `out` (shape and method set by the caller, arrays empty) <- `in` under static masks (mpg_handle_mask); entry: the
+// resolved rule is MPG_MASKRULE_ENTRY (CSR only).  Arguments checked by the API entry point; blocking
+int mpg_k_handle_mask(mpg_handle_s *in, const uint8_t *src_mask, const uint8_t *dst_mask, bool entry, int norm_type, mpg_handle_s *out,
+                      hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

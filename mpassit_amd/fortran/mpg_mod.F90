@@ -59,6 +59,14 @@ module mpg
     integer(c_int) :: num_src_pnts     !< IDAVG: 1 .. MPG_EXTRAP_MAX_PNTS (ESMF's default 8)
     real(c_double) :: dist_exponent    !< IDAVG: finite and > 0 (ESMF's default 2.0)
   end type mpg_extrap_opts
+  !> mpg_handle_mask (include/mpassit_amd.h): the rule and the options
+  integer(c_int), parameter :: MPG_MASKRULE_AUTO = 0, MPG_MASKRULE_ROW = 1, MPG_MASKRULE_ENTRY = 2
+  type, bind(C) :: mpg_store_mask_opts
+    type(c_ptr) :: src_mask_dev        !< device bytes [n_src], non-zero = masked; c_null_ptr: none
+    type(c_ptr) :: dst_mask_dev        !< device bytes [n_dst], non-zero = masked; c_null_ptr: none
+    integer(c_int) :: rule             !< MPG_MASKRULE_*
+    integer(c_int) :: norm_type        !< ENTRY rule only: MPG_NORM_*, the one the Store was called with
+  end type mpg_store_mask_opts
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -593,6 +601,25 @@ module mpg
       integer(c_int), value :: staggerloc
       integer(c_int) :: rc
     end function mpg_grid_get_xyz
+    !> Store-time masks (srcMaskValues / dstMaskValues): static masks applied to a handle's pattern, and the extrapolation restricted to
+    !> the unmasked sources; both return a new handle (mpg_handle_release it).  Masks: device bytes, non-zero = masked, c_null_ptr = none
+    function mpg_handle_mask(rh, opts, out) bind(C, name="mpg_handle_mask") result(rc)
+      import :: c_int, c_ptr, mpg_store_mask_opts
+      type(c_ptr), value :: rh
+      type(mpg_store_mask_opts), intent(in) :: opts
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_mask
+    function mpg_handle_extrapolate_masked(rh, src, dst, opts, src_mask_dev, dst_skip_dev, out) &
+        bind(C, name="mpg_handle_extrapolate_masked") result(rc)
+      import :: c_int, c_ptr, mpg_points, mpg_extrap_opts
+      type(c_ptr), value :: rh
+      type(mpg_points), intent(in) :: src, dst
+      type(mpg_extrap_opts), intent(in) :: opts
+      type(c_ptr), value :: src_mask_dev, dst_skip_dev
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_extrapolate_masked
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

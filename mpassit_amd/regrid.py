@@ -17,7 +17,7 @@ from . import _lib as L
 from ._lib import (LAYOUT_CELL_FAST, LAYOUT_LEV_FAST, MESHLOC_ELEMENT, MESHLOC_NODE, MESHLOC_EDGE, REGRIDMETHOD_BILINEAR, REGRIDMETHOD_CONSERVE,
                    REGRIDMETHOD_NEAREST_STOD, STAGGERLOC_CENTER, STAGGERLOC_CORNER, STAGGERLOC_EDGE1, STAGGERLOC_EDGE2,
                    NORM_DSTAREA, NORM_FRACAREA, POLEMETHOD_NONE, POLEMETHOD_ALLAVG, EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG,
-                   EXTRAP_MAX_PNTS, check)
+                   EXTRAP_MAX_PNTS, MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY, check)
 
 __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "regrid_store", "regrid_store_grid", "regrid_store_begin", "regrid_store_grid_begin", "rotate_winds_cgrid", "wind_destagger", "regrid_autograd",
            "regrid_store_to_mesh", "regrid_to_mesh_autograd", "regrid_store_conserve_to_mesh", "regrid_csr_to_mesh_autograd", "NORM_DSTAREA",
@@ -30,7 +30,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
            "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights",
            "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd",
-           "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS"]
+           "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS",
+           "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY"]
 
 
 def _f64(a):
@@ -1886,3 +1887,74 @@ def extrapolate(rh, src, dst, method=EXTRAPMETHOD_NEAREST_STOD, num_src_pnts=8, 
     h = C.c_void_p()
     check(L.handle_extrapolate(rh._h if rh is not None else None, C.byref(ps), C.byref(pd), C.byref(opts), C.byref(h)))
     return RouteHandle(h)
+
+
+# ---- Store-time masks: ESMF's srcMaskValues / dstMaskValues as handle-to-handle calls ------------------------------------------------------
+def _mask_dev(m, n, who, name):
+    """A byte mask of n elements on the device (non-zero = masked) from numpy or torch, bool or uint8; a host mask is uploaded.  None stays
+    None.  -> the tensor (keep it alive over the call)."""
+    if m is None:
+        return None
+    import torch
+    if not _is_torch(m):
+        m = np.asarray(m)
+        if m.dtype not in (np.bool_, np.uint8):
+            raise ValueError("%s: %s must be bool or uint8" % (who, name))
+        m = torch.from_numpy(np.ascontiguousarray(m.reshape(-1)).astype(np.uint8))
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s: %s must be bool or uint8" % (who, name))
+    m = m.reshape(-1).contiguous()
+    if m.numel() != n:
+        raise ValueError("%s: %s has %d elements, the handle expects %d" % (who, name, m.numel(), n))
+    return m if m.is_cuda else m.cuda()
+
+
+def _mask_ptr(m):
+    return None if m is None or m.numel() == 0 else m.data_ptr()
+
+
+def mask_handle(rh, src_mask=None, dst_mask=None, rule=MASKRULE_AUTO, norm_type=NORM_DSTAREA):
+    """mpg_handle_mask (ESMF's srcMaskValues / dstMaskValues on a finished handle): a new RouteHandle of rh's shape and kind with static
+    masks applied to its pattern.  src_mask [n_src] / dst_mask [n_dst]: numpy or torch, bool or uint8, non-zero = masked (a host mask is
+    uploaded); None = no mask on that side.  A masked destination row becomes unmapped.  MASKRULE_ROW (bilinear, nearest): a row with a
+    stored entry on a masked source becomes unmapped.  MASKRULE_ENTRY (conservative, CSR only): the entries of masked sources are removed,
+    the rest renormalised by norm_type -- the one the Store was called with -- and dst_frac follows.  MASKRULE_AUTO picks by rh's method.
+    The bits of target_grid.mask_rows.  Not cached: release() it; rh may be released."""
+    ms = _mask_dev(src_mask, rh.n_src, "mask_handle", "src_mask")
+    md = _mask_dev(dst_mask, rh.n_dst, "mask_handle", "dst_mask")
+    opts = L.StoreMaskOpts(src_mask_dev=_mask_ptr(ms), dst_mask_dev=_mask_ptr(md), rule=int(rule), norm_type=int(norm_type))
+    h = C.c_void_p()
+    check(L.handle_mask(rh._h, C.byref(opts), C.byref(h)))
+    return RouteHandle(h)
+
+
+def extrapolate_masked(rh, src, dst, src_mask=None, dst_skip=None, method=EXTRAPMETHOD_NEAREST_STOD, num_src_pnts=8, dist_exponent=2.0,
+                       src_loc=None, dst_loc=None):
+    """mpg_handle_extrapolate_masked: extrapolate() with the candidates restricted to the sources whose src_mask is 0 -- K = min(N, unmasked
+    sources), ties to the lower unmasked id -- and the unmapped rows whose dst_skip is non-zero left unmapped.  Masks as in mask_handle.
+    With both masks None the bytes of extrapolate(); with every source masked nothing is filled.  The bits of
+    target_grid.extrapolate_rows_masked fed with src.xyz() / dst.xyz().  Not cached: release() it; rh may be released."""
+    ps, pd = _points(src, src_loc, "src"), _points(dst, dst_loc, "dst")
+    ms = _mask_dev(src_mask, rh.n_src, "extrapolate_masked", "src_mask")
+    md = _mask_dev(dst_skip, rh.n_dst, "extrapolate_masked", "dst_skip")
+    opts = L.ExtrapOpts(method=int(method), num_src_pnts=int(num_src_pnts), dist_exponent=float(dist_exponent))
+    h = C.c_void_p()
+    check(L.handle_extrapolate_masked(rh._h, C.byref(ps), C.byref(pd), C.byref(opts), _mask_ptr(ms), _mask_ptr(md), C.byref(h)))
+    return RouteHandle(h)
+
+
+def store_masks(rh, src, dst, src_mask=None, dst_mask=None, norm_type=NORM_DSTAREA, extrap_method=None, num_src_pnts=8, dist_exponent=2.0,
+                src_loc=None, dst_loc=None):
+    """ESMF_FieldRegridStore(srcMaskValues, dstMaskValues, extrapMethod, normType) on a finished handle: mask_handle (rule by rh's method),
+    then extrapolate_masked with the same source mask and dst_skip = dst_mask.  A NEAREST_STOD handle is always refilled with
+    EXTRAPMETHOD_NEAREST_STOD -- every unmasked destination takes the nearest UNMASKED source, which is ESMF's result; the other methods
+    are refilled with extrap_method only when it is set.  The intermediate handle is released.  Not cached: release() the result."""
+    masked = mask_handle(rh, src_mask, dst_mask, MASKRULE_AUTO, norm_type)
+    nearest = rh.nnz_per_row == 1        # one slot per row: the nearest Stores' handles and no others (mpg_handle_info)
+    if not nearest and extrap_method is None:
+        return masked
+    try:
+        return extrapolate_masked(masked, src, dst, src_mask, dst_mask, EXTRAPMETHOD_NEAREST_STOD if nearest else extrap_method, num_src_pnts,
+                                  dist_exponent, src_loc, dst_loc)
+    finally:
+        masked.release()

@@ -463,6 +463,86 @@ def extrapolate_rows(src_xyz, dst_xyz, unmapped, method=EXTRAPMETHOD_NEAREST_STO
     return rowlen, ids, w
 
 
+MASKRULE_ROW, MASKRULE_ENTRY = 1, 2
+NORM_DSTAREA, NORM_FRACAREA = 0, 1
+
+
+def mask_rows(rowptr, col, val, frac, src_mask, dst_mask, rule, norm_type=NORM_DSTAREA):
+    """The numpy mirror of mpg_handle_mask on a CSR pattern (a fixed handle: fixed_to_csr of its weights(); its rows that come back empty
+    are the ones the call writes as idx -1, w +0.0).  frac: dst_frac [n] or None; src_mask / dst_mask: bool or uint8, None = no mask;
+    rule: MASKRULE_ROW or MASKRULE_ENTRY (no AUTO here: a pattern records no method).
+    A destination-masked row is empty (frac' +0.0).  ROW: a row with an entry on a masked source is empty (frac' +0.0), every other row is
+    copied.  ENTRY: the entries of masked sources go; Wk = ((0.0 + v_0) + v_1) + ... over the kept values in stored order; DSTAREA: values
+    unchanged, frac' = Wk; FRACAREA: w' = w / Wk, frac' = frac * Wk; nothing kept or not Wk > 0: empty, frac' = +0.0; a row with no masked
+    entry is copied verbatim with its frac.
+    -> (rowptr int64, col int32, val, frac' or None, stats): stats = [mapped rows the source rule unmapped, mapped rows the destination
+    mask unmapped, entries removed], mpg_handle_store_stats [1..3]."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64).reshape(-1)
+    val = np.asarray(val, dtype=np.float64).reshape(-1)
+    n = rowptr.size - 1
+    if rule not in (MASKRULE_ROW, MASKRULE_ENTRY):
+        raise ValueError("mask_rows: rule must be MASKRULE_ROW or MASKRULE_ENTRY")
+    if rule == MASKRULE_ENTRY and norm_type not in (NORM_DSTAREA, NORM_FRACAREA):
+        raise ValueError("mask_rows: unknown norm_type")
+    sm = np.zeros(int(col.max()) + 1 if col.size else 0, bool) if src_mask is None else np.asarray(src_mask).reshape(-1) != 0
+    dm = np.zeros(n, bool) if dst_mask is None else np.asarray(dst_mask).reshape(-1) != 0
+    had = np.diff(rowptr)
+    row = np.repeat(np.arange(n), had)
+    hit = sm[col]                                                   # per entry: its source is masked
+    nhit = np.bincount(row, weights=hit, minlength=n).astype(np.int64)
+    fin = np.zeros(n) if frac is None else np.asarray(frac, dtype=np.float64).reshape(-1)
+    fout = fin.copy()
+    keep = ~dm[row]
+    newval = val.copy()
+    if rule == MASKRULE_ROW:
+        keep &= (nhit == 0)[row]
+    else:
+        keep &= ~hit
+        # Wk per row over the kept entries, left to right: pass t adds every row's t-th kept entry
+        live = ~hit
+        rank = np.cumsum(live) - 1
+        first = np.concatenate([[0], np.cumsum(np.bincount(row, weights=live, minlength=n).astype(np.int64))])[:-1]
+        rank = rank - first[row]                                     # position among the row's kept entries (meaningful where live)
+        nkept = had - nhit
+        Wk = np.zeros(n)
+        for t in range(int(nkept.max()) if n else 0):
+            sel = np.flatnonzero(live & (rank == t))
+            Wk[row[sel]] = Wk[row[sel]] + val[sel]
+        touched = nhit > 0
+        dead = touched & ((nkept == 0) | ~(Wk > 0.0))
+        keep &= ~dead[row]
+        scale = touched & ~dead
+        if norm_type == NORM_FRACAREA:
+            with np.errstate(all="ignore"):
+                newval = np.where(scale[row], val / np.where(scale, Wk, 1.0)[row], val)
+            fout = np.where(scale, fin * Wk, fout)
+        else:
+            fout = np.where(scale, Wk, fout)
+        fout = np.where(dead, 0.0, fout)
+    now = np.bincount(row, weights=keep, minlength=n).astype(np.int64)
+    if rule == MASKRULE_ROW:
+        fout = np.where((had > 0) & (now == 0) & ~dm, 0.0, fout)
+    fout = np.where(dm, 0.0, fout)
+    out_rowptr = np.concatenate([[0], np.cumsum(now)]).astype(np.int64)
+    stats = [int(((had > 0) & (now == 0) & ~dm).sum()), int(((had > 0) & dm).sum()), int(had.sum() - now.sum())]
+    return out_rowptr, col[keep].astype(np.int32), np.ascontiguousarray(newval[keep]), (None if frac is None else fout), stats
+
+
+def extrapolate_rows_masked(src_xyz, dst_xyz, unmapped, src_mask, method=EXTRAPMETHOD_NEAREST_STOD, num_src_pnts=8, dist_exponent=2.0):
+    """The numpy mirror of mpg_handle_extrapolate_masked's new rows, by brute force: extrapolate_rows over the compacted unmasked sources
+    (ascending id, so the (d2, id) order and its ties are those of the unmasked ids), the ids mapped back.  src_mask: bool or uint8 of
+    n_src, None = nothing masked.  `unmapped`: the rows to fill -- the caller leaves the dst_skip rows out.  K = min(N, unmasked sources);
+    with every source masked the rows come back with length 0.  -> (rowlen, ids, w) as extrapolate_rows."""
+    src_xyz = np.asarray(src_xyz, np.float64)
+    if src_mask is None:
+        return extrapolate_rows(src_xyz, dst_xyz, unmapped, method, num_src_pnts, dist_exponent)
+    live = np.flatnonzero(np.asarray(src_mask).reshape(-1) == 0)
+    rowlen, ids, w = extrapolate_rows(src_xyz[:, live], dst_xyz, unmapped, method, num_src_pnts, dist_exponent)
+    back = np.where(ids >= 0, live[np.maximum(ids, 0)] if live.size else -1, -1).astype(np.int32) if ids.size else ids
+    return rowlen, back, w
+
+
 _COMPOSE_VECTOR_PASSES = 64   # terms of an entry of C summed by vectorised passes; what lies behind them is summed by a plain loop
 
 
