@@ -39,6 +39,7 @@ enum {
 
 /* ESMF_REGRIDMETHOD_* (interp.F90:119,204,370,420) */
 enum { MPG_REGRIDMETHOD_BILINEAR = 0, MPG_REGRIDMETHOD_CONSERVE = 1, MPG_REGRIDMETHOD_NEAREST_STOD = 2 };
+enum { MPG_REGRIDMETHOD_PATCH = 3 };   /* the method of mpg_handle_patch's handles; no Store takes it */
 /* ESMF_MESHLOC_* (input_data.F90:927,1116-1123) */
 enum { MPG_MESHLOC_ELEMENT = 0, MPG_MESHLOC_NODE = 1, MPG_MESHLOC_EDGE = 2 };   /* EDGE: a destination only, after mpg_mesh_set_edges */
 /* ESMF_STAGGERLOC_* (interp.F90:480,489,509; model_grid.F90:706-728) */
@@ -1083,6 +1084,62 @@ typedef struct mpg_store_mask_opts {
 int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *out);
 int mpg_handle_extrapolate_masked(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_extrap_opts *opts,
                                   const uint8_t *src_mask_dev, const uint8_t *dst_skip_dev, mpg_handle *out);
+
+/* ---- patch regridding: second-degree patch recovery as a CSR handle -------------------------------------------------------------------------
+ * ESMF_REGRIDMETHOD_PATCH, the method the reference names its main route handle after (rh_patch, interp.F90:123,207) and then stores
+ * bilinearly.  mpg_handle_patch turns a finished bilinear handle into a patch handle: per source node a second-degree polynomial is fitted
+ * by least squares through the node's neighbours, per destination point the polynomials of its bilinear row's nodes are blended with the
+ * bilinear weights.  Third-order fields at rows of about 12 entries instead of 3.  The result is an ordinary CSR handle, which every
+ * consumer takes; the call needs no new search and serves Mesh -> Grid, Mesh -> Mesh, Grid -> Mesh and Grid -> Grid at once.
+ *
+ * rh: a fixed bilinear handle of S = 3 or 4 slots (mpg_regrid_store from elements, mpg_regrid_store_mesh, mpg_regrid_store_to_mesh,
+ *   mpg_regrid_store_grid).  src / dst: the point sets the handle was stored between, by the mpg_points rules and size checks of
+ *   mpg_handle_extrapolate (sources: a mesh's cells or a grid stagger).
+ * The rule.  Every operation is rounded on its own (fp contract(off)); the only operations are + - * / sqrt.
+ *   Unit vectors: X is the stored unit vector of a point, the bits mpg_mesh_get_xyz / mpg_grid_get_xyz export.
+ *   Ring-1 patch of a source node c, N1(c), in ascending id.  Mesh cells: c together with the three cells of every valid dual triangle
+ *     (mpg_mesh_get_triangles: no -1 in its column) of every listed vertex of c (the non-zero entries of c's verticesOnCell row).  Grid
+ *     stagger of snx x sny points, id = j * snx + i: the window [i0, i0 + 2] x [j0, j0 + 2] cut to the grid, i0 = clamp(i - 1, 0,
+ *     max(snx - 3, 0)), j0 likewise: border nodes keep a full 3 x 3 block.
+ *   Ring-2 patch, meshes only: N2(c) = the union of N1(d) over d in N1(c), in ascending id.
+ *   A patch is used only when it holds at most MPG_PATCH_MAX_PNTS points (N1 as well as N2).
+ *   Local coordinates about c: n = X_c; a = the unit axis of n's smallest |component|, the lowest axis on ties; t = a - (a . n) n;
+ *     e1 = t / sqrt(t . t); e2 = n x e1 = (n_y e1_z - n_z e1_y, n_z e1_x - n_x e1_z, n_x e1_y - n_y e1_x).  For a point q: d = X_q - X_c,
+ *     h = sqrt(max over the patch of d . d), u = (d . e1) / h, v = (d . e2) / h; the destination point p is mapped the same way (an
+ *     orthographic projection).  Dot products are (x*x' + y*y') + z*z'.
+ *   The fit: phi = (1, u, v, u*u, u*v, v*v) for degree 2, (1, u, v) for degree 1.  G = sum_k phi(q_k) phi(q_k)^T, every element summed in
+ *     patch order from 0.0.  G = R^T R by a Cholesky with left-to-right inner products: for k = 0, 1, ...: s_k = G_kk - R_0k R_0k - ... -
+ *     R_(k-1)k R_(k-1)k, R_kk = sqrt(s_k), and for j > k: R_kj = (G_kj - R_0k R_0j - ... - R_(k-1)k R_(k-1)j) / R_kk, each subtraction
+ *     in that order.  An attempt passes when h > 0 and every pivot s_k > 2^-26 * G_kk: a definition, not a tuning constant.
+ *   Attempts, in this order: (A) degree 2 on N1 if |N1| >= 6; (B) degree 2 on N2, on a mesh with 6 <= |N2| <= MPG_PATCH_MAX_PNTS;
+ *     (C) degree 1 on N1 if |N1| >= 3; (D) degree 0: the node itself with value 1.  The attempt is a property of the node alone.
+ *   Shape values: R^T z = phi(p) by forward substitution (z_k = (phi_k - R_0k z_0 - ... - R_(k-1)k z_(k-1)) / R_kk), R y = z by back
+ *     substitution (y_k = (z_k - R_k(k+1) y_(k+1) - ... ) / R_kk, the terms in ascending column order); L_k = sum_a phi_a(q_k) * y_a from
+ *     0.0 in basis order.
+ *   A row: for a mapped destination point with slots (c_s, b_s), s = 0 .. S - 1, every slot with an index >= 0 takes part, whatever its
+ *     weight.  The row's columns are the distinct ids of the slots' patches, in ascending order; a column's value is acc = acc + (b_s *
+ *     L_(s,k)) from 0.0 over (slot, patch position) in ascending order.  Zero values stay in the row: the pattern does not depend on the
+ *     values.  An unmapped row (slot 0's index < 0) is empty.
+ *   A contract by identity with the numpy mirror target_grid.patch_rows; mpassit_amd/csrc/patch.h is the arithmetic, for device and host.
+ * Output: a new CSR handle with the input's n_src, n_dst, nx_dst and ny_dst; its method is MPG_REGRIDMETHOD_PATCH.  It has no dst_frac; its
+ *   longest row is recorded.  It is not cached and owns its arrays: pair it with mpg_handle_release; rh may be released right after the
+ *   call.  mpg_handle_store_ms is the GPU time of the call.  mpg_handle_store_stats: [1] is the number of rows written, [2] .. [5] are the
+ *   (row, slot) pairs served by attempts A, B, C and D, [6] is the longest row.
+ * Determinism: the same bytes from run to run; no floating-point atomics.
+ * Blocking: the call allocates, reads the entry count back (its only host round trip) and drains the Store worker first.  It orders itself
+ *   after whatever produced rh, as mpg_handle_get_csr does.
+ * Order with the other handle calls: patch first, then mpg_handle_mask / mpg_handle_extrapolate (a polynomial evaluated far outside its
+ *   patch is not an extrapolation).  MPG_MASKRULE_AUTO picks MPG_MASKRULE_ROW for method MPG_REGRIDMETHOD_PATCH.  The Stores go on refusing
+ *   method 3.
+ * Refusals, each with a message that names mpg_handle_patch and the way out.  MPG_ERR_INVALID_ARG: a NULL argument; a point set that
+ *   breaks the mpg_points rules; sizes that differ from the handle's (both numbers are printed); a source mesh location other than
+ *   ELEMENT; a handle whose method is not MPG_REGRIDMETHOD_BILINEAR.  MPG_ERR_UNSUPPORTED: a CSR or 1-slot handle; a handle with pole terms
+ *   (mpg_handle_pole_count > 0); a localized or rebased handle; a handle whose mesh carries a source window; a mesh of
+ *   mpg_mesh_create_window; a source grid with MPG_GRID_PERIODIC_I.  MPG_ERR_OVERFLOW: more than 2^31 - 2 entries.  A failed allocation
+ *   returns its error and leaks nothing.
+ * Not served: periodic sources, node-located sources, CSR inputs, a _begin variant, caching. */
+#define MPG_PATCH_MAX_PNTS 32
+int mpg_handle_patch(mpg_handle rh, const mpg_points *src, const mpg_points *dst, mpg_handle *out);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

@@ -38,6 +38,7 @@ SYMBOLS = [
     "mpg_regrid_masked_transpose_dev",
     "mpg_handle_extrapolate", "mpg_mesh_get_xyz", "mpg_grid_get_xyz",
     "mpg_handle_mask", "mpg_handle_extrapolate_masked",
+    "mpg_handle_patch",
 ]
 
 MPG_SUCCESS = 0
@@ -56,6 +57,9 @@ POLEMETHOD_NONE, POLEMETHOD_ALLAVG = MPG_POLEMETHOD_NONE, MPG_POLEMETHOD_ALLAVG
 MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG = 1, 2
 EXTRAPMETHOD_NEAREST_STOD, EXTRAPMETHOD_NEAREST_IDAVG = MPG_EXTRAPMETHOD_NEAREST_STOD, MPG_EXTRAPMETHOD_NEAREST_IDAVG
 EXTRAP_MAX_PNTS = 8
+MPG_REGRIDMETHOD_PATCH = 3   # the method of mpg_handle_patch's handles; no Store takes it
+REGRIDMETHOD_PATCH = MPG_REGRIDMETHOD_PATCH
+PATCH_MAX_PNTS = 32
 MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY = 0, 1, 2
 MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY = MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY
 
@@ -467,6 +471,18 @@ def handle_extrapolate_masked(*args):
     if "handle_extrapolate_masked" not in _to_mesh_fns:
         _to_mesh_fns["handle_extrapolate_masked"] = _HANDLE_EXTRAPOLATE_MASKED_PROTO(("mpg_handle_extrapolate_masked", load()))
     return _to_mesh_fns["handle_extrapolate_masked"](*args)
+
+
+# Patch regridding (include/mpassit_amd.h): a fixed bilinear handle turned into the CSR handle of second-degree patch recovery
+#   mpg_handle_patch(rh, src, dst, out)
+_HANDLE_PATCH_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Points), C.POINTER(Points), C.c_void_p)
+
+
+def handle_patch(*args):
+    """The typed binding of mpg_handle_patch; returns the call's status code."""
+    if "handle_patch" not in _to_mesh_fns:
+        _to_mesh_fns["handle_patch"] = _HANDLE_PATCH_PROTO(("mpg_handle_patch", load()))
+    return _to_mesh_fns["handle_patch"](*args)
 
 
 _lib = None

@@ -15,6 +15,7 @@
 
 #include "compose_checks.h"
 #include "mpg_internal.h"
+#include "patch.h"
 #include "wind_reconstruct_checks.h"
 #include "wind_vector_checks.h"
 
@@ -130,7 +131,7 @@ void mpg_pool_release() {
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
   X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
-  X(k_handle_mask)
+  X(k_handle_mask) X(k_patch)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1776,7 +1777,7 @@ int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *
           "mpg_handle_mask: unknown rule: MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW or MPG_MASKRULE_ENTRY");
   int rule = opts->rule;
   if (rule == MPG_MASKRULE_AUTO) {
-    if (rh->method == MPG_REGRIDMETHOD_BILINEAR || rh->method == MPG_REGRIDMETHOD_NEAREST_STOD) rule = MPG_MASKRULE_ROW;
+    if (rh->method == MPG_REGRIDMETHOD_BILINEAR || rh->method == MPG_REGRIDMETHOD_NEAREST_STOD || rh->method == MPG_REGRIDMETHOD_PATCH) rule = MPG_MASKRULE_ROW;
     else if (rh->method == MPG_REGRIDMETHOD_CONSERVE) rule = MPG_MASKRULE_ENTRY;
     else {
       mpg_set_error("mpg_handle_mask: MPG_MASKRULE_AUTO follows the handle's regrid method, and this handle records none (from weights, "
@@ -1830,6 +1831,112 @@ int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *
     if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
     if (he != hipSuccess) {
       mpg_set_error("mpg_handle_mask: %s", hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+// ---- patch regridding: a fixed bilinear handle turned into the CSR handle of second-degree patch recovery (k_patch.hip, patch.h) ------------
+int mpg_handle_patch(mpg_handle rh, const mpg_points *src, const mpg_points *dst, mpg_handle *out) {
+  const char *who = "mpg_handle_patch";
+  MPG_CHECK_INIT();
+  if (!(rh && src && dst && out)) {
+    mpg_set_error("%s: NULL argument (rh, src, dst and out are all mandatory)", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  int rc;
+  int64_t ns = 0, nd = 0;
+  int sx = 0, sy = 0, dx = 0, dy = 0;
+  const PointSet *sp = nullptr, *dp = nullptr;
+  if ((rc = ex_points(who, "source", src, true, &ns, &sx, &sy, &sp)) || (rc = ex_points(who, "destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
+  if (rh->method != MPG_REGRIDMETHOD_BILINEAR) {
+    mpg_set_error("%s: the handle's method is %d, not MPG_REGRIDMETHOD_BILINEAR: the patch rule blends the polynomials of a bilinear "
+                  "row's nodes -- store bilinear, then patch", who, rh->method);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (rh->kind != MPG_KIND_FIXED || (rh->nnz_per_row != 3 && rh->nnz_per_row != 4) || !rh->w.p) {
+    mpg_set_error("%s: a %s handle is not served: the rule reads the 3 or 4 slots of a fixed bilinear handle (mpg_regrid_store, _store_mesh, "
+                  "_store_to_mesh, _store_grid) -- patch first, then mpg_handle_mask / mpg_handle_extrapolate", who,
+                  rh->kind == MPG_KIND_CSR ? "CSR" : "1-slot");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->mesh && src->mesh->geo_grid) {
+    mpg_set_error("%s: the source mesh was cut to a grid (mpg_mesh_create_window): the patches need every cell's vertices and triangles "
+                  "-- use the whole mesh (mpg_mesh_create)", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_pole > 0) {
+    mpg_set_error("%s: the handle has pole terms (mpg_handle_pole_count > 0), which a patch handle cannot carry: store with "
+                  "MPG_POLEMETHOD_NONE, or patch a non-periodic handle", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->localized) {
+    mpg_set_error("%s: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no "
+                  "longer source ids -- patch first, re-index the result", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (mpg_handle_is_windowed(rh) || (src->mesh && src->mesh->win_count[MPG_MESHLOC_ELEMENT] >= 0)) {
+    mpg_set_error("%s: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
+                  "window-relative -- reset the window to the whole mesh first", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->grid && (src->grid->periodic & MPG_GRID_PERIODIC_I)) {
+    mpg_set_error("%s: a source grid with MPG_GRID_PERIODIC_I is not served (the 3 x 3 windows do not wrap in i and know no pole): "
+                  "create the grid without the flag, or regrid bilinearly", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_src != ns) {
+    mpg_set_error("%s: the handle has n_src = %lld, the source point set has %lld points (a node-located handle has "
+                  "no source set here)", who, (long long)rh->n_src, (long long)ns);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (rh->n_dst != nd || rh->nx_dst != dx || rh->ny_dst != dy) {
+    mpg_set_error("%s: the handle has n_dst = %lld (%d x %d), the destination point set has %lld points (%d x %d)", who,
+                  (long long)rh->n_dst, rh->nx_dst, rh->ny_dst, (long long)nd, dx, dy);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (ns > 0x7fffffffLL) {
+    mpg_set_error("%s: %lld source points are beyond int32 ids", who, (long long)ns);
+    return MPG_ERR_OVERFLOW;
+  }
+  PtSrc ps;
+  ps.x = sp->x.p; ps.y = sp->y.p; ps.z = sp->z.p;
+  ps.voc = nullptr; ps.tri = nullptr; ps.maxEdges = 0; ps.nV = 0; ps.snx = sx; ps.sny = sy;
+  if (src->mesh) {
+    ps.voc = src->mesh->voc.p; ps.tri = src->mesh->tri.p; ps.maxEdges = src->mesh->maxEdges; ps.nV = src->mesh->nVertices;
+  }
+  // rh is finished (a Store waits for its build before it hands its handle out); a begun Store may still allocate on the worker
+  store_worker_drain();
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = MPG_REGRIDMETHOD_PATCH;
+  h->n_src = rh->n_src;
+  h->n_dst = rh->n_dst;
+  h->nx_dst = rh->nx_dst;
+  h->ny_dst = rh->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("%s: hipEventCreate failed", who);
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_patch(rh, ps, *dp, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("%s: %s", who, hipGetErrorString(he));
       rc = MPG_ERR_HIP;
     }
   }

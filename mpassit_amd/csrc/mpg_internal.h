@@ -523,6 +523,11 @@ int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_gr
 // resolved rule is MPG_MASKRULE_ENTRY (CSR only).  Arguments checked by the API entry point; blocking
 int mpg_k_handle_mask(mpg_handle_s *in, const uint8_t *src_mask, const uint8_t *dst_mask, bool entry, int norm_type, mpg_handle_s *out,
                       hipStream_t s);
+// k_patch.hip: `out` (shape and method set by the caller, arrays empty) <- the patch rule on `in`, a fixed bilinear handle of 3 or 4 slots;
+// src: its source points with what their patches are read from (patch.h), dst: its in->n_dst destination points.  Arguments checked by the
+// API entry point; blocking: it allocates and reads the entry count back
+struct PtSrc;
+int mpg_k_patch(mpg_handle_s *in, const PtSrc &src, const PointSet &dst, mpg_handle_s *out, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

@@ -59,6 +59,9 @@ module mpg
     integer(c_int) :: num_src_pnts     !< IDAVG: 1 .. MPG_EXTRAP_MAX_PNTS (ESMF's default 8)
     real(c_double) :: dist_exponent    !< IDAVG: finite and > 0 (ESMF's default 2.0)
   end type mpg_extrap_opts
+  !> mpg_handle_patch (include/mpassit_amd.h): the method of its handles (no Store takes it) and the largest patch
+  integer(c_int), parameter :: MPG_REGRIDMETHOD_PATCH = 3
+  integer(c_int), parameter :: MPG_PATCH_MAX_PNTS = 32
   !> mpg_handle_mask (include/mpassit_amd.h): the rule and the options
   integer(c_int), parameter :: MPG_MASKRULE_AUTO = 0, MPG_MASKRULE_ROW = 1, MPG_MASKRULE_ENTRY = 2
   type, bind(C) :: mpg_store_mask_opts
@@ -620,6 +623,14 @@ module mpg
       type(c_ptr), intent(out) :: out
       integer(c_int) :: rc
     end function mpg_handle_extrapolate_masked
+    !> patch regridding: a fixed bilinear handle turned into the CSR handle of second-degree patch recovery (the driver does not use it)
+    function mpg_handle_patch(rh, src, dst, out) bind(C, name="mpg_handle_patch") result(rc)
+      import :: c_int, c_ptr, mpg_points
+      type(c_ptr), value :: rh
+      type(mpg_points), intent(in) :: src, dst
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_patch
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -31,7 +31,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "reconstruct_store", "reconstruct_weights", "wind_reconstruct", "wind_reconstruct_autograd", "compose", "compose_weights",
            "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd",
            "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS",
-           "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY"]
+           "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY",
+           "patch", "regrid_store_patch", "REGRIDMETHOD_PATCH", "PATCH_MAX_PNTS"]
 
 
 def _f64(a):
@@ -1958,3 +1959,42 @@ def store_masks(rh, src, dst, src_mask=None, dst_mask=None, norm_type=NORM_DSTAR
                                   dist_exponent, src_loc, dst_loc)
     finally:
         masked.release()
+
+
+# ---- patch regridding: second-degree patch recovery as a CSR handle -------------------------------------------------------------------------
+REGRIDMETHOD_PATCH, PATCH_MAX_PNTS = L.REGRIDMETHOD_PATCH, L.PATCH_MAX_PNTS
+
+
+def patch(rh, src, dst, src_loc=None, dst_loc=None):
+    """mpg_handle_patch (ESMF_REGRIDMETHOD_PATCH): a new CSR RouteHandle of rh's shape in which every source node of a bilinear row is
+    replaced by the second-degree least-squares polynomial through its neighbours, blended with the row's bilinear weights.  rh: a fixed
+    bilinear handle of 3 or 4 slots; src / dst: the Mesh or Grid objects rh was stored between; src_loc / dst_loc: a mesh location or a
+    stagger (default MESHLOC_ELEMENT / STAGGERLOC_CENTER; a source mesh takes part with its cells only).  store_stats: [1] rows written,
+    [2..5] (row, slot) pairs served by attempts A, B, C, D, [6] the longest row.  The bits of target_grid.patch_rows fed with
+    rh.weights(), src.xyz() / dst.xyz() and patch_neighbours_mesh / _grid.  Patch first, then mask_handle / extrapolate.  Not cached:
+    release() it; rh may be released."""
+    ps, pd = _points(src, src_loc, "src"), _points(dst, dst_loc, "dst")
+    h = C.c_void_p()
+    check(L.handle_patch(rh._h if rh is not None else None, C.byref(ps), C.byref(pd), C.byref(h)))
+    return RouteHandle(h)
+
+
+def regrid_store_patch(src, dst, src_loc=None, dst_loc=None):
+    """Store bilinear, patch, release: the patch handle between src and dst (Mesh or Grid each; src is dst for the CENTER -> EDGE1 / EDGE2
+    handles of one grid, with dst_loc the destination stagger).  The bilinear handle goes back to the Store cache.  Not cached itself:
+    release() the result."""
+    if isinstance(src, Mesh) and isinstance(dst, Grid):
+        rh = regrid_store(src, dst, REGRIDMETHOD_BILINEAR, STAGGERLOC_CENTER if dst_loc is None else dst_loc)
+    elif isinstance(src, Mesh) and isinstance(dst, Mesh):
+        rh = regrid_store_mesh(src, dst, REGRIDMETHOD_BILINEAR, MESHLOC_ELEMENT, MESHLOC_ELEMENT if dst_loc is None else dst_loc)
+    elif isinstance(src, Grid) and isinstance(dst, Mesh):
+        rh = regrid_store_to_mesh(src, dst, REGRIDMETHOD_BILINEAR, STAGGERLOC_CENTER if src_loc is None else src_loc,
+                                  MESHLOC_ELEMENT if dst_loc is None else dst_loc)
+    elif isinstance(src, Grid) and src is dst:
+        rh = regrid_store_grid(src, STAGGERLOC_EDGE1 if dst_loc is None else dst_loc, STAGGERLOC_CENTER if src_loc is None else src_loc)
+    else:
+        raise ValueError("regrid_store_patch: src and dst must be Mesh or Grid objects (Grid -> Grid: the staggers of ONE grid)")
+    try:
+        return patch(rh, src, dst, src_loc, dst_loc)
+    finally:
+        rh.release()

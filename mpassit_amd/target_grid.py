@@ -543,6 +543,258 @@ def extrapolate_rows_masked(src_xyz, dst_xyz, unmapped, src_mask, method=EXTRAPM
     return rowlen, back, w
 
 
+REGRIDMETHOD_PATCH = 3
+PATCH_MAX_PNTS = 32
+_PATCH_NONE = np.iinfo(np.int64).max
+_PATCH_TOL = 2.0 ** -26
+
+
+def _patch_pack(cand):
+    """Rows of candidate ids (_PATCH_NONE = no candidate) -> (nbr [n][K] int32 ascending and distinct, -1 behind a row's end;
+    cnt [n], PATCH_MAX_PNTS + 1 for a row that holds more than PATCH_MAX_PNTS)."""
+    cand = np.sort(np.asarray(cand, np.int64), axis=1)
+    dup = np.zeros(cand.shape, bool)
+    dup[:, 1:] = cand[:, 1:] == cand[:, :-1]
+    cand[dup] = _PATCH_NONE
+    cand = np.sort(cand, axis=1)
+    cnt = (cand != _PATCH_NONE).sum(axis=1)
+    width = min(max(int(cnt.max()) if cnt.size else 1, 1), PATCH_MAX_PNTS)
+    head = cand[:, :width]
+    return np.where(head != _PATCH_NONE, head, -1).astype(np.int32), np.minimum(cnt, PATCH_MAX_PNTS + 1)
+
+
+def patch_neighbours_mesh(voc, tri):
+    """The ring-1 patches of a mesh's cells for patch_rows.  voc: verticesOnCell [nCells][maxEdges], 1-based and 0-padded; tri: the dual
+    triangles [nVertices][3] (Mesh.triangles(): cell ids, -1 = none).  N1(c) = c and the three cells of every valid triangle of every
+    listed vertex of c, ascending.  -> (nbr [nCells][K] int32 with -1 behind a row's end, cnt [nCells], True): True = a mesh, whose nodes
+    may fall back on the ring-2 patch."""
+    voc = np.asarray(voc, np.int64)
+    tri = np.asarray(tri, np.int64).reshape(-1, 3)
+    nC, mE = voc.shape
+    v = voc - 1
+    listed = (v >= 0) & (v < tri.shape[0])
+    t = tri[np.where(listed, v, 0)]
+    ok = listed & (t >= 0).all(axis=2)
+    cand = np.where(ok[:, :, None], t, _PATCH_NONE).reshape(nC, mE * 3)
+    nbr, cnt = _patch_pack(np.concatenate([np.arange(nC, dtype=np.int64)[:, None], cand], axis=1))
+    return nbr, cnt, True
+
+
+def patch_neighbours_grid(snx, sny):
+    """The ring-1 patches of a grid stagger of snx x sny points, id = j * snx + i: the window [i0, i0 + 2] x [j0, j0 + 2] cut to the grid,
+    i0 = clamp(i - 1, 0, max(snx - 3, 0)), j0 likewise.  -> (nbr [n][K] int32, cnt [n], False): no ring-2 patch on a grid."""
+    snx, sny = int(snx), int(sny)
+    j, i = np.divmod(np.arange(snx * sny, dtype=np.int64), snx)
+    i0, j0 = np.clip(i - 1, 0, max(snx - 3, 0)), np.clip(j - 1, 0, max(sny - 3, 0))
+    cols = []
+    for dj in range(3):
+        for di in range(3):
+            a, b = i0 + di, j0 + dj
+            cols.append(np.where((a < snx) & (b < sny), b * snx + a, _PATCH_NONE))
+    nbr, cnt = _patch_pack(np.stack(cols, axis=1))
+    return nbr, cnt, False
+
+
+def _patch_dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _patch_frame(X):
+    """e1, e2 [3][m] of the frames about the unit vectors X [3][m], patch.h's pt_frame."""
+    ax = np.argmin(np.abs(X), axis=0)                       # the lowest axis on ties
+    a = [(ax == k).astype(np.float64) for k in range(3)]
+    s = _patch_dot(a, X)
+    t = [a[k] - s * X[k] for k in range(3)]
+    r = np.sqrt(_patch_dot(t, t))
+    e1 = [t[k] / r for k in range(3)]
+    e2 = [X[1] * e1[2] - X[2] * e1[1], X[2] * e1[0] - X[0] * e1[2], X[0] * e1[1] - X[1] * e1[0]]
+    return e1, e2
+
+
+def _patch_phi(u, v, M):
+    return [np.ones_like(u), u, v] + ([u * u, u * v, v * v] if M == 6 else [])
+
+
+def _patch_uv(X, e1, e2, h, Q, gnomonic=False):
+    if gnomonic:                                            # (a mutant of the tests: the point scaled onto the tangent plane first)
+        qn = _patch_dot(Q, X)
+        Q = [Q[k] / qn for k in range(3)]
+    d = [Q[k] - X[k] for k in range(3)]
+    return _patch_dot(d, e1) / h, _patch_dot(d, e2) / h
+
+
+def _patch_fit(src_xyz, nodes, pat, M, gnomonic=False):
+    """pt_fit<M> of patch.h for the nodes [m] on their patches pat [m][K] (-1 = none) -> (passes [m], fit): frame, h, G summed in patch
+    order, the thresholded Cholesky in place."""
+    m, K = pat.shape
+    X = [src_xyz[k][nodes] for k in range(3)]
+    e1, e2 = _patch_frame(X)
+    valid = pat >= 0
+    safe = np.where(valid, pat, 0)
+    hm = np.zeros(m)
+    for k in range(K):
+        d = [src_xyz[c][safe[:, k]] - X[c] for c in range(3)]
+        dd = _patch_dot(d, d)
+        hm = np.where(valid[:, k] & (dd > hm), dd, hm)
+    h = np.sqrt(hm)
+    R = [[np.zeros(m) for _ in range(M)] for _ in range(M)]
+    for k in range(K):
+        u, v = _patch_uv(X, e1, e2, h, [src_xyz[c][safe[:, k]] for c in range(3)], gnomonic)
+        phi = _patch_phi(u, v, M)
+        for a in range(M):
+            for b in range(a, M):
+                R[a][b] = np.where(valid[:, k], R[a][b] + phi[a] * phi[b], R[a][b])
+    ok = h > 0.0
+    for k in range(M):
+        g = R[k][k]
+        p = g
+        for i in range(k):
+            p = p - R[i][k] * R[i][k]
+        ok = ok & (p > _PATCH_TOL * g)
+        r = np.sqrt(p)
+        R[k][k] = r
+        for j in range(k + 1, M):
+            t = R[k][j]
+            for i in range(k):
+                t = t - R[i][k] * R[i][j]
+            R[k][j] = t / r
+    return ok, (X, e1, e2, h, R)
+
+
+def _patch_shape(src_xyz, fit, sel, pat, P, M, gnomonic=False):
+    """pt_shape<M> of patch.h: fit rows `sel` (one per pair), their patches pat [n][K], the destination points P [3][n] -> L [n][K]."""
+    X, e1, e2, h, R = fit
+    X, e1, e2, h = [x[sel] for x in X], [x[sel] for x in e1], [x[sel] for x in e2], h[sel]
+    R = [[R[a][b][sel] for b in range(M)] for a in range(M)]
+    u, v = _patch_uv(X, e1, e2, h, P, gnomonic)
+    y = _patch_phi(u, v, M)
+    for k in range(M):
+        t = y[k]
+        for i in range(k):
+            t = t - R[i][k] * y[i]
+        y[k] = t / R[k][k]
+    for k in range(M - 1, -1, -1):
+        t = y[k]
+        for j in range(k + 1, M):
+            t = t - R[k][j] * y[j]
+        y[k] = t / R[k][k]
+    n, K = pat.shape
+    safe = np.where(pat >= 0, pat, 0)
+    L = np.zeros((n, K))
+    for k in range(K):
+        u, v = _patch_uv(X, e1, e2, h, [src_xyz[c][safe[:, k]] for c in range(3)], gnomonic)
+        phi = _patch_phi(u, v, M)
+        acc = np.zeros(n)
+        for a in range(M):
+            acc = acc + phi[a] * y[a]
+        L[:, k] = acc
+    return L
+
+
+def _patch_rows(idx, w, src_xyz, dst_xyz, neighbours, degree2=True, ring2=True, blend=True, gnomonic=False):
+    """patch_rows with the switches of the mutation tests (tests/test_patch_ref.py): degree2 False = degree 1 everywhere, ring2 False = no
+    attempt B, blend False = the polynomial of the row's heaviest slot alone, gnomonic True = gnomonic local coordinates."""
+    idx = np.asarray(idx, np.int64)
+    idx = idx.reshape(idx.shape[0], -1)
+    w = np.asarray(w, np.float64).reshape(idx.shape)
+    src_xyz, dst_xyz = np.asarray(src_xyz, np.float64), np.asarray(dst_xyz, np.float64)
+    nbr, cnt, is_mesh = neighbours
+    nbr, cnt = np.asarray(nbr, np.int64), np.asarray(cnt, np.int64)
+    n_dst, S = idx.shape
+    n_src = src_xyz.shape[1]
+    take = (idx >= 0) & (idx[:, :1] >= 0)
+    if not blend:
+        top = np.argmax(np.where(take, w, -np.inf), axis=1)
+        take &= np.arange(S)[None, :] == top[:, None]
+    prow, pslot = np.nonzero(take)                              # row-major: (row, slot) ascending
+    pnode, pb = idx[prow, pslot], (w[prow, pslot] if blend else np.ones(prow.size))
+    nodes, inv = np.unique(pnode, return_inverse=True)
+    att = np.full(nodes.size, 3, np.int8)
+    K1 = nbr.shape[1]
+    pat = np.full((nodes.size, PATCH_MAX_PNTS), -1, np.int64)
+    pat[:, 0] = nodes
+    fits = {}
+    with np.errstate(all="ignore"):
+        p1, c1 = nbr[nodes], cnt[nodes]
+        fitsin = c1 <= PATCH_MAX_PNTS
+        todo = fitsin.copy()
+        if degree2:
+            sel = np.flatnonzero(todo & (c1 >= 6))
+            ok, fits[0] = _patch_fit(src_xyz, nodes[sel], p1[sel], 6, gnomonic)
+            fits[0] = (sel, fits[0])
+            att[sel[ok]] = 0
+            pat[sel[ok], :K1] = p1[sel[ok]]
+            todo[sel[ok]] = False
+            if is_mesh and ring2:
+                sel = np.flatnonzero(todo)
+                d = np.where(p1[sel] >= 0, p1[sel], 0)
+                cand = np.where((p1[sel] >= 0)[:, :, None] & (nbr[d] >= 0), nbr[d], _PATCH_NONE).reshape(sel.size, K1 * K1)
+                over = ((p1[sel] >= 0) & (cnt[d] > PATCH_MAX_PNTS)).any(axis=1)
+                p2, c2 = _patch_pack(cand) if sel.size else (np.zeros((0, 1), np.int32), np.zeros(0, np.int64))
+                p2 = np.asarray(p2, np.int64)
+                try2 = ~over & (c2 >= 6) & (c2 <= PATCH_MAX_PNTS)
+                sel, p2 = sel[try2], p2[try2]
+                ok, f = _patch_fit(src_xyz, nodes[sel], p2, 6, gnomonic)
+                fits[1] = (sel, f)
+                att[sel[ok]] = 1
+                pat[sel[ok], :p2.shape[1]] = p2[ok]
+                todo[sel[ok]] = False
+        sel = np.flatnonzero(todo & (c1 >= 3))
+        ok, f = _patch_fit(src_xyz, nodes[sel], p1[sel], 3, gnomonic)
+        fits[2] = (sel, f)
+        att[sel[ok]] = 2
+        pat[sel[ok], :K1] = p1[sel[ok]]
+        # the shape values of every (row, slot) pair under its node's attempt
+        patt = att[inv]
+        ppat = pat[inv]
+        L = np.zeros((prow.size, PATCH_MAX_PNTS))
+        L[patt == 3, 0] = 1.0
+        for a, M in ((0, 6), (1, 6), (2, 3)):
+            if a not in fits:
+                continue
+            sel, f = fits[a]
+            pairs = np.flatnonzero(patt == a)
+            if pairs.size == 0:
+                continue
+            where = np.full(nodes.size, -1, np.int64)
+            where[sel] = np.arange(sel.size)
+            L[pairs] = _patch_shape(src_xyz, f, where[inv[pairs]], ppat[pairs], [dst_xyz[c][prow[pairs]] for c in range(3)], M, gnomonic)
+        term = pb[:, None] * L
+    # the ordered merge: distinct ids ascending per row, the values summed in (slot, patch position) order from 0.0
+    live = ppat >= 0
+    crow = np.broadcast_to(prow[:, None], ppat.shape)[live]
+    cid, cterm = ppat[live], term[live]
+    key = crow * np.int64(max(n_src, 1)) + cid
+    order = np.argsort(key, kind="stable")
+    key, cterm = key[order], cterm[order]
+    first = np.ones(key.size, bool)
+    first[1:] = key[1:] != key[:-1]
+    grp = np.cumsum(first) - 1
+    start = np.flatnonzero(first)
+    rank = np.arange(key.size) - start[grp] if key.size else np.zeros(0, np.int64)
+    val = np.zeros(start.size)
+    for t in range(int(rank.max()) + 1 if key.size else 0):
+        s_ = np.flatnonzero(rank == t)
+        val[grp[s_]] = val[grp[s_]] + cterm[s_]
+    col = (key[start] % max(n_src, 1)).astype(np.int32)
+    rowlen = np.bincount(key[start] // max(n_src, 1), minlength=n_dst).astype(np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(rowlen)]).astype(np.int64)
+    stats = [int((rowlen > 0).sum())] + [int((patt == a).sum()) for a in range(4)] + [int(rowlen.max()) if n_dst else 0]
+    return rowptr, col, val, stats
+
+
+def patch_rows(idx, w, src_xyz, dst_xyz, neighbours):
+    """The numpy mirror of mpg_handle_patch, written elementwise in the order of mpassit_amd/csrc/patch.h so that it has the device's bits.
+    idx, w: the weights() of a fixed bilinear handle, [n_dst][S] with -1 = no entry; src_xyz [3][n_src], dst_xyz [3][n_dst]: the library's
+    stored unit vectors (Mesh.xyz / Grid.xyz); neighbours: patch_neighbours_mesh(voc, tri) or patch_neighbours_grid(snx, sny).
+    Per source node the attempt ladder of include/mpassit_amd.h -- (A) degree 2 on the ring-1 patch, (B) degree 2 on the ring-2 patch (a
+    mesh), (C) degree 1 on ring 1, (D) the node itself; per mapped row the distinct ids of its slots' patches ascending, the values
+    acc = acc + b_s * L_(s,k) over (slot, patch position) from 0.0.
+    -> (rowptr int64, col int32, val, stats): stats = [rows written, pairs served by A, B, C, D, longest row], mpg_handle_store_stats
+    [1..6]."""
+    return _patch_rows(idx, w, src_xyz, dst_xyz, neighbours)
+
+
 _COMPOSE_VECTOR_PASSES = 64   # terms of an entry of C summed by vectorised passes; what lies behind them is summed by a plain loop
 
 
