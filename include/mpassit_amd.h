@@ -1141,6 +1141,87 @@ int mpg_handle_extrapolate_masked(mpg_handle rh, const mpg_points *src, const mp
 #define MPG_PATCH_MAX_PNTS 32
 int mpg_handle_patch(mpg_handle rh, const mpg_points *src, const mpg_points *dst, mpg_handle *out);
 
+/* ---- second-order conservative regridding: a linear reconstruction inside every source cell, as a CSR handle ------------------------------
+ * ESMF_REGRIDMETHOD_CONSERVE_2ND.  The first-order conservative Stores treat a source cell as a constant: precipitation, snow, soil water
+ * or a tracer remapped onto a finer mesh or grid comes out in staircases of source-cell size.  mpg_handle_conserve2nd turns a finished
+ * first-order conservative handle into a second-order one: every source cell carries a least-squares gradient over its neighbours' means,
+ * and every stored (destination, source) piece is evaluated at the piece's own centroid.  The integral is kept as the first-order handle
+ * keeps it; smooth fields are second-order accurate.  The result is an ordinary CSR handle, which every consumer takes; the call needs no
+ * new search -- the stored pairs are the candidate list -- and serves Mesh -> Grid, Grid -> Mesh and Mesh -> Mesh at once.
+ *
+ * rh: a conservative CSR handle of mpg_regrid_store(..., MPG_REGRIDMETHOD_CONSERVE), mpg_regrid_store_conserve_to_mesh or
+ *   mpg_regrid_store_conserve_mesh, also after mpg_handle_mask.  src / dst: the point sets the handle was stored between, by the mpg_points
+ *   rules; a mesh side takes part with its cells (meshloc MPG_MESHLOC_ELEMENT), a grid side with its cells (staggerloc
+ *   MPG_STAGGERLOC_CENTER; the cells are the quadrilaterals of its CORNER points).  opts->norm_type: the one the Store was called with.
+ *   opts->src_mask_dev: optional device bytes [n_src] in the handle's source index space, non-zero = masked.
+ * The rule is ours, built from this header's primitives as the patch rule is; ESMF's Green's-theorem gradient is not reproduced.  Every
+ * operation is rounded on its own (fp contract(off)); the only operations are + - * / sqrt.  Dot products are (x*x' + y*y') + z*z'.
+ *   Triangle area: the signed area of the spherical triangle a, b, c is tri(a, b, c): num = a . ((b - a) x (c - a)), den = ((1 + a . b) +
+ *     b . c) + c . a (sph_tri_area's two numbers); x = num / den; while |x| >= 2^-10: x = x / (1 + sqrt(1 + x * x)), at most 64 times,
+ *     h counting the steps; tri = 2^(h + 1) * (x * (1 - x2 * (1/3 - x2 * (1/5 - x2 * (1/7))))) with x2 = x * x.  den <= 0 gives 0.  The
+ *     half-angle steps stand where sph_tri_area calls atan2: a library function has its library's bits, this form has the same bits
+ *     everywhere (it agrees with sph_tri_area to a few units in the last place).
+ *   1. Polygons.  A mesh cell is its non-zero verticesOnCell entries in listed order.  A grid cell is the four CORNER points around centre
+ *     (i, j) -- (i, j), (i + 1, j), (i + 1, j + 1), (i, j + 1) -- with id = j * nx + i.  The fan area of a polygon is the sum from 0.0 of
+ *     tri(p_0, p_t, p_(t+1)), t = 1 .. n - 2; a polygon is made counter-clockwise by the sign of its own fan area (the listed order
+ *     reversed when that is negative).  The source cell is the subject polygon; it is clipped by the destination cell's sides in listed
+ *     (counter-clockwise) order, the closing side last.  Everything else follows the Mesh -> Mesh Store's contract word for word: normals
+ *     a x (b - a), the 1e-15 * |n| inside rule, and the rule that a side with |b - a|^2 < 1e-24 bounds nothing.  This one clip rule serves
+ *     all three pairings; the areas it gives may differ from the input handle's in the last bits.
+ *   2. Piece (j, i) of every stored entry q.  a_t = tri(p_0, p_t, p_(t+1)) over the clipped polygon's fan from slot 0; A_q = the sum of the
+ *     a_t from 0.0, clamped at 0; the moment m_q = sum_t a_t * (((p_0 + p_t) + p_(t+1)) / 3) from 0.0, per component.  A polygon of fewer
+ *     than three vertices has A_q = 0, m_q = 0.  area(d) is |fan area| of the destination polygon in listed order.
+ *   3. Source cell i.  A_i = sum A_q and M_i = sum m_q over its pieces, from 0.0 in ascending destination id (the handle's transposed
+ *     index).  The geometric centroid G_i is the unit vector m / sqrt(m . m) of the counter-clockwise cell polygon's own fan moment m; it
+ *     is the stored cell centre when the polygon has fewer than 3 vertices or sqrt(m . m) is not > 0.  The frame (e1, e2) is the patch
+ *     rule's frame about n = G_i.
+ *   4. Stencil.  S(i) = N1(i) as mpg_handle_patch defines it (mesh cells; the CENTER stagger of a grid), minus i, minus the cells flagged
+ *     in src_mask_dev (ESMF's rule: masked cells take no part in a gradient).  d_k = ((G_k - G_i) . e1, (G_k - G_i) . e2).  M = sum_k d_k
+ *     d_k^T, every element from 0.0 in ascending k.  The stencil passes when |S| >= 2, |N1| <= MPG_PATCH_MAX_PNTS, i is not masked, and
+ *     det = M00 * M11 - M01 * M01 > 2^-26 * (M00 * M11).  On a pass b_k = ((M11 * dx - M01 * dy) / det, (M00 * dy - M01 * dx) / det) and
+ *     b_i = -(sum_k b_k), the sum from 0.0 in ascending k; the stencil's entries are S(i) and i, ascending.  A stencil that fails has the
+ *     single entry i with b = 0: that source stays first order.
+ *   5. Offsets and weights.  delta_q = ((m_q / A_q - M_i / A_i) . e1, ( ... ) . e2), per component a division, a division and a
+ *     subtraction; 0 when A_q <= 0 or A_i <= 0.  MPG_NORM_DSTAREA: w_q = A_q / area(d).  MPG_NORM_FRACAREA: w_q = A_q / (sum over the row of
+ *     A_q from 0.0 in stored order).  A divisor that is not > 0 gives w_q = 0.
+ *   6. Row j.  Its columns are the ascending distinct union of the stencils of the row's source cells: exactly the pattern of
+ *     mpg_handle_compose(rh, the stencils as a CSR matrix).  The value of column e is acc = acc + (w_q * t) from 0.0 over the row's entries
+ *     q in stored order whose stencil holds e (each holds it at most once): g = (dx * bx) + (dy * by) with delta_q = (dx, dy) and the
+ *     stencil entry's b = (bx, by); t = 1.0 + g when e is the entry's own source cell, else t = g.  Zero values stay in the row.  An empty
+ *     input row stays empty.  A dst_frac is carried over bit for bit.
+ *   Two identities make this the right rule (DESIGN.md s4.2 proves them; both hold up to rounding).  Conservation: sum_j area(d_j) * c_(j,e)
+ *     = A_e under MPG_NORM_DSTAREA -- the integral over the covered part is kept exactly as the first-order handle keeps it, for any field,
+ *     partly covered source cells included -- because sum_q A_q delta_q = 0 over the pieces of a source cell by the construction of
+ *     M_i / A_i.  Row sums: every row's sum equals the first-order row sum, because sum_k b_k = 0 over a stencil.
+ *   The price: weights can be negative, so over- and undershoots occur and there is no limiter; a partly covered source cell expands about
+ *     the centroid of its covered part, so the rim is only first-order accurate.
+ *   A contract by identity with the numpy mirror target_grid.conserve2nd_rows; mpassit_amd/csrc/conserve2nd.h is the arithmetic, for
+ *   device and host.
+ * Output: a new CSR handle with the input's n_src, n_dst, nx_dst and ny_dst; its method is MPG_REGRIDMETHOD_CONSERVE_2ND.  Its longest row
+ *   is recorded.  It is not cached and owns its arrays: pair it with mpg_handle_release; rh may be released right after the call.
+ *   mpg_handle_store_ms is the GPU time of the call.  mpg_handle_store_stats: [1] pairs clipped, [2] sources with a passing stencil,
+ *   [3] sources without one, [4] stencil entries, [6] the longest row.
+ * Determinism: the same bytes from run to run; no floating-point atomics.
+ * Blocking: the call allocates, builds rh's transposed index if it is absent (as mpg_regrid_transpose_dev does), reads the stencils'
+ *   entry count back (its own host round trip; the pattern's row blocks add theirs, mpg_tune("compose_block_rows") covers them) and drains
+ *   the Store worker first.  It orders itself after whatever produced rh, as mpg_handle_get_csr does.
+ * Order with the other handle calls: mask the first-order handle with MPG_MASKRULE_ENTRY (mpg_handle_mask, the Store's norm_type), then
+ *   call this with the same source mask.  mpg_handle_mask is unchanged: MPG_MASKRULE_AUTO refuses method 4, which it does not know.
+ * Refusals, each with a message that names mpg_handle_conserve2nd and the way out.  MPG_ERR_INVALID_ARG: a NULL argument; a point set that
+ *   breaks the mpg_points rules, a mesh location other than ELEMENT or a stagger other than CENTER; sizes that differ from the handle's
+ *   (both numbers are printed); an unknown norm_type; a handle whose method is not MPG_REGRIDMETHOD_CONSERVE; a grid without CORNER
+ *   coordinates.  MPG_ERR_UNSUPPORTED: a fixed handle; a handle with pole terms; a localized, rebased or windowed handle; a mesh of
+ *   mpg_mesh_create_window; maxEdges > 12; a source grid with MPG_GRID_PERIODIC_I (the rings do not wrap).  MPG_ERR_OVERFLOW: more than
+ *   2^31 - 2 entries; a clipped polygon that outgrew its slots (a non-convex cell).  A failed allocation returns its error and leaks nothing.
+ * Not served: ESMF's own gradient; a limiter; periodic source grids and pole terms; node-located fields; caching or a _begin variant;
+ *   multi-GPU sharding; use from interp.py or the Fortran driver; a pin-kit export for -m conserve2nd. */
+enum { MPG_REGRIDMETHOD_CONSERVE_2ND = 4 };   /* the method of mpg_handle_conserve2nd's handles; no Store takes it */
+typedef struct mpg_conserve2nd_opts {
+  int norm_type;                /* MPG_NORM_DSTAREA / MPG_NORM_FRACAREA, the one the Store was called with */
+  const uint8_t *src_mask_dev;  /* [n_src] device bytes in the handle's index space, non-zero = masked; NULL = none */
+} mpg_conserve2nd_opts;
+int mpg_handle_conserve2nd(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_conserve2nd_opts *opts, mpg_handle *out);
+
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the

@@ -39,6 +39,7 @@ SYMBOLS = [
     "mpg_handle_extrapolate", "mpg_mesh_get_xyz", "mpg_grid_get_xyz",
     "mpg_handle_mask", "mpg_handle_extrapolate_masked",
     "mpg_handle_patch",
+    "mpg_handle_conserve2nd",
 ]
 
 MPG_SUCCESS = 0
@@ -60,6 +61,8 @@ EXTRAP_MAX_PNTS = 8
 MPG_REGRIDMETHOD_PATCH = 3   # the method of mpg_handle_patch's handles; no Store takes it
 REGRIDMETHOD_PATCH = MPG_REGRIDMETHOD_PATCH
 PATCH_MAX_PNTS = 32
+MPG_REGRIDMETHOD_CONSERVE_2ND = 4   # the method of mpg_handle_conserve2nd's handles; no Store takes it
+REGRIDMETHOD_CONSERVE_2ND = MPG_REGRIDMETHOD_CONSERVE_2ND
 MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY = 0, 1, 2
 MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY = MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY
 
@@ -483,6 +486,23 @@ def handle_patch(*args):
     if "handle_patch" not in _to_mesh_fns:
         _to_mesh_fns["handle_patch"] = _HANDLE_PATCH_PROTO(("mpg_handle_patch", load()))
     return _to_mesh_fns["handle_patch"](*args)
+
+
+# Second-order conservative regridding (include/mpassit_amd.h): a first-order conservative CSR handle turned into a second-order one
+#   mpg_handle_conserve2nd(rh, src, dst, opts, out)
+class Conserve2ndOpts(C.Structure):
+    """mpg_conserve2nd_opts of include/mpassit_amd.h: the Store's norm type and a device byte mask of the sources (0 / None = none)."""
+    _fields_ = [("norm_type", C.c_int), ("src_mask_dev", C.c_void_p)]
+
+
+_HANDLE_CONSERVE2ND_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Points), C.POINTER(Points), C.POINTER(Conserve2ndOpts), C.c_void_p)
+
+
+def handle_conserve2nd(*args):
+    """The typed binding of mpg_handle_conserve2nd; returns the call's status code."""
+    if "handle_conserve2nd" not in _to_mesh_fns:
+        _to_mesh_fns["handle_conserve2nd"] = _HANDLE_CONSERVE2ND_PROTO(("mpg_handle_conserve2nd", load()))
+    return _to_mesh_fns["handle_conserve2nd"](*args)
 
 
 _lib = None

@@ -10,6 +10,8 @@
 //     k_compose_heads              1 where a key differs from the one before; mpg_scan_excl_i32 of that numbers the distinct entries
 //     k_compose_compact            the distinct columns, in order;  k_compose_rowptr: a row's first entry by a search of the sorted keys
 //   The pattern is a set, so it cannot depend on the blocks; "compose_block_rows" (mpg_tune) forces small blocks for the tests.
+//   mpg_k_compose_pattern is the same job for a caller with a bare CSR pattern as the inner operand and a value pass of its own
+//   (k_conserve2nd.hip: the stencils of the source cells); mpg_k_compose is that job with k_compose_values behind it.
 //
 //   numeric job  (values)   k_compose_values<K, OWN>: one lane per entry (i, e) of C.  The lane finds its row by a search of C's rowptr,
 //     walks A's row i in stored order and, inside each entry, B's row col_A[p] in stored order, and adds a_p * b_q where col_B[q] == e:
@@ -240,10 +242,10 @@ static int co_refused(int rc, const WvErr &e) {
   return rc;
 }
 
-// c (shape set by the caller, arrays empty) <- the composite of a and b: rowptr, col, val, nnz, max_row.  Blocking.
-int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t s) {
+// The symbolic job and what frames it: c (shape set by the caller, arrays empty) <- the pattern of A . B -- rowptr, col, nnz, max_row --
+// with val allocated; `values` is called once the pattern stands and launches whatever fills c->val on stream s.  Blocking.
+static int co_compose(const mpg_handle_s *a, const CoOp &A, const CoOp &B, mpg_handle_s *c, hipStream_t s, const std::function<int()> &values) {
   const int64_t n = a->n_dst;
-  const CoOp A = co_op(a), B = co_op(b);
   int rc;
   if ((rc = c->rowptr.alloc((size_t)n + 1))) return rc;
   // lanes per row of A: by its average row (a long row among short ones takes more turns of the same loop)
@@ -306,12 +308,25 @@ int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t
   c->nnz = nnz;
   if (n > 0) k_compose_max_row<<<co_grid(n), 256, 0, s>>>(c->rowptr.p, n, longest.p);
   MPG_HIP(hipGetLastError());
-  if ((rc = mpg_k_compose_values(c, a, b, 1, nullptr, c->val.p, s))) return rc;
+  if ((rc = values())) return rc;
   int32_t max_row = 0;
   MPG_HIP(hipMemcpyAsync(&max_row, longest.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   MPG_HIP(hipStreamSynchronize(s));   // (also: the chunks may go)
   c->max_row = max_row;
   return MPG_SUCCESS;
+}
+
+// c (shape set by the caller, arrays empty) <- the composite of a and b: rowptr, col, val, nnz, max_row.  Blocking.
+int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t s) {
+  return co_compose(a, co_op(a), co_op(b), c, s, [&]() { return mpg_k_compose_values(c, a, b, 1, nullptr, c->val.p, s); });
+}
+
+// the same with a bare CSR pattern of b_rows rows as the inner operand and the caller's own value pass (k_conserve2nd.hip)
+int mpg_k_compose_pattern(mpg_handle_s *a, const int32_t *b_rowptr, const int32_t *b_col, int64_t b_rows, mpg_handle_s *c, hipStream_t s,
+                          const std::function<int()> &values) {
+  CoOp B;
+  B.rowptr = b_rowptr; B.col = b_col; B.val = nullptr; B.nz = 0; B.n = b_rows;
+  return co_compose(a, co_op(a), B, c, s, values);
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

@@ -131,7 +131,7 @@ void mpg_pool_release() {
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
   X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
-  X(k_handle_mask) X(k_patch)
+  X(k_handle_mask) X(k_patch) X(k_conserve2nd)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -1931,6 +1931,142 @@ int mpg_handle_patch(mpg_handle rh, const mpg_points *src, const mpg_points *dst
   }
   (void)hipEventRecord(e0, g_stream);
   rc = mpg_k_patch(rh, ps, *dp, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("%s: %s", who, hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+// ---- second-order conservative regridding: a first-order conservative CSR handle turned into the CSR handle of a linear reconstruction
+// inside every source cell (k_conserve2nd.hip, conserve2nd.h) ---------------------------------------------------------------------------------
+int mpg_handle_conserve2nd(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_conserve2nd_opts *opts, mpg_handle *out) {
+  const char *who = "mpg_handle_conserve2nd";
+  MPG_CHECK_INIT();
+  if (!(rh && src && dst && opts && out)) {
+    mpg_set_error("%s: NULL argument (rh, src, dst, opts and out are all mandatory)", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  int rc;
+  int64_t ns = 0, nd = 0;
+  int sx = 0, sy = 0, dx = 0, dy = 0;
+  const PointSet *sp = nullptr, *dp = nullptr;
+  if ((rc = ex_points(who, "source", src, true, &ns, &sx, &sy, &sp)) || (rc = ex_points(who, "destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
+  if (dst->mesh && dst->meshloc != MPG_MESHLOC_ELEMENT) {
+    mpg_set_error("%s: the destination mesh takes part with its cells (MPG_MESHLOC_ELEMENT, not location %d): conservative handles map "
+                  "cells to cells", who, dst->meshloc);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if ((src->grid && src->staggerloc != MPG_STAGGERLOC_CENTER) || (dst->grid && dst->staggerloc != MPG_STAGGERLOC_CENTER)) {
+    mpg_set_error("%s: a grid takes part with its cells (MPG_STAGGERLOC_CENTER, not stagger %d): conservative handles map cells to cells", who,
+                  src->grid && src->staggerloc != MPG_STAGGERLOC_CENTER ? src->staggerloc : dst->staggerloc);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (opts->norm_type != MPG_NORM_DSTAREA && opts->norm_type != MPG_NORM_FRACAREA) {
+    mpg_set_error("%s: unknown norm_type %d: MPG_NORM_DSTAREA or MPG_NORM_FRACAREA, the one the Store was called with", who, opts->norm_type);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (rh->method != MPG_REGRIDMETHOD_CONSERVE) {
+    mpg_set_error("%s: the handle's method is %d, not MPG_REGRIDMETHOD_CONSERVE: the rule re-clips the stored pairs of a first-order "
+                  "conservative handle -- store conservatively, then convert", who, rh->method);
+    return MPG_ERR_INVALID_ARG;
+  }
+  for (int side = 0; side < 2; ++side) {
+    const mpg_grid_s *g = side ? dst->grid : src->grid;
+    if (!g) continue;
+    const int64_t want = (int64_t)(g->nx + 1) * (g->ny + 1);
+    if (g->pts[MPG_STAGGERLOC_CORNER].n != want) {
+      mpg_set_error("%s: the %s grid has no CORNER coordinates (%lld points, %lld expected): its cells are the quadrilaterals of the CORNER "
+                    "stagger -- create the grid with them", who, side ? "destination" : "source", (long long)g->pts[MPG_STAGGERLOC_CORNER].n,
+                    (long long)want);
+      return MPG_ERR_INVALID_ARG;
+    }
+  }
+  if (rh->kind != MPG_KIND_CSR) {
+    mpg_set_error("%s: a fixed handle is not served: the rule reads the rows of a conservative CSR handle (mpg_regrid_store with "
+                  "MPG_REGRIDMETHOD_CONSERVE, mpg_regrid_store_conserve_to_mesh, mpg_regrid_store_conserve_mesh)", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_pole > 0) {
+    mpg_set_error("%s: the handle has pole terms (mpg_handle_pole_count > 0), which a second-order handle cannot carry: store with "
+                  "MPG_POLEMETHOD_NONE", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->localized) {
+    mpg_set_error("%s: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase): its indices are no "
+                  "longer source ids -- convert first, re-index the result", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (mpg_handle_is_windowed(rh) || (src->mesh && src->mesh->win_count[MPG_MESHLOC_ELEMENT] >= 0)) {
+    mpg_set_error("%s: the source mesh carries a source window (mpg_mesh_set_source_window): the handle's indices are "
+                  "window-relative -- reset the window to the whole mesh first", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if ((src->mesh && src->mesh->geo_grid) || (dst->mesh && dst->mesh->geo_grid)) {
+    mpg_set_error("%s: the %s mesh was cut to a grid (mpg_mesh_create_window): the re-clip and the rings need every cell's vertices and "
+                  "triangles -- use the whole mesh (mpg_mesh_create)", who, src->mesh && src->mesh->geo_grid ? "source" : "destination");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if ((src->mesh && src->mesh->maxEdges > 12) || (dst->mesh && dst->mesh->maxEdges > 12)) {
+    mpg_set_error("%s: maxEdges %d > 12: the clip holds cells of at most 12 vertices -- split the larger cells", who,
+                  std::max(src->mesh ? src->mesh->maxEdges : 0, dst->mesh ? dst->mesh->maxEdges : 0));
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (src->grid && (src->grid->periodic & MPG_GRID_PERIODIC_I)) {
+    mpg_set_error("%s: a source grid with MPG_GRID_PERIODIC_I is not served (the 3 x 3 rings do not wrap in i and know no pole): "
+                  "create the grid without the flag, or stay first order", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_src != ns) {
+    mpg_set_error("%s: the handle has n_src = %lld, the source point set has %lld cells", who, (long long)rh->n_src, (long long)ns);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (rh->n_dst != nd || rh->nx_dst != dx || rh->ny_dst != dy) {
+    mpg_set_error("%s: the handle has n_dst = %lld (%d x %d), the destination point set has %lld cells (%d x %d)", who,
+                  (long long)rh->n_dst, rh->nx_dst, rh->ny_dst, (long long)nd, dx, dy);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (ns > 0x7fffffffLL) {
+    mpg_set_error("%s: %lld source cells are beyond int32 ids", who, (long long)ns);
+    return MPG_ERR_OVERFLOW;
+  }
+  PtSrc ps;
+  ps.x = sp->x.p; ps.y = sp->y.p; ps.z = sp->z.p;
+  ps.voc = nullptr; ps.tri = nullptr; ps.maxEdges = 0; ps.nV = 0; ps.snx = sx; ps.sny = sy;
+  if (src->mesh) {
+    ps.voc = src->mesh->voc.p; ps.tri = src->mesh->tri.p; ps.maxEdges = src->mesh->maxEdges; ps.nV = src->mesh->nVertices;
+  }
+  // rh is finished (a Store waits for its build before it hands its handle out); a begun Store may still allocate on the worker.  The
+  // build runs on the set-up stream, after whatever produced rh
+  store_worker_drain();
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = MPG_REGRIDMETHOD_CONSERVE_2ND;
+  h->n_src = rh->n_src;
+  h->n_dst = rh->n_dst;
+  h->nx_dst = rh->nx_dst;
+  h->ny_dst = rh->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("%s: hipEventCreate failed", who);
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_conserve2nd(rh, src->mesh, src->grid, dst->mesh, dst->grid, ps, opts->norm_type, opts->src_mask_dev, h, g_stream);
   if (!rc) {
     hipError_t he = hipEventRecord(e1, g_stream);
     if (he == hipSuccess) he = hipEventSynchronize(e1);

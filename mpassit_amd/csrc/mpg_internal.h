@@ -511,6 +511,10 @@ int mpg_k_wind_reconstruct(mpg_handle_s *h, const double *m, int nout, const voi
 int mpg_k_compose(mpg_handle_s *a, mpg_handle_s *b, mpg_handle_s *c, hipStream_t s);
 int mpg_k_compose_values(mpg_handle_s *c, mpg_handle_s *a, mpg_handle_s *b, int nplanes, const double *bm, double *m, hipStream_t s);
 void mpg_set_compose_block_rows(int v);     // "compose_block_rows" knob (k_compose.hip)
+// ... the same symbolic job with a bare CSR pattern (b_rowptr [b_rows + 1], b_col) as the inner operand: c's rowptr, col, nnz and max_row,
+// val allocated; `values` runs once the pattern stands and launches the caller's own value pass on s
+int mpg_k_compose_pattern(mpg_handle_s *a, const int32_t *b_rowptr, const int32_t *b_col, int64_t b_rows, mpg_handle_s *c, hipStream_t s,
+                          const std::function<int()> &values);
 // k_extrapolate.hip: `out` (shape and method set by the caller, arrays empty) <- `in` with its unmapped rows filled from the nearest source
 // points: the cells of src_mesh (its site BVH, built whole) or the `src_stagger` points of src_grid (their point pyramid), exactly one set;
 // dst: the in->n_dst destination points.  Arguments checked by the API entry point; blocking: it allocates and reads counts back.
@@ -528,6 +532,11 @@ int mpg_k_handle_mask(mpg_handle_s *in, const uint8_t *src_mask, const uint8_t *
 // API entry point; blocking: it allocates and reads the entry count back
 struct PtSrc;
 int mpg_k_patch(mpg_handle_s *in, const PtSrc &src, const PointSet &dst, mpg_handle_s *out, hipStream_t s);
+// k_conserve2nd.hip: `out` (shape and method set by the caller, arrays empty) <- the second-order conservative rule on `in`, a first-order
+// conservative CSR handle stored between the cells of (smesh or sgrid) and (dmesh or dgrid); ps: the source's rings and stored centres
+// (patch.h); src_mask: device bytes [n_src] or nullptr.  Arguments checked by the API entry point; blocking.  Builds in's transposed index
+int mpg_k_conserve2nd(mpg_handle_s *in, mpg_mesh_s *smesh, mpg_grid_s *sgrid, mpg_mesh_s *dmesh, mpg_grid_s *dgrid, const PtSrc &ps, int norm_type,
+                      const uint8_t *src_mask, mpg_handle_s *out, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

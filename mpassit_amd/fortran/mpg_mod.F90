@@ -70,6 +70,12 @@ module mpg
     integer(c_int) :: rule             !< MPG_MASKRULE_*
     integer(c_int) :: norm_type        !< ENTRY rule only: MPG_NORM_*, the one the Store was called with
   end type mpg_store_mask_opts
+  !> mpg_handle_conserve2nd (include/mpassit_amd.h): the method of its handles (no Store takes it) and the options
+  integer(c_int), parameter :: MPG_REGRIDMETHOD_CONSERVE_2ND = 4
+  type, bind(C) :: mpg_conserve2nd_opts
+    integer(c_int) :: norm_type        !< MPG_NORM_*, the one the Store was called with
+    type(c_ptr) :: src_mask_dev        !< device bytes [n_src], non-zero = masked; c_null_ptr: none
+  end type mpg_conserve2nd_opts
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -631,6 +637,16 @@ module mpg
       type(c_ptr), intent(out) :: out
       integer(c_int) :: rc
     end function mpg_handle_patch
+    !> second-order conservative regridding: a first-order conservative CSR handle turned into the CSR handle of a linear reconstruction
+    !> inside every source cell (the driver does not use it)
+    function mpg_handle_conserve2nd(rh, src, dst, opts, out) bind(C, name="mpg_handle_conserve2nd") result(rc)
+      import :: c_int, c_ptr, mpg_points, mpg_conserve2nd_opts
+      type(c_ptr), value :: rh
+      type(mpg_points), intent(in) :: src, dst
+      type(mpg_conserve2nd_opts), intent(in) :: opts
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_conserve2nd
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

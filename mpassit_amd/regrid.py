@@ -32,7 +32,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "rotate_winds_cgrid_transpose", "wind_destagger_transpose", "wind_destagger_autograd",
            "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS",
            "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY",
-           "patch", "regrid_store_patch", "REGRIDMETHOD_PATCH", "PATCH_MAX_PNTS"]
+           "patch", "regrid_store_patch", "REGRIDMETHOD_PATCH", "PATCH_MAX_PNTS",
+           "conserve_2nd", "regrid_store_conserve_2nd", "REGRIDMETHOD_CONSERVE_2ND"]
 
 
 def _f64(a):
@@ -1996,5 +1997,47 @@ def regrid_store_patch(src, dst, src_loc=None, dst_loc=None):
         raise ValueError("regrid_store_patch: src and dst must be Mesh or Grid objects (Grid -> Grid: the staggers of ONE grid)")
     try:
         return patch(rh, src, dst, src_loc, dst_loc)
+    finally:
+        rh.release()
+
+
+# ---- second-order conservative regridding: a linear reconstruction inside every source cell, as a CSR handle -------------------------------
+REGRIDMETHOD_CONSERVE_2ND = L.REGRIDMETHOD_CONSERVE_2ND
+
+
+def conserve_2nd(rh, src, dst, norm=NORM_DSTAREA, src_mask=None, src_loc=None, dst_loc=None):
+    """mpg_handle_conserve2nd (ESMF_REGRIDMETHOD_CONSERVE_2ND): a new CSR RouteHandle of rh's shape in which every source cell carries a
+    least-squares gradient over its neighbours' means and every stored piece is evaluated at its own centroid.  rh: a first-order
+    conservative CSR handle (regrid_store with REGRIDMETHOD_CONSERVE, regrid_store_conserve_to_mesh, regrid_store_conserve_mesh), also
+    after mask_handle(rule=MASKRULE_ENTRY); src / dst: the Mesh or Grid objects rh was stored between (cells on both sides: MESHLOC_ELEMENT
+    / STAGGERLOC_CENTER, the defaults of src_loc / dst_loc); norm: the one the Store was called with; src_mask [n_src]: numpy or torch,
+    bool or uint8, non-zero = masked -- masked cells take no part in a gradient (mask rh with the same mask first).  The integral is kept
+    as rh keeps it and the row sums are rh's; weights may be negative (no limiter).  store_stats: [1] pairs clipped, [2] sources with a
+    passing stencil, [3] sources without one, [4] stencil entries, [6] the longest row.  The bits of target_grid.conserve2nd_rows.  Not
+    cached: release() it; rh may be released."""
+    ps, pd = _points(src, src_loc, "src"), _points(dst, dst_loc, "dst")
+    ms = _mask_dev(src_mask, rh.n_src, "conserve_2nd", "src_mask") if rh is not None else None
+    opts = L.Conserve2ndOpts(norm_type=int(norm), src_mask_dev=_mask_ptr(ms))
+    h = C.c_void_p()
+    check(L.handle_conserve2nd(rh._h if rh is not None else None, C.byref(ps), C.byref(pd), C.byref(opts), C.byref(h)))
+    return RouteHandle(h)
+
+
+def regrid_store_conserve_2nd(src, dst, norm=NORM_DSTAREA):
+    """Store first-order conservative, convert, release: the second-order conservative handle between the cells of src and dst (Mesh ->
+    Grid, Grid -> Mesh or Mesh -> Mesh, picked by the operand types).  The first-order handle goes back to the Store cache.  Not cached
+    itself: release() the result."""
+    if isinstance(src, Mesh) and isinstance(dst, Grid):
+        if norm != NORM_DSTAREA:
+            raise ValueError("regrid_store_conserve_2nd: the Mesh -> Grid conservative Store normalises by the destination area (NORM_DSTAREA) only")
+        rh = regrid_store(src, dst, REGRIDMETHOD_CONSERVE)
+    elif isinstance(src, Grid) and isinstance(dst, Mesh):
+        rh = regrid_store_conserve_to_mesh(src, dst, norm)
+    elif isinstance(src, Mesh) and isinstance(dst, Mesh):
+        rh = regrid_store_conserve_mesh(src, dst, norm)
+    else:
+        raise ValueError("regrid_store_conserve_2nd: src and dst must be a Mesh and a Grid, a Grid and a Mesh, or two Meshes")
+    try:
+        return conserve_2nd(rh, src, dst, norm)
     finally:
         rh.release()

@@ -795,6 +795,256 @@ def patch_rows(idx, w, src_xyz, dst_xyz, neighbours):
     return _patch_rows(idx, w, src_xyz, dst_xyz, neighbours)
 
 
+REGRIDMETHOD_CONSERVE_2ND = 4
+_C2_DET_TOL = 2.0 ** -26
+_C2_HALF_TOL = 2.0 ** -10
+
+
+def _c2_dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _c2_cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _c2_tri_area(a, b, c):
+    """c2_tri_area of conserve2nd.h on [..., 3] unit vectors: sph_tri_area's num / den, half-angle steps down to |x| < 2^-10, the series."""
+    num = _c2_dot(a, _c2_cross(b - a, c - a))
+    den = ((1.0 + _c2_dot(a, b)) + _c2_dot(b, c)) + _c2_dot(c, a)
+    ok = den > 0.0
+    x = num / np.where(ok, den, 1.0)
+    scale = np.full(x.shape, 2.0)
+    for _ in range(64):
+        big = ~(np.abs(x) < _C2_HALF_TOL)
+        if not big.any():
+            break
+        x = np.where(big, x / (1.0 + np.sqrt(1.0 + x * x)), x)
+        scale = np.where(big, scale * 2.0, scale)
+    x2 = x * x
+    return np.where(ok, scale * (x * (1.0 - x2 * (1.0 / 3.0 - x2 * (1.0 / 5.0 - x2 * (1.0 / 7.0))))), 0.0)
+
+
+def _c2_fan(xyz, cnt):
+    """The fan from slot 0 of the polygons (xyz [n][M][3], cnt [n]): the signed area and the moment [n][3], both from 0.0 in slot order."""
+    n, M = xyz.shape[:2]
+    area, m = np.zeros(n), np.zeros((n, 3))
+    for t in range(1, M - 1):
+        on = cnt > t + 1
+        if not on.any():
+            break
+        a = np.where(on, _c2_tri_area(xyz[:, 0], xyz[:, t], xyz[:, t + 1]), 0.0)
+        c = ((xyz[:, 0] + xyz[:, t]) + xyz[:, t + 1]) / 3.0
+        area = np.where(on, area + a, area)
+        m = np.where(on[:, None], m + a[:, None] * c, m)
+    return area, m
+
+
+def _c2_ccw(xyz, cnt, rev):
+    out = xyz.copy()
+    k = np.arange(xyz.shape[1])[None, :]
+    src = np.where(k < cnt[:, None], cnt[:, None] - 1 - k, k)
+    out[rev] = np.take_along_axis(xyz[rev], src[rev][:, :, None], axis=1)
+    return out
+
+
+def _c2_clip(subj, n, clip, clip_n):
+    """Sutherland-Hodgman of conserve_clip.h over aligned pairs: subject polygons (subj [Np][Ms][3], n [Np]) by the sides of the clip
+    polygons in order (both counter-clockwise) -> (polygon [Np][Ms + Mc][3], count)."""
+    Np, Ms = subj.shape[:2]
+    Mc = clip.shape[1]
+    cap = Ms + Mc
+    poly = np.zeros((Np, cap, 3))
+    poly[:, :Ms] = subj
+    n = n.astype(np.int64).copy()
+    rows_all = np.arange(Np)
+    for e in range(Mc):
+        nxt = np.where(e + 1 == clip_n, 0, np.minimum(e + 1, Mc - 1))
+        qa, qb = clip[:, e], clip[rows_all, nxt]
+        side = qb - qa
+        act = (e < clip_n) & (n >= 3) & ~(_c2_dot(side, side) < 1e-24)
+        if not act.any():
+            continue
+        nrm = _c2_cross(qa, side)
+        eps = 1e-15 * np.sqrt(_c2_dot(nrm, nrm))
+        out = np.zeros_like(poly)
+        m = np.zeros(Np, np.int64)
+        for i in range(int(n[act].max())):
+            r = rows_all[act & (i < n)]
+            X1 = poly[r, i]
+            X2 = poly[r, np.where(i + 1 == n[r], 0, i + 1)]
+            d1, d2 = _c2_dot(nrm[r], X1), _c2_dot(nrm[r], X2)
+            in1, in2 = d1 >= -eps[r], d2 >= -eps[r]
+            k = r[in1]
+            out[k, m[k]] = X1[in1]
+            m[k] += 1
+            x = in1 != in2
+            X = X1[x] * d2[x][:, None] - X2[x] * d1[x][:, None]
+            sgn = np.where((d2[x] - d1[x]) > 0.0, 1.0, -1.0)
+            nn = np.sqrt(_c2_dot(X, X))
+            good = nn > 0.0
+            k = r[x][good]
+            out[k, m[k]] = X[good] * (sgn[good] / nn[good])[:, None]
+            m[k] += 1
+        poly[act] = out[act]
+        n[act] = m[act]
+    return poly, n
+
+
+def _c2_seq_sum(val, group, ngroups):
+    """acc[g] = ((0.0 + v_0) + v_1) + ... over the items of group g in their given order; val [N] or [N][C]."""
+    val = np.asarray(val, np.float64)
+    acc = np.zeros((ngroups,) + val.shape[1:])
+    if val.shape[0] == 0:
+        return acc
+    order = np.argsort(group, kind="stable")
+    g = group[order]
+    start = np.searchsorted(g, np.arange(ngroups))
+    rank = np.arange(g.size) - start[g]
+    for t in range(int(rank.max()) + 1):
+        sel = order[rank == t]
+        acc[group[sel]] = acc[group[sel]] + val[sel]
+    return acc
+
+
+def conserve2nd_polygons_mesh(voc, vert_xyz, cell_xyz=None):
+    """The cells of a mesh for conserve2nd_rows: voc = verticesOnCell [nCells][maxEdges] (1-based, 0 = pad), vert_xyz / cell_xyz [3][n]:
+    Mesh.xyz(MESHLOC_NODE) / Mesh.xyz(MESHLOC_ELEMENT) -> (xyz [nCells][maxEdges][3] valid entries first in listed order, cnt, centres)."""
+    voc = np.asarray(voc, np.int64)
+    v = np.asarray(vert_xyz, np.float64).T
+    ok = (voc > 0) & (voc <= v.shape[0])
+    cnt = ok.sum(axis=1)
+    ids = np.take_along_axis(voc, np.argsort(~ok, axis=1, kind="stable"), axis=1)
+    xyz = v[np.clip(ids, 1, max(v.shape[0], 1)) - 1]
+    xyz[np.arange(voc.shape[1])[None, :] >= cnt[:, None]] = 0.0
+    return xyz, cnt, (None if cell_xyz is None else np.asarray(cell_xyz, np.float64).T)
+
+
+def conserve2nd_polygons_grid(corner_xyz, nx, ny, center_xyz=None):
+    """The cells of a grid for conserve2nd_rows, id = j * nx + i: corner_xyz / center_xyz [3][n]: Grid.xyz(STAGGERLOC_CORNER) /
+    Grid.xyz(STAGGERLOC_CENTER) -> corners (i, j), (i + 1, j), (i + 1, j + 1), (i, j + 1) of every cell, 4 each, the centres."""
+    c = np.asarray(corner_xyz, np.float64).T.reshape(ny + 1, nx + 1, 3)
+    xyz = np.stack([c[:-1, :-1], c[:-1, 1:], c[1:, 1:], c[1:, :-1]], axis=2).reshape(nx * ny, 4, 3)
+    return xyz, np.full(nx * ny, 4, np.int64), (None if center_xyz is None else np.asarray(center_xyz, np.float64).T)
+
+
+def _conserve2nd_rows(rowptr, col, src_polys, dst_polys, neighbours, norm, src_mask=None, first_order=False):
+    """conserve2nd_rows with the switch of the tests (first_order True: every stencil fails) -> (rowptr, col, val, info): info holds the
+    pieces' areas Aq, area_d, the sources' A_i and the statistics [pairs, passing, failing, stencil entries, longest row]."""
+    rowptr, col = np.asarray(rowptr, np.int64), np.asarray(col, np.int64).reshape(-1)
+    sx, sn = np.asarray(src_polys[0], np.float64), np.asarray(src_polys[1], np.int64)
+    dx, dn = np.asarray(dst_polys[0], np.float64), np.asarray(dst_polys[1], np.int64)
+    nS, nD, nnz = sx.shape[0], rowptr.size - 1, col.size
+    centre = src_polys[2] if len(src_polys) > 2 and src_polys[2] is not None else np.zeros((nS, 3))
+    mask = np.zeros(nS, bool) if src_mask is None else np.asarray(src_mask).reshape(-1) != 0
+    with np.errstate(all="ignore"):
+        # cells: orientation, area(d), G_i
+        fa_s, _ = _c2_fan(sx, sn)
+        fa_d, _ = _c2_fan(dx, dn)
+        none_s, none_d = (sn < 3) | (fa_s == 0.0), (dn < 3) | (fa_d == 0.0)
+        sc, dc = _c2_ccw(sx, sn, fa_s < 0.0), _c2_ccw(dx, dn, fa_d < 0.0)
+        area_d = np.where(none_d, 0.0, np.abs(fa_d))
+        _, mom = _c2_fan(sc, sn)
+        r = np.sqrt(_c2_dot(mom, mom))
+        useG = (sn >= 3) & (r > 0.0)
+        G = np.where(useG[:, None], mom / np.where(useG, r, 1.0)[:, None], centre)
+        e1, e2 = _patch_frame([G[:, 0], G[:, 1], G[:, 2]])
+        e1, e2 = np.stack(e1, axis=1), np.stack(e2, axis=1)
+        # pieces
+        row = np.repeat(np.arange(nD), np.diff(rowptr))
+        Aq, mq = np.zeros(nnz), np.zeros((nnz, 3))
+        live = np.flatnonzero(~none_s[col] & ~none_d[row])
+        for a in range(0, live.size, 1 << 15):                              # bounded memory
+            q = live[a:a + (1 << 15)]
+            poly, n = _c2_clip(sc[col[q]], sn[col[q]], dc[row[q]], dn[row[q]])
+            ar, m = _c2_fan(poly, n)
+            keep = n >= 3
+            Aq[q] = np.where(keep & (ar > 0.0), ar, 0.0)
+            mq[q] = np.where(keep[:, None], m, 0.0)
+        rsum = _c2_seq_sum(Aq, row, nD)
+        by_src = np.argsort(col, kind="stable")                               # a source's pieces in ascending destination id
+        Ai = _c2_seq_sum(Aq[by_src], col[by_src], nS)
+        Mi = _c2_seq_sum(mq[by_src], col[by_src], nS)
+        # stencils
+        nbr, cnt = np.asarray(neighbours[0], np.int64), np.asarray(neighbours[1], np.int64)
+        K = nbr.shape[1]
+        ids = np.arange(nS)
+        safe = np.clip(nbr, 0, max(nS - 1, 0))
+        member = (nbr >= 0) & (nbr < nS) & (nbr != ids[:, None]) & ~mask[safe]
+        usable = (cnt <= PATCH_MAX_PNTS) & ~mask & (not first_order)
+        member &= usable[:, None]
+        dxk, dyk = np.zeros((nS, K)), np.zeros((nS, K))
+        m00, m01, m11, ns = np.zeros(nS), np.zeros(nS), np.zeros(nS), np.zeros(nS, np.int64)
+        for k in range(K):
+            d = G[safe[:, k]] - G
+            dxk[:, k], dyk[:, k] = _c2_dot(d, e1), _c2_dot(d, e2)
+            on = member[:, k]
+            m00 = np.where(on, m00 + dxk[:, k] * dxk[:, k], m00)
+            m01 = np.where(on, m01 + dxk[:, k] * dyk[:, k], m01)
+            m11 = np.where(on, m11 + dyk[:, k] * dyk[:, k], m11)
+            ns += on
+        p = m00 * m11
+        det = p - m01 * m01
+        ok = usable & (ns >= 2) & (det > _C2_DET_TOL * p)
+        bxk = (m11[:, None] * dxk - m01[:, None] * dyk) / det[:, None]
+        byk = (m00[:, None] * dyk - m01[:, None] * dxk) / det[:, None]
+        member &= ok[:, None]
+        sbx_own, sby_own = np.zeros(nS), np.zeros(nS)
+        for k in range(K):
+            on = member[:, k]
+            sbx_own = np.where(on, sbx_own + bxk[:, k], sbx_own)
+            sby_own = np.where(on, sby_own + byk[:, k], sby_own)
+        own_bx, own_by = np.where(ok, -sbx_own, 0.0), np.where(ok, -sby_own, 0.0)
+        # the stencil CSR: members and the cell itself, ascending
+        cand_id = np.concatenate([np.where(member, nbr, _PATCH_NONE), ids[:, None]], axis=1)
+        cand_bx = np.concatenate([bxk, own_bx[:, None]], axis=1)
+        cand_by = np.concatenate([byk, own_by[:, None]], axis=1)
+        order = np.argsort(cand_id, axis=1, kind="stable")
+        cand_id = np.take_along_axis(cand_id, order, axis=1)
+        cand_bx, cand_by = np.take_along_axis(cand_bx, order, axis=1), np.take_along_axis(cand_by, order, axis=1)
+        have = cand_id != _PATCH_NONE
+        slen = have.sum(axis=1)
+        sptr = np.concatenate([[0], np.cumsum(slen)]).astype(np.int64)
+        scol, sbx, sby = cand_id[have], cand_bx[have], cand_by[have]
+        # offsets and weights
+        okq = (Aq > 0.0) & (Ai[col] > 0.0)
+        dq = mq / np.where(okq, Aq, 1.0)[:, None] - Mi[col] / np.where(okq, Ai[col], 1.0)[:, None]
+        ex, ey = np.where(okq, _c2_dot(dq, e1[col]), 0.0), np.where(okq, _c2_dot(dq, e2[col]), 0.0)
+        div = area_d[row] if norm == NORM_DSTAREA else rsum[row]
+        w = np.where(div > 0.0, Aq / np.where(div > 0.0, div, 1.0), 0.0)
+        # the rows: every (entry, stencil position) pair in order
+        plen = slen[col]
+        pair_p = np.repeat(np.arange(nnz), plen)
+        first = np.cumsum(plen) - plen
+        pair_k = sptr[col][pair_p] + (np.arange(pair_p.size) - first[pair_p])
+        key = (row[pair_p] << 32) | scol[pair_k]
+        ukey, entry = np.unique(key, return_inverse=True)
+        entry = entry.reshape(-1)
+        g = (ex[pair_p] * sbx[pair_k]) + (ey[pair_p] * sby[pair_k])
+        t = np.where(scol[pair_k] == col[pair_p], 1.0 + g, g)
+        val = _c2_seq_sum(w[pair_p] * t, entry, ukey.size)
+    out_rowptr = np.searchsorted(ukey >> 32, np.arange(nD + 1)).astype(np.int64)
+    out_col = (ukey & 0xFFFFFFFF).astype(np.int32)
+    longest = int(np.diff(out_rowptr).max()) if nD else 0
+    info = {"Aq": Aq, "area_d": area_d, "Ai": Ai, "pass": ok, "sptr": sptr, "scol": scol,
+            "stats": [int(nnz), int(ok.sum()), int(nS - ok.sum()), int(scol.size), longest]}
+    return out_rowptr, out_col, val, info
+
+
+def conserve2nd_rows(rowptr, col, src_polys, dst_polys, neighbours, norm, src_mask=None):
+    """The numpy mirror of mpg_handle_conserve2nd, written elementwise in the order of mpassit_amd/csrc/conserve2nd.h and conserve_clip.h so
+    that it has the device's bits.  rowptr, col: the csr() pattern of a first-order conservative handle; src_polys / dst_polys: the cells
+    of the two sides from conserve2nd_polygons_mesh / _grid fed with the library's own unit vectors (Mesh.xyz(MESHLOC_NODE), Grid.xyz(
+    STAGGERLOC_CORNER); the cell centres are the fallback of G_i); neighbours: patch_neighbours_mesh(voc, tri) of the source mesh or
+    patch_neighbours_grid(nx, ny) of the source grid's CENTER stagger; norm: the Store's NORM_*; src_mask [n_src]: non-zero = masked.
+    Per stored entry the re-clipped piece's area and moment, per source cell the centroid of its covered part and the least-squares
+    stencil b over N1 minus itself minus the masked cells (failing: the cell alone, b = 0), per row the ascending union of its sources'
+    stencils with acc = acc + w_q * t in stored order from 0.0 (include/mpassit_amd.h states every step).
+    -> (rowptr int64, col int32, val)."""
+    return _conserve2nd_rows(rowptr, col, src_polys, dst_polys, neighbours, norm, src_mask)[:3]
+
+
 _COMPOSE_VECTOR_PASSES = 64   # terms of an entry of C summed by vectorised passes; what lies behind them is summed by a plain loop
 
 
