@@ -1222,6 +1222,70 @@ typedef struct mpg_conserve2nd_opts {
 } mpg_conserve2nd_opts;
 int mpg_handle_conserve2nd(mpg_handle rh, const mpg_points *src, const mpg_points *dst, const mpg_conserve2nd_opts *opts, mpg_handle *out);
 
+/* ---- creep-fill extrapolation: the unmapped rows of a handle filled level by level from their neighbours' rows ------------------------------
+ * ESMF_EXTRAPMETHOD_CREEP with extrapNumLevels, the one value of ESMF_FieldRegridStore's extrapMethod that mpg_handle_extrapolate does not
+ * take (this section supersedes the "creep fills" remark that ends the Store-time-mask section above; mpg_handle_extrapolate, its enum
+ * and its refusals are unchanged, which is why this is a call of its own).  The nearest-source fill jumps between neighbouring points,
+ * reaches arbitrarily far and ignores the interpolation that was just stored.  A creep fill continues the mapped field outward: every
+ * newly filled point takes the average of its already filled neighbours, repeated for a number of levels -- the grid points just outside
+ * a limited-area mesh, the rim of a mesh under a regional analysis, SST and soil fields carried a few points across a coastline.  It is a
+ * pure handle-to-handle transform: the new row of a filled point is the average of its neighbours' rows.  It needs no source geometry
+ * and no search, only the destination's connectivity, and it returns an ordinary CSR handle, which every consumer takes.
+ * ESMF_EXTRAPMETHOD_CREEP_NRST_D is this call followed by mpg_handle_extrapolate with MPG_EXTRAPMETHOD_NEAREST_STOD for what is left
+ * (regrid.creep_nearest in Python).  Masks are served this way: mpg_handle_mask first, then mpg_handle_creep with dst_skip_dev = the
+ * destination mask.
+ *
+ * rh: any handle without pole terms, fixed or CSR.  dst: the destination point set rh was stored onto, by the mpg_points rules and size
+ *   checks of mpg_handle_extrapolate: any stagger of a grid, or a mesh's cells.  No source set is given: none is read.
+ * The rule.  A contract by identity with the numpy mirror target_grid.creep_rows; mpassit_amd/csrc/creep.h is the arithmetic, for
+ *   device and host.  Every operation is rounded on its own (fp contract(off)); the only operations are + and /.
+ *   Rows.  An unmapped row is as mpg_handle_extrapolate defines it: of a fixed handle, slot 0's index < 0; of a CSR handle, an empty row.
+ *     Every mapped row is copied verbatim by that section's CSR-output rule: a fixed row's slots in slot order, -1 slots dropped, weight
+ *     1.0 for a nearest handle without a weight array; a CSR row's entries in stored order.
+ *   Neighbours Nb(p) of a destination point p, in ascending id, p itself excluded.  Any stagger of a grid with snx x sny points,
+ *     id = j * snx + i: the points of [i - 1, i + 1] x [j - 1, j + 1] that lie inside the grid, up to 8; this is NOT the shifted 3 x 3
+ *     window of the patch rule, and there is no wrap.  A mesh's cells (MPG_MESHLOC_ELEMENT): N1(p) as mpg_handle_patch defines it, minus
+ *     p -- the cells that share a valid dual triangle with p, i.e. the node neighbours of ESMF's dual mesh.  A mesh of bare centres (no
+ *     verticesOnCell entries) has no neighbours: nothing is filled, and that is success.
+ *   Levels.  level[p] = 0 for a mapped row.  An unmapped row with dst_skip[p] != 0 never gets a level: it is never filled and never a
+ *     neighbour.  For L = 1, 2, ... up to num_levels: an unmapped, unskipped p without a level gets level L iff some q in Nb(p) has
+ *     level[q] == L - 1.  The loop ends early at the first L that assigns nothing.  A skipped row that is mapped keeps its row and is
+ *     level 0: dst_skip only stops filling.
+ *   Row of a point of level L >= 1.  The contributors are Q = { q in Nb(p) : level[q] == L - 1 }, ascending, m = |Q| >= 1.  The columns
+ *     are the ascending distinct union of the contributors' columns.  The value of column e is acc = acc + v from 0.0, the sum running
+ *     over the contributors in ascending id and within a contributor over its entries with column e in stored order; then
+ *     w = acc / (double)m.  Zero values stay in the row: the pattern does not depend on the values.  Duplicate columns in a mapped input
+ *     row are one term each.
+ *   Two consequences.  With m = 1 the row is that neighbour's row with its columns sorted and merged, and values that appear once are
+ *     copied exactly.  Chain identity: creep(creep(h, a), b) has the bytes of creep(h, a + b).
+ *   Row sums are kept up to rounding: a column's value is a sum of k terms and one division, so with weights of one sign a filled row's
+ *     sum differs from the average of its contributors' sums by at most k * 2^-53 relative per level -- k <= 8 on a grid whose mapped
+ *     rows hold no duplicate column; with m = 1 and no duplicate column the row is an exact copy.
+ * Output: always a new CSR handle with the input's n_src, n_dst, nx_dst, ny_dst and method.  It has no dst_frac; its longest row is
+ *   recorded.  It is not cached and owns its arrays: pair it with mpg_handle_release; rh may be released right after the call.
+ *   mpg_handle_store_ms is the GPU time of the call.  mpg_handle_store_stats: [1] rows filled, [2] the last level that filled a row,
+ *   [3] rows still unmapped (skipped ones included), [6] the longest row.  Nothing unmapped is success: a CSR copy of the pattern.
+ * Determinism: the same bytes from run to run; no floating-point atomics; the one sort is stable.  There is no blocking knob: rows of any
+ *   length take the same path.
+ * Blocking: the call allocates, drains the Store worker first, orders itself after whatever produced rh (as mpg_handle_get_csr does)
+ *   and reads counts back: once before the first level, twice per level (the front's size with its candidates, then the level's
+ *   entries), once for the output's entry count.
+ * Refusals, each with a message that names mpg_handle_creep and the way out.  MPG_ERR_INVALID_ARG: a NULL rh, dst, opts or out; a point
+ *   set that breaks the mpg_points rules; num_levels < 1; rh's n_dst, nx_dst or ny_dst differ from the destination set (both are printed).
+ *   MPG_ERR_UNSUPPORTED: a destination MPG_MESHLOC_NODE or MPG_MESHLOC_EDGE (no ring is defined there); a mesh of
+ *   mpg_mesh_create_window; maxEdges > 12; a destination grid with MPG_GRID_PERIODIC_I (the seam would be a wall); a handle with pole
+ *   terms (mpg_handle_pole_count > 0); a localized, rebased or windowed handle.  MPG_ERR_OVERFLOW: more than 2^31 - 2 entries in the
+ *   output, or among the candidate entries of one level (the contributors' rows before they are merged).  A failed allocation returns
+ *   its error and leaks nothing.
+ * Not served: vertices and edges; periodic destinations; distance-weighted averages; a fixed-handle output; caching or a _begin variant;
+ *   multi-GPU sharding; use from interp.py or the Fortran driver. */
+enum { MPG_CREEP_ALL_LEVELS = 0x7fffffff };
+typedef struct mpg_creep_opts {
+  int num_levels;               /* ESMF's extrapNumLevels: >= 1; MPG_CREEP_ALL_LEVELS = until no row is filled any more */
+  const uint8_t *dst_skip_dev;  /* [n_dst] device bytes, non-zero = never filled and never a neighbour; NULL = none */
+} mpg_creep_opts;
+int mpg_handle_creep(mpg_handle rh, const mpg_points *dst, const mpg_creep_opts *opts, mpg_handle *out);
+
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the

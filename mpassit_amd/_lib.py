@@ -40,6 +40,7 @@ SYMBOLS = [
     "mpg_handle_mask", "mpg_handle_extrapolate_masked",
     "mpg_handle_patch",
     "mpg_handle_conserve2nd",
+    "mpg_handle_creep",
 ]
 
 MPG_SUCCESS = 0
@@ -63,6 +64,8 @@ REGRIDMETHOD_PATCH = MPG_REGRIDMETHOD_PATCH
 PATCH_MAX_PNTS = 32
 MPG_REGRIDMETHOD_CONSERVE_2ND = 4   # the method of mpg_handle_conserve2nd's handles; no Store takes it
 REGRIDMETHOD_CONSERVE_2ND = MPG_REGRIDMETHOD_CONSERVE_2ND
+MPG_CREEP_ALL_LEVELS = 0x7fffffff   # mpg_creep_opts.num_levels: until no row is filled any more
+CREEP_ALL_LEVELS = MPG_CREEP_ALL_LEVELS
 MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY = 0, 1, 2
 MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY = MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY
 
@@ -503,6 +506,24 @@ def handle_conserve2nd(*args):
     if "handle_conserve2nd" not in _to_mesh_fns:
         _to_mesh_fns["handle_conserve2nd"] = _HANDLE_CONSERVE2ND_PROTO(("mpg_handle_conserve2nd", load()))
     return _to_mesh_fns["handle_conserve2nd"](*args)
+
+
+# Creep-fill extrapolation (include/mpassit_amd.h): the unmapped rows of a handle filled level by level from their neighbours' rows
+#   mpg_handle_creep(rh, dst, opts, out)
+class CreepOpts(C.Structure):
+    """mpg_creep_opts of include/mpassit_amd.h: the number of levels (>= 1, CREEP_ALL_LEVELS = all) and a device byte mask of the
+    destination rows that are never filled and never a neighbour (0 / None = none)."""
+    _fields_ = [("num_levels", C.c_int), ("dst_skip_dev", C.c_void_p)]
+
+
+_HANDLE_CREEP_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Points), C.POINTER(CreepOpts), C.c_void_p)
+
+
+def handle_creep(*args):
+    """The typed binding of mpg_handle_creep; returns the call's status code."""
+    if "handle_creep" not in _to_mesh_fns:
+        _to_mesh_fns["handle_creep"] = _HANDLE_CREEP_PROTO(("mpg_handle_creep", load()))
+    return _to_mesh_fns["handle_creep"](*args)
 
 
 _lib = None

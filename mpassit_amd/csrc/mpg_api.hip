@@ -16,6 +16,7 @@
 #include "compose_checks.h"
 #include "mpg_internal.h"
 #include "patch.h"
+#include "creep.h"
 #include "wind_reconstruct_checks.h"
 #include "wind_vector_checks.h"
 
@@ -131,7 +132,7 @@ void mpg_pool_release() {
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
   X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
-  X(k_handle_mask) X(k_patch) X(k_conserve2nd)
+  X(k_handle_mask) X(k_patch) X(k_conserve2nd) X(k_creep)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -2067,6 +2068,108 @@ int mpg_handle_conserve2nd(mpg_handle rh, const mpg_points *src, const mpg_point
   }
   (void)hipEventRecord(e0, g_stream);
   rc = mpg_k_conserve2nd(rh, src->mesh, src->grid, dst->mesh, dst->grid, ps, opts->norm_type, opts->src_mask_dev, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("%s: %s", who, hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+// ---- creep-fill extrapolation: the unmapped rows of a handle filled level by level from their neighbours' rows (k_creep.hip, creep.h) -------
+int mpg_handle_creep(mpg_handle rh, const mpg_points *dst, const mpg_creep_opts *opts, mpg_handle *out) {
+  const char *who = "mpg_handle_creep";
+  MPG_CHECK_INIT();
+  if (!(rh && dst && opts && out)) {
+    mpg_set_error("%s: NULL argument (rh, dst, opts and out are all mandatory)", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  int rc;
+  int64_t nd = 0;
+  int dx = 0, dy = 0;
+  const PointSet *dp = nullptr;
+  if ((rc = ex_points(who, "destination", dst, false, &nd, &dx, &dy, &dp))) return rc;   // (mpg_handle_extrapolate's point-set rules)
+  if (opts->num_levels < 1) {
+    mpg_set_error("%s: num_levels = %d must be >= 1 (ESMF's extrapNumLevels; MPG_CREEP_ALL_LEVELS fills until no row is reached any more)", who,
+                  opts->num_levels);
+    return MPG_ERR_INVALID_ARG;
+  }
+  // the handle first (a handle with pole terms only ever meets a periodic destination), then the destination
+  if (rh->n_pole > 0) {
+    mpg_set_error("%s: the handle has pole terms (mpg_handle_pole_count > 0), which a crept copy cannot carry: store with "
+                  "MPG_POLEMETHOD_NONE, or creep a non-periodic handle", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->localized || mpg_handle_is_windowed(rh)) {
+    mpg_set_error("%s: the handle was localized or rebased (mpg_handle_localize / mpg_handle_rebase), or its mesh carries a source window "
+                  "(mpg_mesh_set_source_window): its indices are no longer source ids -- creep first, re-index the result", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->mesh && dst->meshloc != MPG_MESHLOC_ELEMENT) {
+    mpg_set_error("%s: a destination mesh is crept over its cells only (MPG_MESHLOC_ELEMENT, not location %d): no ring is defined on "
+                  "vertices or edges -- fill those with mpg_handle_extrapolate", who, dst->meshloc);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->mesh && dst->mesh->geo_grid) {
+    mpg_set_error("%s: the destination mesh was cut to a grid (mpg_mesh_create_window): the rings need every cell's vertices and triangles "
+                  "-- use the whole mesh (mpg_mesh_create)", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->mesh && dst->mesh->maxEdges > CR_MAX_EDGES) {
+    mpg_set_error("%s: maxEdges %d > %d: a cell's ring holds at most %d neighbours -- split the larger cells", who, dst->mesh->maxEdges,
+                  CR_MAX_EDGES, CR_MAX_NB);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (dst->grid && (dst->grid->periodic & MPG_GRID_PERIODIC_I)) {
+    mpg_set_error("%s: a destination grid with MPG_GRID_PERIODIC_I is not served (the neighbourhoods do not wrap in i: the seam would be a "
+                  "wall): create the grid without the flag, or fill with mpg_handle_extrapolate", who);
+    return MPG_ERR_UNSUPPORTED;
+  }
+  if (rh->n_dst != nd || rh->nx_dst != dx || rh->ny_dst != dy) {
+    mpg_set_error("%s: the handle has n_dst = %lld (%d x %d), the destination point set has %lld points (%d x %d)", who,
+                  (long long)rh->n_dst, rh->nx_dst, rh->ny_dst, (long long)nd, dx, dy);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (nd > 0x7ffffffeLL) {
+    mpg_set_error("%s: %lld destination points are beyond int32 ids", who, (long long)nd);
+    return MPG_ERR_OVERFLOW;
+  }
+  PtSrc pd;   // the destination's connectivity alone: no coordinates are read
+  pd.x = pd.y = pd.z = nullptr;
+  pd.voc = nullptr; pd.tri = nullptr; pd.maxEdges = 0; pd.nV = 0; pd.snx = dx; pd.sny = dy;
+  if (dst->mesh) {
+    pd.voc = dst->mesh->voc.p; pd.tri = dst->mesh->tri.p; pd.maxEdges = dst->mesh->maxEdges; pd.nV = dst->mesh->nVertices;
+  }
+  // rh is finished (a Store waits for its build before it hands its handle out); a begun Store may still allocate on the worker.  The
+  // build runs on the set-up stream, after whatever produced rh
+  store_worker_drain();
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = rh->method;
+  h->n_src = rh->n_src;
+  h->n_dst = rh->n_dst;
+  h->nx_dst = rh->nx_dst;
+  h->ny_dst = rh->ny_dst;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("%s: hipEventCreate failed", who);
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_creep(rh, pd, opts->num_levels, opts->dst_skip_dev, h, g_stream);
   if (!rc) {
     hipError_t he = hipEventRecord(e1, g_stream);
     if (he == hipSuccess) he = hipEventSynchronize(e1);

@@ -537,6 +537,11 @@ int mpg_k_patch(mpg_handle_s *in, const PtSrc &src, const PointSet &dst, mpg_han
 // (patch.h); src_mask: device bytes [n_src] or nullptr.  Arguments checked by the API entry point; blocking.  Builds in's transposed index
 int mpg_k_conserve2nd(mpg_handle_s *in, mpg_mesh_s *smesh, mpg_grid_s *sgrid, mpg_mesh_s *dmesh, mpg_grid_s *dgrid, const PtSrc &ps, int norm_type,
                       const uint8_t *src_mask, mpg_handle_s *out, hipStream_t s);
+// k_creep.hip: `out` (shape and method set by the caller, arrays empty) <- `in` with its unmapped rows filled level by level from their
+// neighbours' rows (creep.h); dst: the connectivity of the in->n_dst destination points (a whole mesh's voc / tri, or a stagger's snx x sny;
+// no coordinates are read); dst_skip [n_dst]: device bytes or nullptr.  Arguments checked by the API entry point; blocking: it allocates
+// and reads counts back twice per level
+int mpg_k_creep(mpg_handle_s *in, const PtSrc &dst, int num_levels, const uint8_t *dst_skip, mpg_handle_s *out, hipStream_t s);
 // k_target_grid.hip: cos / sin of the Lambert rotation angle at n points given by their unit vectors (mpg_mesh_rotang_dev)
 int mpg_k_mesh_rotang(const mpg_grid_s *g, int64_t n, const double *x, const double *y, double *cosa, double *sina, hipStream_t s);
 // ... and cos / sin of phi = angle - alpha at n edge points (mpg_mesh_edge_rotang_dev); g == nullptr: alpha = 0

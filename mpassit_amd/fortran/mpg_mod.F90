@@ -76,6 +76,12 @@ module mpg
     integer(c_int) :: norm_type        !< MPG_NORM_*, the one the Store was called with
     type(c_ptr) :: src_mask_dev        !< device bytes [n_src], non-zero = masked; c_null_ptr: none
   end type mpg_conserve2nd_opts
+  !> mpg_handle_creep (include/mpassit_amd.h): all levels, and the options
+  integer(c_int), parameter :: MPG_CREEP_ALL_LEVELS = 2147483647
+  type, bind(C) :: mpg_creep_opts
+    integer(c_int) :: num_levels       !< ESMF's extrapNumLevels: >= 1; MPG_CREEP_ALL_LEVELS: until no row is filled any more
+    type(c_ptr) :: dst_skip_dev        !< device bytes [n_dst], non-zero = never filled and never a neighbour; c_null_ptr: none
+  end type mpg_creep_opts
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -647,6 +653,16 @@ module mpg
       type(c_ptr), intent(out) :: out
       integer(c_int) :: rc
     end function mpg_handle_conserve2nd
+    !> creep-fill extrapolation: the unmapped rows of rh filled level by level from their neighbours' rows, as a new CSR handle
+    !> (mpg_handle_release it; the driver does not use it)
+    function mpg_handle_creep(rh, dst, opts, out) bind(C, name="mpg_handle_creep") result(rc)
+      import :: c_int, c_ptr, mpg_points, mpg_creep_opts
+      type(c_ptr), value :: rh
+      type(mpg_points), intent(in) :: dst
+      type(mpg_creep_opts), intent(in) :: opts
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_handle_creep
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

@@ -33,7 +33,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "regrid_masked_autograd", "extrapolate", "EXTRAPMETHOD_NEAREST_STOD", "EXTRAPMETHOD_NEAREST_IDAVG", "EXTRAP_MAX_PNTS",
            "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY",
            "patch", "regrid_store_patch", "REGRIDMETHOD_PATCH", "PATCH_MAX_PNTS",
-           "conserve_2nd", "regrid_store_conserve_2nd", "REGRIDMETHOD_CONSERVE_2ND"]
+           "conserve_2nd", "regrid_store_conserve_2nd", "REGRIDMETHOD_CONSERVE_2ND",
+           "creep", "creep_nearest", "CREEP_ALL_LEVELS"]
 
 
 def _f64(a):
@@ -2041,3 +2042,38 @@ def regrid_store_conserve_2nd(src, dst, norm=NORM_DSTAREA):
         return conserve_2nd(rh, src, dst, norm)
     finally:
         rh.release()
+
+
+# ---- creep-fill extrapolation: the unmapped rows of a handle filled level by level from their neighbours' rows ------------------------------
+CREEP_ALL_LEVELS = L.CREEP_ALL_LEVELS
+
+
+def creep(rh, dst, num_levels=CREEP_ALL_LEVELS, dst_skip=None, dst_loc=None):
+    """mpg_handle_creep (ESMF_EXTRAPMETHOD_CREEP with extrapNumLevels): a new CSR RouteHandle of rh's shape whose unmapped rows -- idx -1 in
+    slot 0, or an empty CSR row -- are filled level by level: a point next to level L - 1 takes level L, and its row is the average of
+    the rows of its neighbours of level L - 1 (mapped rows are level 0 and are copied).  dst: the Mesh or Grid rh was stored onto;
+    dst_loc: a stagger (default STAGGERLOC_CENTER; the 8 surrounding points are the neighbours) or MESHLOC_ELEMENT (the cells that share
+    a dual triangle).  num_levels >= 1, CREEP_ALL_LEVELS = until no row is filled any more.  dst_skip [n_dst]: numpy or torch, bool or
+    uint8, non-zero = never filled and never a neighbour (after mask_handle: its destination mask).  store_stats: [1] rows filled, [2]
+    the last level that filled a row, [3] rows still unmapped, [6] the longest row.  The bits of target_grid.creep_rows fed with rh.csr()
+    / fixed_to_csr(rh.weights()) and creep_neighbours_grid / _mesh.  Not cached: release() it; rh may be released."""
+    pd = _points(dst, dst_loc, "dst")
+    md = _mask_dev(dst_skip, rh.n_dst, "creep", "dst_skip") if rh is not None else None
+    opts = L.CreepOpts(num_levels=int(num_levels), dst_skip_dev=_mask_ptr(md))
+    h = C.c_void_p()
+    check(L.handle_creep(rh._h if rh is not None else None, C.byref(pd), C.byref(opts), C.byref(h)))
+    return RouteHandle(h)
+
+
+def creep_nearest(rh, src, dst, num_levels, src_mask=None, dst_skip=None, src_loc=None, dst_loc=None):
+    """ESMF_EXTRAPMETHOD_CREEP_NRST_D: creep() for num_levels levels, then what is left unmapped takes the nearest source
+    (EXTRAPMETHOD_NEAREST_STOD): extrapolate(), or extrapolate_masked() when src_mask or dst_skip is given -- the nearest UNMASKED source,
+    the dst_skip rows left unmapped by both steps.  src / dst: the Mesh or Grid objects rh was stored between.  The crept intermediate is
+    released.  The result is CSR (the creep's output kind).  Not cached: release() it; rh may be released."""
+    crept = creep(rh, dst, num_levels, dst_skip, dst_loc)
+    try:
+        if src_mask is None and dst_skip is None:
+            return extrapolate(crept, src, dst, EXTRAPMETHOD_NEAREST_STOD, src_loc=src_loc, dst_loc=dst_loc)
+        return extrapolate_masked(crept, src, dst, src_mask, dst_skip, EXTRAPMETHOD_NEAREST_STOD, src_loc=src_loc, dst_loc=dst_loc)
+    finally:
+        crept.release()

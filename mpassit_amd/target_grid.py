@@ -543,6 +543,109 @@ def extrapolate_rows_masked(src_xyz, dst_xyz, unmapped, src_mask, method=EXTRAPM
     return rowlen, back, w
 
 
+CREEP_ALL_LEVELS = 0x7fffffff
+
+
+def creep_neighbours_grid(snx, sny):
+    """Nb(p) of mpg_handle_creep on a grid stagger of snx x sny points, id = j * snx + i: the points of [i - 1, i + 1] x [j - 1, j + 1]
+    inside the grid, p itself excluded, ascending; no shift and no wrap.  -> (nbr [n][8] int32 with -1 behind a row's end, cnt [n])."""
+    snx, sny = int(snx), int(sny)
+    j, i = np.divmod(np.arange(snx * sny, dtype=np.int64), snx)
+    cols = []
+    for dj in (-1, 0, 1):
+        for di in (-1, 0, 1):
+            if di == 0 and dj == 0:
+                continue
+            a, b = i + di, j + dj
+            cols.append(np.where((a >= 0) & (a < snx) & (b >= 0) & (b < sny), b * snx + a, _PATCH_NONE))
+    cand = np.sort(np.stack(cols, axis=1), axis=1)
+    return np.where(cand != _PATCH_NONE, cand, -1).astype(np.int32), (cand != _PATCH_NONE).sum(axis=1)
+
+
+def creep_neighbours_mesh(voc, tri):
+    """Nb(p) of mpg_handle_creep on a mesh's cells: patch_neighbours_mesh's N1(p) minus p, ascending (the cells that share a valid dual
+    triangle with p).  A cell without verticesOnCell entries has none.  -> (nbr [nCells][K] int32 with -1 behind a row's end, cnt)."""
+    n1, cnt, _ = patch_neighbours_mesh(voc, tri)
+    if (cnt > PATCH_MAX_PNTS).any():
+        raise ValueError("creep_neighbours_mesh: a ring of more than %d cells" % PATCH_MAX_PNTS)
+    cand = np.where((n1 >= 0) & (n1 != np.arange(n1.shape[0])[:, None]), n1.astype(np.int64), _PATCH_NONE)
+    cand = np.sort(cand, axis=1)[:, :max(n1.shape[1] - 1, 1)]
+    return np.where(cand != _PATCH_NONE, cand, -1).astype(np.int32), (cand != _PATCH_NONE).sum(axis=1)
+
+
+def creep_rows(rowptr, col, val, neighbours, num_levels=CREEP_ALL_LEVELS, dst_skip=None):
+    """The numpy mirror of mpg_handle_creep on a CSR pattern (a fixed handle: fixed_to_csr of its weights()).  neighbours: (nbr, cnt) of
+    creep_neighbours_grid / creep_neighbours_mesh; dst_skip: bool or uint8 of n_dst, None = none.
+    level[p] = 0 for a non-empty row; an empty row with dst_skip never gets a level; for L = 1 .. num_levels an empty, unskipped row
+    without a level gets level L iff a neighbour has level L - 1, and the loop ends at the first L that assigns nothing.  The row of a
+    point of level L: its contributors are the neighbours of level L - 1 in ascending id, m of them; the columns are the ascending distinct
+    union of theirs; a column's value is acc = acc + v from 0.0 over the contributors in ascending id and, within one, over its entries
+    with that column in stored order, then acc / float(m) -- every operation rounded on its own.
+    -> (level [n] int32 with -1 = no level, rowptr int64, col int32, val)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64).reshape(-1)
+    val = np.asarray(val, dtype=np.float64).reshape(-1)
+    nbr, cnt = neighbours
+    nbr = np.asarray(nbr, dtype=np.int64)
+    n = rowptr.size - 1
+    nbr = nbr.reshape(n, -1)
+    if int(num_levels) < 1:
+        raise ValueError("creep_rows: num_levels must be >= 1")
+    skip = np.zeros(n, bool) if dst_skip is None else np.asarray(dst_skip).reshape(-1) != 0
+    level = np.where(np.diff(rowptr) > 0, 0, -1).astype(np.int32)
+    rows = [None] * n                                                # (col, val) of the filled rows
+    open_ = (level < 0) & ~skip
+    L = 0
+    while L < int(num_levels) and open_.any():
+        L += 1
+        cand = np.flatnonzero(open_)
+        nb = nbr[cand]
+        has = (nb >= 0) & (level[np.maximum(nb, 0)] == L - 1)
+        front = cand[has.any(axis=1)]
+        if front.size == 0:
+            break
+        new = {}
+        for p, q_all, h in zip(front, nb[has.any(axis=1)], has[has.any(axis=1)]):
+            Q = q_all[h]                                             # ascending: nbr is
+            cc, vv = [], []
+            for q in Q:
+                if level[q] == 0:
+                    cc.append(col[rowptr[q]:rowptr[q + 1]])
+                    vv.append(val[rowptr[q]:rowptr[q + 1]])
+                else:
+                    cc.append(rows[q][0])
+                    vv.append(rows[q][1])
+            cc, vv = np.concatenate(cc), np.concatenate(vv)
+            order = np.argsort(cc, kind="stable")                    # a column's terms stay in (contributor, stored) order
+            sc, sv = cc[order], vv[order]
+            head = np.ones(sc.size, bool)
+            head[1:] = sc[1:] != sc[:-1]
+            gid = np.cumsum(head) - 1
+            first = np.flatnonzero(head)
+            rank = np.arange(sc.size) - first[gid]
+            acc = np.zeros(first.size)
+            for t in range(int(rank.max()) + 1):
+                sel = rank == t
+                acc[gid[sel]] = acc[gid[sel]] + sv[sel]
+            new[p] = (sc[first], acc / float(Q.size))
+        for p, r in new.items():                                     # a level reads only the level below it
+            rows[p] = r
+        level[front] = L
+        open_[front] = False
+    lens = np.diff(rowptr).copy()
+    filled = np.flatnonzero(level > 0)
+    for p in filled:
+        lens[p] = rows[p][0].size
+    out_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    out_col, out_val = np.empty(out_ptr[-1], np.int32), np.empty(out_ptr[-1])
+    mapped = np.repeat(level == 0, np.diff(rowptr))
+    keep = np.repeat(level == 0, lens)
+    out_col[keep], out_val[keep] = col[mapped], val[mapped]
+    for p in filled:
+        out_col[out_ptr[p]:out_ptr[p + 1]], out_val[out_ptr[p]:out_ptr[p + 1]] = rows[p]
+    return level, out_ptr, out_col, out_val
+
+
 REGRIDMETHOD_PATCH = 3
 PATCH_MAX_PNTS = 32
 _PATCH_NONE = np.iinfo(np.int64).max
