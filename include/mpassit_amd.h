@@ -179,7 +179,8 @@ int mpg_grid_rotang_dev(mpg_grid grid, const double **cosa_dev, const double **s
  * interp_hist_data (interp.F90:123-148, :207) builds the element -> CENTER bilinear weights once. */
 int mpg_regrid_store(mpg_mesh src, int src_meshloc, mpg_grid dst, int dst_staggerloc, int regridmethod,
                      mpg_handle *out);
-/* Grid -> Grid on the same grid, CENTER -> EDGE1/EDGE2 bilinear (interp.F90:298,316). */
+/* Grid -> Grid on the same grid, CENTER -> EDGE1/EDGE2 bilinear (interp.F90:298,316).  Everything else between two grids -- any stagger
+ * onto any stagger, nearest, periodic sources, conservative -- is mpg_regrid_store_grid_to_grid / mpg_regrid_store_conserve_grid_to_grid. */
 int mpg_regrid_store_grid(mpg_grid grid, int src_staggerloc, int dst_staggerloc, int regridmethod,
                           mpg_handle *out);
 /* Grid -> Mesh: ESMF_FieldRegridStore(srcField on a Grid stagger, dstField on a Mesh location) -- the call that regrids BACK: a gridded
@@ -1285,6 +1286,64 @@ typedef struct mpg_creep_opts {
   const uint8_t *dst_skip_dev;  /* [n_dst] device bytes, non-zero = never filled and never a neighbour; NULL = none */
 } mpg_creep_opts;
 int mpg_handle_creep(mpg_handle rh, const mpg_points *dst, const mpg_creep_opts *opts, mpg_handle *out);
+
+/* ---- Grid -> Grid between two grids: ESMF_FieldRegridStore(srcField on a Grid stagger, dstField on a stagger of another Grid) -- a GFS /
+ * ERA5 lat-lon analysis onto the Lambert target grid, a parent domain onto its nest and the nest back onto the parent, the target grid's
+ * results onto a lat-lon verification grid, precipitation moved conservatively between two regular grids -- without a detour through a
+ * mesh.  mpg_regrid_store_grid above stays the destaggering Store of ONE grid.
+ * Common to both calls.  Sources: the snx x sny points of src_staggerloc of `src`, source index = j * snx + i, n_src = snx * sny.
+ *   Destinations: the points of dst_staggerloc of `dst`, dnx x dny of them; any stagger whose coordinates the grid holds, CORNER
+ *   included.  mpg_handle_info reports n_dst = dnx * dny, nx_dst = dnx, ny_dst = dny: every Regrid writes [lev][dny][dnx].  src == dst is
+ *   allowed.  The destination's periodic flag is irrelevant for bilinear and nearest: its points are just points.  A destination that is
+ *   a row block of a larger grid is an ordinary grid: that is how a row-sharded host uses these calls.
+ * mpg_regrid_store_grid_to_grid, MPG_REGRIDMETHOD_BILINEAR, source without MPG_GRID_PERIODIC_I: per destination point the rule of
+ *   mpg_regrid_store_to_mesh -- the same quads, the lowest passing quad id, the grid_inside_tol_exp tolerance, slots A, B, C, D -- run by
+ *   that call's kernels on the destination stagger's points.  A fixed 4-slot handle; an unmapped point has idx -1.  Both candidate routes
+ *   give identical bytes: the index route through the SOURCE grid's inverse projection, and the pyramid walk;
+ *   mpg_tune("store_boxes", 0), mpg_handle_store_path and mpg_handle_store_stats [1] [2] behave as in that call.
+ * MPG_REGRIDMETHOD_BILINEAR, source with MPG_GRID_PERIODIC_I: src_staggerloc must be MPG_STAGGERLOC_CENTER (any other source stagger ->
+ *   MPG_ERR_UNSUPPORTED).  The rule of mpg_regrid_store_periodic_to_mesh: seam quads, pole caps under pole_method, the end-row hemisphere
+ *   rule and the MPG_GRID_NO_*_POLE flags.  An ordinary CSR handle without pole terms: quad rows have 4 entries, cap rows nx.
+ *   mpg_handle_store_stats are that call's.
+ * pole_method must be MPG_POLEMETHOD_NONE or MPG_POLEMETHOD_ALLAVG on every call; for a non-periodic source (and for nearest) it is
+ *   ignored, and it is 0 in the cache key.
+ * MPG_REGRIDMETHOD_NEAREST_STOD: the rule of the Grid -> Mesh nearest Store, periodic sources included: the smallest chord distance,
+ *   the lowest source index on ties.  A fixed 1-slot handle; every point is mapped.
+ * MPG_REGRIDMETHOD_CONSERVE -> MPG_ERR_UNSUPPORTED; the message names mpg_regrid_store_conserve_grid_to_grid.
+ * mpg_regrid_store_conserve_grid_to_grid: ESMF_FieldRegridStore(regridmethod=CONSERVE, normType=) between the CELLS of two grids.  Cell
+ *   (i, j) is the quadrilateral of CORNER points (i, j), (i + 1, j), (i + 1, j + 1), (i, j + 1), index j * nx + i; a grid without CORNER
+ *   coordinates -> MPG_ERR_INVALID_ARG.  I(d, s) is the Mesh -> Mesh statement above (mpg_regrid_store_conserve_mesh) word for word, with
+ *   "cell polygon" read as this quadrilateral: the source cell is the subject polygon, made counter-clockwise by the sign of its own fan
+ *   area; it is clipped by the destination cell's sides in listed order, that cell made counter-clockwise the same way; clip-plane
+ *   normals in difference form a x (b - a); the in-place clip of the other conservative Stores with its 1e-15 * |n| inside rule; a side
+ *   with |b - a|^2 < 1e-24 bounds nothing; the area is the triangle fan from slot 0, clamped at 0; area(d) is the cell's own fan area; no
+ *   floating-point contraction.  Rows are keyed by destination cell, columns ascending.  MPG_NORM_DSTAREA: w = I / area(d);
+ *   MPG_NORM_FRACAREA: w = I / sum_s I.  An entry is dropped when I <= 1e-14 * area(d); an uncovered cell has an empty row.  The dst
+ *   fraction, summed in ascending source index, stays with the handle (mpg_handle_get_dst_frac).  Two Stores on fresh objects give the
+ *   same bytes: no atomic decides a stored byte.  Periodic grids are accepted on either side: the collapsed pole sides bound nothing, and
+ *   a cell without area is part of no pair.
+ *   Candidates: one thread per destination cell walks the source grid's cell pyramid with the cell's own padded box (the coordinate
+ *   hull of its corners, padded by 2 e2 + 1e-9: DESIGN.md s4.2), so no pair with I > 0 is removed; the pair list has exact size.  The
+ *   pyramid walk is the only candidate route of this Store: mpg_handle_store_path reports 0.  mpg_handle_store_stats: [1] pairs clipped,
+ *   [6] vertex slots of the clip.
+ * Refusals, each with a message that names the call and the way out.  MPG_ERR_INVALID_ARG: NULL arguments; unknown enums; a stagger
+ *   without coordinates; fewer than 2 x 2 source points for bilinear; the periodic call's own argument errors (nx < 3 or ny < 2; two live
+ *   end rows in one hemisphere).  MPG_ERR_UNSUPPORTED: as stated above.  MPG_ERR_OVERFLOW: counts beyond int32; nnz >= 2^31; a clipped
+ *   polygon that outgrew its vertex slots.
+ * Cached like every Store and paired with one mpg_handle_release.  The keys carry kind bits of their own, both grids, both staggers and
+ *   the method, inside_tol_exp for bilinear, pole_method for a periodic source's bilinear Store and norm_type for the conservative Store:
+ *   they collide with no other Store's key -- mpg_regrid_store_grid's included --, and staggers, methods, norms, pole methods and the two
+ *   directions are distinct handles.  Parked entries go when EITHER grid is destroyed.  There are no _begin variants.
+ * The wind chain does not mistake these handles: mpg_wind_destagger[_pitched]_dev and mpg_wind_destagger_transpose_dev recognise the
+ *   destagger pair by shape, so a handle of these Stores whose source grid is not its destination grid is marked, and those calls return
+ *   MPG_ERR_UNSUPPORTED for it.  With src == dst the CENTER -> EDGE1 / EDGE2 handles of this call are served like mpg_regrid_store_grid's.
+ * Everything that takes a fixed 1- or 4-slot handle or a CSR handle takes these unchanged: mpg_regrid_dev / _typed[_pitched]_dev, the
+ *   bundle calls, mpg_regrid_masked_dev, mpg_regrid_transpose_dev, the weight getters, mpg_handle_extrapolate[_masked], mpg_handle_mask,
+ *   mpg_handle_creep, mpg_handle_patch (non-periodic bilinear), mpg_handle_conserve2nd (the conservative handle, non-periodic source) and
+ *   mpg_handle_compose. */
+int mpg_regrid_store_grid_to_grid(mpg_grid src, int src_staggerloc, mpg_grid dst, int dst_staggerloc, int regridmethod, int pole_method,
+                                  mpg_handle *out);
+int mpg_regrid_store_conserve_grid_to_grid(mpg_grid src, mpg_grid dst, int norm_type, mpg_handle *out);
 
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.

@@ -41,6 +41,7 @@ SYMBOLS = [
     "mpg_handle_patch",
     "mpg_handle_conserve2nd",
     "mpg_handle_creep",
+    "mpg_regrid_store_grid_to_grid", "mpg_regrid_store_conserve_grid_to_grid",
 ]
 
 MPG_SUCCESS = 0
@@ -213,6 +214,27 @@ def regrid_store_periodic_to_mesh(*args):
     if "pstore" not in _to_mesh_fns:
         _to_mesh_fns["pstore"] = _STORE_PERIODIC_TO_MESH_PROTO(("mpg_regrid_store_periodic_to_mesh", load()))
     return _to_mesh_fns["pstore"](*args)
+
+
+# The Stores between two grids, bound the same way.
+#   mpg_regrid_store_grid_to_grid(src grid, src_staggerloc, dst grid, dst_staggerloc, regridmethod, pole_method, out)
+#   mpg_regrid_store_conserve_grid_to_grid(src grid, dst grid, norm_type, out)
+_STORE_GRID_TO_GRID_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p))
+_STORE_CONSERVE_GRID_TO_GRID_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p))
+
+
+def regrid_store_grid_to_grid(*args):
+    """The typed binding of mpg_regrid_store_grid_to_grid; returns the call's status code."""
+    if "ggstore" not in _to_mesh_fns:
+        _to_mesh_fns["ggstore"] = _STORE_GRID_TO_GRID_PROTO(("mpg_regrid_store_grid_to_grid", load()))
+    return _to_mesh_fns["ggstore"](*args)
+
+
+def regrid_store_conserve_grid_to_grid(*args):
+    """The typed binding of mpg_regrid_store_conserve_grid_to_grid; returns the call's status code."""
+    if "cggstore" not in _to_mesh_fns:
+        _to_mesh_fns["cggstore"] = _STORE_CONSERVE_GRID_TO_GRID_PROTO(("mpg_regrid_store_conserve_grid_to_grid", load()))
+    return _to_mesh_fns["cggstore"](*args)
 
 
 # The wind chain turned round and the rotation angles it needs, bound the same way.

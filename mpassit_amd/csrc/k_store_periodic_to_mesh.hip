@@ -268,18 +268,19 @@ int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s) {
   return MPG_SUCCESS;
 }
 
-int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s) {
+// The Store onto any list of points: `dst` holds n = nx_dst * ny_dst of them (a mesh location: ny_dst = 1; a stagger of another grid: its
+// snx x sny).  `who` names the entry point in the messages.
+int mpg_k_store_periodic_to_points(mpg_grid_s *g, const PointSet &dst, int64_t n, int nx_dst, int ny_dst, int pole_method, const char *who,
+                                   mpg_handle_s *h, hipStream_t s) {
   int rc;
   const PointSet &src = g->pts[MPG_STAGGERLOC_CENTER];
-  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
   const int nx = g->nx, ny = g->ny;
-  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
   h->kind = MPG_KIND_CSR;
   h->nnz_per_row = 0;
   h->n_src = (int64_t)nx * ny;
   h->n_dst = n;
-  h->nx_dst = (int)n;
-  h->ny_dst = 1;
+  h->nx_dst = nx_dst;
+  h->ny_dst = ny_dst;
   h->nnz = 0;
   if ((rc = h->rowptr.alloc((size_t)n + 1))) return rc;
   if (n == 0) {
@@ -292,15 +293,15 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
   if (caps) {
     if ((rc = mpg_k_grid_end_poles(g, s))) return rc;
     if (!no_pole && g->end_pole[0] == g->end_pole[1]) {
-      mpg_set_error("mpg_regrid_store_periodic_to_mesh: CENTER rows 0 and %d both lie in the %s hemisphere, so at most one of them closes on a "
+      mpg_set_error("%s: CENTER rows 0 and %d both lie in the %s hemisphere, so at most one of them closes on a "
                     "pole; a row block passes MPG_GRID_NO_SOUTH_POLE (row 0) / MPG_GRID_NO_NORTH_POLE (row ny - 1) for the end that does not",
-                    g->ny - 1, g->end_pole[0] > 0 ? "northern" : "southern");
+                    who, g->ny - 1, g->end_pole[0] > 0 ? "northern" : "southern");
       return MPG_ERR_INVALID_ARG;
     }
   }
   Pyramid &pyr = g->wrappyr;
   if (!pyr.built && (rc = mpg_k_build_wrap_pyramid(src, nx, ny, pyr, s))) return rc;
-  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], "mpg_regrid_store_periodic_to_mesh"))) return rc;
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], who))) return rc;
   TmpBuf<float> ij;
   const bool use_ij = ptm_index_route(g);
   if (use_ij) {
@@ -348,9 +349,9 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
   MPG_HIP(hipMemcpyAsync(hc, cnt.p, sizeof(hc), hipMemcpyDeviceToHost, s));
   MPG_HIP(hipStreamSynchronize(s));
   if (nnz < 0 || total != (long long)nnz) {
-    mpg_set_error("mpg_regrid_store_periodic_to_mesh: %lld entries (%lld cap rows of %d) exceed 2^31; MPG_POLEMETHOD_NONE stores no cap rows, "
-                  "and a mesh split into parts stores fewer each",
-                  total, (long long)hc[1], nx);
+    mpg_set_error("%s: %lld entries (%lld cap rows of %d) exceed 2^31; MPG_POLEMETHOD_NONE stores no cap rows, "
+                  "and a destination split into parts stores fewer each",
+                  who, total, (long long)hc[1], nx);
     return MPG_ERR_OVERFLOW;
   }
   h->nnz = nnz;
@@ -370,6 +371,12 @@ int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int 
   h->store_stats[3] = (int64_t)hc[1];
   h->store_stats[4] = (int64_t)hc[2];
   return MPG_SUCCESS;
+}
+
+int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s) {
+  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
+  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+  return mpg_k_store_periodic_to_points(g, dst, n, (int)n, 1, pole_method, "mpg_regrid_store_periodic_to_mesh", h, s);
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

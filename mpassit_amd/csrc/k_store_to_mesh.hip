@@ -167,24 +167,24 @@ __global__ __launch_bounds__(256) void k_to_mesh_nearest(int64_t n, const double
   idx[p] = best;
 }
 
-int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s) {
+// The Store onto any list of points: `dst` holds n = nx_dst * ny_dst of them (a mesh location: ny_dst = 1; a stagger of another grid: its
+// snx x sny).  `who` names the entry point in the messages.
+int mpg_k_store_to_points(mpg_grid_s *g, int stagger, const PointSet &dst, int64_t n, int nx_dst, int ny_dst, int method, const char *who,
+                          mpg_handle_s *h, hipStream_t s) {
   int rc;
   const PointSet &src = g->pts[stagger];
-  // the destination points: cells, vertices or (mpg_mesh_set_edges) edges -- nothing else differs between the three
-  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
   const int snx = g->snx[stagger], sny = g->sny[stagger];
-  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
   const bool nearest = method == MPG_REGRIDMETHOD_NEAREST_STOD;
   if (!nearest && (snx < 2 || sny < 2)) {
-    mpg_set_error("mpg_regrid_store_to_mesh: a bilinear Store needs at least 2 x 2 points of stagger %d", stagger);
+    mpg_set_error("%s: a bilinear Store needs at least 2 x 2 points of stagger %d", who, stagger);
     return MPG_ERR_INVALID_ARG;
   }
   h->kind = MPG_KIND_FIXED;
   h->nnz_per_row = nearest ? 1 : 4;
   h->n_src = (int64_t)snx * sny;
   h->n_dst = n;
-  h->nx_dst = (int)n;
-  h->ny_dst = 1;
+  h->nx_dst = nx_dst;
+  h->ny_dst = ny_dst;
   h->nnz = (int64_t)h->nnz_per_row * n;
   if ((rc = h->idx.alloc((size_t)h->nnz_per_row * (size_t)n))) return rc;
   if (!nearest && (rc = h->w.alloc(4 * (size_t)n))) return rc;
@@ -195,7 +195,7 @@ int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, 
     rc = nearest ? mpg_k_build_pyramid(src, snx, sny, pyr, s) : mpg_k_build_cell_pyramid(src, snx - 1, sny - 1, pyr, s);
     if (rc) return rc;
   }
-  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], "mpg_regrid_store_to_mesh"))) return rc;
+  if ((rc = mpg_walk_check<PyrTree>((int64_t)pyr.nx[0] * pyr.ny[0], who))) return rc;
   // index space: bilinear quads only where the Stores' boxes are valid; the nearest seed is good wherever the inverse answers
   TmpBuf<float> ij;
   const bool use_ij = mpg_grid_has_inverse(g, stagger) && mpg_store_boxes();
@@ -227,6 +227,13 @@ int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, 
   h->store_stats[1] = (int64_t)fell;
   h->store_stats[2] = n;
   return MPG_SUCCESS;
+}
+
+int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s) {
+  // the destination points: cells, vertices or (mpg_mesh_set_edges) edges -- nothing else differs between the three
+  const PointSet &dst = meshloc == MPG_MESHLOC_EDGE ? m->edge : meshloc == MPG_MESHLOC_ELEMENT ? m->cell : m->vert;
+  const int64_t n = meshloc == MPG_MESHLOC_EDGE ? m->edge.n : meshloc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+  return mpg_k_store_to_points(g, stagger, dst, n, (int)n, 1, method, "mpg_regrid_store_to_mesh", h, s);
 }
 
 // mpg_init loads this translation unit's code object ahead of its first launch (mpg_api.hip: warm_modules)

@@ -314,6 +314,7 @@ int mpg_wind_pair_dims(const mpg_handle_s *h1, const mpg_handle_s *h2, int *nx_o
   for (const mpg_handle_s *h : {h1, h2}) {
     if (!h) continue;
     const bool e1 = h == h1;
+    if (h->cross_grid) return MPG_ERR_UNSUPPORTED;   // stored between two different grids (mpg_regrid_store_grid_to_grid): the shape alone would pass
     if (h->kind != MPG_KIND_FIXED || h->nnz_per_row != 4 || h->localized || h->n_src != NP || nx < 1 || ny < 1 || h->nx_dst != nx + (e1 ? 1 : 0) ||
         h->ny_dst != ny + (e1 ? 0 : 1))
       return MPG_ERR_UNSUPPORTED;

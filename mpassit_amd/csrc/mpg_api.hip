@@ -132,7 +132,7 @@ void mpg_pool_release() {
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
   X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
-  X(k_handle_mask) X(k_patch) X(k_conserve2nd) X(k_creep)
+  X(k_handle_mask) X(k_patch) X(k_conserve2nd) X(k_creep) X(k_store_conserve_grid)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -699,12 +699,13 @@ struct StoreCtx {   // what a Store's build reads: the key's objects, typed by w
   explicit StoreCtx(const StoreKey &k) : src_loc(k.src_loc), dst_loc(k.dst_loc), method(k.method), pole_method(k.pole_method), norm_type(k.norm_type) {
     if (k.source_is_mesh()) src_mesh = (mpg_mesh_s *)k.src;
     else src_grid = (mpg_grid_s *)k.src;
-    if (k.kind == STORE_MESH_TO_GRID || k.kind == STORE_GRID_TO_GRID) dst_grid = (mpg_grid_s *)k.dst;
+    if (k.kind == STORE_MESH_TO_GRID || k.kind == STORE_GRID_TO_GRID || k.kind == STORE_GRID_TO_OTHER_GRID || k.kind == STORE_CONSERVE_GRID_TO_GRID)
+      dst_grid = (mpg_grid_s *)k.dst;
     else dst_mesh = (mpg_mesh_s *)k.dst;
   }
 };
 typedef int (*StoreBuildFn)(mpg_handle_s *, const StoreCtx &, hipStream_t);
-static StoreBuildFn store_build_fn(StoreKind kind);   // below, after the seven builds
+static StoreBuildFn store_build_fn(StoreKind kind);   // below, after the nine builds
 
 // ---- the Store worker -------------------------------------------------------------------------------------------------
 // interp.F90:207-437 stores its weight sets one after the other, each in front of the Regrids that use it; they are
@@ -1113,9 +1114,105 @@ int mpg_regrid_store_conserve_mesh(mpg_mesh src, mpg_mesh dst, int norm_type, mp
   return store_common(StoreKey::conserve_mesh_to_mesh(src, dst, norm_type), out);
 }
 
+// ---- Grid -> Grid Stores between two grids (k_store_to_mesh.hip, k_store_periodic_to_mesh.hip on another grid's stagger points;
+// k_store_conserve_grid.hip) -------------------------------------------------------------------------------------------------------
+// The bilinear and nearest searches take their destinations as a plain point set: the points of dst_staggerloc of `dst`, dnx x dny of
+// them.  A handle between two different grids is marked: the wind chain must not take it for a grid's own destagger pair.
+static int store_grid_to_grid_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  static const char *who = "mpg_regrid_store_grid_to_grid";
+  const PointSet &dst = x.dst_grid->pts[x.dst_loc];
+  const int dnx = x.dst_grid->snx[x.dst_loc], dny = x.dst_grid->sny[x.dst_loc];
+  h->cross_grid = x.src_grid != x.dst_grid;
+  if (x.method == MPG_REGRIDMETHOD_BILINEAR && (x.src_grid->periodic & MPG_GRID_PERIODIC_I))
+    return mpg_k_store_periodic_to_points(x.src_grid, dst, (int64_t)dnx * dny, dnx, dny, x.pole_method, who, h, s);
+  return mpg_k_store_to_points(x.src_grid, x.src_loc, dst, (int64_t)dnx * dny, dnx, dny, x.method, who, h, s);
+}
+
+int mpg_regrid_store_grid_to_grid(mpg_grid src, int src_staggerloc, mpg_grid dst, int dst_staggerloc, int regridmethod, int pole_method,
+                                  mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_grid_to_grid: NULL argument");
+  MPG_ARG(src_staggerloc >= MPG_STAGGERLOC_CENTER && src_staggerloc <= MPG_STAGGERLOC_CORNER && dst_staggerloc >= MPG_STAGGERLOC_CENTER &&
+              dst_staggerloc <= MPG_STAGGERLOC_CORNER,
+          "mpg_regrid_store_grid_to_grid: unknown stagger location (MPG_STAGGERLOC_CENTER, _EDGE1, _EDGE2 or _CORNER on either side)");
+  MPG_ARG(regridmethod >= 0 && regridmethod <= 2,
+          "mpg_regrid_store_grid_to_grid: unknown regrid method (MPG_REGRIDMETHOD_BILINEAR or MPG_REGRIDMETHOD_NEAREST_STOD)");
+  MPG_ARG(pole_method == MPG_POLEMETHOD_NONE || pole_method == MPG_POLEMETHOD_ALLAVG,
+          "mpg_regrid_store_grid_to_grid: pole_method must be MPG_POLEMETHOD_NONE or MPG_POLEMETHOD_ALLAVG (NPNTAVG and TEETH are not built)");
+  if (regridmethod == MPG_REGRIDMETHOD_CONSERVE) {
+    mpg_set_error("mpg_regrid_store_grid_to_grid: conservative regridding is not served by this call (bilinear and nearest are). "
+                  "mpg_regrid_store_conserve_grid_to_grid is the conservative Store between two grids, with its normalisation argument.");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  const bool periodic_bil = regridmethod == MPG_REGRIDMETHOD_BILINEAR && (src->periodic & MPG_GRID_PERIODIC_I);
+  if (periodic_bil && src_staggerloc != MPG_STAGGERLOC_CENTER) {
+    mpg_set_error("mpg_regrid_store_grid_to_grid: bilinear from a grid created with MPG_GRID_PERIODIC_I takes its CENTER points only (the EDGE / "
+                  "CORNER columns of a periodic grid duplicate column 0): pass MPG_STAGGERLOC_CENTER as src_staggerloc, or use "
+                  "MPG_REGRIDMETHOD_NEAREST_STOD");
+    return MPG_ERR_UNSUPPORTED;
+  }
+  const int64_t n_src = (int64_t)src->snx[src_staggerloc] * src->sny[src_staggerloc];
+  const int64_t n_dst = (int64_t)dst->snx[dst_staggerloc] * dst->sny[dst_staggerloc];
+  if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_grid_to_grid: %lld source points / %lld destination points exceed int32 ids; a destination split into row "
+                  "blocks stores fewer each",
+                  (long long)n_src, (long long)n_dst);
+    return MPG_ERR_OVERFLOW;
+  }
+  if (src->pts[src_staggerloc].n != n_src || dst->pts[dst_staggerloc].n != n_dst) {
+    const bool s_bad = src->pts[src_staggerloc].n != n_src;
+    mpg_set_error("mpg_regrid_store_grid_to_grid: the %s grid holds no coordinates of stagger %d: create the grid with them", s_bad ? "source" : "destination",
+                  s_bad ? src_staggerloc : dst_staggerloc);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (periodic_bil && (src->nx < 3 || src->ny < 2)) {
+    mpg_set_error("mpg_regrid_store_grid_to_grid: a periodic bilinear Store needs nx >= 3 and ny >= 2 CENTER points, not %d x %d; "
+                  "MPG_REGRIDMETHOD_NEAREST_STOD takes any grid",
+                  src->nx, src->ny);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (regridmethod == MPG_REGRIDMETHOD_BILINEAR && !periodic_bil && (src->snx[src_staggerloc] < 2 || src->sny[src_staggerloc] < 2)) {
+    mpg_set_error("mpg_regrid_store_grid_to_grid: a bilinear Store needs at least 2 x 2 source points of stagger %d; MPG_REGRIDMETHOD_NEAREST_STOD "
+                  "takes any grid",
+                  src_staggerloc);
+    return MPG_ERR_INVALID_ARG;
+  }
+  // the inside tolerance in force is part of what a bilinear handle is; the pole method only of a periodic source's
+  return store_common(StoreKey::grid_to_other_grid(src, src_staggerloc, dst, dst_staggerloc, regridmethod, mpg_grid_inside_tol_exp(), pole_method,
+                                                   (src->periodic & MPG_GRID_PERIODIC_I) != 0),
+                      out);
+}
+
+static int store_conserve_grid_build(mpg_handle_s *h, const StoreCtx &x, hipStream_t s) {
+  h->cross_grid = x.src_grid != x.dst_grid;
+  return mpg_k_store_conserve_grid(x.src_grid, x.dst_grid, x.norm_type, h, s);
+}
+
+int mpg_regrid_store_conserve_grid_to_grid(mpg_grid src, mpg_grid dst, int norm_type, mpg_handle *out) {
+  MPG_CHECK_INIT();
+  MPG_ARG(src && dst && out, "mpg_regrid_store_conserve_grid_to_grid: NULL argument");
+  MPG_ARG(norm_type == MPG_NORM_DSTAREA || norm_type == MPG_NORM_FRACAREA,
+          "mpg_regrid_store_conserve_grid_to_grid: norm_type must be MPG_NORM_DSTAREA or MPG_NORM_FRACAREA");
+  for (const mpg_grid_s *g : {(const mpg_grid_s *)src, (const mpg_grid_s *)dst})
+    if (g->nx < 1 || g->ny < 1 || g->pts[MPG_STAGGERLOC_CORNER].n != (int64_t)(g->nx + 1) * (g->ny + 1)) {
+      mpg_set_error("mpg_regrid_store_conserve_grid_to_grid: the %s grid holds no CORNER coordinates (its cells are the quadrilaterals of four "
+                    "CORNER points): create the grid with them",
+                    g == src ? "source" : "destination");
+      return MPG_ERR_INVALID_ARG;
+    }
+  if ((int64_t)(src->nx + 1) * (src->ny + 1) > 0x7fffffffLL || (int64_t)(dst->nx + 1) * (dst->ny + 1) > 0x7fffffffLL) {
+    mpg_set_error("mpg_regrid_store_conserve_grid_to_grid: %lld source cells / %lld destination cells exceed int32 ids; a destination split into "
+                  "row blocks stores fewer each",
+                  (long long)src->nx * src->ny, (long long)dst->nx * dst->ny);
+    return MPG_ERR_OVERFLOW;
+  }
+  return store_common(StoreKey::conserve_grid_to_grid(src, dst, norm_type), out);
+}
+
 static StoreBuildFn store_build_fn(StoreKind kind) {
   static const StoreBuildFn table[STORE_KIND_COUNT] = {store_mesh_build,             store_grid_build,      store_to_mesh_build, store_periodic_to_mesh_build,
-                                                       store_conserve_to_mesh_build, store_mesh_mesh_build, store_conserve_mesh_build};   // in StoreKind's order
+                                                       store_conserve_to_mesh_build, store_mesh_mesh_build, store_conserve_mesh_build,
+                                                       store_grid_to_grid_build,     store_conserve_grid_build};   // in StoreKind's order
   return table[kind];
 }
 
@@ -1123,7 +1220,7 @@ int mpg_handle_get_dst_frac(mpg_handle h, double *frac_host) {
   MPG_CHECK_INIT();
   MPG_ARG(h && frac_host, "mpg_handle_get_dst_frac: NULL argument");
   MPG_ARG(h->dst_frac.p, "mpg_handle_get_dst_frac: the handle has no destination fraction (mpg_regrid_store_conserve_to_mesh stores one, "
-                       "and so does mpg_regrid_store_conserve_mesh)");
+                       "and so does mpg_regrid_store_conserve_mesh, and so does mpg_regrid_store_conserve_grid_to_grid)");
   MPG_HIP(hipStreamSynchronize(g_stream));
   if (h->n_dst > 0) MPG_HIP(hipMemcpy(frac_host, h->dst_frac.p, sizeof(double) * (size_t)h->n_dst, hipMemcpyDeviceToHost));
   return MPG_SUCCESS;

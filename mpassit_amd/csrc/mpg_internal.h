@@ -295,6 +295,7 @@ struct mpg_handle_s {
   int64_t store_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // which branches the Store took (mpg_handle_store_stats; [0] is store_path)
   int store_path = 0;       // candidate search of the Store: 0 hierarchical (pyramid walk / BVH), 1 the grid's index space, 2 index space + BVH for the rest
   bool localized = false;
+  bool cross_grid = false;  // a Grid -> Grid handle between two DIFFERENT grids: never the destagger pair of the wind chain (mpg_wind_pair_dims)
   // [first, end) of the source indices the handle references, in its CURRENT index space, once somebody has asked (the host-array
   // Regrids ask on every call: mpg_hostpipe.hip); dropped whenever the indices are rewritten (rebase, localize, source windows)
   bool src_range_valid = false;
@@ -477,9 +478,14 @@ int mpg_k_transpose_masked(mpg_handle_s *h, const void *g, int g_type, int64_t l
                            void *dst, int dst_type, const mpg_mask_opts *opts, double *work, hipStream_t s);
 // k_store_to_mesh.hip: Grid -> Mesh Store (bilinear: 4 slots, nearest: 1) of the grid's `stagger` points onto the mesh's cells / vertices
 int mpg_k_store_to_mesh(mpg_grid_s *g, int stagger, mpg_mesh_s *m, int meshloc, int method, mpg_handle_s *h, hipStream_t s);
+// ... onto any list of n = nx_dst * ny_dst points (the Grid -> Grid Store hands over a stagger of another grid); `who` names the entry point
+int mpg_k_store_to_points(mpg_grid_s *g, int stagger, const PointSet &dst, int64_t n, int nx_dst, int ny_dst, int method, const char *who,
+                          mpg_handle_s *h, hipStream_t s);
 // k_store_periodic_to_mesh.hip: bilinear Store of a grid periodic in i (CENTER points, the i-wrap and the pole caps) onto the mesh's cells /
 // vertices: a CSR handle, quad rows of 4 entries, cap rows of nx; pole_method MPG_POLEMETHOD_*
 int mpg_k_store_periodic_to_mesh(mpg_grid_s *g, mpg_mesh_s *m, int meshloc, int pole_method, mpg_handle_s *h, hipStream_t s);
+int mpg_k_store_periodic_to_points(mpg_grid_s *g, const PointSet &dst, int64_t n, int nx_dst, int ny_dst, int pole_method, const char *who,
+                                   mpg_handle_s *h, hipStream_t s);
 // ... and the pole each end row of a periodic grid closes on, into g->end_pole (once per grid; a host read of the two CENTER rows)
 int mpg_k_grid_end_poles(mpg_grid_s *g, hipStream_t s);
 // k_apply_to_mesh.hip: Regrid of a fixed-nnz handle from grid planes ld elements apart onto [lev][point] or [point][lev] (`layout`)
@@ -557,6 +563,8 @@ int mpg_k_conserve_rows(mpg_mesh_s *m, const int32_t *poff, const int32_t *pair_
 int mpg_k_mesh_max_valence(mpg_mesh_s *m, hipStream_t s);
 // k_store_conserve_mesh.hip: conservative Mesh -> Mesh Store (CSR rows keyed by the cells of `dst`, columns the cells of `src`, h->dst_frac)
 int mpg_k_store_conserve_mesh(mpg_mesh_s *src, mpg_mesh_s *dst, int norm_type, mpg_handle_s *h, hipStream_t s);
+// k_store_conserve_grid.hip: the conservative Grid -> Grid Store, cell against cell
+int mpg_k_store_conserve_grid(mpg_grid_s *src, mpg_grid_s *dst, int norm_type, mpg_handle_s *h, hipStream_t s);
 // k_apply_csr_rows.hip: Regrid of a CSR handle from [n_src][nlev] rows onto [n_dst][nlev] rows (MPAS file order on both sides)
 int mpg_k_apply_csr_rows(mpg_handle_s *h, const void *src, int src_type, int nlev, int nfields, void *dst, int dst_type, double scale,
                          double offset, hipStream_t s);

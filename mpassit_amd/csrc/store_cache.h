@@ -29,6 +29,8 @@ enum StoreKind {
   STORE_CONSERVE_TO_MESH,
   STORE_MESH_TO_MESH,
   STORE_CONSERVE_MESH_TO_MESH,
+  STORE_GRID_TO_OTHER_GRID,
+  STORE_CONSERVE_GRID_TO_GRID,
   STORE_KIND_COUNT
 };
 
@@ -46,7 +48,7 @@ struct StoreKey {   // an aggregate: the constructors below list the fields in t
   int fan_origin = 0;          // "node_fan_origin": bilinear Mesh -> Grid Stores of node-located sources
   int inside_tol_exp = 0;      // "grid_inside_tol_exp": bilinear Stores FROM a grid
   int pole_method = 0;         // MPG_POLEMETHOD_*: the periodic Store
-  int norm_type = 0;           // MPG_NORM_*: the two conservative Stores onto a mesh
+  int norm_type = 0;           // MPG_NORM_*: the two conservative Stores onto a mesh and the conservative Grid -> Grid Store
 
   static StoreKey mesh_to_grid(const void *mesh, int meshloc, const void *grid, int stagger, int method, int linetype, int fan_origin) {
     const bool bil = method == MPG_REGRIDMETHOD_BILINEAR;
@@ -69,6 +71,15 @@ struct StoreKey {   // an aggregate: the constructors below list the fields in t
   }
   static StoreKey conserve_mesh_to_mesh(const void *src_mesh, const void *dst_mesh, int norm_type) {
     return {STORE_CONSERVE_MESH_TO_MESH, src_mesh, MPG_MESHLOC_ELEMENT, dst_mesh, MPG_MESHLOC_ELEMENT, MPG_REGRIDMETHOD_CONSERVE, 0, 0, 0, 0, norm_type};
+  }
+  // between two grids (mpg_regrid_store_grid_to_grid; src == dst allowed): a kind of its own, so it never meets grid_to_grid's keys
+  static StoreKey grid_to_other_grid(const void *src_grid, int src_stagger, const void *dst_grid, int dst_stagger, int method, int inside_tol_exp,
+                                     int pole_method, bool src_periodic) {
+    const bool bil = method == MPG_REGRIDMETHOD_BILINEAR;
+    return {STORE_GRID_TO_OTHER_GRID, src_grid, src_stagger, dst_grid, dst_stagger, method, 0, 0, bil ? inside_tol_exp : 0, bil && src_periodic ? pole_method : 0};
+  }
+  static StoreKey conserve_grid_to_grid(const void *src_grid, const void *dst_grid, int norm_type) {
+    return {STORE_CONSERVE_GRID_TO_GRID, src_grid, MPG_STAGGERLOC_CENTER, dst_grid, MPG_STAGGERLOC_CENTER, MPG_REGRIDMETHOD_CONSERVE, 0, 0, 0, 0, norm_type};
   }
 
   bool touches(const void *obj) const { return src == obj || dst == obj; }

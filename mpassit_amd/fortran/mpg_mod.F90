@@ -308,6 +308,25 @@ module mpg
       type(c_ptr), intent(out) :: rh
       integer(c_int) :: rc
     end function mpg_regrid_store_periodic_to_mesh
+    ! Grid -> Grid Stores between two grids (or two staggers of one): bilinear / nearest from any stagger onto any stagger (a periodic
+    ! source: CENTER, with pole_method as above; ignored otherwise), and the conservative Store of cell against cell (norm_type:
+    ! MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1).  Results are [lev][dny][dnx] of the destination stagger
+    function mpg_regrid_store_grid_to_grid(src, src_staggerloc, dst, dst_staggerloc, regridmethod, pole_method, rh) &
+        bind(C, name="mpg_regrid_store_grid_to_grid") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: src_staggerloc, dst_staggerloc, regridmethod, pole_method
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_grid_to_grid
+    function mpg_regrid_store_conserve_grid_to_grid(src, dst, norm_type, rh) &
+        bind(C, name="mpg_regrid_store_conserve_grid_to_grid") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: src, dst
+      integer(c_int), value :: norm_type
+      type(c_ptr), intent(out) :: rh
+      integer(c_int) :: rc
+    end function mpg_regrid_store_conserve_grid_to_grid
     ! conservative Grid -> Mesh Store (norm_type: MPG_NORM_DSTAREA = 0, MPG_NORM_FRACAREA = 1), its dst fraction and the CSR Regrid in mesh order
     function mpg_regrid_store_conserve_to_mesh(src, dst, norm_type, rh) bind(C, name="mpg_regrid_store_conserve_to_mesh") result(rc)
       import :: c_int, c_ptr

@@ -24,7 +24,7 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "NORM_FRACAREA", "regrid_store_mesh", "regrid_rows_autograd", "regrid_store_conserve_mesh", "regrid_csr_rows_autograd",
            "REGRIDMETHOD_BILINEAR", "REGRIDMETHOD_CONSERVE", "REGRIDMETHOD_NEAREST_STOD", "STAGGERLOC_CENTER",
            "STAGGERLOC_EDGE1", "STAGGERLOC_EDGE2", "STAGGERLOC_CORNER", "LAYOUT_CELL_FAST", "LAYOUT_LEV_FAST",
-           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
+           "regrid_store_periodic_to_mesh", "POLEMETHOD_NONE", "POLEMETHOD_ALLAVG", "regrid_store_grid_to_grid", "regrid_store_conserve_grid_to_grid", "wind_to_mesh", "mesh_rotang", "wind_to_mesh_autograd",
            "MESHLOC_EDGE", "mesh_edge_rotang", "wind_to_edges", "wind_to_edges_autograd",
            "wind_csr_to_mesh", "wind_csr_to_edges", "wind_csr_to_mesh_autograd", "wind_csr_to_edges_autograd",
            "sphere_frames", "wind_vector_weights", "wind_vector", "wind_vector_autograd",
@@ -1064,6 +1064,37 @@ def regrid_store_periodic_to_mesh(src_grid, dst_mesh, meshloc=MESHLOC_ELEMENT, p
     return RouteHandle(h)
 
 
+def regrid_store_grid_to_grid(src_grid, dst_grid, regridmethod=REGRIDMETHOD_BILINEAR, src_staggerloc=STAGGERLOC_CENTER,
+                              dst_staggerloc=STAGGERLOC_CENTER, pole_method=POLEMETHOD_ALLAVG):
+    """ESMF_FieldRegridStore(grid field -> grid field) between two grids (or two staggers of one): the `src_staggerloc` points of src_grid
+    onto the `dst_staggerloc` points of dst_grid, bilinear or nearest -- a lat-lon analysis onto the target grid, a parent domain onto its
+    nest and back, results onto a verification grid.  From a non-periodic grid the handle is fixed (4 slots bilinear, unmapped points idx
+    -1; 1 slot nearest, every point mapped); bilinear from a grid periodic in i (CENTER points only) gives the CSR handle of
+    regrid_store_periodic_to_mesh with the seam column and, under POLEMETHOD_ALLAVG, the pole caps; pole_method is ignored otherwise.
+    n_dst = dnx * dny and every Regrid writes [lev][dny][dnx].  Conservative is refused (MpgError, rc 4):
+    regrid_store_conserve_grid_to_grid is that Store."""
+    if not (isinstance(src_grid, Grid) and isinstance(dst_grid, Grid)):
+        raise TypeError("regrid_store_grid_to_grid: src_grid and dst_grid must be Grid objects")
+    h = C.c_void_p()
+    check(L.regrid_store_grid_to_grid(src_grid._h, int(src_staggerloc), dst_grid._h, int(dst_staggerloc), int(regridmethod), int(pole_method),
+                                      C.byref(h)))
+    return RouteHandle(h)
+
+
+def regrid_store_conserve_grid_to_grid(src_grid, dst_grid, norm=NORM_DSTAREA):
+    """ESMF_FieldRegridStore(grid field -> grid field, regridmethod=CONSERVE, normType=norm): the cells of src_grid (CORNER quadrilaterals)
+    onto the cells of dst_grid, first-order conservative.  NORM_DSTAREA: w = I / area(cell); NORM_FRACAREA: w = I / covered area.  A CSR
+    handle (n_src = snx * sny, n_dst = dnx * dny, results [lev][dny][dnx]): regrid_typed, regrid_masked, regrid_transpose, csr() and
+    dst_frac() work on it.  Both grids need CORNER coordinates (rc 2 without)."""
+    if not (isinstance(src_grid, Grid) and isinstance(dst_grid, Grid)):
+        raise TypeError("regrid_store_conserve_grid_to_grid: src_grid and dst_grid must be Grid objects")
+    if norm not in (NORM_DSTAREA, NORM_FRACAREA):
+        raise ValueError("regrid_store_conserve_grid_to_grid: norm must be NORM_DSTAREA or NORM_FRACAREA, not %r" % (norm,))
+    h = C.c_void_p()
+    check(L.regrid_store_conserve_grid_to_grid(src_grid._h, dst_grid._h, int(norm), C.byref(h)))
+    return RouteHandle(h)
+
+
 def regrid_store(src_mesh, dst_grid, regridmethod=REGRIDMETHOD_BILINEAR, staggerloc=STAGGERLOC_CENTER,
                  meshloc=MESHLOC_ELEMENT):
     """ESMF_FieldRegridStore(mesh field -> grid field); srcTermProcessing=1, unmappedaction=IGNORE."""
@@ -1983,7 +2014,7 @@ def patch(rh, src, dst, src_loc=None, dst_loc=None):
 
 def regrid_store_patch(src, dst, src_loc=None, dst_loc=None):
     """Store bilinear, patch, release: the patch handle between src and dst (Mesh or Grid each; src is dst for the CENTER -> EDGE1 / EDGE2
-    handles of one grid, with dst_loc the destination stagger).  The bilinear handle goes back to the Store cache.  Not cached itself:
+    handles of one grid, with dst_loc the destination stagger; two different grids go through regrid_store_grid_to_grid).  The bilinear handle goes back to the Store cache.  Not cached itself:
     release() the result."""
     if isinstance(src, Mesh) and isinstance(dst, Grid):
         rh = regrid_store(src, dst, REGRIDMETHOD_BILINEAR, STAGGERLOC_CENTER if dst_loc is None else dst_loc)
@@ -1994,8 +2025,11 @@ def regrid_store_patch(src, dst, src_loc=None, dst_loc=None):
                                   MESHLOC_ELEMENT if dst_loc is None else dst_loc)
     elif isinstance(src, Grid) and src is dst:
         rh = regrid_store_grid(src, STAGGERLOC_EDGE1 if dst_loc is None else dst_loc, STAGGERLOC_CENTER if src_loc is None else src_loc)
+    elif isinstance(src, Grid) and isinstance(dst, Grid):
+        rh = regrid_store_grid_to_grid(src, dst, REGRIDMETHOD_BILINEAR, STAGGERLOC_CENTER if src_loc is None else src_loc,
+                                       STAGGERLOC_CENTER if dst_loc is None else dst_loc)
     else:
-        raise ValueError("regrid_store_patch: src and dst must be Mesh or Grid objects (Grid -> Grid: the staggers of ONE grid)")
+        raise ValueError("regrid_store_patch: src and dst must be Mesh or Grid objects")
     try:
         return patch(rh, src, dst, src_loc, dst_loc)
     finally:
@@ -2026,7 +2060,7 @@ def conserve_2nd(rh, src, dst, norm=NORM_DSTAREA, src_mask=None, src_loc=None, d
 
 def regrid_store_conserve_2nd(src, dst, norm=NORM_DSTAREA):
     """Store first-order conservative, convert, release: the second-order conservative handle between the cells of src and dst (Mesh ->
-    Grid, Grid -> Mesh or Mesh -> Mesh, picked by the operand types).  The first-order handle goes back to the Store cache.  Not cached
+    Grid, Grid -> Mesh, Mesh -> Mesh or Grid -> Grid between two different grids, picked by the operand types).  The first-order handle goes back to the Store cache.  Not cached
     itself: release() the result."""
     if isinstance(src, Mesh) and isinstance(dst, Grid):
         if norm != NORM_DSTAREA:
@@ -2036,8 +2070,10 @@ def regrid_store_conserve_2nd(src, dst, norm=NORM_DSTAREA):
         rh = regrid_store_conserve_to_mesh(src, dst, norm)
     elif isinstance(src, Mesh) and isinstance(dst, Mesh):
         rh = regrid_store_conserve_mesh(src, dst, norm)
+    elif isinstance(src, Grid) and isinstance(dst, Grid) and src is not dst:
+        rh = regrid_store_conserve_grid_to_grid(src, dst, norm)
     else:
-        raise ValueError("regrid_store_conserve_2nd: src and dst must be a Mesh and a Grid, a Grid and a Mesh, or two Meshes")
+        raise ValueError("regrid_store_conserve_2nd: src and dst must be a Mesh and a Grid, a Grid and a Mesh, two Meshes or two different Grids")
     try:
         return conserve_2nd(rh, src, dst, norm)
     finally:
