@@ -1345,6 +1345,49 @@ int mpg_regrid_store_grid_to_grid(mpg_grid src, int src_staggerloc, mpg_grid dst
                                   mpg_handle *out);
 int mpg_regrid_store_conserve_grid_to_grid(mpg_grid src, mpg_grid dst, int norm_type, mpg_handle *out);
 
+/* ---- nearest destination to source: ESMF_FieldRegridStore(regridmethod=ESMF_REGRIDMETHOD_NEAREST_DTOS) --------------------------------------
+ * The one method that scatters: every source point goes to the ONE destination point nearest to it, and a destination point receives the
+ * sum of all sources that chose it.  No source is lost; a destination may receive nothing.  Counts (flashes, point emissions, "how many
+ * fine cells fall in this box"), a cell-to-box membership table, with MPG_DTOS_MEAN a cheap box average onto a verification grid -- and
+ * the only aggregating route for fields on vertices and edges, since the conservative Stores know cells only.
+ *
+ * Point sets (mpg_points): exactly one of mesh / grid is non-NULL, as for mpg_handle_extrapolate.  Sources are the QUERIES: any stagger of
+ *   a grid that holds its coordinates, or a mesh's cells, vertices or edges (edges after mpg_mesh_set_edges).  Destinations are the
+ *   SEARCHED set: any stagger of a grid (through that stagger's point pyramid) or a mesh's cells (MPG_MESHLOC_ELEMENT, through the site BVH
+ *   built whole).  Ids are the handle's usual indices: the cell, vertex or edge id, or j * snx + i.
+ * Rule.  For a source s that is not masked the candidates are the destination points that are not masked.  nearest(s) is the candidate
+ *   with the smallest (d2, id) in lexicographic order; d2 is dist2_nofma of the stored unit vectors, ((dx*dx + dy*dy) + dz*dz) in float64
+ *   without contraction (mpg_mesh_get_xyz / mpg_grid_get_xyz export their bits).  A tie goes to the lower destination id.  A masked
+ *   source, or a call in which every destination is masked, gives nearest(s) = -1.  A mask is bytes on the device, [n_src] / [n_dst];
+ *   non-zero = masked, NULL = no mask.
+ * Handle: an ordinary CSR handle of method MPG_REGRIDMETHOD_NEAREST_DTOS with n_src of the source set and n_dst, nx_dst, ny_dst of the
+ *   destination set.  Row d holds the sources with nearest(s) == d in ascending source id, which is the Regrid's summation order.
+ *   MPG_DTOS_SUM (ESMF's rule): every value is 1.0.  MPG_DTOS_MEAN: every value of row d is 1.0 / (double)len(d), rounded once.  A
+ *   destination that no source chose has an empty row: every Regrid writes +0.0 there and mpg_regrid_masked_dev the fill value.  The val
+ *   array is always present; the handle carries no dst_frac; the longest row is recorded.  mpg_handle_store_stats: [1] sources mapped,
+ *   [2] non-empty rows, [3] the longest row.  mpg_handle_store_ms is the GPU time of the call.
+ *   mpg_handle_get_src_nearest downloads nearest[] -- the binning index itself, which the handle keeps at 4 bytes per source; for a
+ *   handle of any other origin it returns MPG_ERR_INVALID_ARG.
+ * Determinism and ownership: no atomic decides a stored byte (integer atomics count, none places); two Stores on fresh objects give the
+ *   same bytes.  The handle is not cached: pair it with mpg_handle_release.  The call blocks and drains the Store worker first, as
+ *   mpg_handle_extrapolate does.
+ * Refusals, each with a message that names mpg_regrid_store_nearest_dtos and the way out.  MPG_ERR_INVALID_ARG: a NULL argument (src, dst
+ *   and out are mandatory); both or neither of mesh / grid set in a point set; an unknown mesh location, stagger or norm; a stagger
+ *   without coordinates; an edge source on a mesh without edges.  MPG_ERR_UNSUPPORTED: a destination at MPG_MESHLOC_NODE or
+ *   MPG_MESHLOC_EDGE (no tree is built over them); a mesh of mpg_mesh_create_window on either side; a destination mesh that carries a
+ *   source window.  MPG_ERR_OVERFLOW: counts beyond int32.  Empty input is success: a source set without points, or a source mask that
+ *   masks everything, gives an all-empty pattern.
+ * Consumers: every CSR consumer takes the handle unchanged -- mpg_regrid_typed[_pitched]_dev, mpg_regrid_csr_to_mesh_dev,
+ *   mpg_regrid_csr_rows_dev, mpg_regrid_masked_dev, mpg_regrid_transpose_dev, mpg_handle_compose, mpg_handle_get_csr.  The transpose of a
+ *   MPG_DTOS_SUM handle hands each source the value of its destination: the nearest gather in the other direction.  mpg_handle_mask with
+ *   MPG_MASKRULE_AUTO refuses the handle with MPG_ERR_UNSUPPORTED -- a destination masked afterwards would not re-route its sources: pass
+ *   the masks to this Store -- while the explicit rules work as for any CSR handle. */
+enum { MPG_REGRIDMETHOD_NEAREST_DTOS = 5 };
+enum { MPG_DTOS_SUM = 0, MPG_DTOS_MEAN = 1 };
+int mpg_regrid_store_nearest_dtos(const mpg_points *src, const mpg_points *dst, int norm,
+                                  const uint8_t *src_mask_dev, const uint8_t *dst_mask_dev, mpg_handle *out);
+int mpg_handle_get_src_nearest(mpg_handle rh, int32_t *nearest_host /* [n_src] */);
+
 /* ---- output epilogues: what write_data.F90 computes on rank 0 between ESMF_FieldGather and nf90_put_var, done on
  * the device-resident regridded fields so that only final float32 arrays leave the GPU.
  * Every output variable is NF90_FLOAT (write_data.F90:312-980) while the fields are float64: the cast below is the

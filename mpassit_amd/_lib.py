@@ -42,6 +42,7 @@ SYMBOLS = [
     "mpg_handle_conserve2nd",
     "mpg_handle_creep",
     "mpg_regrid_store_grid_to_grid", "mpg_regrid_store_conserve_grid_to_grid",
+    "mpg_regrid_store_nearest_dtos", "mpg_handle_get_src_nearest",
 ]
 
 MPG_SUCCESS = 0
@@ -67,6 +68,10 @@ MPG_REGRIDMETHOD_CONSERVE_2ND = 4   # the method of mpg_handle_conserve2nd's han
 REGRIDMETHOD_CONSERVE_2ND = MPG_REGRIDMETHOD_CONSERVE_2ND
 MPG_CREEP_ALL_LEVELS = 0x7fffffff   # mpg_creep_opts.num_levels: until no row is filled any more
 CREEP_ALL_LEVELS = MPG_CREEP_ALL_LEVELS
+MPG_REGRIDMETHOD_NEAREST_DTOS = 5   # the method of mpg_regrid_store_nearest_dtos's handles
+REGRIDMETHOD_NEAREST_DTOS = MPG_REGRIDMETHOD_NEAREST_DTOS
+MPG_DTOS_SUM, MPG_DTOS_MEAN = 0, 1
+DTOS_SUM, DTOS_MEAN = MPG_DTOS_SUM, MPG_DTOS_MEAN
 MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY = 0, 1, 2
 MASKRULE_AUTO, MASKRULE_ROW, MASKRULE_ENTRY = MPG_MASKRULE_AUTO, MPG_MASKRULE_ROW, MPG_MASKRULE_ENTRY
 
@@ -499,6 +504,27 @@ def handle_extrapolate_masked(*args):
     if "handle_extrapolate_masked" not in _to_mesh_fns:
         _to_mesh_fns["handle_extrapolate_masked"] = _HANDLE_EXTRAPOLATE_MASKED_PROTO(("mpg_handle_extrapolate_masked", load()))
     return _to_mesh_fns["handle_extrapolate_masked"](*args)
+
+
+# Nearest destination to source (include/mpassit_amd.h), bound the same way.
+#   mpg_regrid_store_nearest_dtos(src, dst, norm, src_mask_dev, dst_mask_dev, out)
+#   mpg_handle_get_src_nearest(rh, nearest_host)
+_STORE_NEAREST_DTOS_PROTO = C.CFUNCTYPE(C.c_int, C.POINTER(Points), C.POINTER(Points), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+_HANDLE_GET_SRC_NEAREST_PROTO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
+
+
+def regrid_store_nearest_dtos(*args):
+    """The typed binding of mpg_regrid_store_nearest_dtos; returns the call's status code."""
+    if "store_nearest_dtos" not in _to_mesh_fns:
+        _to_mesh_fns["store_nearest_dtos"] = _STORE_NEAREST_DTOS_PROTO(("mpg_regrid_store_nearest_dtos", load()))
+    return _to_mesh_fns["store_nearest_dtos"](*args)
+
+
+def handle_get_src_nearest(*args):
+    """The typed binding of mpg_handle_get_src_nearest; returns the call's status code."""
+    if "handle_get_src_nearest" not in _to_mesh_fns:
+        _to_mesh_fns["handle_get_src_nearest"] = _HANDLE_GET_SRC_NEAREST_PROTO(("mpg_handle_get_src_nearest", load()))
+    return _to_mesh_fns["handle_get_src_nearest"](*args)
 
 
 # Patch regridding (include/mpassit_amd.h): a fixed bilinear handle turned into the CSR handle of second-degree patch recovery

@@ -14,8 +14,8 @@ OBJDIR = os.path.join(HERE, "_build")
 SO = os.path.join(HERE, "libmpassit_amd.so")
 SOURCES = ["mpg_api.hip", "mpg_comm.hip", "mpg_hostpipe.hip", "mpg_fileio.hip", "k_setup.hip", "k_mesh_window.hip", "k_target_grid.hip", "k_store_bilinear.hip", "k_store_nearest.hip", "k_store_conserve.hip",
            "k_store_gridbil.hip", "k_apply.hip", "k_apply_lfu.hip", "k_apply_typed.hip", "k_wind.hip", "k_pole.hip", "k_post.hip", "k_halo.hip", "k_prims.hip", "k_sort.hip", "k_transpose.hip", "k_apply_masked.hip", "k_store_to_mesh.hip", "k_apply_to_mesh.hip", "k_apply_csr_to_mesh.hip", "k_store_mesh.hip", "k_apply_rows.hip",
-           "k_store_conserve_mesh.hip", "k_apply_csr_rows.hip", "k_store_periodic_to_mesh.hip", "k_wind_pair.hip", "k_wind_csr.hip", "k_wind_vector.hip", "k_wind_reconstruct.hip", "k_compose.hip", "k_wind_transpose.hip", "k_transpose_masked.hip", "k_extrapolate.hip", "k_handle_mask.hip", "k_patch.hip", "k_conserve2nd.hip", "k_creep.hip", "k_store_conserve_grid.hip"]
-HEADERS = ["mpg_internal.h", "geom.h", "quad_solve.h", "conserve_clip.h", "apply_mesh.h", "tree_walk.h", "store_cache.h", "wind_policies.h", "wind_vector_checks.h", "wind_reconstruct_checks.h", "compose_checks.h", "transpose_seg.h", "masked_par.h", "knn.h", "knn_mask.h", "handle_mask.h", "patch.h", "conserve2nd.h", "creep.h", os.path.join("..", "..", "include", "mpassit_amd.h")]
+           "k_store_conserve_mesh.hip", "k_apply_csr_rows.hip", "k_store_periodic_to_mesh.hip", "k_wind_pair.hip", "k_wind_csr.hip", "k_wind_vector.hip", "k_wind_reconstruct.hip", "k_compose.hip", "k_wind_transpose.hip", "k_transpose_masked.hip", "k_extrapolate.hip", "k_handle_mask.hip", "k_patch.hip", "k_conserve2nd.hip", "k_creep.hip", "k_store_conserve_grid.hip", "k_store_dtos.hip"]
+HEADERS = ["mpg_internal.h", "geom.h", "quad_solve.h", "conserve_clip.h", "apply_mesh.h", "tree_walk.h", "store_cache.h", "wind_policies.h", "wind_vector_checks.h", "wind_reconstruct_checks.h", "compose_checks.h", "transpose_seg.h", "masked_par.h", "knn.h", "knn_mask.h", "handle_mask.h", "patch.h", "conserve2nd.h", "creep.h", "knn_src.h", "dtos.h", os.path.join("..", "..", "include", "mpassit_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (Round 5 carried an MPASSIT_STRIP_DEVICE switch here whose one documented setting, `-Xoffload-linker --strip-all`, drops the device objects'
 # .symtab and makes the first hipLaunchKernel of this runtime SEGFAULT after a successful mpg_init -- profiles/r05_init_breakdown.md,

@@ -19,9 +19,12 @@
 // source mask, K = min(N, unmasked sources) (k_ex_unmasked, summed), one `alive` byte per tree node is built bottom-up (k_ex_alive_leaf,
 // then k_ex_alive_up per level: knn_mask.h says why) and k_ex_knn_masked<Src, KCAP> walks the AliveTree: it never enters a subtree without
 // an unmasked source, and its leaf bodies test mask[id] before they compute a distance.  Without a mask the unmasked kernels run as they are.
+// The two searched sets -- ExMeshSrc, ExGridSrc: the tree plus its leaf bodies leaf / leaf_masked / leaf_alive -- live in knn_src.h, which
+// k_store_dtos.hip shares; leaf_masked opens every item with `if (mask[c]) continue;`, ahead of dist2_nofma.
 #include "geom.h"
 #include "knn.h"
 #include "knn_mask.h"
+#include "knn_src.h"
 #include "mpg_internal.h"
 
 #define EX_MAX_SLOTS 4   // slots per row of a fixed handle (3, 4 or 1)
@@ -44,70 +47,6 @@ static ExIn ex_in(const mpg_handle_s *h) {
   o.n = h->n_dst;
   return o;
 }
-
-// the two sources: the tree, and the leaf body that hands every item of a leaf to f(d2, id)
-struct ExMeshSrc {
-  typedef BvhTree Tree;
-  SiteBvhView b;
-  __device__ __forceinline__ Tree tree() const { return BvhTree{b}; }
-  template <class F>
-  __device__ __forceinline__ void leaf(int node, double X, double Y, double Z, F f) const {
-    const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
-    for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) f(dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]), b.sid[i]);
-  }
-  // ... every UNMASKED item: the mask is read first, a masked item costs no distance
-  template <class F>
-  __device__ __forceinline__ void leaf_masked(int node, double X, double Y, double Z, const uint8_t *__restrict__ mask, F f) const {
-    const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
-    for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) {
-      const int32_t c = b.sid[i];
-      if (mask[c]) continue;
-      f(dist2_nofma(X, Y, Z, b.sx[i], b.sy[i], b.sz[i]), c);
-    }
-  }
-  __device__ __forceinline__ bool leaf_alive(int node, const uint8_t *__restrict__ mask) const {
-    const int64_t e1 = min(b.n, ((int64_t)node + 1) * MPG_BVH_LEAF);
-    bool a = false;
-    for (int64_t i = (int64_t)node * MPG_BVH_LEAF; i < e1; ++i) a |= mask[b.sid[i]] == 0;
-    return a;
-  }
-};
-struct ExGridSrc {
-  typedef PyrTree Tree;
-  PyramidView pyr;
-  int snx, sny;
-  const double *sx, *sy, *sz;
-  __device__ __forceinline__ Tree tree() const { return PyrTree{pyr}; }
-  template <class F>
-  __device__ __forceinline__ void leaf(int node, double X, double Y, double Z, F f) const {
-    const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
-    const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
-    for (int j = bj * MPG_PYR_B0; j < j1; ++j)
-      for (int i = bi * MPG_PYR_B0; i < i1; ++i) {
-        const int c = j * snx + i;
-        f(dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]), c);
-      }
-  }
-  template <class F>
-  __device__ __forceinline__ void leaf_masked(int node, double X, double Y, double Z, const uint8_t *__restrict__ mask, F f) const {
-    const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
-    const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
-    for (int j = bj * MPG_PYR_B0; j < j1; ++j)
-      for (int i = bi * MPG_PYR_B0; i < i1; ++i) {
-        const int c = j * snx + i;
-        if (mask[c]) continue;
-        f(dist2_nofma(X, Y, Z, sx[c], sy[c], sz[c]), c);
-      }
-  }
-  __device__ __forceinline__ bool leaf_alive(int node, const uint8_t *__restrict__ mask) const {
-    const int bi = node % pyr.nx[0], bj = node / pyr.nx[0];
-    const int i1 = min(bi * MPG_PYR_B0 + MPG_PYR_B0, snx), j1 = min(bj * MPG_PYR_B0 + MPG_PYR_B0, sny);
-    bool a = false;
-    for (int j = bj * MPG_PYR_B0; j < j1; ++j)
-      for (int i = bi * MPG_PYR_B0; i < i1; ++i) a |= mask[j * snx + i] == 0;
-    return a;
-  }
-};
 
 static inline unsigned ex_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 

@@ -132,7 +132,7 @@ void mpg_pool_release() {
   X(k_transpose) X(k_apply_masked) X(k_store_to_mesh) X(k_apply_to_mesh) X(k_apply_csr_to_mesh) \
   X(k_store_mesh) X(k_apply_rows) X(k_store_conserve_mesh) X(k_apply_csr_rows) X(k_store_periodic_to_mesh) X(k_wind_pair) \
   X(k_wind_csr) X(k_wind_vector) X(k_wind_reconstruct) X(k_compose) X(k_wind_transpose) X(k_transpose_masked) X(k_extrapolate) \
-  X(k_handle_mask) X(k_patch) X(k_conserve2nd) X(k_creep) X(k_store_conserve_grid)
+  X(k_handle_mask) X(k_patch) X(k_conserve2nd) X(k_creep) X(k_store_conserve_grid) X(k_store_dtos)
 #define X(n) const void *mpg_anchor_##n();
 MPG_ANCHORS(X)
 #undef X
@@ -684,6 +684,7 @@ static void handle_free(mpg_handle_s *h) {
   h->col.free();
   h->val.free();
   h->dst_frac.free();
+  h->src_nearest.free();
   h->pole_dst.free();
   h->pole_src0.free();
   h->pole_w.free();
@@ -1867,6 +1868,136 @@ static int ex_extrapolate(const char *who, mpg_handle rh, const mpg_points *src,
   return MPG_SUCCESS;
 }
 
+// ---- nearest destination to source: every source onto its nearest destination point, a CSR handle built by scattering (k_store_dtos.hip) ------
+// a point set of the call: how many points, their row shape as a handle records it, and where they are
+static int dtos_points(const char *who, const char *role, const mpg_points *p, bool source, int64_t *n, int *nx, int *ny, const PointSet **pts) {
+  if ((p->mesh != nullptr) == (p->grid != nullptr)) {
+    mpg_set_error("%s: exactly one of mesh / grid must be set in the %s point set (%s are)", who, role, p->mesh ? "both" : "neither");
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (p->mesh) {
+    mpg_mesh_s *m = p->mesh;
+    const int loc = p->meshloc;
+    if (loc != MPG_MESHLOC_ELEMENT && loc != MPG_MESHLOC_NODE && loc != MPG_MESHLOC_EDGE) {
+      mpg_set_error("%s: bad mesh location %d in the %s point set", who, loc, role);
+      return MPG_ERR_INVALID_ARG;
+    }
+    if (!source && loc != MPG_MESHLOC_ELEMENT) {
+      mpg_set_error("%s: a destination mesh is searched through its cells only (MPG_MESHLOC_ELEMENT, not location %d): no tree is built over "
+                    "vertices or edges -- aggregate onto the cells, or onto a grid stagger", who, loc);
+      return MPG_ERR_UNSUPPORTED;
+    }
+    if (m->geo_grid) {
+      mpg_set_error("%s: the %s mesh was cut to a grid (mpg_mesh_create_window): its resident points are a window; use the whole mesh "
+                    "(mpg_mesh_create)", who, role);
+      return MPG_ERR_UNSUPPORTED;
+    }
+    if (!source && m->win_count[MPG_MESHLOC_ELEMENT] >= 0) {
+      mpg_set_error("%s: the destination mesh carries a source window (mpg_mesh_set_source_window): reset the window to the whole mesh "
+                    "first", who);
+      return MPG_ERR_UNSUPPORTED;
+    }
+    if (loc == MPG_MESHLOC_EDGE && m->edge.n == 0) {
+      mpg_set_error("%s: the %s mesh has no edges: call mpg_mesh_set_edges first", who, role);
+      return MPG_ERR_INVALID_ARG;
+    }
+    *pts = loc == MPG_MESHLOC_EDGE ? &m->edge : loc == MPG_MESHLOC_ELEMENT ? &m->cell : &m->vert;
+    *n = loc == MPG_MESHLOC_EDGE ? m->edge.n : loc == MPG_MESHLOC_ELEMENT ? m->nCells : m->nVertices;
+    if (*n > 0x7fffffffll) {
+      mpg_set_error("%s: the %s point set has %lld points, more than int32 ids hold", who, role, (long long)*n);
+      return MPG_ERR_OVERFLOW;
+    }
+    *nx = (int)*n;
+    *ny = 1;
+    return MPG_SUCCESS;
+  }
+  mpg_grid_s *g = p->grid;
+  const int st = p->staggerloc;
+  if (st < 0 || st >= 4) {
+    mpg_set_error("%s: bad stagger location %d in the %s point set", who, st, role);
+    return MPG_ERR_INVALID_ARG;
+  }
+  *nx = g->snx[st];
+  *ny = g->sny[st];
+  *n = (int64_t)*nx * *ny;
+  *pts = &g->pts[st];
+  if (g->pts[st].n != *n) {
+    mpg_set_error("%s: stagger %d of the %s grid has no coordinates: create the grid with them", who, st, role);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (*n > 0x7fffffffll) {
+    mpg_set_error("%s: the %s point set has %lld points, more than int32 ids hold", who, role, (long long)*n);
+    return MPG_ERR_OVERFLOW;
+  }
+  return MPG_SUCCESS;
+}
+
+int mpg_regrid_store_nearest_dtos(const mpg_points *src, const mpg_points *dst, int norm, const uint8_t *src_mask_dev,
+                                  const uint8_t *dst_mask_dev, mpg_handle *out) {
+  const char *who = "mpg_regrid_store_nearest_dtos";
+  MPG_CHECK_INIT();
+  if (!(src && dst && out)) {
+    mpg_set_error("%s: NULL argument (src, dst and out are all mandatory)", who);
+    return MPG_ERR_INVALID_ARG;
+  }
+  if (norm != MPG_DTOS_SUM && norm != MPG_DTOS_MEAN) {
+    mpg_set_error("%s: unknown norm %d: MPG_DTOS_SUM or MPG_DTOS_MEAN", who, norm);
+    return MPG_ERR_INVALID_ARG;
+  }
+  int rc;
+  int64_t ns = 0, nd = 0;
+  int sx = 0, sy = 0, dx = 0, dy = 0;
+  const PointSet *sp = nullptr, *dp = nullptr;
+  if ((rc = dtos_points(who, "source", src, true, &ns, &sx, &sy, &sp)) || (rc = dtos_points(who, "destination", dst, false, &nd, &dx, &dy, &dp))) return rc;
+  // The search builds the destination's tree (a grid's point pyramid, a mesh's site BVH): a begun Store may be building the same one on the worker.
+  store_worker_drain();
+  mpg_handle_s *h = new mpg_handle_s();
+  h->method = MPG_REGRIDMETHOD_NEAREST_DTOS;
+  h->n_src = ns;
+  h->n_dst = nd;
+  h->nx_dst = dx;
+  h->ny_dst = dy;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    mpg_set_error("%s: hipEventCreate failed", who);
+    handle_free(h);
+    return MPG_ERR_HIP;
+  }
+  (void)hipEventRecord(e0, g_stream);
+  rc = mpg_k_store_dtos(*sp, ns, src->mesh != nullptr, dst->mesh, dst->grid, dst->staggerloc, norm, src_mask_dev, dst_mask_dev, h, g_stream);
+  if (!rc) {
+    hipError_t he = hipEventRecord(e1, g_stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&h->store_ms, e0, e1);
+    if (he != hipSuccess) {
+      mpg_set_error("%s: %s", who, hipGetErrorString(he));
+      rc = MPG_ERR_HIP;
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) {
+    (void)hipStreamSynchronize(g_stream);   // nothing of the failed build still runs on arrays that go now
+    handle_free(h);
+    return rc;
+  }
+  *out = h;
+  return MPG_SUCCESS;
+}
+
+int mpg_handle_get_src_nearest(mpg_handle h, int32_t *nearest_host) {
+  MPG_CHECK_INIT();
+  MPG_ARG(h && nearest_host, "mpg_handle_get_src_nearest: NULL argument");
+  MPG_ARG(h->has_src_nearest, "mpg_handle_get_src_nearest: the handle keeps no nearest[] (mpg_regrid_store_nearest_dtos stores one; no other "
+                              "call does)");
+  if (h->n_src > 0) {
+    MPG_HIP(hipStreamSynchronize(g_stream));
+    MPG_HIP(hipMemcpy(nearest_host, h->src_nearest.p, sizeof(int32_t) * (size_t)h->n_src, hipMemcpyDeviceToHost));
+  }
+  return MPG_SUCCESS;
+}
+
 // ---- Store-time masks on a handle's pattern (k_handle_mask.hip): no geometry, every Store and every consumer served at once ----------------
 int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *out) {
   MPG_CHECK_INIT();
@@ -1877,7 +2008,12 @@ int mpg_handle_mask(mpg_handle rh, const mpg_store_mask_opts *opts, mpg_handle *
   if (rule == MPG_MASKRULE_AUTO) {
     if (rh->method == MPG_REGRIDMETHOD_BILINEAR || rh->method == MPG_REGRIDMETHOD_NEAREST_STOD || rh->method == MPG_REGRIDMETHOD_PATCH) rule = MPG_MASKRULE_ROW;
     else if (rh->method == MPG_REGRIDMETHOD_CONSERVE) rule = MPG_MASKRULE_ENTRY;
-    else {
+    else if (rh->method == MPG_REGRIDMETHOD_NEAREST_DTOS) {
+      mpg_set_error("mpg_handle_mask: MPG_MASKRULE_AUTO does not serve a nearest-destination-to-source handle: a destination masked afterwards "
+                    "would not re-route its sources -- pass the masks to mpg_regrid_store_nearest_dtos (src_mask_dev, dst_mask_dev), or name "
+                    "MPG_MASKRULE_ROW / MPG_MASKRULE_ENTRY");
+      return MPG_ERR_UNSUPPORTED;
+    } else {
       mpg_set_error("mpg_handle_mask: MPG_MASKRULE_AUTO follows the handle's regrid method, and this handle records none (from weights, "
                     "composed, reconstruct): pass MPG_MASKRULE_ROW or MPG_MASKRULE_ENTRY");
       return MPG_ERR_INVALID_ARG;

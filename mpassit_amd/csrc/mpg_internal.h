@@ -287,6 +287,8 @@ struct mpg_handle_s {
   int64_t nnz = 0;
   int64_t max_row = -1;      // longest CSR row as the Store counted it on the host (mpg_handle_from_weights, mpg_reconstruct_store); -1: not recorded
   DevBuf<double> dst_frac;   // [n_dst] covered fraction of every destination cell (conservative Grid -> Mesh and Mesh -> Mesh Stores; absent otherwise)
+  DevBuf<int32_t> src_nearest;   // [n_src] the destination every source chose, -1 = none (mpg_regrid_store_nearest_dtos; absent otherwise)
+  bool has_src_nearest = false;  // ... the handle is that Store's (an empty source set has no array to tell it by)
   int refcount = 1;
   bool cached = false;
   uint64_t parked_at = 0;   // release order of a handle waiting in the cache with refcount 0 (mpg_api.hip)
@@ -529,6 +531,12 @@ int mpg_k_compose_pattern(mpg_handle_s *a, const int32_t *b_rowptr, const int32_
 int mpg_k_extrapolate(mpg_handle_s *in, mpg_mesh_s *src_mesh, mpg_grid_s *src_grid, int src_stagger, const PointSet &dst, int method, int npnts,
                       double e, mpg_handle_s *out, hipStream_t s, const uint8_t *src_mask = nullptr, const uint8_t *dst_skip = nullptr,
                       const char *who = "mpg_handle_extrapolate");
+// k_store_dtos.hip: the nearest-destination-to-source Store (mpg_regrid_store_nearest_dtos).  src: the n_src query points; exactly one of
+// dst_mesh (its cells: the site BVH, built whole) / dst_grid (its `dst_stagger` points: their point pyramid) is the searched set.
+// src_morton: visit the sources in Morton order (a mesh's points; a grid's row-major ids are neighbours already).  h: shape and method
+// set by the caller, arrays empty.  Arguments checked by the API entry point; blocking: it allocates and reads counts back
+int mpg_k_store_dtos(const PointSet &src, int64_t n_src, bool src_morton, mpg_mesh_s *dst_mesh, mpg_grid_s *dst_grid, int dst_stagger, int norm,
+                     const uint8_t *src_mask, const uint8_t *dst_mask, mpg_handle_s *h, hipStream_t s);
 // k_handle_mask.hip: `out` (shape and method set by the caller, arrays empty) <- `in` under static masks (mpg_handle_mask); entry: the
 // resolved rule is MPG_MASKRULE_ENTRY (CSR only).  Arguments checked by the API entry point; blocking
 int mpg_k_handle_mask(mpg_handle_s *in, const uint8_t *src_mask, const uint8_t *dst_mask, bool entry, int norm_type, mpg_handle_s *out,

@@ -82,6 +82,9 @@ module mpg
     integer(c_int) :: num_levels       !< ESMF's extrapNumLevels: >= 1; MPG_CREEP_ALL_LEVELS: until no row is filled any more
     type(c_ptr) :: dst_skip_dev        !< device bytes [n_dst], non-zero = never filled and never a neighbour; c_null_ptr: none
   end type mpg_creep_opts
+  !> mpg_regrid_store_nearest_dtos (include/mpassit_amd.h): the method of its handles, and the two norms
+  integer(c_int), parameter :: MPG_REGRIDMETHOD_NEAREST_DTOS = 5
+  integer(c_int), parameter :: MPG_DTOS_SUM = 0, MPG_DTOS_MEAN = 1
 
   interface
     function mpg_init(device) bind(C, name="mpg_init") result(rc)
@@ -682,6 +685,24 @@ module mpg
       type(c_ptr), intent(out) :: out
       integer(c_int) :: rc
     end function mpg_handle_creep
+    !> nearest destination to source (ESMF_REGRIDMETHOD_NEAREST_DTOS): every source onto its nearest destination point, a CSR handle;
+    !> norm MPG_DTOS_SUM / MPG_DTOS_MEAN; the masks are device bytes [n_src] / [n_dst], non-zero = masked, c_null_ptr: none.
+    !> mpg_handle_get_src_nearest: the destination every source chose, [n_src] int32, -1 = none
+    function mpg_regrid_store_nearest_dtos(src, dst, norm, src_mask_dev, dst_mask_dev, out) &
+        bind(C, name="mpg_regrid_store_nearest_dtos") result(rc)
+      import :: c_int, c_ptr, mpg_points
+      type(mpg_points), intent(in) :: src, dst
+      integer(c_int), value :: norm
+      type(c_ptr), value :: src_mask_dev, dst_mask_dev
+      type(c_ptr), intent(out) :: out
+      integer(c_int) :: rc
+    end function mpg_regrid_store_nearest_dtos
+    function mpg_handle_get_src_nearest(rh, nearest_host) bind(C, name="mpg_handle_get_src_nearest") result(rc)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: rh
+      integer(c_int32_t), intent(out) :: nearest_host(*)
+      integer(c_int) :: rc
+    end function mpg_handle_get_src_nearest
 
     !> device buffers for fields that stay in HBM between the input and the output file
     function mpg_dev_alloc(nbytes, dev) bind(C, name="mpg_dev_alloc") result(rc)

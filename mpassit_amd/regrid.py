@@ -34,7 +34,8 @@ __all__ = ["MESHLOC_ELEMENT", "MESHLOC_NODE", "Mesh", "Grid", "RouteHandle", "re
            "mask_handle", "extrapolate_masked", "store_masks", "MASKRULE_AUTO", "MASKRULE_ROW", "MASKRULE_ENTRY",
            "patch", "regrid_store_patch", "REGRIDMETHOD_PATCH", "PATCH_MAX_PNTS",
            "conserve_2nd", "regrid_store_conserve_2nd", "REGRIDMETHOD_CONSERVE_2ND",
-           "creep", "creep_nearest", "CREEP_ALL_LEVELS"]
+           "creep", "creep_nearest", "CREEP_ALL_LEVELS",
+           "regrid_store_nearest_dtos", "REGRIDMETHOD_NEAREST_DTOS", "DTOS_SUM", "DTOS_MEAN"]
 
 
 def _f64(a):
@@ -645,6 +646,13 @@ class RouteHandle:
         frac = np.empty(self.n_dst, np.float64)
         check(L.handle_get_dst_frac(self._h, _ptr(frac)))
         return frac
+
+    def src_nearest(self):
+        """mpg_handle_get_src_nearest: the destination every source chose, [n_src] int32 with -1 for none -- the binning index of a
+        regrid_store_nearest_dtos handle (any other handle is refused)."""
+        nearest = np.empty(self.n_src, np.int32)
+        check(L.handle_get_src_nearest(self._h, _ptr(nearest)))
+        return nearest
 
     def transpose_stats(self):
         """(n_referenced, max_per_source): sources with at least one entry and the longest transposed row
@@ -2113,3 +2121,34 @@ def creep_nearest(rh, src, dst, num_levels, src_mask=None, dst_skip=None, src_lo
         return extrapolate_masked(crept, src, dst, src_mask, dst_skip, EXTRAPMETHOD_NEAREST_STOD, src_loc=src_loc, dst_loc=dst_loc)
     finally:
         crept.release()
+
+
+# ---- nearest destination to source: every source onto its nearest destination point -------------------------------------------------------
+REGRIDMETHOD_NEAREST_DTOS, DTOS_SUM, DTOS_MEAN = L.REGRIDMETHOD_NEAREST_DTOS, L.DTOS_SUM, L.DTOS_MEAN
+
+
+def _points_n(obj, loc):
+    if isinstance(obj, Mesh):
+        loc = MESHLOC_ELEMENT if loc is None else loc
+        return obj.nEdges if loc == MESHLOC_EDGE else obj.nCells if loc == MESHLOC_ELEMENT else obj.nVertices
+    return int(np.prod(obj.stagger_shape(STAGGERLOC_CENTER if loc is None else loc)))
+
+
+def regrid_store_nearest_dtos(src, dst, norm=DTOS_SUM, src_mask=None, dst_mask=None, src_loc=None, dst_loc=None):
+    """mpg_regrid_store_nearest_dtos (ESMF_REGRIDMETHOD_NEAREST_DTOS): every point of `src` goes to the ONE point of `dst` nearest to it --
+    the smallest (d2, id), a tie to the lower destination id -- and row d of the CSR RouteHandle lists the sources that chose d in
+    ascending id.  src: a Mesh (src_loc MESHLOC_ELEMENT, _NODE or _EDGE; default cells) or a Grid (src_loc a stagger; default CENTER);
+    dst: a Grid (dst_loc a stagger) or a Mesh's cells.  DTOS_SUM: every value 1.0 (a count / a sum per destination, ESMF's rule);
+    DTOS_MEAN: 1.0 / the row's length (a box average).  src_mask [n_src] / dst_mask [n_dst]: numpy or torch, bool or uint8, non-zero =
+    masked (a host mask is uploaded): a masked source goes nowhere, a masked destination is no candidate.  A destination nobody chose
+    has an empty row.  src_nearest() is the binning index.  The bits of target_grid.nearest_dtos_rows fed with src.xyz() / dst.xyz().
+    Not cached: release() it."""
+    ps, pd = _points(src, src_loc, "src"), _points(dst, dst_loc, "dst")
+    ms = md = None
+    if src_mask is not None:
+        ms = _mask_dev(src_mask, _points_n(src, src_loc), "regrid_store_nearest_dtos", "src_mask")
+    if dst_mask is not None:
+        md = _mask_dev(dst_mask, _points_n(dst, dst_loc), "regrid_store_nearest_dtos", "dst_mask")
+    h = C.c_void_p()
+    check(L.regrid_store_nearest_dtos(C.byref(ps), C.byref(pd), int(norm), _mask_ptr(ms), _mask_ptr(md), C.byref(h)))
+    return RouteHandle(h)

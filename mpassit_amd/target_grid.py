@@ -543,6 +543,48 @@ def extrapolate_rows_masked(src_xyz, dst_xyz, unmapped, src_mask, method=EXTRAPM
     return rowlen, back, w
 
 
+DTOS_SUM, DTOS_MEAN = 0, 1
+
+
+def nearest_dtos_rows(src_xyz, dst_xyz, norm=DTOS_SUM, src_mask=None, dst_mask=None):
+    """The numpy mirror of mpg_regrid_store_nearest_dtos, by brute force.  src_xyz [3][n_src], dst_xyz [3][n_dst]: the library's stored unit
+    vectors (Mesh.xyz / Grid.xyz); src_mask / dst_mask: bool or uint8, non-zero = masked, None = nothing masked.  For every unmasked source
+    nearest = the first of a lexsort on (d2, id) over the unmasked destinations, d2 = (dx*dx + dy*dy) + dz*dz in float64 (dist2_nofma's
+    expression): a tie goes to the lower id; -1 for a masked source and when every destination is masked.  The sources are visited in
+    chunks, so that memory stays small.  Row d holds the sources with nearest == d in ascending id; DTOS_SUM: every value 1.0, DTOS_MEAN:
+    1.0 / len(d), one float64 division.  -> (rowptr [n_dst + 1] int64, col int32, val float64, nearest [n_src] int32)."""
+    if norm not in (DTOS_SUM, DTOS_MEAN):
+        raise ValueError("nearest_dtos_rows: unknown norm")
+    src_xyz, dst_xyz = np.asarray(src_xyz, np.float64).reshape(3, -1), np.asarray(dst_xyz, np.float64).reshape(3, -1)
+    n_src, n_dst = src_xyz.shape[1], dst_xyz.shape[1]
+    live_s = np.arange(n_src) if src_mask is None else np.flatnonzero(np.asarray(src_mask).reshape(-1) == 0)
+    live_d = np.arange(n_dst) if dst_mask is None else np.flatnonzero(np.asarray(dst_mask).reshape(-1) == 0)
+    nearest = np.full(n_src, -1, np.int32)
+    if live_s.size and live_d.size:
+        q = dst_xyz[:, live_d]
+        step = max(1, (1 << 22) // live_d.size)
+        for a in range(0, live_s.size, step):
+            rows = live_s[a:a + step]
+            p = src_xyz[:, rows]
+            dx, dy, dz = (p[k][:, None] - q[k][None, :] for k in range(3))
+            d2 = (dx * dx + dy * dy) + dz * dz
+            lo = d2.min(axis=1)
+            for u in range(rows.size):
+                cand = np.flatnonzero(d2[u] <= lo[u])            # every tie at the first rank is among them
+                nearest[rows[u]] = live_d[cand[np.lexsort((live_d[cand], d2[u][cand]))[0]]]
+    mapped = np.flatnonzero(nearest >= 0)
+    order = mapped[np.argsort(nearest[mapped], kind="stable")]   # by destination, ascending source id inside a row
+    cnt = np.bincount(nearest[mapped], minlength=n_dst).astype(np.int64)
+    rowptr = np.zeros(n_dst + 1, np.int64)
+    np.cumsum(cnt, out=rowptr[1:])
+    col = order.astype(np.int32)
+    if norm == DTOS_MEAN:
+        val = np.float64(1.0) / np.repeat(cnt[cnt > 0], cnt[cnt > 0]).astype(np.float64)
+    else:
+        val = np.ones(col.size, np.float64)
+    return rowptr, col, np.ascontiguousarray(val, dtype=np.float64), nearest
+
+
 CREEP_ALL_LEVELS = 0x7fffffff
 
 
